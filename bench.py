@@ -14,9 +14,11 @@ over all ranks = N * rows_per_gpu * nq * K / t.
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N
                                        # one rank per GPU, RCCL broadcast + all-gather (codesearch_amd/sharded.py)
 
-Adds to the JSON line:
+A plain run sets up, warms up, times --steps steps and prints the line with its headline figure and
   roofline     — the scan kernel against the 8 TB/s HBM peak: algorithmic bytes per launch
-                 (rows*dim*4) / HIP-event duration of that kernel, measured live.
+                 (rows*dim*4) / HIP-event duration of that kernel, measured live in the timed steps.
+`--dump-outputs DIR` writes what the last timed step returned (DIR/cos.npy, ids.npy, counts.npy).
+`--full` adds to the JSON line:
   cpu_baseline — the CPU oracle's tuned port timed on this box's host cores over a bounded
                  sample (reported baseline, not the target).
   encoder      — BASELINE configs[2] (BGE-small shape, 256 x 256 tokens) with its own roofline
@@ -24,6 +26,7 @@ Adds to the JSON line:
                  reference's effective batch of 32); the reference's 32-chunk call shape beside it.
   embed_search / embedded_and_searched_chunks_per_s — the literal wording of BASELINE's metric.
   e2e_index_search — BASELINE configs[3]: 100k chunks embedded on the GPU, then 64 queries top-10.
+  default_routing, config_1m, hbm_reference — the default route of the same search, the 1M-row leg, the read probe.
 `--only-scan` runs the timed loop alone (for rocprofv3: one kernel population per CSV row).
 """
 from __future__ import annotations
@@ -79,10 +82,33 @@ def parse_args():
                          "(well under the driver's own limit: the one-process line must still be printed)")
     ap.add_argument("--only-scan", action="store_true",
                     help="timed loop only: no CPU baseline, no 1M / filter / encoder / e2e legs, no recall sample")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: CPU baseline + recall, default routing, configs[1] (1M rows), "
+                         "read-bandwidth reference, encoder / embed+search legs, configs[3] e2e; --gpus N: the RCCL child, "
+                         "the opt-in gather mode, default routing and the 1,000-query leg.  Off: set up, warm up, time, report")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(cos f32 [nq, k], ids f64 [nq, k], counts f64 [nq])")
     a = ap.parse_args()
-    if a.only_scan:
+    if a.only_scan or not a.full:
         a.no_cpu_baseline = a.no_encoder = a.no_1m = a.no_e2e = True
     return a
+
+
+def dump_outputs(out_dir, cos, ids, counts, nq, k):
+    """--dump-outputs: the result of the last timed step as a caller of the search receives it (cosines best-first, their ids,
+    the number of valid entries per query).  ids / counts are u32 on the device: f64 holds them exactly.  At most
+    CS_MAX_QUERIES x CS_MAX_K = 4096 x 1024 entries: 48 MB in all."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {
+        "cos": cos.detach().cpu().numpy().astype(np.float32).reshape(nq, k),
+        "ids": ids.detach().cpu().numpy().view(np.uint32).astype(np.float64).reshape(nq, k),
+        "counts": counts.detach().cpu().numpy().view(np.uint32).astype(np.float64).reshape(nq),
+    }
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
 
 
 def _encoder_flops(cfg, B, L):
@@ -863,7 +889,7 @@ def main_one_process(args):
         phases[name] = round(now - t_ph, 3)
         t_ph = now
 
-    if not args.no_rccl_child:
+    if args.full and not args.no_rccl_child:
         distinct = len(set(devices))
         rccl = rccl_child_record(args, distinct, force_dist=(distinct == 1))
     phase("rccl_child_s")
@@ -975,6 +1001,8 @@ def main_one_process(args):
     _lib.check(lib.cs_index_profile(sh0, 0))
     timed_same = bool(torch.equal(keys, ref_keys))
     phase("warmup_and_timed_s")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, cos, ids, cnt, nq, k)
     scan_us = s_ms.value * 1e3 / max(n_l.value, 1)
     alg_bytes = rows * dim * 4
     achieved = alg_bytes / (scan_us * 1e-6) / 1e9 if scan_us else 0.0
@@ -1025,6 +1053,12 @@ def main_one_process(args):
         failed.append("timed searches disagree with the first one")
     if failed:
         line["error"] = "; ".join(failed)
+    if not args.full:
+        print(json.dumps(line), flush=True)
+        st.close()
+        if failed:
+            raise SystemExit(3)
+        return
     # The record is on stdout BEFORE any optional leg runs (the opt-in gather mode, the default route, configs[4]'s
     # 1,000-query step): a leg that hangs or is ended from outside cannot take the measured line with it.  The complete
     # line — the same keys plus the legs' — follows as the LAST line when they finish.
@@ -1192,6 +1226,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out["cos"], out["ids"], out["counts"], args.nq, args.k)
     ids0 = out["ids"].cpu().numpy().astype("uint32").reshape(args.nq, args.k)
     cos0 = out["cos"].cpu().numpy().reshape(args.nq, args.k)
     # N > 1: the device merge of the last timed step against a HOST merge of the keys the all-gather delivered (every
@@ -1346,7 +1382,7 @@ def main():
             line["recall_checks"] = dict(checks, quoted=f"recall_at_10 and max_abs_cos_err_vs_cpu are the '{timed_route}' entry "
                                                          f"(the route `value` was timed on); the 10M-row results of both routes are "
                                                          f"held to the oracle by tests/test_gpu_scan.py")
-        if world == 1 and args.nq == 1 and args.route == "stream" and not args.only_scan:
+        if world == 1 and args.nq == 1 and args.route == "stream" and args.full and not args.only_scan:
             # The DEFAULT route of the same search (CS_ROUTE_COST, index.hip run_search): one query over >= 32,768 rows (k < 48; 300,000 from k = 48) goes
             # through the MFMA filter over the int8 copy (a quarter of the f32 bytes) + exact f32 re-score — the shape of the
             # reference's MCP and HTTP searches (src/mcp/mod.rs:252, src/server/mod.rs:547).  Same bits as the streaming scan.
@@ -1389,7 +1425,7 @@ def main():
             }
         if world == 1 and args.nq == 1 and args.dim == 384 and not args.no_1m:
             line["config_1m"] = scan_1m_leg(args.dim, args.k, local_rank, VectorStore)
-        if world == 1 and not args.only_scan:
+        if world == 1 and args.full and not args.only_scan:
             ref = hbm_reference(f"cuda:{local_rank}")
             line["hbm_reference"] = ref
             if line["roofline"]["bound"] == "hbm" and ref.get("read_probe_GBps"):

@@ -4,7 +4,7 @@ set -e
 R=$PWD
 O=$R/gpurun_out/r01e
 mkdir -p $O
-python bench.py > $O/bench_full_run.json 2> $O/bench_full_run.err
+python bench.py --full > $O/bench_full_run.json 2> $O/bench_full_run.err
 echo "bench done" 
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/scan_q1 -- python3 $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-encoder > $O/scan_q1.log 2>&1

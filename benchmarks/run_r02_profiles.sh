@@ -6,7 +6,7 @@ set -e
 R=$PWD
 O=$R/gpurun_out/r02
 mkdir -p $O
-python bench.py > $O/bench_full_run.json 2> $O/bench_full_run.err
+python bench.py --full > $O/bench_full_run.json 2> $O/bench_full_run.err
 echo "bench done"
 python benchmarks/gemm_time.py > $O/gemm_time.log 2>&1
 cd /tmp && export TMPDIR=/tmp

@@ -7,10 +7,10 @@ set -e
 R=$PWD
 O=$R/gpurun_out/r03
 mkdir -p $O
-python bench.py > $O/bench_full_run.json 2> $O/bench_full_run.err
+python bench.py --full > $O/bench_full_run.json 2> $O/bench_full_run.err
 echo "bench done"
 # the one-process multi-GPU path rehearsed on this box's single GPU (two shards on device 0: NOT a scaling figure)
-CS_BENCH_SHARD_DEVICES=0,0 python bench.py --gpus 2 --rows 5000000 --steps 100 --warmup 10 > $O/bench_one_process_2shards_on_1gpu.json 2> $O/bench_one_process.err
+CS_BENCH_SHARD_DEVICES=0,0 python bench.py --full --gpus 2 --rows 5000000 --steps 100 --warmup 10 > $O/bench_one_process_2shards_on_1gpu.json 2> $O/bench_one_process.err
 python benchmarks/ffn_time.py > $O/ffn_fused_time_and_ablations.log 2>&1
 bash benchmarks/ab_attention_p.sh > $O/attention_p_single_f16_experiment.log 2>&1 || true
 for f in 1 0; do CS_FFN_FUSED=$f python3 benchmarks/encoder_bench.py --iters 10 --stages 2>&1 | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('CS_FFN_FUSED=$f', round(d['device_ms_per_batch'],3), d.get('stages_us_per_layer'))"; done > $O/encoder_ffn_fused_ab.log 2>&1

@@ -4,7 +4,7 @@
 set -o pipefail
 out=gpurun_out/r05
 mkdir -p $out
-python bench.py > $out/bench_n1.json 2> $out/bench_n1.err || { tail -30 $out/bench_n1.err; exit 1; }
+python bench.py --full > $out/bench_n1.json 2> $out/bench_n1.err || { tail -30 $out/bench_n1.err; exit 1; }
 python3 -c "
 import json; d=json.load(open('$out/bench_n1.json'))
 e=d['encoder']; es=d['embed_search']
@@ -17,7 +17,7 @@ print('embed_search', {k: v for k, v in es.items() if not isinstance(v, (dict, s
 print('cls embed_search', es['cls_pool_variant'])
 print('config_1m', d.get('config_1m')); print('e2e', d.get('e2e_index_search'))
 "
-CS_BENCH_SHARD_DEVICES=0,0 python bench.py --gpus 2 --steps 50 --warmup 5 > $out/bench_2shards_1gpu.json 2> $out/bench_2shards.err || { tail -30 $out/bench_2shards.err; cat $out/bench_2shards_1gpu.json | cut -c1-3000; exit 1; }
+CS_BENCH_SHARD_DEVICES=0,0 python bench.py --full --gpus 2 --steps 50 --warmup 5 > $out/bench_2shards_1gpu.json 2> $out/bench_2shards.err || { tail -30 $out/bench_2shards.err; cat $out/bench_2shards_1gpu.json | cut -c1-3000; exit 1; }
 python3 -c "
 import json; d=json.loads(open('$out/bench_2shards_1gpu.json').read().strip().split('\n')[-1])  # (the record is printed before the optional legs and again, complete, behind them)
 print('N=2 rehearsal value', d['value'], 'ms', d['ms_per_step']); print(json.dumps(d['multi_gpu_checks'])); print(json.dumps(d['rccl'])); print(json.dumps(d.get('default_routing'))); print(json.dumps(d.get('config_5')))
