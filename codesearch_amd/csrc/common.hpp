@@ -67,6 +67,19 @@ struct PerDeviceOnce {
     }
 };
 
+// Compute units of the device (multiProcessorCount, 256 if the query fails), asked once per process: the persistent
+// kernels size their grids by it.  Each caller keeps its own rounding to whole XCD octets.
+inline int cu_count() {
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+            n > 0)
+            return n;
+        return 256;
+    }();
+    return cus;
+}
+
 // RAII: make `device` current for the calling thread, restore on scope exit.
 struct DeviceGuard {
     int prev = -1;

@@ -1829,14 +1829,7 @@ int32_t launch_q8_quantize(int src_kind, const void* d_src, uint32_t T, uint32_t
 
 // two blocks per CU (64 KiB of LDS each), a multiple of 8 so that a block's slots stay on its XCD
 static uint32_t q8_persistent_grid(uint32_t slots) {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    const uint32_t want = (uint32_t)(2 * cus + 7) / 8 * 8;
+    const uint32_t want = (uint32_t)(2 * cu_count() + 7) / 8 * 8;
     return slots < want ? slots : want;
 }
 
@@ -1845,16 +1838,6 @@ static uint32_t q8_persistent_grid(uint32_t slots) {
 static bool q8_rows_takes(uint32_t M, uint32_t K) {
     static const int min_m = [] { const char* e = cs_lab_env("CS_Q8_ROWS"); return e ? std::atoi(e) : 4096; }();
     return K == 128 * QR_KC && min_m > 0 && M >= (uint32_t)min_m;
-}
-static int q8_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    return cus;
 }
 template <int EPI, int SRC = QR_PREQUANT, bool MU = false>
 static int32_t launch_rows(const void* d_xq, const Q8RowMeta* d_rmeta, const int8_t* d_wq, const Q8ColMeta* d_cmeta,
@@ -1867,7 +1850,7 @@ static int32_t launch_rows(const void* d_xq, const Q8RowMeta* d_rmeta, const int
         CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_q8_rows_kernel<EPI, SRC, MU>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
         return CS_OK;
     }));
-    const uint32_t mtiles = (M + 127) / 128, ntiles = N / 128, cus = (uint32_t)q8_cus();
+    const uint32_t mtiles = (M + 127) / 128, ntiles = N / 128, cus = (uint32_t)cu_count();
     // a unit = one row block x a range of its n-tiles: whole row blocks when there is one per CU, else cut so every CU has work
     uint32_t parts = mtiles >= cus ? 1u : (cus + mtiles - 1) / mtiles;
     if (parts > ntiles) parts = ntiles;
@@ -1927,7 +1910,7 @@ int32_t launch_gemm_q8_ln(int src_kind, const void* d_src, const Q8RowMeta* d_rm
     }));
     auto go = [&](auto kernel, uint32_t nw, int nst) -> int32_t {
         const size_t ldsb = (size_t)qn_lds(nst, nst == 3);
-        const uint32_t groups = (M + 16 * nw - 1) / (16 * nw), slots = (uint32_t)q8_cus() * (nw == 4 ? 2u : 1u);
+        const uint32_t groups = (M + 16 * nw - 1) / (16 * nw), slots = (uint32_t)cu_count() * (nw == 4 ? 2u : 1u);
         hipLaunchKernelGGL(kernel, dim3(groups < slots ? groups : slots), dim3(64 * nw), ldsb, s, d_src, d_rmeta, d_in_range, d_wq, d_cmeta, X, ln_g, ln_b,
                            eps, M, d_range_pairs, d_out_slot, w_stage_major ? 1u : 0u);
         CS_HIP(hipGetLastError());

@@ -562,17 +562,6 @@ gemm_q8_slab_kernel(const void* __restrict__ Xv, const int8_t* __restrict__ W, c
 #endif
 }
 
-int qs_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    return cus;
-}
-
 // X [M][384] f32 -> xq [M][384] s8 with the tensor's parameters: the slab kernel's own quantising arithmetic (reciprocal quotient, the true
 // division inside the tie window: the bytes of q8_quantize_kernel), one thread per 16 values.  For calls of few slabs, whose units
 // (slab x a range of n-tiles) would otherwise each quantise the slab's 256 rows again.
@@ -608,7 +597,7 @@ qs_prequant_kernel(const float* __restrict__ X, const uint32_t* __restrict__ in_
 
 // units per slab the launch below cuts (1 when every CU has a slab of its own)
 static uint32_t qs_parts(uint32_t M, uint32_t N) {
-    const uint32_t slabs = (M + QS_ROWS - 1) / QS_ROWS, ntiles = N / 128, cus = (uint32_t)qs_cus();
+    const uint32_t slabs = (M + QS_ROWS - 1) / QS_ROWS, ntiles = N / 128, cus = (uint32_t)cu_count();
     uint32_t parts = slabs >= cus ? 1u : (cus + slabs - 1) / slabs;
     return parts > ntiles ? ntiles : parts;
 }
@@ -622,7 +611,7 @@ int32_t launch_slab(const void* d_x, const uint32_t* d_in_range, const int8_t* d
         CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_q8_slab_kernel<EPI, PREQ>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
         return CS_OK;
     }));
-    const uint32_t slabs = (M + QS_ROWS - 1) / QS_ROWS, ntiles = N / 128, cus = (uint32_t)qs_cus();
+    const uint32_t slabs = (M + QS_ROWS - 1) / QS_ROWS, ntiles = N / 128, cus = (uint32_t)cu_count();
     // a unit = one slab x a range of its n-tiles: whole slabs when there is one per CU, else cut so every CU has work
     uint32_t parts = slabs >= cus ? 1u : (cus + slabs - 1) / slabs;
     if (parts > ntiles) parts = ntiles;

@@ -303,7 +303,7 @@ struct cs_index {
     int single_route = CS_ROUTE_COST;
     uint64_t single_filter_min_rows = 2000000;  // ... with the f16 copy (and k >= single_filter_min_k)
     // ... with the int8 copy: the measured crossover of the two routes, which depends on the list length because the
-    // filter's round plan does (scan_filter.hip: growth up to 24 - one round up to 60 x 3,072 rows - below k = 48, 5.5 from
+    // filter's round plan does (filter_plan.hpp: growth up to 24 - one round up to 60 x 3,072 rows - below k = 48, 5.5 from
     // there on).  profiles/r04_route_crossover_by_k.log, us per search, stream / filter: k = 10: 20k rows 54 / 57, 35k 63 / 58,
     // 100k 83 / 65, 184k 105 / 72; k = 25: 35k 71 / 63, 100k 104 / 86; k = 40: 200k 158 / 102 — k = 50: 150k 97 / 114, 300k 129 / 127,
     // 400k 150 / 131; k = 75: 300k 141 / 135; k = 99: 300k 142 / 141.  (Round 4's first figure, 150,000 rows for every k, was

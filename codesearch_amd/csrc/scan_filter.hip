@@ -36,8 +36,10 @@
 // Phases (row-ordered, growing 5x: 1 K, 5 K, 25 K ... rows) and the overflow escape hatch are those
 // of scan_mfma.hip.  Serves `variants.par_iter().map(|e| store.search(e, limit))`
 // (/root/reference/src/search/mod.rs:508-511) and BASELINE.json configs 4/5.
+#include <array>
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 #include <cmath>
 #include "scan.hpp"
@@ -1450,6 +1452,98 @@ int32_t launch_corpus_q8(const float* d_corpus, const float* d_norms, int8_t* d_
     return CS_OK;
 }
 
+// The laboratory knobs of the filter plan (filter_plan.hpp), read once; in the product library they are the defaults.
+static const FilterKnobs& filter_knobs() {
+    static const FilterKnobs kn = [] {
+        FilterKnobs d;
+        const auto num = [](const char* name, auto& v) {
+            if (const char* e = cs_lab_env(name)) v = (std::decay_t<decltype(v)>)std::atoi(e);
+        };
+        const auto real = [](const char* name, double& v) {
+            if (const char* e = cs_lab_env(name)) v = std::atof(e);
+        };
+        const auto on = [](const char* name, bool& v) {
+            if (const char* e = cs_lab_env(name)) v = e[0] != '0';
+        };
+        num("CS_FILTER_INT8_MAX_Q", d.int8_max_q);
+        num("CS_FILTER_INT8_RW_MAX_Q", d.int8_rw_max_q);
+        on("CS_FILTER_INT8_RQ", d.int8_rq);
+        num("CS_FILTER_INT8_Q2", d.int8_q2);
+        num("CS_FILTER_WIDE_MIN_Q", d.wide_min_q);
+        num("CS_FILTER_RW", d.rw);
+        num("CS_FILTER_GROWTH", d.growth);
+        if (d.growth == 1) d.growth = 2;
+        num("CS_FILTER_GROWTH1", d.growth1);
+        real("CS_FILTER_GMAX", d.gmax);
+        real("CS_FILTER_G1MAX", d.g1max);
+        num("CS_FILTER_G1_MAXQ", d.g1_maxq);
+        real("CS_FILTER_G1_CAND", d.g1_cand);
+        on("CS_FILTER_INT8_RW256", d.int8_rw256);
+        on("CS_FILTER_NT", d.nt);
+        num("CS_FILTER_PHASE0_BLOCKS", d.phase0_blocks);
+        return d;
+    }();
+    return kn;
+}
+
+// The filter instantiations scan_split_impl<J> can launch, as (kernel, 32-query groups per tile).  Their dynamic-LDS
+// limits are set from this list and a launch finds its kernel in it, so no instantiation runs without its limit.
+struct FilterInst {
+    FilterKernel kernel;
+    uint32_t nqt;
+};
+template <int J>
+constexpr auto filter_insts() {
+    using K = FilterKernel;
+    if constexpr (J == 3)
+        return std::array<FilterInst, 14>{{{K::F16Tile128, 0}, {K::F16Tile256, 0}, {K::Q8Tile256, 0}, {K::F16Rw, 1},
+                                           {K::F16Rw, 2}, {K::F16Rw, 4}, {K::Q8Rw, 1}, {K::Q8Rw, 2}, {K::Q8Rw, 4},
+                                           {K::Q8Rw, 8}, {K::Q8Rw2, 1}, {K::Q8Rw2, 2}, {K::Q8Rq, 8}, {K::Q8Rq1, 8}}};
+    else if constexpr (J == 6)
+        return std::array<FilterInst, 10>{{{K::F16Tile128, 0}, {K::F16Tile256, 0}, {K::Q8Tile256, 0}, {K::F16Rw, 1},
+                                           {K::F16Rw, 2}, {K::Q8Rw, 1}, {K::Q8Rw, 2}, {K::Q8Rw, 4}, {K::Q8Rw2, 1},
+                                           {K::Q8Rw2, 2}}};
+    else
+        return std::array<FilterInst, 6>{{{K::F16Tile128, 0}, {K::F16Tile256, 0}, {K::Q8Tile256, 0}, {K::F16Rw, 1},
+                                          {K::Q8Rw, 1}, {K::Q8Rw, 2}}};
+}
+
+template <class Fn>
+struct FilterFn {
+    Fn fn;
+    size_t lds;  // dynamic LDS bytes
+};
+template <class Fn>
+FilterFn(Fn, size_t) -> FilterFn<Fn>;
+
+// entry I of filter_insts<J>(): the kernel and its dynamic LDS
+template <int J, size_t I>
+static auto filter_fn() {
+    constexpr FilterInst f = filter_insts<J>()[I];
+    constexpr int N = (int)f.nqt;
+    using K = FilterKernel;
+    if constexpr (f.kernel == K::F16Tile128) return FilterFn{&score_filter_kernel, (size_t)SH_LDS_BYTES};
+    else if constexpr (f.kernel == K::F16Tile256) return FilterFn{&score_filter256p_kernel<false>, (size_t)UF2_LDS};
+    else if constexpr (f.kernel == K::Q8Tile256) return FilterFn{&score_filter256p_kernel<true>, (size_t)UF2_LDS};
+    else if constexpr (f.kernel == K::F16Rw) return FilterFn{&score_filter_rw_kernel<N, 2 * J>, (size_t)RwGeom<N, 2 * J>::LDS_ALL};
+    else if constexpr (f.kernel == K::Q8Rw) return FilterFn{&score_filter_rw8_kernel<N, J>, (size_t)Rw8Geom<N, J>::LDS_ALL};
+    else if constexpr (f.kernel == K::Q8Rw2)
+        return FilterFn{&score_filter_rw8_kernel<N, J, true>, (size_t)Rw8GeomT<N, J, true>::LDS_ALL};
+    else return FilterFn{&score_filter_rq8_kernel<N, J, f.kernel == K::Q8Rq1>, (size_t)kRq8Lds<N, J>};
+}
+
+template <int J, class F, size_t... I>
+static void for_each_filter(F&& f, std::index_sequence<I...>) {
+    (f(std::integral_constant<size_t, I>{}), ...);
+}
+template <int J, class F>
+static void for_each_filter(F&& f) {
+    for_each_filter<J>(f, std::make_index_sequence<filter_insts<J>().size()>{});
+}
+
+static_assert(UF2_BM == 256 && UF2_BN == 256 && SH_BM == 128 && SH_BN == 128, "filter_plan.hpp's tile sizes");
+
+// Launches what plan_filter plans: prep, then per phase the filter kernel, the int8 tail, the exact re-score and the select.
 template <int J>
 static int32_t scan_split_impl(const BatchedState& st, const SplitQueryWs& qw, const float* d_corpus,
                                const _Float16* d_split, uint64_t n_rows, const float* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_dead,
@@ -1460,319 +1554,65 @@ static int32_t scan_split_impl(const BatchedState& st, const SplitQueryWs& qw, c
     const uint32_t cap = batched_cap(k);
     static PerDeviceOnce attr_set;  // function attributes are per device
     CS_TRY(attr_set.run([&]() -> int32_t {
-        CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(score_filter_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, SH_LDS_BYTES));
-        CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(score_filter256p_kernel<false>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, UF2_LDS));
-        CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(score_filter256p_kernel<true>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, UF2_LDS));
-        if constexpr (J == 3) {
-            CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(score_filter_rw_kernel<1, 6>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, RwGeom<1, 6>::LDS_ALL));
-            CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(score_filter_rw_kernel<2, 6>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, RwGeom<2, 6>::LDS_ALL));
-            CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(score_filter_rw_kernel<4, 6>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, RwGeom<4, 6>::LDS_ALL));
-        } else if constexpr (J == 6) {
-            CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(score_filter_rw_kernel<1, 12>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, RwGeom<1, 12>::LDS_ALL));
-            CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(score_filter_rw_kernel<2, 12>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, RwGeom<2, 12>::LDS_ALL));
-        } else {
-            CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(score_filter_rw_kernel<1, 16>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, RwGeom<1, 16>::LDS_ALL));
-        }
-        CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(score_filter_rw8_kernel<1, J>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, Rw8Geom<1, J>::LDS_ALL));
-        if constexpr (J <= 6) {
-            CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(score_filter_rw8_kernel<1, J, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (Rw8GeomT<1, J, true>::LDS_ALL)));
-            CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(score_filter_rw8_kernel<2, J, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (Rw8GeomT<2, J, true>::LDS_ALL)));
-        }
-        CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(score_filter_rw8_kernel<2, J>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, Rw8Geom<2, J>::LDS_ALL));
-        if constexpr (J <= 6)
-            CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(score_filter_rw8_kernel<4, J>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, Rw8Geom<4, J>::LDS_ALL));
-        if constexpr (J == 3) {
-            CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(score_filter_rw8_kernel<8, J>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, Rw8Geom<8, J>::LDS_ALL));
-            CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(score_filter_rq8_kernel<8, 3, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kRq8Lds<8, 3>));
-            CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(score_filter_rq8_kernel<8, 3, false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kRq8Lds<8, 3>));
-        }
-
+        hipError_t e = hipSuccess;
+        for_each_filter<J>([&](auto i) {
+            const auto f = filter_fn<J, i>();
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute(reinterpret_cast<const void*>(f.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds);
+        });
+        CS_HIP(e);
         return CS_OK;
     }));
-    // int8 copy: the filter's operand whenever one exists and covers at least one tile behind phase 0
-    static const uint32_t q8_max_env = [] {
-        const char* e = cs_lab_env("CS_FILTER_INT8_MAX_Q");  // A/B: query count up to which the int8 copy is the operand
-        return e ? (uint32_t)std::atoi(e) : 0u;
-    }();
-    static const uint32_t q8_rw_env = [] {
-        const char* e = cs_lab_env("CS_FILTER_INT8_RW_MAX_Q");  // A/B: ... and up to which its resident-query kernel runs
-        return e ? (uint32_t)std::atoi(e) : 0u;
-    }();
-    // one persistent block per (query tile, row group) slot of an XCD: at most 32 query tiles
-    const uint32_t q8_rw_limit = dim <= 768 ? 32u * 128u : 32u * 64u;
-    // Measured over 10M x 384, k = 10, 129 / 256 / 512 / 1,000 queries: f16 256 x 256 tiles 2.79 / 2.88 / 5.12 / 8.92 ms,
-    // the same tile kernel on int8 2.30 / 2.45 / 4.36 / 7.98 (LDS traffic, not MFMA rate, paces it), the resident-query
-    // kernel on int8 1.61 / 1.82 / 3.20 / 5.95 — so the tile kernel only takes what exceeds 32 query tiles.
-    const uint32_t q8_rw_max = q8_rw_env ? std::min(q8_rw_env, q8_rw_limit) : q8_rw_limit;
-    static const bool rq8_on = [] { const char* e = cs_lab_env("CS_FILTER_INT8_RQ"); return !(e && e[0] == '0'); }();
-    // phase 0 re-scores its rows once PER QUERY (L2 traffic nq x rows x dim x 4): 3,072 rows up to 32 queries, 1,024 above
-    const uint32_t phase0 = nq <= 32 ? kFilterPhase0 : 1024u;
-    const bool use_q8 = q8 && q8->d_q8 && q8->rows > kFilterPhase0 && (!q8_max_env || nq <= q8_max_env) && qw.d_q8q && qw.d_qmeta;
-    // Long lists for up to 32 queries (dim <= 768) take the queries in two int8 planes: a 128 times finer query scale
-    // (band ~0.010 instead of ~0.017 for evenly spread vectors: the k-th best of a long list sits where scores are dense,
-    // and the band decides how many rows pass) for a second MFMA per step (score_filter_rw8_kernel<.., true>).  The
-    // second MFMA is not free even where the kernel streams — same-box A/B over 10M rows: 9 x 200 0.877 -> 0.863 ms,
-    // 1 x 200 0.836 -> 0.811, but 8 x 10 0.681 -> 0.712 and 64 x 10 0.81 -> 1.04 — so short lists and more than 32
-    // queries keep one plane.  CS_FILTER_INT8_Q2=0: never; =2: whenever the kernel exists (<= 64 queries).
-    static const int q2_mode = [] { const char* e = cs_lab_env("CS_FILTER_INT8_Q2"); return e ? std::atoi(e) : 1; }();
-    const bool two_planes = use_q8 && q2_mode > 0 && J <= 6 && qw.d_q8q_hi && qw.d_q8q_lo &&
-                            (q2_mode >= 2 ? nq <= 64 : (nq <= 32 && k >= 48));
+    const FilterKnobs& kn = filter_knobs();
+    const bool q8_ready = q8 && q8->d_q8 && qw.d_q8q && qw.d_qmeta;
+    const FilterPlan plan = plan_filter(dim, n_rows, nq, k, q8_ready ? q8->rows : 0, qw.d_q8q_hi && qw.d_q8q_lo, cu_count(), kn);
     hipLaunchKernelGGL(prep_queries_kernel<J>, dim3((nq + 7) / 8), dim3(256), 0, stream,
                        qw.q_pinned ? qw.q_pinned : d_queries, qw.q_pinned ? const_cast<float*>(d_queries) : nullptr, nq,
-                       qw.d_qmag, qw.d_qsplit, st.d_tau, st.d_cnt, st.d_carry, k, st.d_overflow,
-                       (uint32_t)(n_rows < phase0 ? n_rows : phase0), use_q8 ? qw.d_q8q : nullptr, qw.d_qmeta,
-                       use_q8 ? q8->d_mu : nullptr, st.h_mirror, two_planes ? qw.d_q8q_hi : nullptr, qw.d_q8q_lo);
+                       qw.d_qmag, qw.d_qsplit, st.d_tau, st.d_cnt, st.d_carry, k, st.d_overflow, plan.phase0_rows,
+                       plan.use_q8 ? qw.d_q8q : nullptr, qw.d_qmeta, plan.use_q8 ? q8->d_mu : nullptr, st.h_mirror,
+                       plan.two_planes ? qw.d_q8q_hi : nullptr, qw.d_q8q_lo);
     CS_HIP(hipGetLastError());
     uint32_t* cand = reinterpret_cast<uint32_t*>(st.d_cand);
-    const uint32_t ntiles = (nq + SH_BN - 1) / SH_BN;
-    static int wide_min = -1;  // query count from which the 256 x 256 tile kernel is used
-    if (wide_min < 0) {
-        const char* e = cs_lab_env("CS_FILTER_WIDE_MIN_Q");
-        wide_min = e ? std::atoi(e) : 129;
-    }
-    const bool wide = (int)nq >= wide_min;
-    static int rw_mode = -1;  // resident-query / deep-ring kernel: <= 64 queries at dim 384 / 768, <= 32 at 1024
-    if (rw_mode < 0) {
-        const char* e = cs_lab_env("CS_FILTER_RW");
-        rw_mode = e ? std::atoi(e) : 1;
-    }
-    // resident-query kernel: up to 64 queries always; above that when CS_FILTER_RW=2 (128-query tiles)
-    const bool small = rw_mode && (dim == 384 ? (nq <= 64 || (rw_mode >= 2 && (nq + 127) / 128 <= 32))
-                                              : nq <= (dim == 768 ? 64u : 32u));
-
-    // refine blocks per query (blocks past a query's candidate count exit at once): enough that a
-    // k = 200 phase (~500 rows per query) is one or two rounds of 32 rows per block
-    const uint32_t rk_blocks = nq <= 128 ? 32 : (4096 / nq < 4 ? 4 : 4096 / nq);
-    uint64_t done = 0;
-    uint64_t phase = n_rows < phase0 ? n_rows : phase0;  // phase 0: tau = -inf, every row is a candidate
-    // A phase that takes the rows scanned from D to g D yields about k (g - 1) candidates per query (each new row beats
-    // the k-th best of D exchangeable rows with probability k / D), plus the few inside the margin.  Small growth wins on
-    // refine work (re-scoring + sorting grow with it), large growth on launches: a phase is three kernels (filter,
-    // re-score, select) and the early ones are launch-bound whatever their size.  Measured over 10M rows (r01-r03):
-    // g = 5 from k = 48 on, g = 9 ... 16 below.  Round 4 plans the boundaries as ONE geometric sequence from phase 0 to
-    // the last row with the fewest phases whose ratio stays within that growth (5.5 from k = 48, up to 24 below): 10M rows
-    // take 5 filter phases at k = 200 (was 6) and 3 at k = 10 (was 4), 1M rows 2 at k = 10.  CS_FILTER_GROWTH / CS_FILTER_GROWTH1 restore fixed growth.
-    static int growth_env = -1;
-    if (growth_env < 0) {
-        const char* e = cs_lab_env("CS_FILTER_GROWTH");
-        growth_env = e ? std::atoi(e) : 0;
-        if (growth_env == 1) growth_env = 2;
-    }
-    static const uint32_t growth1_env = [] {
-        const char* e = cs_lab_env("CS_FILTER_GROWTH1");
-        return e ? (uint32_t)std::atoi(e) : 0u;
-    }();
-    const bool fixed_growth = growth_env > 0 || growth1_env > 1;
-    const uint32_t growth = growth_env > 0 ? (uint32_t)growth_env : (k >= 48 ? 4u : 8u);
-    double ratio = 0.0;  // planned D_next / D
-    if (!fixed_growth && n_rows > phase) {
-        static const double gmax_env = [] { const char* e = cs_lab_env("CS_FILTER_GMAX"); return e ? std::atof(e) : 0.0; }();
-        // Short lists: a round from D to r D rows brings ~k r candidates times the band's factor (the tail just below tau:
-        // exp(z band / sigma) = 3.3 at the 25th best of 175k isotropic rows) into a 4,096-slot buffer — r = 57 overflowed
-        // at k = 25 and fell back to the exact scan (profiles/r04_filter_gmax_ab.log); 24, capped by 900 / k, keeps a
-        // factor of 4.5 in hand and lets 1M rows take two rounds instead of three (153 -> 138 us at k = 10)
-        // ... except where ONE round reaches the last row: up to four queries over at most min(60, 970 / k) x 3,072 rows expect
-        // ~k r 3.3 <= 3,200 candidates, and should the buffer overflow after all, the exact rerun behind it costs what a
-        // streaming scan of so few rows costs (~100 us), not the 2.2 ms of a 10M-row corpus: one query over 100,000 rows 77 -> 65 us
-        // at k = 10, 84 -> 74 at k = 20, 86 -> 78 at k = 25.  (Five to ten queries gain 5 % at 100,000 rows and lose 7 % at
-        // 184,000 — their candidates multiply the refine: they keep the capped plan; profiles/r04_filter_one_round_ab.log.)
-        static const double g1_env = [] { const char* e = cs_lab_env("CS_FILTER_G1MAX"); return e ? std::atof(e) : 60.0; }();
-        static const uint32_t g1_maxq = [] { const char* e = cs_lab_env("CS_FILTER_G1_MAXQ"); return e ? (uint32_t)std::atoi(e) : 4u; }();
-        static const double g1_cand = [] { const char* e = cs_lab_env("CS_FILTER_G1_CAND"); return e ? std::atof(e) : 970.0; }();
-        const double g1 = std::min(g1_env, g1_cand / (double)k);  // 60 up to k = 16, 38.8 at k = 25, no more than the cap of 24 from k = 40
-        const bool one_round = nq <= g1_maxq && g1 > 24.0 && (double)n_rows <= g1 * (double)phase;
-        const double gshort = one_round ? g1 : std::min(24.0, 900.0 / (double)k);
-        const double gmax = gmax_env > 1.0 ? gmax_env : (k >= 48 ? 5.5 : gshort), span = (double)n_rows / (double)phase;
-        const double nph = std::ceil(std::log(span) / std::log(gmax) - 1e-9);
-        ratio = std::pow(span, 1.0 / (nph < 1.0 ? 1.0 : nph));
-    }
-    do {
-        const uint64_t lo = done, hi = done + phase;
-        const bool first = lo == 0;  // phase 0 goes straight to the refine (rescore_keys_kernel, first_rows)
-        if (hi > lo && !first) {
-            if (use_q8) {
-                static int cus8 = 0;  // one persistent block per CU (grid rounded down to whole XCD octets)
-                if (!cus8) {
-                    int dev = 0, n = 0;
-                    if (hipGetDevice(&dev) == hipSuccess &&
-                        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n >= 8)
-                        cus8 = n / 8 * 8;
-                    else
-                        cus8 = 256;
-                }
-                const uint64_t q_hi = hi < q8->rows ? hi : q8->rows;  // lo is a multiple of 1024
-                if (q_hi > lo && nq > q8_rw_max) {
-                    const uint32_t mt2 = (uint32_t)((q_hi - lo + UF2_BM - 1) / UF2_BM), nt2 = (nq + UF2_BN - 1) / UF2_BN;
-                    const uint32_t slots = sh_grid_blocks(mt2, nt2);
-                    const uint32_t grid = std::min<uint32_t>(slots, (uint32_t)cus8);  // a multiple of 8: a block stays on its XCD slot
-                    hipLaunchKernelGGL(score_filter256p_kernel<true>, dim3(grid), dim3(512), UF2_LDS, stream,
-                                       reinterpret_cast<const _Float16*>(q8->d_q8), lo, q_hi, dim / 128,
-                                       reinterpret_cast<const _Float16*>(qw.d_q8q), nq, st.d_tau, d_dead, cand, st.d_cnt, cap,
-                                       slots, q8_slack(dim), q8->d_tmeta, qw.d_qmeta);
-                    CS_HIP(hipGetLastError());
-                } else if (q_hi > lo && J == 3 && nq > 128 && rq8_on) {
-                    // many queries at dim 384: eight waves over 256 resident queries, corpus fragments through registers
-                    if constexpr (J == 3) {
-                        const uint32_t qtiles = (nq + 255) / 256;
-                        const uint64_t units = ((q_hi - lo) / 128 + 1) / 2;
-                        uint64_t slots = (units + 7) / 8 * qtiles;  // per XCD
-                        if (slots > (uint64_t)cus8 / 8) slots = (uint64_t)cus8 / 8;
-                        if (slots < qtiles) slots = qtiles;
-                        const uint32_t blocks = (uint32_t)slots * 8;
-                        if (qtiles == 1)
-                            hipLaunchKernelGGL((score_filter_rq8_kernel<8, 3, true>), dim3(blocks), dim3(512), (kRq8Lds<8, 3>), stream,
-                                               q8->d_q8, q8->d_tmeta, lo, q_hi, qw.d_q8q, qw.d_qmeta, nq, st.d_tau, d_dead, cand,
-                                               st.d_cnt, cap, qtiles, q8_slack(dim));
-                        else
-                            hipLaunchKernelGGL((score_filter_rq8_kernel<8, 3, false>), dim3(blocks), dim3(512), (kRq8Lds<8, 3>), stream,
-                                               q8->d_q8, q8->d_tmeta, lo, q_hi, qw.d_q8q, qw.d_qmeta, nq, st.d_tau, d_dead, cand,
-                                               st.d_cnt, cap, qtiles, q8_slack(dim));
-                        CS_HIP(hipGetLastError());
-                    }
-                } else if (q_hi > lo) {
-                    // above 128 queries at dim 384: 256 resident queries per block — half the query tiles re-reading the
-                    // corpus through L2 (1,000 queries over 10M rows: 7.21 -> 5.95 ms; 129: 1.97 -> 1.61); "0" = A/B
-                    static const bool rw8_256 = [] {
-                        const char* e = cs_lab_env("CS_FILTER_INT8_RW256");
-                        return !(e && e[0] == '0');
-                    }();
-                    const uint32_t per = nq <= 32 ? 32 : (nq <= 64 || J > 6) ? 64 : (J == 3 && rw8_256 && nq > 128) ? 256 : 128;
-                    const uint32_t qtiles = (nq + per - 1) / per;
-                    const uint64_t tiles = (q_hi - lo) / 128;
-                    uint64_t slots = (tiles + 7) / 8 * qtiles;  // per XCD
-                    if (slots > (uint64_t)cus8 / 8) slots = (uint64_t)cus8 / 8;
-                    if (slots < qtiles) slots = qtiles;
-                    const uint32_t blocks = (uint32_t)slots * 8;
-                    static const uint32_t nt_stream8 = [] {
-                        const char* e = cs_lab_env("CS_FILTER_NT");
-                        return (uint32_t)!(e && e[0] == '0');
-                    }();
-#define CS_RW8_LAUNCH(NQT_)                                                                                        \
-    hipLaunchKernelGGL((score_filter_rw8_kernel<NQT_, J>), dim3(blocks), dim3(256), (Rw8Geom<NQT_, J>::LDS_ALL), stream, \
-                       q8->d_q8, q8->d_tmeta, lo, q_hi, qw.d_q8q, qw.d_qmeta, nq, st.d_tau, d_dead, cand, st.d_cnt, cap, \
-                       qtiles, nt_stream8, q8_slack(dim))
-#define CS_RW8_LAUNCH2(NQT_)                                                                                       \
-    hipLaunchKernelGGL((score_filter_rw8_kernel<NQT_, J, true>), dim3(blocks), dim3(256), (Rw8GeomT<NQT_, J, true>::LDS_ALL), \
-                       stream, q8->d_q8, q8->d_tmeta, lo, q_hi, qw.d_q8q_hi, qw.d_qmeta, nq, st.d_tau, d_dead, cand, st.d_cnt, \
-                       cap, qtiles, nt_stream8, q8_slack(dim), qw.d_q8q_lo)
-                    if (per <= 64 && two_planes) {
-                        if constexpr (J <= 6) { if (per == 32) CS_RW8_LAUNCH2(1); else CS_RW8_LAUNCH2(2); }
-                    } else if (per == 32) CS_RW8_LAUNCH(1);
-                    else if (per == 64) CS_RW8_LAUNCH(2);
-                    else if constexpr (J == 3) { if (per == 256) CS_RW8_LAUNCH(8); else CS_RW8_LAUNCH(4); }
-                    else if constexpr (J <= 6) CS_RW8_LAUNCH(4);
-#undef CS_RW8_LAUNCH
-#undef CS_RW8_LAUNCH2
-                    CS_HIP(hipGetLastError());
-                }
-                const uint64_t t_lo = lo > q8->rows ? lo : q8->rows;
-                if (hi > t_lo)  // fewer than 128 rows behind the last complete tile
-                    hipLaunchKernelGGL(tail_candidates_kernel, dim3(nq), dim3(128), 0, stream, t_lo, hi, d_dead, cand, st.d_cnt, cap);
-            } else if (small) {
-                static int cus = 0;  // one persistent block per CU (grid rounded down to whole XCD octets)
-                if (!cus) {
-                    int dev = 0, n = 0;
-                    if (hipGetDevice(&dev) == hipSuccess &&
-                        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n >= 8)
-                        cus = n / 8 * 8;
-                    else
-                        cus = 256;
-                }
-                const uint32_t per = nq <= 32 ? 32 : nq <= 64 ? 64 : 128;
-                const uint32_t qtiles = (nq + per - 1) / per;
-                const uint64_t tiles = (hi - lo + 127) / 128;
-                // row groups needed: one per corpus tile at most
-                uint64_t slots = (tiles + 7) / 8 * qtiles;  // per XCD
-                if (slots > (uint64_t)cus / 8) slots = (uint64_t)cus / 8;
-                if (slots < qtiles) slots = qtiles;
-                const uint32_t blocks = (uint32_t)slots * 8;
-                static const uint32_t nt_stream = [] {
-                    const char* e = cs_lab_env("CS_FILTER_NT");  // "0": default cache policy on the corpus stream
-                    return (uint32_t)!(e && e[0] == '0');
-                }();
-#define CS_RW_LAUNCH(NQT_)                                                                                   \
-    do {                                                                                                     \
-        using RwG = RwGeom<NQT_, 2 * J>;                                                                     \
-        constexpr size_t rw_lds = RwG::LDS_ALL;                                                              \
-        hipLaunchKernelGGL((score_filter_rw_kernel<NQT_, 2 * J>), dim3(blocks), dim3(256), rw_lds, stream, d_split, lo, \
-                           hi, qw.d_qsplit, nq, st.d_tau, d_dead, cand, st.d_cnt, cap, qtiles, nt_stream, margin); \
-    } while (0)
-                if constexpr (J == 3) {
-                    if (per == 32) CS_RW_LAUNCH(1);
-                    else if (per == 64) CS_RW_LAUNCH(2);
-                    else CS_RW_LAUNCH(4);
-                } else if constexpr (J == 6) {
-                    if (per == 32) CS_RW_LAUNCH(1);
-                    else CS_RW_LAUNCH(2);
-                } else {
-                    CS_RW_LAUNCH(1);
-                }
-#undef CS_RW_LAUNCH
-            } else if (wide) {
-                const uint32_t mt2 = (uint32_t)((hi - lo + UF2_BM - 1) / UF2_BM), nt2 = (nq + UF2_BN - 1) / UF2_BN;
-                static int cus = 0;
-                if (!cus) {
-                    int dev = 0;
-                    hipDeviceProp_t prop;
-                    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-                        cus = prop.multiProcessorCount;
-                    if (cus <= 0) cus = 256;
-                }
-                const uint32_t slots = sh_grid_blocks(mt2, nt2);
-                const uint32_t grid = std::min<uint32_t>(slots, ((uint32_t)cus + 7) / 8 * 8);  // a multiple of 8: a block stays on its XCD slot
-                hipLaunchKernelGGL(score_filter256p_kernel<false>, dim3(grid), dim3(512), UF2_LDS, stream, d_split, lo, hi,
-                                   dim / 64, qw.d_qsplit, nq, st.d_tau, d_dead, cand, st.d_cnt, cap, slots, margin,
-                                   (const float4*)nullptr, (const float4*)nullptr);
-            } else {
-                const uint32_t mtiles = (uint32_t)((hi - lo + SH_BM - 1) / SH_BM);
-                hipLaunchKernelGGL(score_filter_kernel, dim3(sh_grid_blocks(mtiles, ntiles)), dim3(256), SH_LDS_BYTES,
-                                   stream, d_split, lo, hi, dim / 64, qw.d_qsplit, nq, st.d_tau, d_dead, cand, st.d_cnt,
-                                   cap, margin);
-            }
-            CS_HIP(hipGetLastError());
-        }
-        done = hi;
-        const bool last = done >= n_rows;
-        // refine: exact keys in place (each query's rows spread over rk_blocks CUs), then the select
-        // phase 0 of a few queries: its 3,072 rows in ONE round of 32 rows per block (96 blocks per query instead of three
-        // rounds on 32: the phase is a dependent launch in front of every filter search, 12 -> 7 us for one query)
-        static const uint32_t rk0_env = [] { const char* e = cs_lab_env("CS_FILTER_PHASE0_BLOCKS"); return e ? (uint32_t)std::atoi(e) : 96u; }();
-        const uint32_t rk_now = (first && nq * rk0_env <= 1024 && rk0_env > rk_blocks) ? rk0_env : rk_blocks;  // up to ten queries
-        hipLaunchKernelGGL(rescore_keys_kernel<J>, dim3(rk_now, nq), dim3(RK_THREADS), 0, stream, d_corpus, d_queries,
-                           qw.d_qmag, st.d_cand, st.d_cnt, cap, id_base, first ? (uint32_t)hi : 0u, d_dead);
+    const uint32_t nt = kn.nt;
+    for (uint32_t p = 0; p < plan.nphases; ++p) {
+        const FilterPhase& ph = plan.phase[p];
+        for_each_filter<J>([&](auto i) {
+            constexpr FilterInst f = filter_insts<J>()[i];
+            if (ph.kernel != f.kernel || ph.nqt != f.nqt) return;
+            const auto k = filter_fn<J, i>();
+            using K = FilterKernel;
+            if constexpr (f.kernel == K::F16Tile128)
+                hipLaunchKernelGGL(k.fn, dim3(ph.grid), dim3(256), k.lds, stream, d_split, ph.lo, ph.hi, dim / 64, qw.d_qsplit, nq,
+                                   st.d_tau, d_dead, cand, st.d_cnt, cap, margin);
+            else if constexpr (f.kernel == K::F16Tile256)
+                hipLaunchKernelGGL(k.fn, dim3(ph.grid), dim3(512), k.lds, stream, d_split, ph.lo, ph.hi, dim / 64, qw.d_qsplit, nq,
+                                   st.d_tau, d_dead, cand, st.d_cnt, cap, ph.slots, margin, (const float4*)nullptr,
+                                   (const float4*)nullptr);
+            else if constexpr (f.kernel == K::Q8Tile256)
+                hipLaunchKernelGGL(k.fn, dim3(ph.grid), dim3(512), k.lds, stream, reinterpret_cast<const _Float16*>(q8->d_q8), ph.lo,
+                                   ph.filter_hi, dim / 128, reinterpret_cast<const _Float16*>(qw.d_q8q), nq, st.d_tau, d_dead,
+                                   cand, st.d_cnt, cap, ph.slots, q8_slack(dim), q8->d_tmeta, qw.d_qmeta);
+            else if constexpr (f.kernel == K::F16Rw)
+                hipLaunchKernelGGL(k.fn, dim3(ph.grid), dim3(256), k.lds, stream, d_split, ph.lo, ph.hi, qw.d_qsplit, nq, st.d_tau,
+                                   d_dead, cand, st.d_cnt, cap, ph.qtiles, nt, margin);
+            else if constexpr (f.kernel == K::Q8Rw || f.kernel == K::Q8Rw2)
+                hipLaunchKernelGGL(k.fn, dim3(ph.grid), dim3(256), k.lds, stream, q8->d_q8, q8->d_tmeta, ph.lo, ph.filter_hi,
+                                   f.kernel == K::Q8Rw2 ? qw.d_q8q_hi : qw.d_q8q, qw.d_qmeta, nq, st.d_tau, d_dead, cand,
+                                   st.d_cnt, cap, ph.qtiles, nt, q8_slack(dim), f.kernel == K::Q8Rw2 ? qw.d_q8q_lo : nullptr);
+            else
+                hipLaunchKernelGGL(k.fn, dim3(ph.grid), dim3(512), k.lds, stream, q8->d_q8, q8->d_tmeta, ph.lo, ph.filter_hi,
+                                   qw.d_q8q, qw.d_qmeta, nq, st.d_tau, d_dead, cand, st.d_cnt, cap, ph.qtiles, q8_slack(dim));
+        });
+        if (ph.tail_hi > ph.tail_lo)  // fewer than 128 rows behind the int8 copy's last complete tile
+            hipLaunchKernelGGL(tail_candidates_kernel, dim3(nq), dim3(128), 0, stream, ph.tail_lo, ph.tail_hi, d_dead, cand,
+                               st.d_cnt, cap);
+        const bool first = ph.lo == 0, last = ph.hi >= n_rows;
+        if (ph.hi > ph.lo && !first) CS_HIP(hipGetLastError());
+        hipLaunchKernelGGL(rescore_keys_kernel<J>, dim3(ph.rk_blocks, nq), dim3(RK_THREADS), 0, stream, d_corpus, d_queries,
+                           qw.d_qmag, st.d_cand, st.d_cnt, cap, id_base, first ? (uint32_t)ph.hi : 0u, d_dead);
         CS_HIP(hipGetLastError());
         CS_TRY(launch_select_candidates(st, nq, cap, k, last, d_out_keys, d_out_cos, d_out_ids, d_out_counts, stream));
-        if (fixed_growth) {
-            // (round 3's rule: the phase right behind phase 0 takes 16 x the rows seen for short lists, growth + 1 otherwise)
-            const uint32_t growth1 = growth1_env > 1 ? growth1_env : (k < 48 && growth_env <= 0 ? 16u : growth + 1);
-            phase = done * (first ? growth1 - 1 : growth);
-        } else {
-            // next boundary of the geometric plan, on the filter kernels' 1,024-row granule
-            uint64_t next = (uint64_t)std::ceil((double)done * ratio);
-            next = (next + 1023) / 1024 * 1024;
-            if (next <= done) next = done + 1024;
-            phase = next - done;
-            if ((double)(n_rows - done) < (double)phase * 1.25) phase = n_rows - done;  // no sliver of a last phase
-        }
-        if (phase > n_rows - done) phase = n_rows - done;
-    } while (done < n_rows);
+    }
     return CS_OK;
 }
 
@@ -1780,13 +1620,10 @@ int32_t launch_scan_split(const BatchedState& st, const SplitQueryWs& qw, const 
                           const _Float16* d_split, uint64_t n_rows, uint32_t dim, const float* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_dead,
                           RowIds id_base, uint64_t* d_out_keys, float* d_out_cos, uint32_t* d_out_ids,
                           uint32_t* d_out_counts, hipStream_t stream, float margin, const Q8View* q8) {
-#define CS_SPLIT_ARGS st, qw, d_corpus, d_split, n_rows, d_queries, nq, k, d_dead, id_base, d_out_keys, \
-                      d_out_cos, d_out_ids, d_out_counts, stream, margin, q8
-    if (dim == 384) return scan_split_impl<3>(CS_SPLIT_ARGS);
-    if (dim == 768) return scan_split_impl<6>(CS_SPLIT_ARGS);
-    if (dim == 1024) return scan_split_impl<8>(CS_SPLIT_ARGS);
-#undef CS_SPLIT_ARGS
-    return fail(CS_ERR_UNSUPPORTED, "split scan supports dim 384/768/1024, got %u", dim);
+    const auto impl = dim == 384 ? scan_split_impl<3> : dim == 768 ? scan_split_impl<6> : dim == 1024 ? scan_split_impl<8> : nullptr;
+    if (!impl) return fail(CS_ERR_UNSUPPORTED, "split scan supports dim 384/768/1024, got %u", dim);
+    return impl(st, qw, d_corpus, d_split, n_rows, d_queries, nq, k, d_dead, id_base, d_out_keys, d_out_cos, d_out_ids,
+                d_out_counts, stream, margin, q8);
 }
 
 }  // namespace cs
