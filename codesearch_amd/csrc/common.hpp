@@ -127,6 +127,20 @@ __host__ __device__ __forceinline__ float key_cos(uint64_t key) {
 }
 __host__ __device__ __forceinline__ uint32_t key_id(uint64_t key) { return ~(uint32_t)key; }
 
+// Host side of the packed-key outputs: nq best-first lists of k keys -> cosines and ids (an empty slot, key 0, gives 0 and
+// 0xFFFFFFFF) and, when `out_counts` is given, each list's filled slots.
+inline void unpack_keys(const uint64_t* keys, uint32_t nq, uint32_t k, float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
+    for (uint32_t q = 0; q < nq; ++q) {
+        uint32_t c = 0;
+        for (size_t j = (size_t)q * k; j < (size_t)(q + 1) * k; ++j) {
+            c += keys[j] != 0;
+            out_cos[j] = keys[j] ? key_cos(keys[j]) : 0.0f;
+            out_ids[j] = keys[j] ? key_id(keys[j]) : 0xFFFFFFFFu;
+        }
+        if (out_counts) out_counts[q] = c;
+    }
+}
+
 // tokenizer.cpp: per-text id lists ([CLS] ... [SEP], truncated to max_length), texts in parallel
 void tokenize_texts(const cs_tokenizer* t, const char* utf8, const uint64_t* offsets, uint32_t n,
                     uint32_t max_length, std::vector<std::vector<int32_t>>& out);

@@ -36,27 +36,49 @@ struct EventTriple {
     hipEvent_t e0, e1, e2;
 };
 
+// Frees p (pinned host memory when `pinned`) and, for n > 0, allocates n elements in its place: null on failure.
+template <class T>
+hipError_t realloc_buf(T*& p, size_t n, bool pinned = false) {
+    if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+    if (!n) return hipSuccess;
+    return pinned ? hipHostMalloc(&p, n * sizeof(T)) : hipMalloc(&p, n * sizeof(T));
+}
+template <class... T>
+void free_bufs(bool pinned, T*&... p) {
+    ((void)realloc_buf(p, 0, pinned), ...);
+}
+// p holds at least n elements afterwards; cap = how many it holds (0 after a failed allocation)
+template <class T>
+int32_t reserve_buf(T*& p, size_t& cap, size_t n, bool pinned = false) {
+    if (n <= cap) return CS_OK;
+    cap = 0;
+    CS_HIP(realloc_buf(p, n, pinned));
+    cap = n;
+    return CS_OK;
+}
+
 // Per-call scratch.  Host-API calls borrow one from the pool (own stream); device-API
 // calls use the one bound to the caller's stream (stream order makes reuse safe).
 struct Workspace {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     uint64_t* d_partial = nullptr; size_t partial_cap = 0;
-    uint64_t* d_tmp_a = nullptr; uint64_t* d_tmp_b = nullptr; size_t tmp_cap = 0;
-    ScanPrime prime; size_t prime_max_cap = 0, prime_nq_cap = 0;
+    uint64_t* d_tmp_a = nullptr; uint64_t* d_tmp_b = nullptr; size_t tmp_a_cap = 0, tmp_b_cap = 0;
+    ScanPrime prime; size_t wave_max_cap = 0, done_cap = 0, floor_cap = 0;
     float* d_queries = nullptr; size_t q_cap = 0;
-    uint64_t* d_keys = nullptr; float* d_cos = nullptr; uint32_t* d_ids = nullptr; size_t out_cap = 0;
-    uint32_t* d_counts = nullptr; size_t cnt_cap = 0;
+    uint64_t* d_keys = nullptr; float* d_cos = nullptr; uint32_t* d_ids = nullptr; size_t keys_cap = 0, cos_cap = 0, ids_cap = 0;
+    uint32_t* d_counts = nullptr; size_t counts_cap = 0;
     // pinned staging of the host-buffer API: queries in, packed keys out (ONE copy each way; the host
     // unpacks cosine / id / count from the keys — three more small D2H copies cost ~8 us apiece)
     float* h_queries = nullptr; size_t h_q_cap = 0;
-    uint64_t* h_keys = nullptr; size_t h_out_cap = 0;
+    uint64_t* h_keys = nullptr; size_t h_keys_cap = 0;
     uint32_t* h_variant_meta = nullptr;  // pinned: [0] count, [1] high-confidence flag (cs_index_search_variants)
     std::vector<EventTriple> free_events;
     BatchedState bs;
-    size_t bs_nq = 0, bs_cand = 0, bs_carry = 0;
+    size_t cnt_cap = 0, tau_cap = 0, cand_cap = 0, carry_cap = 0;
     SplitQueryWs qw;
-    size_t qw_elems = 0, qw_nq = 0, q8_elems = 0;
+    size_t qsplit_cap = 0, qmag_cap = 0, qmeta_cap = 0, q8_elems = 0;
     uint32_t* h_overflow = nullptr;
     uint32_t mirror_seen = 0;  // value of h_overflow[3] already accounted for
     bool last_via_q8 = false;  // the previous filter search on this workspace read the int8 copy (strike bookkeeping)
@@ -65,172 +87,76 @@ struct Workspace {
     // *q8_ok = false (never an error) when they do not fit: the caller filters on the f16 copy instead
     int32_t reserve_split_queries(uint32_t nq, uint32_t dim, bool want_q8, bool* q8_ok) {
         const size_t elems = (size_t)nq * dim;
-        *q8_ok = false;
-        if (elems > qw_elems) {
-            if (qw.d_qsplit) (void)hipFree(qw.d_qsplit);
-            qw.d_qsplit = nullptr; qw_elems = 0;
-            CS_HIP(hipMalloc(&qw.d_qsplit, elems * sizeof(_Float16)));
-            qw_elems = elems;
-        }
+        CS_TRY(reserve_buf(qw.d_qsplit, qsplit_cap, elems));
         if (want_q8 && elems > q8_elems) {
-            if (qw.d_q8q) (void)hipFree(qw.d_q8q);
-            if (qw.d_q8q_hi) (void)hipFree(qw.d_q8q_hi);
-            qw.d_q8q = qw.d_q8q_hi = qw.d_q8q_lo = nullptr; q8_elems = 0;
-            if (hipMalloc(&qw.d_q8q, elems) != hipSuccess || hipMalloc(&qw.d_q8q_hi, 2 * elems) != hipSuccess) {
-                (void)hipGetLastError();
-                if (qw.d_q8q) (void)hipFree(qw.d_q8q);
-                qw.d_q8q = nullptr;
-            } else {
+            q8_elems = 0;
+            qw.d_q8q_lo = nullptr;
+            if (realloc_buf(qw.d_q8q, elems) == hipSuccess && realloc_buf(qw.d_q8q_hi, 2 * elems) == hipSuccess) {
                 qw.d_q8q_lo = qw.d_q8q_hi + elems;
                 q8_elems = elems;
+            } else {
+                (void)hipGetLastError();
+                free_bufs(false, qw.d_q8q, qw.d_q8q_hi);
             }
         }
         *q8_ok = want_q8 && elems <= q8_elems;
-        if (nq > qw_nq) {
-            if (qw.d_qmag) (void)hipFree(qw.d_qmag);
-            if (qw.d_qmeta) (void)hipFree(qw.d_qmeta);
-            qw.d_qmag = nullptr; qw.d_qmeta = nullptr; qw_nq = 0;
-            CS_HIP(hipMalloc(&qw.d_qmag, nq * sizeof(float)));
-            CS_HIP(hipMalloc(&qw.d_qmeta, 4 * (size_t)nq * sizeof(float4)));
-            qw_nq = nq;
-        }
-        return CS_OK;
+        CS_TRY(reserve_buf(qw.d_qmag, qmag_cap, nq));
+        return reserve_buf(qw.d_qmeta, qmeta_cap, 4 * (size_t)nq);
     }
 
     int32_t reserve_prime(const ScanPlan& pp, uint32_t nq) {
-        const size_t nmax = (size_t)nq * pp.blocks * 4;
-        if (nmax > prime_max_cap) {
-            if (prime.d_wave_max) (void)hipFree(prime.d_wave_max);
-            prime.d_wave_max = nullptr; prime_max_cap = 0;
-            CS_HIP(hipMalloc(&prime.d_wave_max, nmax * sizeof(float)));
-            prime_max_cap = nmax;
-        }
-        if (nq > prime_nq_cap) {  // passes <= nq
-            if (prime.d_done) (void)hipFree(prime.d_done);
-            if (prime.d_floor) (void)hipFree(prime.d_floor);
-            prime.d_done = nullptr; prime.d_floor = nullptr; prime_nq_cap = 0;
-            CS_HIP(hipMalloc(&prime.d_done, nq * sizeof(uint32_t)));
-            CS_HIP(hipMalloc(&prime.d_floor, nq * sizeof(float)));
+        CS_TRY(reserve_buf(prime.d_wave_max, wave_max_cap, (size_t)nq * pp.blocks * 4));
+        if (nq > done_cap) {  // passes <= nq
+            CS_TRY(reserve_buf(prime.d_done, done_cap, nq));
             CS_HIP(hipMemset(prime.d_done, 0, nq * sizeof(uint32_t)));
-            prime_nq_cap = nq;
         }
-        return CS_OK;
+        return reserve_buf(prime.d_floor, floor_cap, nq);
     }
 
     int32_t reserve_batched(uint32_t nq, uint32_t k) {
-        const size_t cand = (size_t)nq * batched_cap(k), carry = (size_t)nq * k;
         if (!h_overflow) {
-            CS_HIP(hipHostMalloc(&h_overflow, 4 * sizeof(uint32_t)));
+            CS_HIP(realloc_buf(h_overflow, 4, true));
             h_overflow[3] = 0;
             bs.h_mirror = h_overflow + 3;  // written by the device (scan.hpp BatchedState::h_mirror)
         }
         if (!bs.d_overflow) {  // [0] this search, [1] sticky, [2] overflowed searches so far (scan.hpp BatchedState)
-            CS_HIP(hipMalloc(&bs.d_overflow, 4 * sizeof(uint32_t)));
+            CS_HIP(realloc_buf(bs.d_overflow, 4));
             CS_HIP(hipMemset(bs.d_overflow, 0, 4 * sizeof(uint32_t)));
         }
-        if (nq > bs_nq) {
-            if (bs.d_cnt) (void)hipFree(bs.d_cnt);
-            if (bs.d_tau) (void)hipFree(bs.d_tau);
-            bs.d_cnt = nullptr; bs.d_tau = nullptr; bs_nq = 0;
-            CS_HIP(hipMalloc(&bs.d_cnt, (size_t)nq * kCntStride * sizeof(uint32_t)));
-            CS_HIP(hipMalloc(&bs.d_tau, nq * sizeof(float)));
-            bs_nq = nq;
-        }
-        if (cand > bs_cand) {
-            if (bs.d_cand) (void)hipFree(bs.d_cand);
-            bs.d_cand = nullptr; bs_cand = 0;
-            CS_HIP(hipMalloc(&bs.d_cand, cand * sizeof(uint64_t)));
-            bs_cand = cand;
-        }
-        if (carry > bs_carry) {
-            if (bs.d_carry) (void)hipFree(bs.d_carry);
-            bs.d_carry = nullptr; bs_carry = 0;
-            CS_HIP(hipMalloc(&bs.d_carry, carry * sizeof(uint64_t)));
-            bs_carry = carry;
-        }
-        return CS_OK;
+        CS_TRY(reserve_buf(bs.d_cnt, cnt_cap, (size_t)nq * kCntStride));
+        CS_TRY(reserve_buf(bs.d_tau, tau_cap, nq));
+        CS_TRY(reserve_buf(bs.d_cand, cand_cap, (size_t)nq * batched_cap(k)));
+        return reserve_buf(bs.d_carry, carry_cap, (size_t)nq * k);
     }
 
     int32_t reserve(const ScanPlan& p, uint32_t nq, uint32_t dim, uint32_t k, bool host_io) {
-        if (p.partial_keys > partial_cap) {
-            if (d_partial) (void)hipFree(d_partial);
-            d_partial = nullptr; partial_cap = 0;
-            CS_HIP(hipMalloc(&d_partial, p.partial_keys * sizeof(uint64_t)));
-            partial_cap = p.partial_keys;
-        }
-        if (p.merge_keys > tmp_cap) {
-            if (d_tmp_a) (void)hipFree(d_tmp_a);
-            if (d_tmp_b) (void)hipFree(d_tmp_b);
-            d_tmp_a = d_tmp_b = nullptr; tmp_cap = 0;
-            CS_HIP(hipMalloc(&d_tmp_a, p.merge_keys * sizeof(uint64_t)));
-            CS_HIP(hipMalloc(&d_tmp_b, p.merge_keys * sizeof(uint64_t)));
-            tmp_cap = p.merge_keys;
-        }
+        CS_TRY(reserve_buf(d_partial, partial_cap, p.partial_keys));
+        CS_TRY(reserve_buf(d_tmp_a, tmp_a_cap, p.merge_keys));
+        CS_TRY(reserve_buf(d_tmp_b, tmp_b_cap, p.merge_keys));
         if (!host_io) return CS_OK;
         const size_t qn = (size_t)nq * dim, on = (size_t)nq * k;
-        if (qn > q_cap) {
-            if (d_queries) (void)hipFree(d_queries);
-            d_queries = nullptr; q_cap = 0;
-            CS_HIP(hipMalloc(&d_queries, qn * sizeof(float)));
-            q_cap = qn;
-        }
-        if (on > out_cap) {
-            if (d_keys) (void)hipFree(d_keys);
-            if (d_cos) (void)hipFree(d_cos);
-            if (d_ids) (void)hipFree(d_ids);
-            d_keys = nullptr; d_cos = nullptr; d_ids = nullptr; out_cap = 0;
-            CS_HIP(hipMalloc(&d_keys, on * sizeof(uint64_t)));
-            CS_HIP(hipMalloc(&d_cos, on * sizeof(float)));
-            CS_HIP(hipMalloc(&d_ids, on * sizeof(uint32_t)));
-            out_cap = on;
-        }
-        if (nq > cnt_cap) {
-            if (d_counts) (void)hipFree(d_counts);
-            d_counts = nullptr; cnt_cap = 0;
-            CS_HIP(hipMalloc(&d_counts, nq * sizeof(uint32_t)));
-            cnt_cap = nq;
-        }
-        if (on > h_out_cap) {
-            if (h_keys) (void)hipHostFree(h_keys);
-            h_keys = nullptr; h_out_cap = 0;
-            CS_HIP(hipHostMalloc(&h_keys, on * sizeof(uint64_t)));
-            h_out_cap = on;
-        }
-        if ((size_t)nq * dim > h_q_cap) {
-            if (h_queries) (void)hipHostFree(h_queries);
-            h_queries = nullptr; h_q_cap = 0;
-            CS_HIP(hipHostMalloc(&h_queries, (size_t)nq * dim * sizeof(float)));
-            h_q_cap = (size_t)nq * dim;
-        }
+        CS_TRY(reserve_buf(d_queries, q_cap, qn));
+        CS_TRY(reserve_buf(d_keys, keys_cap, on));
+        CS_TRY(reserve_buf(d_cos, cos_cap, on));
+        CS_TRY(reserve_buf(d_ids, ids_cap, on));
+        CS_TRY(reserve_buf(d_counts, counts_cap, nq));
+        CS_TRY(reserve_buf(h_keys, h_keys_cap, on, true));
+        return reserve_buf(h_queries, h_q_cap, qn, true);
+    }
+
+    // the overflow word of the search just enqueued (host-buffer API: it synchronises for its results anyway)
+    int32_t read_overflow(hipStream_t s, bool* overflow) {
+        CS_HIP(hipMemcpyAsync(h_overflow, bs.d_overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        CS_HIP(hipStreamSynchronize(s));
+        *overflow = *h_overflow != 0;
         return CS_OK;
     }
 
     void release_all() {
-        if (d_partial) (void)hipFree(d_partial);
-        if (prime.d_wave_max) (void)hipFree(prime.d_wave_max);
-        if (prime.d_done) (void)hipFree(prime.d_done);
-        if (prime.d_floor) (void)hipFree(prime.d_floor);
-        if (d_tmp_a) (void)hipFree(d_tmp_a);
-        if (d_tmp_b) (void)hipFree(d_tmp_b);
-        if (d_queries) (void)hipFree(d_queries);
-        if (d_keys) (void)hipFree(d_keys);
-        if (d_cos) (void)hipFree(d_cos);
-        if (d_ids) (void)hipFree(d_ids);
-        if (d_counts) (void)hipFree(d_counts);
-        if (h_keys) (void)hipHostFree(h_keys);
-        if (h_queries) (void)hipHostFree(h_queries);
-        if (h_overflow) (void)hipHostFree(h_overflow);
-        if (h_variant_meta) (void)hipHostFree(h_variant_meta);
-        if (bs.d_cand) (void)hipFree(bs.d_cand);
-        if (bs.d_cnt) (void)hipFree(bs.d_cnt);
-        if (bs.d_tau) (void)hipFree(bs.d_tau);
-        if (bs.d_carry) (void)hipFree(bs.d_carry);
-        if (bs.d_overflow) (void)hipFree(bs.d_overflow);
-        if (qw.d_qsplit) (void)hipFree(qw.d_qsplit);
-        if (qw.d_qmag) (void)hipFree(qw.d_qmag);
-        if (qw.d_q8q) (void)hipFree(qw.d_q8q);
-        if (qw.d_q8q_hi) (void)hipFree(qw.d_q8q_hi);
-        if (qw.d_qmeta) (void)hipFree(qw.d_qmeta);
+        free_bufs(false, d_partial, d_tmp_a, d_tmp_b, d_queries, d_keys, d_cos, d_ids, d_counts, prime.d_wave_max, prime.d_done,
+                  prime.d_floor, bs.d_cand, bs.d_cnt, bs.d_tau, bs.d_carry, bs.d_overflow, qw.d_qsplit, qw.d_qmag, qw.d_q8q,
+                  qw.d_q8q_hi, qw.d_qmeta);
+        free_bufs(true, h_keys, h_queries, h_overflow, h_variant_meta);
         for (auto& t : free_events) {
             (void)hipEventDestroy(t.e0); (void)hipEventDestroy(t.e1); (void)hipEventDestroy(t.e2);
         }
@@ -294,32 +220,7 @@ struct cs_index {
     float q8_spread = 0.0f;      // median over tiles of max |u - mu| * sqrt(dim) at the last build (isotropic rows: ~4.4)
     float q8_max_spread = 7.0f;  // CS_FILTER_INT8_MAX_SPREAD
     float filter_margin = 0.0f;  // scan_filter.hip: bound of the f16 filter's error for this dim
-    int filter_min_q = 2;  // query count from which the f16 filter + exact refine path is used
-    uint32_t single_filter_min_k = 100;  // ... and one query too from this k on, over >= 2M rows (0 = never)
-    // One query: CS_ROUTE_COST (default) takes the filter over >= single_int8_min_rows rows whenever the int8 copy serves
-    // (same bits, 0.66 vs 2.16 ms over 10M x 384 at k = 10: the filter streams a quarter of the bytes), and from
-    // single_filter_min_k on over >= single_filter_min_rows rows with the f16 copy; CS_ROUTE_STREAM always runs the f32 streaming scan (the north-star
-    // kernel: bench.py selects it for `value`); CS_ROUTE_FILTER takes the filter whenever a copy can serve.
-    int single_route = CS_ROUTE_COST;
-    uint64_t single_filter_min_rows = 2000000;  // ... with the f16 copy (and k >= single_filter_min_k)
-    // ... with the int8 copy: the measured crossover of the two routes, which depends on the list length because the
-    // filter's round plan does (filter_plan.hpp: growth up to 24 - one round up to 60 x 3,072 rows - below k = 48, 5.5 from
-    // there on).  profiles/r04_route_crossover_by_k.log, us per search, stream / filter: k = 10: 20k rows 54 / 57, 35k 63 / 58,
-    // 100k 83 / 65, 184k 105 / 72; k = 25: 35k 71 / 63, 100k 104 / 86; k = 40: 200k 158 / 102 — k = 50: 150k 97 / 114, 300k 129 / 127,
-    // 400k 150 / 131; k = 75: 300k 141 / 135; k = 99: 300k 142 / 141.  (Round 4's first figure, 150,000 rows for every k, was
-    // taken before the phase plan and the one-round phase 0.)
-    uint64_t single_int8_min_rows = 32768;        // k < 48 (CS_FILTER_SINGLE_MIN_ROWS)
-    uint64_t single_int8_min_rows_long = 300000;  // k >= 48 (CS_FILTER_SINGLE_MIN_ROWS_LONG)
-    uint64_t few_queries_min_rows = 40000;        // two or three queries: rows from which they take the filter (CS_FILTER_FEW_MIN_ROWS) ...
-    uint64_t few_queries_min_rows_short = 16384;  // ... with k <= 16 (both follow CS_FILTER_FEW_MIN_ROWS when it is set)
-    uint64_t single_batched_max_rows = 1024;  // ... and one query over at most this many rows (0 = never; CS_SINGLE_BATCHED_MAX_ROWS)
-    // primed streaming scan (scan.hip PRIME mode): from this k and this many rows on, a pass over
-    // the first prime_rows rows bounds the list inserts of the full scan
-    // (measured, 1 query x 384-d: 10M rows k=10 2.37 -> 2.31 ms, k=200 2.62 -> 2.41 ms; 1M rows
-    // k=200 382 -> 279 us).  prime_rows 0 = n_rows / 256 clamped to [4096, 16384]; prime_min_rows 0 =
-    // 500,000 rows below k = 48 and 100,000 from there on.
-    uint32_t prime_min_k = 1;
-    uint64_t prime_min_rows = 0, prime_rows = 0;
+    RouteKnobs route;  // search_route.hpp: the thresholds of plan_route (route_knobs_from_env)
     uint64_t batched_searches = 0, batched_fallbacks = 0, q8_reruns = 0;
     std::vector<uint32_t> h_dead;
     bool built = false;
@@ -644,9 +545,86 @@ bool take_events(cs_index* h, Workspace* w, EventTriple* t) {
     return true;
 }
 
-// scan + merge on `stream`; outputs are device pointers (any may be null).
-// h_queries_pinned != null: the queries are still in that pinned host buffer and d_queries is empty;
-// the filter path lets its prep kernel bring them over, every other path copies them first.
+// what every launch of one search shares; outputs are device pointers (any may be null)
+struct SearchArgs {
+    const ScanPlan& plan;
+    const float* d_queries;
+    uint32_t nq, k;
+    uint64_t* d_keys; float* d_cos; uint32_t* d_ids; uint32_t* d_counts;
+    hipStream_t stream;
+    const uint32_t* d_dead;  // null when no row is tombstoned
+};
+
+int32_t close_timing(cs_index* h, const EventTriple& ev, hipStream_t stream) {
+    CS_HIP(hipEventRecord(ev.e2, stream));
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->pending.push_back(ev);
+    return CS_OK;
+}
+
+// overflowed searches the device has reported since this workspace last looked: a strike against the int8 copy
+// only when the search that overflowed read it (the exact-f32 batched path and the f16 filter share the word)
+void fold_overflows(cs_index* h, Workspace* w) {
+    if (!w->bs.h_mirror) return;
+    const uint32_t seen = *reinterpret_cast<volatile uint32_t*>(w->bs.h_mirror);
+    if (seen == w->mirror_seen) return;
+    w->mirror_seen = seen;
+    if (w->last_via_q8 && h->q8_active.load()) h->q8_strike();
+}
+
+// the exact list-based scan and its merge (gate: launch_scan)
+int32_t list_scan(cs_index* h, Workspace* w, const SearchArgs& a, const uint32_t* gate) {
+    CS_TRY(launch_scan(a.plan, h->d_corpus, h->n_rows, h->dim, a.d_queries, a.nq, a.k, a.d_dead, h->row_ids(), w->d_partial,
+                       a.stream, nullptr, false, gate));
+    return launch_merge(w->d_partial, a.plan.blocks, a.nq, a.k, false, w->d_tmp_a, w->d_tmp_b, a.d_keys, a.d_cos, a.d_ids,
+                        a.d_counts, a.stream, gate);
+}
+
+int32_t split_filter(cs_index* h, Workspace* w, const SearchArgs& a, const Q8View* q8) {
+    return launch_scan_split(w->bs, w->qw, h->d_corpus, h->d_split, h->n_rows, h->dim, a.d_queries, a.nq, a.k, a.d_dead,
+                             h->row_ids(), a.d_keys, a.d_cos, a.d_ids, a.d_counts, a.stream, h->filter_margin, q8);
+}
+
+// After a batched search (filter or exact MFMA): a candidate buffer holds batched_cap(k) entries and a phase appends at
+// most one per row, so it can only overflow over more rows than that (adversarial row order; thousands of near-duplicate
+// rows).  Then the exact answer comes from a rerun.
+int32_t settle_overflow(cs_index* h, Workspace* w, const SearchArgs& a, bool via_q8, bool may_sync, const EventTriple* ev) {
+    const bool can_overflow = h->n_rows > batched_cap(a.k);
+    bool overflow = false, reran = false;
+    if (!may_sync) {
+        // Device API: never wait for the device.  Up to kGatedMaxQ queries, the exact list-based scan and
+        // its merge are enqueued right behind the search with the overflow word as their gate: every
+        // block exits at once unless the search overflowed (then they overwrite its outputs), so what
+        // the caller's stream delivers is exact either way; cost when not taken ~3 near-empty launches.
+        // Above that (hundreds of query passes would be enqueued) the sticky word is left for
+        // cs_index_search_status().
+        if (can_overflow && a.nq <= kGatedMaxQ) CS_TRY(list_scan(h, w, a, w->bs.d_overflow));
+    } else if (can_overflow) {
+        CS_TRY(w->read_overflow(a.stream, &overflow));
+        if (overflow && via_q8) h->q8_strike();  // the int8 copy's band let too many rows through
+        if (overflow && via_q8 && ensure_f16(h)) {
+            // ... and the f16 copy (band 0.001; built now if this is the first time it is needed) answers this search
+            // before the exact list-based scan is asked to
+            w->last_via_q8 = false;
+            CS_TRY(split_filter(h, w, a, nullptr));
+            CS_TRY(w->read_overflow(a.stream, &overflow));
+            // the rerun's first kernel has mirrored the count of overflowed searches, this one included: seen
+            w->mirror_seen = *reinterpret_cast<volatile uint32_t*>(w->bs.h_mirror);
+            reran = true;
+        }
+    }
+    {
+        std::lock_guard<std::mutex> lk(h->mu);
+        h->batched_searches++;
+        if (overflow) h->batched_fallbacks++;
+        if (reran) h->q8_reruns++;
+    }
+    if (ev) CS_TRY(close_timing(h, *ev, a.stream));
+    return overflow ? list_scan(h, w, a, nullptr) : CS_OK;  // overflowed: the exact list-based rerun
+}
+
+// Plans the search (search_route.hpp), resolves its filter copy and launches it on `stream`.
+// h_queries_pinned != null: the queries are still in that pinned host buffer and d_queries is empty.
 int32_t run_search(cs_index* h, Workspace* w, const ScanPlan& plan, const float* d_queries,
                    uint32_t nq, uint32_t k, uint64_t* d_keys, float* d_cos, uint32_t* d_ids,
                    uint32_t* d_counts, hipStream_t stream, const float* h_queries_pinned = nullptr,
@@ -654,190 +632,76 @@ int32_t run_search(cs_index* h, Workspace* w, const ScanPlan& plan, const float*
     EventTriple ev{};
     const bool timed = take_events(h, w, &ev);
     if (timed) CS_HIP(hipEventRecord(ev.e0, stream));
-    // >= 5 queries: MFMA scoring + phased candidate selection (scan_mfma.hip)
-    // One query normally stays on the exact f32 streaming scan (the north-star kernel).  With a long list over a
-    // multi-million-row index — the reference's own retrieval_limit (100 or 200) when a search has no query variants —
-    // the filter + refine path is taken instead: same bits, 1.40 vs 2.36 ms at k = 200 over 10M x 384, because
-    // the scan's list inserts need a second block per CU there and the filter reads half the bytes.
-    // ... and over a corpus of the reference's own size (hundreds of chunks) the batched path — prep, direct scoring of
-    // every row, select: three small launches, no filter involved below a candidate buffer's worth of rows — answers one
-    // query faster than the streaming scan's per-wave lists do (592 rows: 30 vs 41 us; 1,000: 33 vs 46; from 2,000
-    // rows on the scan is ahead: 43 vs 48 us).
-    const bool single_filter =
-        nq == 1 && h->single_route != CS_ROUTE_STREAM &&
-        (h->single_route == CS_ROUTE_FILTER ||
-         (q8_serves(h) && h->n_rows >= (k < 48 ? h->single_int8_min_rows : h->single_int8_min_rows_long)) ||
-         (h->n_rows >= h->single_filter_min_rows && h->single_filter_min_k && k >= h->single_filter_min_k));
-    // (First measurement, round 4:) two to four queries over a corpus between one phase 0 and ~50,000 rows: the streaming scan (one pass per query
-    // tile) is ahead of the filter's fixed rounds (profiles/r04_batched_route_by_size.log, us per search at nq = 2, k = 25,
-    // filter / stream: 2,000 rows 37 / 45; 5,000 63 / 45; 20,000 71 / 60; 100,000 97 / 117); from five queries on the filter
-    // wins at every size (9 x 200: 41 ... 277 us against 81 ... 600 on the exact-f32 MFMA path).
-    // Re-measured behind the one-round phase 0 and the one-round plan of small corpora (profiles/r04_few_queries_crossover.log,
-    // us per search, stream / filter): FOUR queries are ahead on the filter from 5,000 rows on (k = 10: 5k 63 / 54, 20k 78 / 61,
-    // 50k 119 / 67; k = 25: 5k 64 / 58, 50k 95 / 76); TWO stream up to ~16,000 rows with a short list (k = 10: 10k 47 / 56,
-    // 20k 66 / 61) and up to ~40,000 rows above (k = 25: 20k 60 / 65, 35k 66 / 69, 50k 82 / 73), and THREE cost the streaming
-    // scan what two do (one pass: 5k rows 44 / 55, 10k 48 / 57, 20k at k = 25 60 / 66; four take a second pass: 63), so they
-    // follow two.
-    const uint64_t few_min = k <= 16 ? h->few_queries_min_rows_short : h->few_queries_min_rows;
-    const bool few_small = nq >= 2 && nq <= 3 && h->filter_min_q == 2 && h->n_rows > kFilterPhase0 && h->n_rows < few_min;
-    const bool wants_filter = ((int)nq >= h->filter_min_q && !few_small) || single_filter ||
-                              (nq == 1 && h->n_rows <= h->single_batched_max_rows);
-    const bool normed = h->n_rows > 0 && h->normed_rows >= h->n_rows;
+    const SearchShape shape{nq, k, h->dim, h->n_rows, h->num_cus, h->n_rows > 0 && h->normed_rows >= h->n_rows, h->use_split,
+                            batched_supported(h->dim), scan_prime_supported(h->dim), h_queries_pinned != nullptr,
+                            (uint64_t)plan.blocks * plan.passes};
     // Which copy filters: the int8 one when it serves; else the f16 one, built here, once, if it is not there yet; with
-    // neither (no room) the search takes the exact paths below.
-    bool via_q8 = false, use_filter = false;
-    if (h->use_split && wants_filter && normed) {
-        CS_TRY(w->reserve_batched(nq, k));
-        // overflowed searches the device has reported since this workspace last looked: a strike against the int8 copy
-        // only when the search that overflowed read it (the exact-f32 batched path and the f16 filter share the word).
-        // A strike can retire the copy: the choice is made after it.
-        if (w->bs.h_mirror) {
-            const uint32_t seen = *reinterpret_cast<volatile uint32_t*>(w->bs.h_mirror);
-            if (seen != w->mirror_seen) {
-                w->mirror_seen = seen;
-                if (w->last_via_q8 && h->q8_active.load()) h->q8_strike();
-            }
-        }
+    // neither (no room) the search takes the exact paths.  A strike can retire the int8 copy: the choice is made after it.
+    bool via_q8 = false, have_copy = false;
+    if (route_wants_filter(h->route, shape, q8_serves(h))) {
+        fold_overflows(h, w);
         via_q8 = q8_serves(h);
         bool planes = false;
         CS_TRY(w->reserve_split_queries(nq, h->dim, via_q8, &planes));
-        if (via_q8 && !planes) via_q8 = false;  // no room for the int8 query planes
-        use_filter = via_q8 || ensure_f16(h);
+        via_q8 = via_q8 && planes;  // no room for the int8 query planes: the f16 copy
+        have_copy = via_q8 || ensure_f16(h);
     }
-    const bool filter_path = use_filter;
-    w->qw.q_pinned = filter_path ? h_queries_pinned : nullptr;
-    // A streaming scan of a few blocks (a corpus of the reference's own size: hundreds to thousands of chunks) reads
-    // the queries straight from the pinned buffer too: a copy launch costs more than <= 64 blocks' reads over the link.
-    const bool streaming = !filter_path && !(normed && nq >= 5 && batched_supported(h->dim));
-    if (h_queries_pinned && streaming && scan_prime_supported(h->dim) /* queries go to registers once */ &&
-        (uint64_t)plan.blocks * plan.passes <= 64)
-        d_queries = h_queries_pinned;
-    else if (h_queries_pinned && !filter_path)
+    const SearchRoute route = plan_route(h->route, shape, have_copy);
+    w->qw.q_pinned = route.queries == QuerySource::PrepPinned ? h_queries_pinned : nullptr;
+    if (route.queries == QuerySource::StreamPinned) d_queries = h_queries_pinned;
+    if (route.queries == QuerySource::Copy)
         CS_HIP(hipMemcpyAsync(const_cast<float*>(d_queries), h_queries_pinned, (size_t)nq * h->dim * sizeof(float),
                               hipMemcpyHostToDevice, stream));
-    // Two or more queries: the filter reads a quarter (int8) or half (f16) of the bytes of the f32 scan once for up to
-    // 128 queries and the refine step keeps the result bit-identical.  One query stays on the streaming f32 scan
-    // (the north-star kernel).  Without a filter copy, >= 5 queries use the exact-f32 MFMA path.
-    if (normed && (use_filter || (nq >= 5 && batched_supported(h->dim)))) {
-        CS_TRY(w->reserve_batched(nq, k));
-        if (use_filter) {
-            Q8View q8;
-            w->last_via_q8 = via_q8;
-            if (via_q8) {
-                q8.d_q8 = h->d_q8; q8.d_tmeta = h->d_tmeta; q8.d_mu = h->d_mu; q8.rows = h->q8_rows;
-                h->q8_searches.fetch_add(1);
-            }
-            CS_TRY(launch_scan_split(w->bs, w->qw, h->d_corpus, h->d_split, h->n_rows, h->dim,
-                                     d_queries, nq, k, h->n_removed ? h->d_dead : nullptr, h->row_ids(), d_keys,
-                                     d_cos, d_ids, d_counts, stream, h->filter_margin, &q8));
-        } else {
-            w->last_via_q8 = false;
-            CS_TRY(launch_scan_batched(w->bs, h->d_corpus, h->d_norms, h->n_rows, h->dim, d_queries, nq, k,
-                                       h->n_removed ? h->d_dead : nullptr, h->row_ids(), h->num_cus, d_keys, d_cos,
-                                       d_ids, d_counts, stream));
+    const SearchArgs a{plan, d_queries, nq, k, d_keys, d_cos, d_ids, d_counts, stream, h->n_removed ? h->d_dead : nullptr};
+    if (route.path == SearchPath::Stream) {
+        const ScanPrime* prime = nullptr;
+        if (route.prime_rows) {
+            const ScanPlan pp = plan_prime(route.prime_rows, h->dim, nq, k, h->num_cus);
+            CS_TRY(w->reserve_prime(pp, nq));
+            CS_TRY(launch_scan(pp, h->d_corpus, route.prime_rows, h->dim, d_queries, nq, k, a.d_dead, h->row_ids(), nullptr,
+                               stream, &w->prime, true));
+            prime = &w->prime;
         }
+        CS_TRY(launch_scan(plan, h->d_corpus, h->n_rows, h->dim, d_queries, nq, k, a.d_dead, h->row_ids(), w->d_partial,
+                           stream, prime));
         if (timed) CS_HIP(hipEventRecord(ev.e1, stream));
-        // A candidate buffer holds batched_cap(k) entries and a phase appends at most one per row: it can
-        // only overflow over more rows than that (adversarial row order; thousands of near-duplicate rows).
-        const bool can_overflow = h->n_rows > batched_cap(k);
-        if (!may_sync) {
-            // Device API: never wait for the device.  Up to kGatedMaxQ queries, the exact list-based scan and
-            // its merge are enqueued right behind the search with the overflow word as their gate: every
-            // block exits at once unless the search overflowed (then they overwrite its outputs), so what
-            // the caller's stream delivers is exact either way; cost when not taken ~3 near-empty launches.
-            // Above that (hundreds of query passes would be enqueued) the sticky word is left for
-            // cs_index_search_status().
-            if (can_overflow && nq <= kGatedMaxQ) {
-                const uint32_t* gate = w->bs.d_overflow;
-                CS_TRY(launch_scan(plan, h->d_corpus, h->n_rows, h->dim, d_queries, nq, k,
-                                   h->n_removed ? h->d_dead : nullptr, h->row_ids(), w->d_partial, stream, nullptr, false,
-                                   gate));
-                CS_TRY(launch_merge(w->d_partial, plan.blocks, nq, k, false, w->d_tmp_a, w->d_tmp_b, d_keys, d_cos, d_ids,
-                                    d_counts, stream, gate));
-            }
-            std::lock_guard<std::mutex> lk(h->mu);
-            h->batched_searches++;
-            if (timed) {
-                CS_HIP(hipEventRecord(ev.e2, stream));
-                h->pending.push_back(ev);
-            }
-            return CS_OK;
-        }
-        bool overflow = false;
-        if (can_overflow) {  // host-buffer API: it synchronises for its results anyway
-            CS_HIP(hipMemcpyAsync(w->h_overflow, w->bs.d_overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            CS_HIP(hipStreamSynchronize(stream));
-            overflow = *w->h_overflow != 0;
-            if (overflow && via_q8) h->q8_strike();  // the int8 copy's band let too many rows through
-            if (overflow && via_q8 && ensure_f16(h)) {
-                // ... and the f16 copy (band 0.001; built now if this is the first time it is needed) answers this search
-                // before the exact list-based scan is asked to
-                w->last_via_q8 = false;
-                CS_TRY(launch_scan_split(w->bs, w->qw, h->d_corpus, h->d_split, h->n_rows, h->dim, d_queries, nq, k,
-                                         h->n_removed ? h->d_dead : nullptr, h->row_ids(), d_keys, d_cos, d_ids, d_counts,
-                                         stream, h->filter_margin, nullptr));
-                CS_HIP(hipMemcpyAsync(w->h_overflow, w->bs.d_overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-                CS_HIP(hipStreamSynchronize(stream));
-                overflow = *w->h_overflow != 0;
-                // the rerun's first kernel has mirrored the count of overflowed searches, this one included: seen
-                w->mirror_seen = *reinterpret_cast<volatile uint32_t*>(w->bs.h_mirror);
-                std::lock_guard<std::mutex> lk(h->mu);
-                h->q8_reruns++;
-            }
-        }
-        {
-            std::lock_guard<std::mutex> lk(h->mu);
-            h->batched_searches++;
-            if (overflow) h->batched_fallbacks++;
-            if (timed) {
-                CS_HIP(hipEventRecord(ev.e2, stream));
-                h->pending.push_back(ev);
-            }
-        }
-        if (!overflow) return CS_OK;
-        // candidate buffer overflowed: exact list-based rerun below
-        EventTriple none{};
-        ev = none;
-        return [&]() -> int32_t {
-            CS_TRY(launch_scan(plan, h->d_corpus, h->n_rows, h->dim, d_queries, nq, k,
-                               h->n_removed ? h->d_dead : nullptr, h->row_ids(), w->d_partial, stream));
-            return launch_merge(w->d_partial, plan.blocks, nq, k, false, w->d_tmp_a, w->d_tmp_b, d_keys, d_cos,
-                                d_ids, d_counts, stream);
-        }();
+        CS_TRY(launch_merge(w->d_partial, plan.blocks, nq, k, false, w->d_tmp_a, w->d_tmp_b, d_keys, d_cos, d_ids, d_counts,
+                            stream));
+        return timed ? close_timing(h, ev, stream) : CS_OK;
     }
-    const uint32_t* d_dead = h->n_removed ? h->d_dead : nullptr;
-    const ScanPrime* prime = nullptr;
-    uint64_t prime_rows = h->prime_rows;
-    if (!prime_rows) {
-        prime_rows = (h->n_rows / 256) & ~(uint64_t)63;
-        // short lists need fewer wave maxima for a useful bound: 8,192 rows (512 waves of 16) up to k = 16 — over 10M
-        // rows the pass costs 18 instead of 26 us and the scan the same (k = 10: 2,122 -> 2,114 us; k = 64 and 99 lose
-        // 5 and 17 us with the smaller sample and keep 16,384)
-        const uint64_t prime_cap = k <= 16 ? 8192 : 16384;
-        prime_rows = prime_rows < 4096 ? 4096 : (prime_rows > prime_cap ? prime_cap : prime_rows);
-        const uint64_t big = prime_sample_rows(prime_rows, k, h->num_cus);  // k > 256: more waves, 32 rows each
-        if (h->n_rows >= 4 * big) prime_rows = big;
+    CS_TRY(w->reserve_batched(nq, k));
+    w->last_via_q8 = via_q8;
+    if (route.path == SearchPath::Filter) {
+        Q8View q8;
+        if (via_q8) {
+            q8.d_q8 = h->d_q8; q8.d_tmeta = h->d_tmeta; q8.d_mu = h->d_mu; q8.rows = h->q8_rows;
+            h->q8_searches.fetch_add(1);
+        }
+        CS_TRY(split_filter(h, w, a, &q8));
+    } else {
+        CS_TRY(launch_scan_batched(w->bs, h->d_corpus, h->d_norms, h->n_rows, h->dim, d_queries, nq, k, a.d_dead, h->row_ids(),
+                                   h->num_cus, d_keys, d_cos, d_ids, d_counts, stream));
     }
-    const uint64_t prime_min_rows = h->prime_min_rows ? h->prime_min_rows : (k >= 48 ? 100000 : 500000);
-    if (h->prime_min_k && k >= h->prime_min_k && h->n_rows >= prime_min_rows &&
-        h->n_rows >= 4 * prime_rows && scan_prime_supported(h->dim)) {
-        const ScanPlan pp = plan_prime(prime_rows, h->dim, nq, k, h->num_cus);
-        CS_TRY(w->reserve_prime(pp, nq));
-        CS_TRY(launch_scan(pp, h->d_corpus, prime_rows, h->dim, d_queries, nq, k, d_dead, h->row_ids(),
-                           nullptr, stream, &w->prime, true));
-        prime = &w->prime;
-    }
-    CS_TRY(launch_scan(plan, h->d_corpus, h->n_rows, h->dim, d_queries, nq, k, d_dead, h->row_ids(),
-                       w->d_partial, stream, prime));
     if (timed) CS_HIP(hipEventRecord(ev.e1, stream));
-    CS_TRY(launch_merge(w->d_partial, plan.blocks, nq, k, false, w->d_tmp_a, w->d_tmp_b, d_keys, d_cos,
-                        d_ids, d_counts, stream));
-    if (timed) {
-        CS_HIP(hipEventRecord(ev.e2, stream));
-        std::lock_guard<std::mutex> lk(h->mu);
-        h->pending.push_back(ev);
+    return settle_overflow(h, w, a, via_q8, may_sync, timed ? &ev : nullptr);
+}
+
+// The route's thresholds of a new index: RouteKnobs' defaults, or what the environment sets.
+RouteKnobs route_knobs_from_env() {
+    RouteKnobs r;
+    if (const char* e = std::getenv("CS_FILTER_MIN_Q")) r.filter_min_q = std::max(1, std::atoi(e));
+    if (const char* e = std::getenv("CS_FILTER_SINGLE_MIN_K")) {  // "0": one query never takes the filter (= CS_ROUTE_STREAM)
+        r.single_filter_min_k = (uint32_t)std::atol(e);
+        if (r.single_filter_min_k == 0) r.single_route = CS_ROUTE_STREAM;
     }
-    return CS_OK;
+    if (const char* e = std::getenv("CS_FILTER_SINGLE_MIN_ROWS")) r.single_int8_min_rows = (uint64_t)std::atoll(e);
+    if (const char* e = std::getenv("CS_FILTER_SINGLE_MIN_ROWS_LONG")) r.single_int8_min_rows_long = (uint64_t)std::atoll(e);
+    if (const char* e = cs_lab_env("CS_FILTER_FEW_MIN_ROWS")) r.few_queries_min_rows = r.few_queries_min_rows_short = (uint64_t)std::atoll(e);
+    if (const char* e = std::getenv("CS_SINGLE_BATCHED_MAX_ROWS")) r.single_batched_max_rows = (uint64_t)std::atoll(e);
+    if (const char* e = std::getenv("CS_SCAN_PRIME_MIN_K")) r.prime_min_k = (uint32_t)std::atol(e);  // 0 = off
+    if (const char* e = std::getenv("CS_SCAN_PRIME_MIN_ROWS")) r.prime_min_rows = (uint64_t)std::atoll(e);
+    if (const char* e = std::getenv("CS_SCAN_PRIME_ROWS")) r.prime_rows = (uint64_t)std::atoll(e);
+    return r;
 }
 
 int32_t check_search(const cs_index* h, uint32_t nq, uint32_t dim, uint32_t k) {
@@ -894,23 +758,9 @@ int32_t cs_index_create(uint32_t dim, uint64_t capacity_rows, int32_t device, ui
         const char* ee = std::getenv("CS_FILTER_F16_EAGER");  // "1": keep the f16 copy beside a serving int8 copy
         h->f16_eager = (ee && ee[0] == '1') || cs_lab_env("CS_FILTER_INT8_MAX_Q") != nullptr;
         if (const char* e = std::getenv("CS_FILTER_INT8_MAX_SPREAD")) h->q8_max_spread = (float)std::atof(e);
-        if (const char* e = std::getenv("CS_FILTER_MIN_Q")) {
-            h->filter_min_q = std::atoi(e);
-            if (h->filter_min_q < 1) h->filter_min_q = 1;
-        }
-        if (const char* e = std::getenv("CS_FILTER_SINGLE_MIN_K")) {  // "0": one query never takes the filter (= CS_ROUTE_STREAM)
-            h->single_filter_min_k = (uint32_t)std::atol(e);
-            if (h->single_filter_min_k == 0) h->single_route = CS_ROUTE_STREAM;
-        }
         if (const char* e = std::getenv("CS_INDEX_COMPACT_DEAD_PCT")) h->compact_dead_pct = (uint32_t)std::max(0, std::min(100, std::atoi(e)));
-        if (const char* e = std::getenv("CS_FILTER_SINGLE_MIN_ROWS")) h->single_int8_min_rows = (uint64_t)std::atoll(e);
-        if (const char* e = std::getenv("CS_FILTER_SINGLE_MIN_ROWS_LONG")) h->single_int8_min_rows_long = (uint64_t)std::atoll(e);
-        if (const char* e = cs_lab_env("CS_FILTER_FEW_MIN_ROWS")) h->few_queries_min_rows = h->few_queries_min_rows_short = (uint64_t)std::atoll(e);
-        if (const char* e = std::getenv("CS_SINGLE_BATCHED_MAX_ROWS")) h->single_batched_max_rows = (uint64_t)std::atoll(e);
-        if (const char* e = std::getenv("CS_SCAN_PRIME_MIN_K")) h->prime_min_k = (uint32_t)std::atol(e);  // 0 = off
-        if (const char* e = std::getenv("CS_SCAN_PRIME_MIN_ROWS")) h->prime_min_rows = (uint64_t)std::atoll(e);
-        if (const char* e = std::getenv("CS_SCAN_PRIME_ROWS")) h->prime_rows = (uint64_t)std::atoll(e);
     }
+    h->route = route_knobs_from_env();
     if (h->use_split) {
         // does the f16 MFMA take subnormal inputs exactly?  One one-wave launch per device per process.
         static std::mutex mu;
@@ -1163,16 +1013,7 @@ int32_t cs_index_search(cs_index* h, const float* queries, uint32_t nq, uint32_t
             CS_TRY(run_search(h, w, plan, w->d_queries, nq, k, w->h_keys, nullptr, nullptr, nullptr, w->stream,
                               w->h_queries));
             CS_HIP(hipStreamSynchronize(w->stream));
-            for (uint32_t q = 0; q < nq; ++q) {  // keys are best-first, 0 = empty slot
-                uint32_t c = 0;
-                for (uint32_t j = 0; j < k; ++j) {
-                    const uint64_t key = w->h_keys[(size_t)q * k + j];
-                    if (key) ++c;
-                    out_cos[(size_t)q * k + j] = key ? key_cos(key) : 0.0f;
-                    out_ids[(size_t)q * k + j] = key ? key_id(key) : 0xFFFFFFFFu;
-                }
-                out_counts[q] = c;
-            }
+            unpack_keys(w->h_keys, nq, k, out_cos, out_ids, out_counts);
             return CS_OK;
         }();
     }
@@ -1216,11 +1057,7 @@ int32_t cs_index_search_variants(cs_index* h, const float* queries, uint32_t nq,
             CS_TRY(launch_merge_variants(w->d_keys, nq, k, k, w->h_keys, nullptr, nullptr, w->h_variant_meta,
                                          w->h_variant_meta + 1, w->stream));
             CS_HIP(hipStreamSynchronize(w->stream));
-            for (uint32_t j = 0; j < k; ++j) {
-                const uint64_t key = w->h_keys[j];
-                out_cos[j] = key ? key_cos(key) : 0.0f;
-                out_ids[j] = key ? key_id(key) : 0xFFFFFFFFu;
-            }
+            unpack_keys(w->h_keys, 1, k, out_cos, out_ids, nullptr);
             *out_count = w->h_variant_meta[0];
             if (out_high_confidence) *out_high_confidence = (int32_t)w->h_variant_meta[1];
             return CS_OK;
@@ -1415,7 +1252,7 @@ int32_t cs_index_read_rows(cs_index* h, uint64_t first_row, uint64_t n, float* o
 
 int32_t cs_index_set_filter_min_queries(cs_index* h, uint32_t min_queries) {
     if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
-    h->filter_min_q = min_queries < 1 ? 1 : (int)min_queries;
+    h->route.filter_min_q = min_queries < 1 ? 1 : (int)min_queries;
     return CS_OK;
 }
 
@@ -1423,7 +1260,7 @@ int32_t cs_index_set_single_query_route(cs_index* h, int32_t route) {
     if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
     if (route != CS_ROUTE_COST && route != CS_ROUTE_STREAM && route != CS_ROUTE_FILTER)
         return fail(CS_ERR_BAD_ARG, "route must be CS_ROUTE_COST, CS_ROUTE_STREAM or CS_ROUTE_FILTER, got %d", route);
-    h->single_route = route;
+    h->route.single_route = route;
     return CS_OK;
 }
 

@@ -22,6 +22,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kBlock = 256;   // 4 waves
 constexpr int kWaves = kBlock / 64;
+static_assert(kWaves == (int)kScanWaves, "search_route.hpp sizes the prime sample by it");
 constexpr int kMergeBlock = 1024;
 constexpr int kMergeCap = 4096;  // keys a merge block can sort (2048 used up to k = 512, see merge_group)
 
@@ -603,12 +604,6 @@ __global__ void synth_fill_kernel(float* __restrict__ out, uint64_t total, uint6
 
 // ---- host side ----------------------------------------------------------------------------
 
-static uint32_t kpad_for(uint32_t k) {
-    uint32_t p = 64;
-    while (p < k) p <<= 1;
-    return p;
-}
-
 static bool fast_dim(uint32_t dim) { return dim == 384 || dim == 768 || dim == 1024; }
 
 template <int J, int U, int QT>
@@ -688,25 +683,6 @@ ScanPlan plan_scan(uint64_t n_rows, uint32_t dim, uint32_t nq, uint32_t k, int n
 }
 
 bool scan_prime_supported(uint32_t dim) { return fast_dim(dim); }
-
-// Prime pass geometry.  The bound is the k-th largest of W wave maxima, so W must exceed k by a
-// good factor and every wave should see a few tiles: up to k = 256 one block per CU (W <= 1024
-// waves); above, four per CU (W <= 4096, the most keys the selecting block's LDS holds) — with
-// W = 1024 a k = 1024 bound is the smallest of all maxima, a third of the rows pass it and the scan
-// takes 4.9 ms instead of 2.5.  Never more blocks than kpad (waves = 4 * blocks <= 4 * kpad).
-static uint32_t prime_block_cap(uint32_t k, int num_cus) {
-    const uint32_t kpad = kpad_for(k);
-    uint32_t cap = (uint32_t)num_cus * (k > 256 ? 4u : 1u);
-    if (cap > 1024) cap = 1024;
-    return cap > kpad ? kpad : cap;
-}
-
-// Rows of the prime sample: the caller's default, raised to 32 rows per wave when k > 256.
-uint64_t prime_sample_rows(uint64_t default_rows, uint32_t k, int num_cus) {
-    if (k <= 256) return default_rows;
-    const uint64_t want = (uint64_t)prime_block_cap(k, num_cus) * kWaves * 32;
-    return want > default_rows ? want : default_rows;
-}
 
 ScanPlan plan_prime(uint64_t sample_rows, uint32_t dim, uint32_t nq, uint32_t k, int num_cus) {
     ScanPlan p = plan_scan(sample_rows, dim, nq, k, num_cus);

@@ -2,7 +2,7 @@
 #pragma once
 
 #include "common.hpp"
-#include "filter_plan.hpp"  // kFilterPhase0
+#include "search_route.hpp"  // kFilterPhase0, kpad_for, prime_sample_rows
 
 namespace cs {
 
@@ -27,7 +27,6 @@ struct ScanPrime {
     float* d_floor = nullptr;     // [nq]
 };
 bool scan_prime_supported(uint32_t dim);
-uint64_t prime_sample_rows(uint64_t default_rows, uint32_t k, int num_cus);
 ScanPlan plan_prime(uint64_t sample_rows, uint32_t dim, uint32_t nq, uint32_t k, int num_cus);
 
 // Scores every live row of corpus[0..n_rows) against each query and leaves, per

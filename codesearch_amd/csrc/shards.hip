@@ -309,25 +309,12 @@ int32_t shards_search_impl(cs_shards* h, const float* queries, uint32_t nq, uint
         CS_TRY(rerun_overflowed(h, c, nq, k, &again));
         if (again) CS_TRY(merge());
         if (variants) {
-            for (uint32_t j = 0; j < k; ++j) {
-                const uint64_t key = c->h_keys[j];
-                out_cos[j] = key ? key_cos(key) : 0.0f;
-                out_ids[j] = key ? key_id(key) : 0xFFFFFFFFu;
-            }
+            unpack_keys(c->h_keys, 1, k, out_cos, out_ids, nullptr);
             variants[0] = c->h_meta[0];
             variants[1] = c->h_meta[1];
             return CS_OK;
         }
-        for (uint32_t q = 0; q < nq; ++q) {  // keys are best-first, 0 = empty slot
-            uint32_t cnt = 0;
-            for (uint32_t j = 0; j < k; ++j) {
-                const uint64_t key = c->h_keys[(size_t)q * k + j];
-                if (key) ++cnt;
-                out_cos[(size_t)q * k + j] = key ? key_cos(key) : 0.0f;
-                out_ids[(size_t)q * k + j] = key ? key_id(key) : 0xFFFFFFFFu;
-            }
-            out_counts[q] = cnt;
-        }
+        unpack_keys(c->h_keys, nq, k, out_cos, out_ids, out_counts);
         return CS_OK;
     }();
     if (st != CS_OK) drain_ctx(h, c);
