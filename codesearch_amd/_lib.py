@@ -79,6 +79,10 @@ SIGNATURES = {
     "cs_index_search": (C.c_int32, [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p]),
     "cs_index_search_device": (C.c_int32, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]),
     "cs_index_search_variants": (C.c_int32, [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p, i32p]),
+    "cs_index_search_masked": (C.c_int32, [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, u32p, C.c_uint64, f32p, u32p,
+                                           u32p]),
+    "cs_index_search_variants_masked": (C.c_int32, [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, u32p, C.c_uint64, f32p,
+                                                    u32p, u32p, i32p]),
     "cs_merge_variants_device": (C.c_int32, [C.c_int32, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]),
     "cs_index_search_status": (C.c_int32, [vp, vp, u32p]),
     "cs_index_release_stream": (C.c_int32, [vp, vp]),
@@ -106,6 +110,10 @@ SIGNATURES = {
     "cs_shards_shard_device": (C.c_int32, [vp, C.c_uint32]),
     "cs_shards_shard_index": (vp, [vp, C.c_uint32]),
     "cs_shards_search_variants": (C.c_int32, [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p, i32p]),
+    "cs_shards_search_masked": (C.c_int32, [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, u32p, C.c_uint64, f32p, u32p,
+                                            u32p]),
+    "cs_shards_search_variants_masked": (C.c_int32, [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, u32p, C.c_uint64, f32p,
+                                                     u32p, u32p, i32p]),
     "cs_shards_read_rows": (C.c_int32, [vp, C.c_uint64, C.c_uint64, f32p]),
     "cs_index_read_rows": (C.c_int32, [vp, C.c_uint64, C.c_uint64, f32p]),
     "cs_index_debug_counters": (C.c_int32, [vp, u64p, u64p]),

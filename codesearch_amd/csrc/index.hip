@@ -13,6 +13,7 @@
 
 #include <cstdlib>
 
+#include "masked_plan.hpp"
 #include "scan.hpp"
 
 namespace cs {
@@ -74,6 +75,10 @@ struct Workspace {
     float* h_queries = nullptr; size_t h_q_cap = 0;
     uint64_t* h_keys = nullptr; size_t h_keys_cap = 0;
     uint32_t* h_variant_meta = nullptr;  // pinned: [0] count, [1] high-confidence flag (cs_index_search_variants)
+    // masked searches (run_masked): the words of the caller's mask that cover the index's ids, the row list and the
+    // row-list pass's per-block offsets (+ the list length)
+    uint32_t* d_allow = nullptr; uint32_t* d_list = nullptr; uint32_t* d_mblocks = nullptr;
+    size_t allow_cap = 0, list_cap = 0, mblocks_cap = 0;
     std::vector<EventTriple> free_events;
     BatchedState bs;
     size_t cnt_cap = 0, tau_cap = 0, cand_cap = 0, carry_cap = 0;
@@ -111,6 +116,12 @@ struct Workspace {
             CS_HIP(hipMemset(prime.d_done, 0, nq * sizeof(uint32_t)));
         }
         return reserve_buf(prime.d_floor, floor_cap, nq);
+    }
+
+    int32_t reserve_masked(uint64_t words, uint64_t list_rows, uint32_t list_blocks) {
+        CS_TRY(reserve_buf(d_allow, allow_cap, words));
+        CS_TRY(reserve_buf(d_list, list_cap, list_rows));
+        return reserve_buf(d_mblocks, mblocks_cap, (size_t)list_blocks + 1);
     }
 
     int32_t reserve_batched(uint32_t nq, uint32_t k) {
@@ -155,7 +166,7 @@ struct Workspace {
     void release_all() {
         free_bufs(false, d_partial, d_tmp_a, d_tmp_b, d_queries, d_keys, d_cos, d_ids, d_counts, prime.d_wave_max, prime.d_done,
                   prime.d_floor, bs.d_cand, bs.d_cnt, bs.d_tau, bs.d_carry, bs.d_overflow, qw.d_qsplit, qw.d_qmag, qw.d_q8q,
-                  qw.d_q8q_hi, qw.d_qmeta);
+                  qw.d_q8q_hi, qw.d_qmeta, d_allow, d_list, d_mblocks);
         free_bufs(true, h_keys, h_queries, h_overflow, h_variant_meta);
         for (auto& t : free_events) {
             (void)hipEventDestroy(t.e0); (void)hipEventDestroy(t.e1); (void)hipEventDestroy(t.e2);
@@ -686,6 +697,45 @@ int32_t run_search(cs_index* h, Workspace* w, const ScanPlan& plan, const float*
     return settle_overflow(h, w, a, via_q8, may_sync, timed ? &ev : nullptr);
 }
 
+// Upper bound of the live rows a mask allows (masked_plan.hpp allowed_bound): 0 = the search launches nothing.
+uint64_t masked_bound(const cs_index* h, const uint32_t* allow, uint64_t allow_bits) {
+    return allowed_bound(allow, allow_bits, h->id_base, (uint64_t)h->id_base + h->n_ids, h->n_rows - h->n_removed);
+}
+
+// A masked search (scan_masked.hip) on `stream`, for a mask whose bound (masked_bound) is > 0 and a plan sized by it: the
+// row list, the optional prime pass and the gathered scan, then the shared merge -> the best k keys per query in
+// d_keys [nq][k].  `allow` is host memory that must stay valid until the stream has passed the search.
+int32_t run_masked(cs_index* h, Workspace* w, const ScanPlan& plan, uint64_t bound, const float* d_queries, uint32_t nq,
+                   uint32_t k, const uint32_t* allow, uint64_t allow_bits, uint64_t* d_keys, hipStream_t stream) {
+    const MaskWindow win = mask_window(allow_bits, h->id_base, (uint64_t)h->id_base + h->n_ids);
+    const uint32_t nb = mask_list_blocks(h->n_rows);
+    CS_TRY(w->reserve_masked(win.words, bound, nb));
+    CS_HIP(hipMemcpyAsync(w->d_allow, allow + (win.lo >> 5), (size_t)win.words * sizeof(uint32_t), hipMemcpyHostToDevice,
+                          stream));
+    CS_TRY(launch_mask_rows(w->d_allow, win.lo, win.hi, h->n_removed ? h->d_dead : nullptr, h->row_ids(), h->n_rows,
+                            w->d_mblocks, w->d_list, bound, stream));
+    const uint32_t* d_len = w->d_mblocks + nb;
+    const uint64_t prime_rows = masked_prime_rows(h->route, bound, nq, k, h->dim, h->num_cus, scan_prime_supported(h->dim));
+    const ScanPrime* prime = nullptr;
+    if (prime_rows) {
+        const ScanPlan pp = plan_prime(prime_rows, h->dim, nq, k, h->num_cus);
+        CS_TRY(w->reserve_prime(pp, nq));
+        CS_TRY(launch_scan_masked(pp, h->d_corpus, h->dim, w->d_list, d_len, d_queries, nq, k, h->row_ids(), nullptr, stream,
+                                  &w->prime, true, prime_rows));
+        prime = &w->prime;
+    }
+    CS_TRY(launch_scan_masked(plan, h->d_corpus, h->dim, w->d_list, d_len, d_queries, nq, k, h->row_ids(), w->d_partial,
+                              stream, prime));
+    return launch_merge(w->d_partial, plan.blocks, nq, k, false, w->d_tmp_a, w->d_tmp_b, d_keys, nullptr, nullptr, nullptr,
+                        stream);
+}
+
+// The empty answer of a host-buffer search: every slot empty, as unpack_keys leaves it.
+void fill_empty(uint32_t nq, uint32_t k, float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
+    for (size_t i = 0; i < (size_t)nq * k; ++i) { out_cos[i] = 0.0f; out_ids[i] = 0xFFFFFFFFu; }
+    if (out_counts) memset(out_counts, 0, (size_t)nq * sizeof(uint32_t));
+}
+
 // The route's thresholds of a new index: RouteKnobs' defaults, or what the environment sets.
 RouteKnobs route_knobs_from_env() {
     RouteKnobs r;
@@ -1067,6 +1117,77 @@ int32_t cs_index_search_variants(cs_index* h, const float* queries, uint32_t nq,
     return s;
 }
 
+int32_t cs_index_search_masked(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                               const uint32_t* allow, uint64_t allow_bits, float* out_cos, uint32_t* out_ids,
+                               uint32_t* out_counts) {
+    CS_TRY(check_search(h, nq, dim, k));
+    if (!queries || !out_cos || !out_ids || !out_counts) return fail(CS_ERR_BAD_ARG, "null buffer");
+    if (!allow && allow_bits) return fail(CS_ERR_BAD_ARG, "allow is null");
+    const uint64_t bound = masked_bound(h, allow, allow_bits);
+    if (bound == 0) {  // nothing allowed is stored: no launch
+        fill_empty(nq, k, out_cos, out_ids, out_counts);
+        return CS_OK;
+    }
+    DeviceGuard g(h->device);
+    const ScanPlan plan = plan_scan(bound, h->dim, nq, k, h->num_cus);  // the grid follows the allowed rows
+    Workspace* w = acquire_pooled(h);
+    if (!w) return fail(CS_ERR_HIP, "could not create a HIP stream");
+    int32_t s = w->reserve(plan, nq, h->dim, k, true);
+    if (s == CS_OK) {
+        s = [&]() -> int32_t {
+            memcpy(w->h_queries, queries, (size_t)nq * h->dim * sizeof(float));
+            CS_HIP(hipMemcpyAsync(w->d_queries, w->h_queries, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice,
+                                  w->stream));
+            CS_TRY(run_masked(h, w, plan, bound, w->d_queries, nq, k, allow, allow_bits, w->h_keys, w->stream));
+            CS_HIP(hipStreamSynchronize(w->stream));
+            unpack_keys(w->h_keys, nq, k, out_cos, out_ids, out_counts);
+            return CS_OK;
+        }();
+    }
+    release_pooled(h, w);
+    return s;
+}
+
+int32_t cs_index_search_variants_masked(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                                        const uint32_t* allow, uint64_t allow_bits, float* out_cos, uint32_t* out_ids,
+                                        uint32_t* out_count, int32_t* out_high_confidence) {
+    CS_TRY(check_search(h, nq, dim, k));
+    if (nq > CS_MAX_VARIANTS)
+        return fail(CS_ERR_BAD_ARG, "at most %u query variants per call, got %u", CS_MAX_VARIANTS, nq);
+    if (!queries || !out_cos || !out_ids || !out_count) return fail(CS_ERR_BAD_ARG, "null buffer");
+    if (!allow && allow_bits) return fail(CS_ERR_BAD_ARG, "allow is null");
+    const uint64_t bound = masked_bound(h, allow, allow_bits);
+    if (bound == 0) {
+        fill_empty(1, k, out_cos, out_ids, nullptr);
+        *out_count = 0;
+        if (out_high_confidence) *out_high_confidence = 0;
+        return CS_OK;
+    }
+    DeviceGuard g(h->device);
+    const ScanPlan plan = plan_scan(bound, h->dim, nq, k, h->num_cus);
+    Workspace* w = acquire_pooled(h);
+    if (!w) return fail(CS_ERR_HIP, "could not create a HIP stream");
+    int32_t s = w->reserve(plan, nq, h->dim, k, true);
+    if (s == CS_OK) {
+        s = [&]() -> int32_t {
+            if (!w->h_variant_meta) CS_HIP(hipHostMalloc(&w->h_variant_meta, 2 * sizeof(uint32_t)));
+            memcpy(w->h_queries, queries, (size_t)nq * h->dim * sizeof(float));
+            CS_HIP(hipMemcpyAsync(w->d_queries, w->h_queries, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice,
+                                  w->stream));
+            CS_TRY(run_masked(h, w, plan, bound, w->d_queries, nq, k, allow, allow_bits, w->d_keys, w->stream));
+            CS_TRY(launch_merge_variants(w->d_keys, nq, k, k, w->h_keys, nullptr, nullptr, w->h_variant_meta,
+                                         w->h_variant_meta + 1, w->stream));
+            CS_HIP(hipStreamSynchronize(w->stream));
+            unpack_keys(w->h_keys, 1, k, out_cos, out_ids, nullptr);
+            *out_count = w->h_variant_meta[0];
+            if (out_high_confidence) *out_high_confidence = (int32_t)w->h_variant_meta[1];
+            return CS_OK;
+        }();
+    }
+    release_pooled(h, w);
+    return s;
+}
+
 int32_t cs_merge_variants_device(int32_t device, const uint64_t* d_keys, uint32_t nv, uint32_t k, uint32_t limit,
                                  uint64_t* d_out_keys, float* d_out_cos, uint32_t* d_out_ids, uint32_t* d_out_count,
                                  uint32_t* d_out_high_confidence, void* stream) {
@@ -1149,6 +1270,23 @@ void cs::merge_scratch_release(int device, hipStream_t stream) {
             it = g_merge_pool.erase(it);
         } else ++it;
     }
+}
+
+int32_t cs::index_search_masked_device(cs_index* h, const float* d_queries, uint32_t nq, uint32_t k, const uint32_t* allow,
+                                       uint64_t allow_bits, uint64_t* d_out_keys, hipStream_t stream) {
+    CS_TRY(check_search(h, nq, h ? h->dim : 0, k));
+    if (!d_queries || !d_out_keys) return fail(CS_ERR_BAD_ARG, "null buffer");
+    if (!allow && allow_bits) return fail(CS_ERR_BAD_ARG, "allow is null");
+    DeviceGuard g(h->device);
+    const uint64_t bound = masked_bound(h, allow, allow_bits);
+    if (bound == 0) {  // empty lists for the merge behind
+        CS_HIP(hipMemsetAsync(d_out_keys, 0, (size_t)nq * k * sizeof(uint64_t), stream));
+        return CS_OK;
+    }
+    const ScanPlan plan = plan_scan(bound, h->dim, nq, k, h->num_cus);
+    Workspace* w = for_stream(h, stream);
+    CS_TRY(w->reserve(plan, nq, h->dim, k, false));
+    return run_masked(h, w, plan, bound, d_queries, nq, k, allow, allow_bits, d_out_keys, stream);
 }
 
 int32_t cs::index_reserve(cs_index* h, uint64_t rows) {

@@ -68,6 +68,26 @@ int32_t launch_merge_variants(const uint64_t* d_keys, uint32_t nv, uint32_t k, u
                               float* d_out_cos, uint32_t* d_out_ids, uint32_t* d_out_count,
                               uint32_t* d_out_high_confidence, hipStream_t stream);
 
+// ---- masked search (scan_masked.hip, plan: masked_plan.hpp) ------------------------------------
+// Row list of a masked search: the stored rows [0, n_rows) whose id lies in [allow_lo, allow_hi), has its bit set in
+// d_allow (word w covers ids allow_lo + 32 w ...) and is not tombstoned, ascending, into d_list[0, list_cap);
+// d_blocks[mask_list_blocks(n_rows) + 1] receives the per-block offsets and, last, the list length.
+int32_t launch_mask_rows(const uint32_t* d_allow, uint64_t allow_lo, uint64_t allow_hi, const uint32_t* d_dead,
+                         RowIds ids, uint64_t n_rows, uint32_t* d_blocks, uint32_t* d_list, uint64_t list_cap,
+                         hipStream_t stream);
+// The streaming scan over the rows d_list[0, *d_list_len) (plan: plan_scan of an upper bound of the length): the same
+// per-block partial lists as launch_scan, for launch_merge.  prime + prime_pass: the prime pass over the first
+// min(prime_rows, *d_list_len) entries (plan from plan_prime); prime alone: the lists start from prime->d_floor.
+int32_t launch_scan_masked(const ScanPlan& plan, const float* d_corpus, uint32_t dim, const uint32_t* d_list,
+                           const uint32_t* d_list_len, const float* d_queries, uint32_t nq, uint32_t k, RowIds ids,
+                           uint64_t* d_partial, hipStream_t stream, const ScanPrime* prime = nullptr,
+                           bool prime_pass = false, uint64_t prime_rows = 0);
+// index.hip: a masked search of nq queries already in HBM (d_queries) enqueued on `stream` with the device-API scratch of
+// (stream, calling thread); the best k per query as packed keys into d_out_keys [nq][k].  `allow` is host memory that must
+// stay valid until the stream has passed the search.  Used by the sharded store.
+int32_t index_search_masked_device(cs_index* h, const float* d_queries, uint32_t nq, uint32_t k, const uint32_t* allow,
+                                   uint64_t allow_bits, uint64_t* d_out_keys, hipStream_t stream);
+
 // corpus[(first_out_row + r) * dim + c] = cs_synth_value(seed, (first_row + r) * dim + c)
 int32_t launch_synth_fill(float* d_rows, uint64_t n, uint32_t dim, uint64_t seed,
                           uint64_t first_row, hipStream_t stream);

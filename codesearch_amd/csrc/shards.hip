@@ -31,6 +31,7 @@
 #include <mutex>
 #include <vector>
 
+#include "masked_plan.hpp"
 #include "scan.hpp"
 
 using namespace cs;
@@ -80,6 +81,12 @@ struct cs_shards {
 namespace {
 
 struct Piece { uint32_t shard; uint64_t local_row, count, offset; };
+
+// A masked search's mask restated per shard over its local ids (masked_plan.hpp shard_mask).
+struct ShardMasks {
+    std::vector<std::vector<uint32_t>> words;
+    std::vector<uint64_t> bits;
+};
 
 // ids [first, first + n) as runs that stay inside one stripe
 std::vector<Piece> pieces_of(const cs_shards* h, uint64_t first, uint64_t n) {
@@ -186,8 +193,9 @@ int32_t reserve_ctx(cs_shards* h, SearchCtx* c, uint32_t nq, uint32_t k, bool ho
 // (row stride of the gather buffer is the FULL nq).  src != null: the [nq, dim] queries are first brought to the
 // shard's device — from pinned host memory (src_device < 0) or from HBM of device src_device (the root of a
 // device-pointer search; a shard living on that device reads them in place).
+// masks != null: the masked search of that shard (index.hip index_search_masked_device) instead.
 int32_t enqueue_shard(cs_shards* h, SearchCtx* c, uint32_t s, uint32_t q0, uint32_t qn, uint32_t nq, uint32_t k,
-                      const float* src, int src_device) {
+                      const float* src, int src_device, const ShardMasks* masks = nullptr) {
     DeviceGuard g(h->devices[s]);
     ShardCtx& x = c->sh[s];
     const size_t qbytes = (size_t)nq * h->dim * sizeof(float);
@@ -204,8 +212,12 @@ int32_t enqueue_shard(cs_shards* h, SearchCtx* c, uint32_t s, uint32_t q0, uint3
     // its slot itself
     const bool local = !h->direct && (h->force_copy || h->devices[s] != h->root);
     uint64_t* dst = local ? x.d_keys + (size_t)q0 * k : slot;
-    CS_TRY(cs_index_search_device(h->idx[s], q + (size_t)q0 * h->dim, qn, h->dim, k, dst, nullptr, nullptr,
-                                  nullptr, x.stream));
+    if (masks)
+        CS_TRY(index_search_masked_device(h->idx[s], q + (size_t)q0 * h->dim, qn, k, masks->words[s].data(), masks->bits[s],
+                                          dst, x.stream));
+    else
+        CS_TRY(cs_index_search_device(h->idx[s], q + (size_t)q0 * h->dim, qn, h->dim, k, dst, nullptr, nullptr,
+                                      nullptr, x.stream));
     if (local)
         CS_HIP(hipMemcpyPeerAsync(slot, h->root, dst, h->devices[s], (size_t)qn * k * sizeof(uint64_t), x.stream));
     return CS_OK;
@@ -271,8 +283,9 @@ int32_t check_shards_search(const cs_shards* h, uint32_t nq, uint32_t dim, uint3
 
 // variants != null: after the shard merge the nq lists are merged as query variants (scan.hip merge_variants_kernel) and
 // out_cos / out_ids hold ONE list of k; variants[0] = count, variants[1] = high-confidence flag.
+// masks != null: every shard runs the masked search (never a batched path: nothing to rerun).
 int32_t shards_search_impl(cs_shards* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k, float* out_cos,
-                           uint32_t* out_ids, uint32_t* out_counts, uint32_t* variants) {
+                           uint32_t* out_ids, uint32_t* out_counts, uint32_t* variants, const ShardMasks* masks = nullptr) {
     CS_TRY(check_shards_search(h, nq, dim, k));
     if (!queries || !out_cos || !out_ids || !out_counts) return fail(CS_ERR_BAD_ARG, "null buffer");
     SearchCtx* c = take_ctx(h);
@@ -282,7 +295,7 @@ int32_t shards_search_impl(cs_shards* h, const float* queries, uint32_t nq, uint
         CS_TRY(order_behind_previous(h, c));
         memcpy(c->h_queries, queries, (size_t)nq * h->dim * sizeof(float));
         for (uint32_t s = 0; s < h->n; ++s) {
-            CS_TRY(enqueue_shard(h, c, s, 0, nq, nq, k, c->h_queries, -1));
+            CS_TRY(enqueue_shard(h, c, s, 0, nq, nq, k, c->h_queries, -1, masks));
             DeviceGuard g(h->devices[s]);
             CS_HIP(hipEventRecord(c->sh[s].done, c->sh[s].stream));
         }
@@ -306,7 +319,7 @@ int32_t shards_search_impl(cs_shards* h, const float* queries, uint32_t nq, uint
         CS_TRY(merge());
         c->merged_pending = false;  // every stream of the context is idle now
         bool again = false;
-        CS_TRY(rerun_overflowed(h, c, nq, k, &again));
+        if (!masks) CS_TRY(rerun_overflowed(h, c, nq, k, &again));
         if (again) CS_TRY(merge());
         if (variants) {
             unpack_keys(c->h_keys, 1, k, out_cos, out_ids, nullptr);
@@ -643,6 +656,70 @@ int32_t cs_shards_search_variants(cs_shards* h, const float* queries, uint32_t n
     if (!out_count) return fail(CS_ERR_BAD_ARG, "null buffer");
     uint32_t meta[2] = {0, 0};
     CS_TRY(shards_search_impl(h, queries, nq, dim, k, out_cos, out_ids, out_count, meta));
+    *out_count = meta[0];
+    if (out_high_confidence) *out_high_confidence = (int32_t)meta[1];
+    return CS_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// Argument checks of a masked shard search, then the mask restated per shard.  *empty: nothing is allowed (no launch).
+int32_t prepare_masks(cs_shards* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k, const uint32_t* allow,
+                      uint64_t allow_bits, const void* out_a, const void* out_b, const void* out_c, ShardMasks* m,
+                      bool* empty) {
+    CS_TRY(check_shards_search(h, nq, dim, k));
+    if (!queries || !out_a || !out_b || !out_c) return fail(CS_ERR_BAD_ARG, "null buffer");
+    if (!allow && allow_bits) return fail(CS_ERR_BAD_ARG, "allow is null");
+    m->words.resize(h->n);
+    m->bits.assign(h->n, 0);
+    *empty = true;
+    for (uint32_t s = 0; s < h->n; ++s) {
+        shard_mask(allow, allow_bits, h->next, h->stripe, h->n, s, m->words[s], &m->bits[s]);
+        if (m->bits[s]) *empty = false;
+    }
+    return CS_OK;
+}
+
+void fill_empty_lists(uint32_t nq, uint32_t k, float* out_cos, uint32_t* out_ids) {
+    for (size_t i = 0; i < (size_t)nq * k; ++i) { out_cos[i] = 0.0f; out_ids[i] = 0xFFFFFFFFu; }
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t cs_shards_search_masked(cs_shards* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                                const uint32_t* allow, uint64_t allow_bits, float* out_cos, uint32_t* out_ids,
+                                uint32_t* out_counts) {
+    ShardMasks m;
+    bool empty = true;
+    CS_TRY(prepare_masks(h, queries, nq, dim, k, allow, allow_bits, out_cos, out_ids, out_counts, &m, &empty));
+    if (empty) {
+        fill_empty_lists(nq, k, out_cos, out_ids);
+        memset(out_counts, 0, (size_t)nq * sizeof(uint32_t));
+        return CS_OK;
+    }
+    return shards_search_impl(h, queries, nq, dim, k, out_cos, out_ids, out_counts, nullptr, &m);
+}
+
+int32_t cs_shards_search_variants_masked(cs_shards* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                                         const uint32_t* allow, uint64_t allow_bits, float* out_cos, uint32_t* out_ids,
+                                         uint32_t* out_count, int32_t* out_high_confidence) {
+    if (nq > CS_MAX_VARIANTS) return fail(CS_ERR_BAD_ARG, "at most %u query variants per call, got %u", CS_MAX_VARIANTS, nq);
+    if (!out_count) return fail(CS_ERR_BAD_ARG, "null buffer");
+    ShardMasks m;
+    bool empty = true;
+    CS_TRY(prepare_masks(h, queries, nq, dim, k, allow, allow_bits, out_cos, out_ids, out_count, &m, &empty));
+    if (empty) {
+        fill_empty_lists(1, k, out_cos, out_ids);
+        *out_count = 0;
+        if (out_high_confidence) *out_high_confidence = 0;
+        return CS_OK;
+    }
+    uint32_t meta[2] = {0, 0};
+    CS_TRY(shards_search_impl(h, queries, nq, dim, k, out_cos, out_ids, out_count, meta, &m));
     *out_count = meta[0];
     if (out_high_confidence) *out_high_confidence = (int32_t)meta[1];
     return CS_OK;

@@ -148,10 +148,49 @@ class VectorStore {
     // store.rs:745
     bool is_indexed() const { return (sh_ ? cs_shards_is_built(sh_) : cs_index_is_built(h_)) != 0; }
 
+    // the mask of a masked search: bit id of word id / 32 for every allowed id below next_id; *bits = next_id
+    std::vector<uint32_t> allow_mask(const std::vector<uint32_t>& allowed_ids, uint64_t* bits) const {
+        const uint64_t next = sh_ ? cs_shards_next_id(sh_) : cs_index_next_id(h_);
+        std::vector<uint32_t> mask((size_t)((next + 31) / 32), 0u);
+        for (uint32_t id : allowed_ids)
+            if (id < next) mask[id >> 5] |= 1u << (id & 31);
+        *bits = mask.empty() ? 0 : next;
+        return mask;
+    }
+    std::vector<SearchResult> results(const std::vector<float>& cos, const std::vector<uint32_t>& ids, uint32_t count) const {
+        std::vector<SearchResult> out;
+        for (uint32_t j = 0; j < count; ++j) {
+            auto it = meta_.find(ids[j]);
+            if (it == meta_.end()) continue;  // store.rs:465
+            SearchResult r;
+            r.id = ids[j];
+            r.meta = it->second;
+            r.distance = cs_cos_to_distance(cos[j]);
+            r.score = 1.0f - r.distance;
+            out.push_back(std::move(r));
+        }
+        return out;
+    }
+
     // store.rs:431-486
     std::vector<SearchResult> search(const std::vector<float>& query_embedding, size_t limit) const {
         auto all = search_batch({query_embedding}, limit);
         return all.empty() ? std::vector<SearchResult>{} : all[0];
+    }
+    // filter_path done exactly (src/mcp/mod.rs:251-252,400-425): the best `limit` among the chunks `allowed_ids` names
+    // (cs_index_search_masked / cs_shards_search_masked)
+    std::vector<SearchResult> search(const std::vector<float>& query_embedding, size_t limit,
+                                     const std::vector<uint32_t>& allowed_ids) const {
+        std::vector<float> cos(limit);
+        std::vector<uint32_t> ids(limit), counts(1);
+        uint64_t bits = 0;
+        const std::vector<uint32_t> mask = allow_mask(allowed_ids, &bits);
+        const uint32_t dim = (uint32_t)query_embedding.size();
+        check(sh_ ? cs_shards_search_masked(sh_, query_embedding.data(), 1, dim, (uint32_t)limit, mask.data(), bits,
+                                            cos.data(), ids.data(), counts.data())
+                  : cs_index_search_masked(h_, query_embedding.data(), 1, dim, (uint32_t)limit, mask.data(), bits,
+                                           cos.data(), ids.data(), counts.data()));
+        return results(cos, ids, counts[0]);
     }
     // all query variants in one call (src/search/mod.rs:508-511)
     std::vector<std::vector<SearchResult>> search_batch(const std::vector<std::vector<float>>& queries,
@@ -187,6 +226,31 @@ class VectorStore {
     // search::search's vector leg in one call (src/search/mod.rs:508-611): every variant searched for `limit` rows, a
     // chunk found by several variants keeps its best score, the best `limit` distinct chunks best-first — merged on the
     // device; *high_confidence = the top five all have distance < 0.15 (the reference then skips its FTS leg).
+    // search_variants over the chunks `allowed_ids` names (cs_index_search_variants_masked)
+    std::vector<SearchResult> search_variants(const std::vector<std::vector<float>>& variants, size_t limit,
+                                              const std::vector<uint32_t>& allowed_ids,
+                                              bool* high_confidence = nullptr) const {
+        const size_t nq = variants.size();
+        if (nq == 0) return {};
+        const size_t qdim = variants[0].size();
+        std::vector<float> q;
+        for (const auto& v : variants) {
+            if (v.size() != qdim) throw Error(CS_ERR_BAD_ARG, "queries of unequal length");
+            q.insert(q.end(), v.begin(), v.end());
+        }
+        std::vector<float> cos(limit);
+        std::vector<uint32_t> ids(limit);
+        uint32_t count = 0;
+        int32_t flag = 0;
+        uint64_t bits = 0;
+        const std::vector<uint32_t> mask = allow_mask(allowed_ids, &bits);
+        check(sh_ ? cs_shards_search_variants_masked(sh_, q.data(), (uint32_t)nq, (uint32_t)qdim, (uint32_t)limit,
+                                                     mask.data(), bits, cos.data(), ids.data(), &count, &flag)
+                  : cs_index_search_variants_masked(h_, q.data(), (uint32_t)nq, (uint32_t)qdim, (uint32_t)limit, mask.data(),
+                                                    bits, cos.data(), ids.data(), &count, &flag));
+        if (high_confidence) *high_confidence = flag != 0;
+        return results(cos, ids, count);
+    }
     std::vector<SearchResult> search_variants(const std::vector<std::vector<float>>& variants, size_t limit,
                                               bool* high_confidence = nullptr) const {
         const size_t nq = variants.size();

@@ -34,6 +34,38 @@ def merge_variant_results(per_variant: Sequence[Sequence[SearchResult]], limit: 
     return merged
 
 
+def _trim_start(s: str, p: str) -> str:
+    while p and s.startswith(p):  # Rust's trim_start_matches: every repetition
+        s = s[len(p):]
+    return s
+
+
+def _trim_end(s: str, p: str) -> str:
+    while p and s.endswith(p):
+        s = s[:-len(p)]
+    return s
+
+
+def normalize_path_str(path: str) -> str:
+    """src/cache/file_meta.rs:23-25: the UNC prefix stripped, backslashes as forward slashes."""
+    return _trim_start(path, "\\\\?\\").replace("\\", "/")
+
+
+def path_matches(path: str, filter_path: str, project_root: str = "", mcp: bool = True) -> bool:
+    """The reference's filter_path test of one result path: both normalised, the project root stripped, a leading `/`
+    and `./` trimmed from the path and `./` from the filter, then a prefix test.  MCP (src/mcp/mod.rs:400-425) also
+    trims the filter's trailing `/`; the CLI (src/search/mod.rs:700-705, :728-738) does not."""
+    root = _trim_end(normalize_path_str(project_root), "/")
+    p = normalize_path_str(path)
+    if p.startswith(root):
+        p = p[len(root):]
+    p = _trim_start(_trim_start(p, "/"), "./")
+    f = _trim_start(normalize_path_str(filter_path), "./")
+    if mcp:
+        f = _trim_end(f, "/")
+    return p.startswith(f)
+
+
 def should_use_vector_only(results: Sequence[SearchResult], vector_only: bool) -> bool:
     """mod.rs:601-611: skip FTS when the top-5 all have distance < 0.15."""
     if vector_only:

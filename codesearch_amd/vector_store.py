@@ -129,6 +129,17 @@ def cos_to_score(cos):
     return np.float32(1.0) - cos_to_distance(cos)
 
 
+def allow_mask(chunk_ids, next_id: int) -> np.ndarray:
+    """The mask of a masked search (cs_index_search_masked): a bitmap over chunk ids [0, next_id), bit i = bit i & 31 of
+    word i >> 5, set for every id in `chunk_ids`.  Ids outside [0, next_id) are dropped."""
+    next_id = int(next_id)
+    words = np.zeros((next_id + 31) // 32, np.uint32)
+    ids = np.asarray(chunk_ids, np.int64).ravel()
+    ids = ids[(ids >= 0) & (ids < next_id)]
+    np.bitwise_or.at(words, ids >> 5, np.left_shift(np.uint32(1), (ids & 31).astype(np.uint32)))
+    return words
+
+
 # ---- the store ---------------------------------------------------------------------------------
 
 class VectorStore:
@@ -491,8 +502,15 @@ class VectorStore:
         the deleted rows (cs_index_build, from 10 % dead rows on), more in between."""
         return int(self._fn("stored_rows")(self._h))
 
-    def search_raw(self, queries, limit: int):
-        """-> (cos [nq, limit] f32, ids [nq, limit] u32, counts [nq] u32); rows best-first."""
+    def _mask_args(self, chunk_ids):
+        """(allow pointer, allow_bits, keep-alive) of a masked search over `chunk_ids`."""
+        nxt = self.next_id()
+        mask = allow_mask(chunk_ids, nxt)
+        return (mask.ctypes.data_as(u32p) if mask.size else None), (nxt if mask.size else 0), mask
+
+    def search_raw(self, queries, limit: int, chunk_ids=None):
+        """-> (cos [nq, limit] f32, ids [nq, limit] u32, counts [nq] u32); rows best-first.
+        chunk_ids: only these chunks are searched (cs_index_search_masked: the exact top `limit` among them)."""
         q = np.ascontiguousarray(queries, np.float32)
         if q.ndim == 1:
             q = q[None, :]
@@ -500,26 +518,32 @@ class VectorStore:
         cos = np.zeros((nq, max(limit, 1)), np.float32)
         ids = np.zeros((nq, max(limit, 1)), np.uint32)
         counts = np.zeros(nq, np.uint32)
-        _lib.check(self._fn("search")(self._h, q.ctypes.data_as(f32p), nq, dim, limit,
-                                             cos.ctypes.data_as(f32p), ids.ctypes.data_as(u32p),
-                                             counts.ctypes.data_as(u32p)))
+        if chunk_ids is None:
+            _lib.check(self._fn("search")(self._h, q.ctypes.data_as(f32p), nq, dim, limit,
+                                                 cos.ctypes.data_as(f32p), ids.ctypes.data_as(u32p),
+                                                 counts.ctypes.data_as(u32p)))
+        else:
+            allow, bits, _keep = self._mask_args(chunk_ids)
+            _lib.check(self._fn("search_masked")(self._h, q.ctypes.data_as(f32p), nq, dim, limit, allow, bits,
+                                                 cos.ctypes.data_as(f32p), ids.ctypes.data_as(u32p),
+                                                 counts.ctypes.data_as(u32p)))
         return cos, ids, counts
 
-    def search(self, query_embedding, limit: int) -> List[SearchResult]:
-        """store.rs:431-486.  Results whose metadata is missing are skipped (store.rs:465)."""
-        cos, ids, counts = self.search_raw(query_embedding, limit)
+    def search(self, query_embedding, limit: int, chunk_ids=None) -> List[SearchResult]:
+        """store.rs:431-486.  Results whose metadata is missing are skipped (store.rs:465).  chunk_ids: search_raw."""
+        cos, ids, counts = self.search_raw(query_embedding, limit, chunk_ids=chunk_ids)
         return self._results(cos[0], ids[0], int(counts[0]))
 
-    def search_batch(self, query_embeddings, limit: int) -> List[List[SearchResult]]:
-        """One call for all query variants (the par_iter of src/search/mod.rs:508-511)."""
-        cos, ids, counts = self.search_raw(query_embeddings, limit)
+    def search_batch(self, query_embeddings, limit: int, chunk_ids=None) -> List[List[SearchResult]]:
+        """One call for all query variants (the par_iter of src/search/mod.rs:508-511).  chunk_ids: search_raw."""
+        cos, ids, counts = self.search_raw(query_embeddings, limit, chunk_ids=chunk_ids)
         return [self._results(cos[i], ids[i], int(counts[i])) for i in range(len(counts))]
 
-    def search_variants(self, query_embeddings, limit: int):
+    def search_variants(self, query_embeddings, limit: int, chunk_ids=None):
         """search::search's vector leg (src/search/mod.rs:508-611) in one call: every variant searched for `limit`
         rows, union with a chunk keeping its best score, best `limit` distinct chunks best-first, merged on
         the device.  -> (results, high_confidence) where high_confidence is the early-termination predicate
-        (top five all distance < 0.15)."""
+        (top five all distance < 0.15).  chunk_ids: only these chunks are searched (search_raw)."""
         q = np.ascontiguousarray(query_embeddings, np.float32)
         if q.ndim == 1:
             q = q[None, :]
@@ -527,10 +551,22 @@ class VectorStore:
         cos = np.zeros(max(limit, 1), np.float32)
         ids = np.zeros(max(limit, 1), np.uint32)
         count, flag = C.c_uint32(), C.c_int32()
-        _lib.check(self._fn("search_variants")(self._h, q.ctypes.data_as(f32p), nq, dim, limit,
-                                                      cos.ctypes.data_as(f32p), ids.ctypes.data_as(u32p),
-                                                      C.byref(count), C.byref(flag)))
+        if chunk_ids is None:
+            _lib.check(self._fn("search_variants")(self._h, q.ctypes.data_as(f32p), nq, dim, limit,
+                                                          cos.ctypes.data_as(f32p), ids.ctypes.data_as(u32p),
+                                                          C.byref(count), C.byref(flag)))
+        else:
+            allow, bits, _keep = self._mask_args(chunk_ids)
+            _lib.check(self._fn("search_variants_masked")(self._h, q.ctypes.data_as(f32p), nq, dim, limit, allow, bits,
+                                                          cos.ctypes.data_as(f32p), ids.ctypes.data_as(u32p),
+                                                          C.byref(count), C.byref(flag)))
         return self._results(cos, ids, int(count.value)), bool(flag.value)
+
+    def chunk_ids_under(self, filter_path: str, project_root: str = "", mcp: bool = True) -> List[int]:
+        """Ids of the chunks whose metadata path passes the reference's filter_path rule (search.path_matches; MCP or
+        CLI form), ascending: the chunk_ids of a masked search narrowed to a directory."""
+        from .search import path_matches
+        return sorted(i for i, m in self._meta.items() if path_matches(m.path, filter_path, project_root, mcp))
 
     def _results(self, cos, ids, count) -> List[SearchResult]:
         out = []

@@ -177,6 +177,27 @@ CS_API int32_t cs_merge_variants_device(int32_t device, const uint64_t* d_keys, 
                                  uint64_t* d_out_keys, float* d_out_cos, uint32_t* d_out_ids,
                                  uint32_t* d_out_count, uint32_t* d_out_high_confidence, void* stream);
 
+/* Masked search — the exact form of the reference's `filter_path`: semantic_search runs store.search(q, limit * 3)
+ * and drops every hit outside the directory (src/mcp/mod.rs:251-252,400-425), so a directory holding a few percent
+ * of the chunks returns fewer than `limit` hits, often none.  Here only rows whose chunk id is allowed are scored:
+ *   allow      : bitmap over chunk ids, bit i = bit (i & 31) of allow[i >> 5] allows id i (absolute ids, as a
+ *                search returns them: from id_base on)
+ *   allow_bits : ids >= allow_bits are not allowed; 0 = nothing is (every count 0); allow == NULL with
+ *                allow_bits > 0 fails with CS_ERR_BAD_ARG
+ * Per query the k best live allowed rows, (cosine desc, id asc): the rows and cosines of cs_index_search on the
+ * streaming route over a fresh index of those rows alone, bit for bit.  out_counts[q] = min(k, live allowed rows).
+ * Deleted rows never come back, set bit or not; ids never issued are ignored.  Errors and limits are those of
+ * cs_index_search; concurrent calls with different masks are safe. */
+CS_API int32_t cs_index_search_masked(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                               const uint32_t* allow, uint64_t allow_bits,
+                               float* out_cos, uint32_t* out_ids, uint32_t* out_counts);
+/* cs_index_search_variants over the allowed rows: masked per-variant lists, then the variant merge (same
+ * high-confidence predicate).  nq <= CS_MAX_VARIANTS. */
+CS_API int32_t cs_index_search_variants_masked(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                                        const uint32_t* allow, uint64_t allow_bits,
+                                        float* out_cos, uint32_t* out_ids, uint32_t* out_count,
+                                        int32_t* out_high_confidence);
+
 /* Synchronises `stream` and reports in *overflowed whether any cs_index_search_device call of more
  * than 16 queries issued by this thread on it since the previous status call overflowed a candidate buffer
  * (its results are then incomplete); clears the condition. */
@@ -263,6 +284,16 @@ CS_API cs_index* cs_shards_shard_index(cs_shards* h, uint32_t shard);
  * variant merge (src/search/mod.rs:513-611) on the first device. */
 CS_API int32_t cs_shards_search_variants(cs_shards* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
                                   float* out_cos, uint32_t* out_ids, uint32_t* out_count, int32_t* out_high_confidence);
+/* cs_index_search_masked / cs_index_search_variants_masked over the sharded store (src/mcp/mod.rs:251-252,400-425):
+ * `allow` is over global ids; every shard searches with the mask restated in its own local ids, on its own stream,
+ * and the shard merge returns global ids. */
+CS_API int32_t cs_shards_search_masked(cs_shards* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                                const uint32_t* allow, uint64_t allow_bits,
+                                float* out_cos, uint32_t* out_ids, uint32_t* out_counts);
+CS_API int32_t cs_shards_search_variants_masked(cs_shards* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                                         const uint32_t* allow, uint64_t allow_bits,
+                                         float* out_cos, uint32_t* out_ids, uint32_t* out_count,
+                                         int32_t* out_high_confidence);
 CS_API int32_t cs_shards_read_rows(cs_shards* h, uint64_t first_id, uint64_t n, float* out_rows);
 
 /* Copy the rows of ids [id_base + first_row, id_base + first_row + n) back to host memory (test and
