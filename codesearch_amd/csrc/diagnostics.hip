@@ -258,7 +258,7 @@ int32_t cs_debug_gemm_q8_units(int32_t device, int32_t epilogue, const float* A,
                                const uint32_t* row_slot, uint32_t units, float* row_params, int32_t* rowsums) {
     if (!A || !W || !wscale || !bias || !C || !row_slot || (epilogue == 2 && !resid)) return fail(CS_ERR_BAD_ARG, "null buffer");
     if (epilogue != 2 && epilogue != 4 && epilogue != 5) return fail(CS_ERR_BAD_ARG, "unknown epilogue %d", epilogue);
-    if (M == 0 || units == 0 || N % 128 || !q8_rows_from_source(M, K))
+    if (M == 0 || units == 0 || N % 128 || !q8_rows_from_source(forward_knobs(), M, K))
         return fail(CS_ERR_UNSUPPORTED, "cs_debug_gemm_q8_units: M=%u N=%u K=%u is not a row-block product", M, N, K);
     for (uint32_t m = 0; m < M; ++m)
         if ((row_slot[m] & 0x7fffffffu) >= units || (m && (row_slot[m] & 0x7fffffffu) < (row_slot[m - 1] & 0x7fffffffu)))

@@ -75,6 +75,7 @@ static int32_t create_impl(const cs_bert_config* cfg, const float* params, uint6
     DeviceGuard g(device);
     cs_embedder* h = new cs_embedder();
     h->device = device;
+    (void)hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, device);  // (0 where the query fails: plan_streams)
     h->cfg = *cfg;
     cs_bert_layout(cfg, &h->off);
     const size_t H = cfg->hidden;

@@ -73,6 +73,7 @@ struct cs_embedder {
     std::shared_ptr<QueuePool> qpool;
     uint64_t next_ticket = 1;
     int device = 0;
+    int cus = 0;                    // the device's compute units, asked once at create (forward_plan.hpp plan_streams)
     cs_bert_config cfg{};
     cs_bert_offsets off{};
     float* d_params = nullptr;

@@ -2,6 +2,7 @@
 #pragma once
 
 #include "common.hpp"
+#include "forward_plan.hpp"
 
 #include "../../include/cs_bert_params.h"
 
@@ -66,7 +67,7 @@ int32_t launch_gemm_split(int epi, const _Float16* A, const _Float16* W, const f
                           hipStream_t s);
 // gemm_wide.hip: the same product as a persistent kernel over 128 x 384 tiles with one accumulator per output
 // (w_hi scaled by 2^11 in registers).  N % 384 == 0; weights must pass sh_weights_fit_wide (|w| < 31.98).
-bool gemm_wide_supported(uint32_t N, uint32_t K);
+// (gemm_wide_supported: forward_plan.hpp)
 // epilogue of launch_gemm_wide only: W = value and gate rows interleaved in groups of 16 ([N][K], N = 2 x gated width);
 // Cs [M][N/64][64] = value * silu(gate) in split form (gemm_wide.hip; nomic.hip holds the stand-alone form)
 constexpr int GW_OUT_SWIGLU = 17;
@@ -108,6 +109,9 @@ double gemm_wide_read_clock_ghz(double* main_cycles, double* epi_cycles);  // af
 #else
 constexpr int g_gemm_wide_ablation = 0, g_gemm_wide_shape = 0, g_gemm_wide_mfma = 0;
 #endif
+// The thresholds of the forward's route, read once per process (embedder_forward.hip forward_knobs_from_env): the plan decides
+// with them and the launchers check their arguments against the same values.
+const ForwardKnobs& forward_knobs();
 int32_t sh_weights_fit_wide(const _Float16* d_wsplit, uint64_t n_f16, uint32_t* d_scratch_flag, bool* ok, hipStream_t s);
 int32_t launch_synth_params(float* d_out, const cs_bert_config& cfg, uint64_t seed, hipStream_t s);
 

@@ -825,7 +825,7 @@ gemm_q8_skinny_kernel(const void* __restrict__ src, const float* __restrict__ ra
 // rides along as two more DMA instructions, the row block's metadata sits in LDS too, so the loop issues no ordinary
 // load at all.  Wave tile 64 x 32 (waves as 2 x 4); the C tile leaves in two 64-row halves through 32 KiB of LDS (or as
 // the 16 KiB s8 tile of the re-quantising pass).  One block per CU (134 KiB of LDS, <= 256 registers at two waves per SIMD).
-constexpr int QR_KC = 3;
+// (QR_KC = 3: forward_plan.hpp)
 constexpr int QR_WTILE = 128 * 128 * QR_KC;          // one n-tile of weights over all of K
 constexpr int QR_OUT_BYTES = 64 * 128 * 4;           // half a C tile in f32
 constexpr int QR_CM_BYTES = 128 * 16;                // an n-tile's column metadata (scale, zero point, column sum, bias)
@@ -1435,7 +1435,7 @@ template <class F, int... I>
 __device__ __forceinline__ void qn_static_for(std::integer_sequence<int, I...>, F&& f) {
     (f(std::integral_constant<int, I>{}), ...);
 }
-constexpr int QN_N = 384;
+// (QN_N = 384: forward_plan.hpp)
 constexpr int QN_STAGE = QN_N * 64;                    // 24,576 B
 // (the metadata sits at the bottom of LDS: every read of it is then one base register + an immediate offset; above 64 KiB the
 // offsets do not fit the instruction and the compiler keeps — and spills — an address register per (array, tile))
@@ -1833,12 +1833,8 @@ static uint32_t q8_persistent_grid(uint32_t slots) {
     return slots < want ? slots : want;
 }
 
-// The row-block kernel (gemm_q8_rows_kernel) takes K = 384 layers from rows_min_m rows on: below that a row block per CU
-// leaves most of the chip idle and the tile-per-block kernel spreads the same work over more CUs.  CS_Q8_ROWS=0: never.
-static bool q8_rows_takes(uint32_t M, uint32_t K) {
-    static const int min_m = [] { const char* e = cs_lab_env("CS_Q8_ROWS"); return e ? std::atoi(e) : 4096; }();
-    return K == 128 * QR_KC && min_m > 0 && M >= (uint32_t)min_m;
-}
+// The row-block kernel (gemm_q8_rows_kernel) takes what the forward's plan sends to it (forward_plan.hpp q8_rows_takes)
+static bool q8_rows_takes(uint32_t M, uint32_t K) { return q8_rows_takes(forward_knobs(), M, K); }
 template <int EPI, int SRC = QR_PREQUANT, bool MU = false>
 static int32_t launch_rows(const void* d_xq, const Q8RowMeta* d_rmeta, const int8_t* d_wq, const Q8ColMeta* d_cmeta,
                            const float* bias, const float* resid, float* C, _Float16* Cs, uint32_t M, uint32_t N,
@@ -1875,10 +1871,6 @@ int32_t launch_q8_stage_major(const int8_t* d_wq, uint32_t N, uint32_t K, int8_t
     return CS_OK;
 }
 
-bool q8_ln_fused_takes(uint32_t M, uint32_t N, uint32_t K) {
-    const char* e = cs_lab_env("CS_Q8_LN_FUSED");  // (read per call: tests and A/B scripts flip it mid-process)
-    return !(e && e[0] == '0') && N == (uint32_t)QN_N && (K == 384 || K == 1536) && q8_rows_takes(M, 384);
-}
 int32_t launch_gemm_q8_ln(int src_kind, const void* d_src, const Q8RowMeta* d_rmeta, const uint32_t* d_in_range, const int8_t* d_wq,
                           const Q8ColMeta* d_cmeta, float* X, const float* ln_g, const float* ln_b, float eps, uint32_t M, uint32_t K,
                           float* d_range_pairs, uint32_t* out_pairs, hipStream_t s, uint32_t* d_out_slot, bool w_stage_major) {
@@ -1964,11 +1956,6 @@ int32_t launch_gemm_q8(int epi, const int8_t* d_xq, const Q8RowMeta* d_rmeta, co
     return CS_OK;
 }
 
-bool q8_rows_from_source(uint32_t M, uint32_t K) {
-    static const bool on = [] { const char* e = cs_lab_env("CS_Q8_ROWS_SRC"); return !(e && e[0] == '0'); }();
-    return on && q8_rows_takes(M, K);
-}
-
 int32_t launch_q8_range(int src_kind, const void* d_src, uint32_t T, uint32_t K, uint32_t* d_range, hipStream_t s,
                         const float* d_range_pairs, uint32_t n_pairs) {
     if (T == 0) return CS_OK;
@@ -2011,11 +1998,6 @@ int32_t launch_gemm_q8_from_source(int epi, int src_kind, const void* d_src, con
     if (epi == SH_OUT_F32_RESID && src_kind == Q8_SRC_SPLIT)
         return launch_rows<SH_OUT_F32_RESID, Q8_SRC_SPLIT>(d_src, nullptr, d_wq, d_cmeta, bias, resid, C, Cs, M, N, d_flag, none, s, d_in_range);
     return fail(CS_ERR_UNSUPPORTED, "quantise-on-load product: epilogue %d from source kind %d is not built", epi, src_kind);
-}
-
-uint32_t q8_skinny_max_m() {
-    static const uint32_t v = [] { const char* e = cs_lab_env("CS_Q8_SKINNY_MAX_M"); return e ? (uint32_t)std::atoll(e) : 512u; }();
-    return v;
 }
 
 int32_t launch_gemm_q8_skinny(int epi, int src_kind, const void* d_src, const float* d_range_pairs, uint32_t n_pairs,

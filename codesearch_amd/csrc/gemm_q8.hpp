@@ -1,6 +1,6 @@
 // gemm_q8.hpp — launch interface of the dynamic-quantised dense layers (gemm_q8.hip).
 #pragma once
-#include "common.hpp"
+#include "encoder.hpp"  // forward_knobs: the launchers check their arguments with the plan's q8_rows_takes
 
 namespace cs {
 
@@ -55,10 +55,9 @@ int32_t launch_gemm_q8(int epi, const int8_t* d_xq, const Q8RowMeta* d_rmeta, co
                        const float* bias, const float* resid, float* C, _Float16* Cs, uint32_t M, uint32_t N, uint32_t K,
                        uint32_t* d_flag, hipStream_t s, int32_t* d_acc_dbg = nullptr);
 
-// From 4,096 rows a K = 384 layer can take the f32-class tensor itself (q8_rows_from_source): the product kernel's
-// blocks quantise their own rows on the way in, only the tensor's range (launch_q8_range: a reduction of the producer's
-// pairs, or a pass over the tensor) is needed first.  One quantisation unit only.  CS_Q8_ROWS_SRC=0: never.
-bool q8_rows_from_source(uint32_t M, uint32_t K);
+// From 4,096 rows a K = 384 layer can take the f32-class tensor itself (forward_plan.hpp q8_rows_from_source): the product
+// kernel's blocks quantise their own rows on the way in, only the tensor's range (launch_q8_range: a reduction of the
+// producer's pairs, or a pass over the tensor) is needed first.  One quantisation unit only.  CS_Q8_ROWS_SRC=0: never.
 int32_t launch_q8_range(int src_kind, const void* d_src, uint32_t T, uint32_t K, uint32_t* d_range, hipStream_t s,
                         const float* d_range_pairs = nullptr, uint32_t n_pairs = 0);
 // d_row_slot (optional): SEVERAL units in the tensor — d_in_range / d_range_out are then the units' slot arrays and every
@@ -89,7 +88,6 @@ int32_t launch_gemm_q8_slab_gelu_requant(const float* d_x, const uint32_t* d_in_
 // Q8_SRC_PREQUANT (d_src s8 [M][K], d_rmeta its rows; K = 384 | 1536).  X [M][384]: the residual on entry, the normalised rows on
 // return; d_range_pairs receives *out_pairs (lo, hi) pairs (one per 16 rows) for the quantisation that follows.
 constexpr int Q8_SRC_PREQUANT = -1;
-bool q8_ln_fused_takes(uint32_t M, uint32_t N, uint32_t K);
 int32_t launch_gemm_q8_ln(int src_kind, const void* d_src, const Q8RowMeta* d_rmeta, const uint32_t* d_in_range, const int8_t* d_wq,
                           const Q8ColMeta* d_cmeta, float* X, const float* ln_g, const float* ln_b, float eps, uint32_t M, uint32_t K,
                           float* d_range_pairs, uint32_t* out_pairs, hipStream_t s, uint32_t* d_out_slot = nullptr, bool w_stage_major = false);
@@ -102,10 +100,9 @@ int32_t launch_q8_stage_major(const int8_t* d_wq, uint32_t N, uint32_t K, int8_t
 int32_t launch_q8_range_units(const float* d_range_pairs, uint32_t pairs_per_seq, bool pairs_are_rows, const uint32_t* d_seq_unit,
                               const uint32_t* d_unit_len, uint32_t B, uint32_t units, uint32_t* d_range, hipStream_t s);
 
-// A few token rows (up to q8_skinny_max_m; CS_Q8_SKINNY_MAX_M, 0 = never): one launch per Linear — each block reduces
+// A few token rows (up to ForwardKnobs::q8_skinny_max_m; CS_Q8_SKINNY_MAX_M, 0 = never): one launch per Linear — each block reduces
 // the (lo, hi) pairs its input's producer left, quantises its 16 rows into LDS and multiplies one 16 x 16 tile with K
 // split over its waves.  With d_range_out every block leaves the (lo, hi) of what it stored (*out_pairs of them).
-uint32_t q8_skinny_max_m();
 int32_t launch_gemm_q8_skinny(int epi, int src_kind, const void* d_src, const float* d_range_pairs, uint32_t n_pairs,
                               const int8_t* d_wq, const Q8ColMeta* d_cmeta, const float* resid, float* C, _Float16* Cs, uint32_t M,
                               uint32_t N, uint32_t K, uint32_t* d_flag, float* d_range_out, uint32_t* out_pairs, hipStream_t s);

@@ -525,8 +525,6 @@ int32_t sh_weights_fit_wide(const _Float16* d_wsplit, uint64_t n_f16, uint32_t* 
     return CS_OK;
 }
 
-bool gemm_wide_supported(uint32_t N, uint32_t K) { return N % 192 == 0 && K % 32 == 0 && N > 0 && K > 0; }
-
 #ifdef CS_DIAGNOSTICS
 int g_gemm_wide_ablation = 0;  // diagnostics only (cs_debug_gemm_time)
 int g_gemm_wide_shape = 0;     // diagnostics only: 192 / 384 overrides CS_GEMM_WIDE_SHAPE

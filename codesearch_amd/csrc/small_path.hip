@@ -436,10 +436,6 @@ sp_attn_proj_kernel(const _Float16* __restrict__ qkvs, const int32_t* __restrict
 
 // sequences of L <= 32 tokens in a 384-wide, 12-head model, any number of them the small path takes: a 16-row tile then touches at
 // most 2 L <= 32 (L <= 16) or 64 consecutive token rows
-bool sp_attn_proj_supported(uint32_t H, uint32_t heads, uint32_t T, uint32_t L) {
-    return H == 384 && heads == 12 && T >= 1 && T <= SP_MAX_ROWS && L >= 1 && L <= 32 && T % L == 0;
-}
-
 int32_t launch_sp_attn_proj(const _Float16* qkvs, const int32_t* mask, const _Float16* W, const float* bias, const float* resid, float* C,
                             uint32_t T, uint32_t L, uint32_t H, uint32_t heads, uint32_t* flag, hipStream_t s) {
     if (!sp_attn_proj_supported(H, heads, T, L))
@@ -463,10 +459,6 @@ int32_t launch_sp_attn_proj(const _Float16* qkvs, const int32_t* mask, const _Fl
     }
     CS_HIP(hipGetLastError());
     return CS_OK;
-}
-
-bool small_path_supported(uint32_t H, uint32_t I, uint32_t T) {
-    return (H == 384 || H == 768 || H == 1024) && I == 4 * H && T >= 1 && T <= SP_MAX_ROWS;
 }
 
 // rows from which the dense layers take the wide form (a block = 16 x 64): CS_SMALL_WIDE_MIN_ROWS (laboratory knob; 0 = never)

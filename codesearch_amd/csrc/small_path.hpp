@@ -2,10 +2,9 @@
 #pragma once
 
 #include "encoder.hpp"
+#include "forward_plan.hpp"  // SP_MAX_ROWS, small_path_supported, sp_attn_proj_supported
 
 namespace cs {
-
-constexpr uint32_t SP_MAX_ROWS = 256;  // token rows this path takes (workspace: 5 x SP_MAX_ROWS x H floats)
 
 struct SpLnGemmArgs {
     // prologue 0: rows of Y [T, H] f32
@@ -30,7 +29,6 @@ struct SpLnGemmArgs {
     uint32_t* flag;
 };
 
-bool small_path_supported(uint32_t H, uint32_t I, uint32_t T);
 // epi: SH_OUT_SPLIT | SH_OUT_SPLIT_GELU; pro: 0 | 1 | 2 (above)
 int32_t launch_sp_ln_gemm(int epi, int pro, const SpLnGemmArgs& a, uint32_t H, hipStream_t s);
 // parts[ks][T][N] = A[:, K slice ks] W[:, K slice ks]^T for the four quarters of K = 4 H (A [T][K/32][64], W [N][K/32][64])
@@ -39,7 +37,6 @@ int32_t launch_sp_partial(const _Float16* A, const _Float16* W, float* parts, ui
 // E3 + E4 in one launch for sequences of up to 32 tokens of a 384-wide, 12-head model (sp_attn_proj_kernel): C [T][384] =
 // attention(qkvs) W^T + bias + resid; qkvs [T][36][64] split form (Q heads | K heads | V heads), mask [T] (row-major [B][L]),
 // W [384][12][64] split form
-bool sp_attn_proj_supported(uint32_t H, uint32_t heads, uint32_t T, uint32_t L);
 int32_t launch_sp_attn_proj(const _Float16* qkvs, const int32_t* mask, const _Float16* W, const float* bias, const float* resid, float* C,
                             uint32_t T, uint32_t L, uint32_t H, uint32_t heads, uint32_t* flag, hipStream_t s);
 
