@@ -17,3 +17,4 @@ from .vector_store import (  # noqa: F401
 )
 from .bert_params import POOL_CLS, POOL_MEAN, BertConfig  # noqa: F401
 from .embedder import EmbedderReplicas, FastEmbedder, ModelType  # noqa: F401
+from .rerank import RERANK_WEIGHT, RRF_WEIGHT, NeuralReranker  # noqa: F401

@@ -156,6 +156,8 @@ SIGNATURES = {
     "cs_tokenizer_token_to_id": (C.c_int32, [vp, C.c_char_p]),
     "cs_tokenizer_encode_batch": (C.c_int32, [vp, C.c_char_p, u64p, C.c_uint32, C.c_uint32, i32p, i32p,
                                               C.c_uint32, u32p]),
+    "cs_tokenizer_encode_pairs": (C.c_int32, [vp, C.c_char_p, u64p, C.c_uint32, C.c_char_p, u64p, C.c_uint32, C.c_uint32, i32p, i32p,
+                                              i32p, C.c_uint32, u32p]),
     "cs_embedder_embed_texts": (C.c_int32, [vp, vp, C.c_char_p, u64p, C.c_uint64, C.c_uint32, f32p, i32p]),
     "cs_embedder_embed_texts_device": (C.c_int32, [vp, vp, C.c_char_p, u64p, C.c_uint64, C.c_uint32, vp, i32p]),
     "cs_embedder_submit_texts": (C.c_int32, [vp, vp, C.c_char_p, u64p, C.c_uint64, u64p]),
@@ -177,6 +179,16 @@ SIGNATURES = {
     "cs_embedders_embed_ids": (C.c_int32, [vp, i32p, i32p, C.c_uint64, C.c_uint32, C.c_uint32, f32p, i32p]),
     "cs_embedders_index_texts": (C.c_int32, [vp, vp, vp, C.c_char_p, u64p, C.c_uint64, C.c_uint32, u32p, i32p]),
     "cs_embedders_index_ids": (C.c_int32, [vp, vp, i32p, i32p, C.c_uint64, C.c_uint32, C.c_uint32, u32p, i32p]),
+    "cs_rerank_head_count": (C.c_uint64, [C.POINTER(BertConfig)]),
+    "cs_reranker_create": (C.c_int32, [C.POINTER(BertConfig), f32p, f32p, C.c_uint64, C.c_int32, C.POINTER(vp)]),
+    "cs_rerank_head_from_safetensors": (C.c_int32, [C.c_char_p, C.POINTER(BertConfig), f32p, C.c_uint64]),
+    "cs_reranker_create_from_dir": (C.c_int32, [C.c_char_p, C.c_int32, C.POINTER(vp)]),
+    "cs_reranker_destroy": (None, [vp]),
+    "cs_reranker_embedder": (vp, [vp]),
+    "cs_reranker_score_ids": (C.c_int32, [vp, i32p, i32p, i32p, C.c_uint64, C.c_uint32, C.c_uint32, f32p, i32p]),
+    "cs_reranker_rerank_texts": (C.c_int32, [vp, vp, C.c_char_p, C.c_char_p, u64p, C.c_uint64, C.c_uint32, f32p, u32p, f32p]),
+    "cs_rerank_order": (C.c_int32, [f32p, C.c_uint64, u32p, f32p]),
+    "cs_rerank_blend": (C.c_int32, [f32p, f32p, C.c_uint64, u32p, f32p]),
 }
 
 # include/codesearch_gpu_diag.h: exported by libcsgpu_diag.so only (operator-level parity tests, benchmarks/)

@@ -10,6 +10,8 @@
 #include <unordered_map>
 #include <vector>
 
+#include "pair_form.hpp"
+
 struct cs_tokenizer;
 
 namespace cs {
@@ -32,6 +34,7 @@ struct BpeSpec {
     struct Added { std::string text; int32_t id = -1; bool lstrip = false, rstrip = false, normalized = false; };
     std::vector<Added> added;
     int32_t bos = -1, eos = -1, pad = -1;                          // <bos> $A <eos> (RobertaProcessing / TemplateProcessing); -1 = none
+    PairForm pair;                                                 // the post-processor's pair form (cs_tokenizer_encode_pairs)
 };
 
 class BpeEngine {
@@ -44,6 +47,7 @@ public:
     int32_t pad() const { return spec_.pad; }
     int32_t bos() const { return spec_.bos; }
     int32_t eos() const { return spec_.eos; }
+    const PairForm& pair() const { return spec_.pair; }
     uint32_t specials() const { return (spec_.bos >= 0) + (spec_.eos >= 0); }
 
 private:

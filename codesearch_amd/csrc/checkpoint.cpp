@@ -628,17 +628,12 @@ int32_t cs_bert_config_from_dir(const char* model_dir, int32_t pooling, cs_bert_
     return CS_OK;
 }
 
-int32_t cs_bert_params_from_safetensors(const char* path, const cs_bert_config* cfg, float* params,
-                                        uint64_t n_params) {
-    if (!path || !cfg || !params) return fail(CS_ERR_BAD_ARG, "null argument");
-    cs_bert_offsets o;
-    cs_bert_layout(cfg, &o);
-    if (n_params != o.total)
-        return fail(CS_ERR_BAD_ARG, "Failed to initialize embedding model: expected %llu parameters, got %llu",
-                    (unsigned long long)o.total, (unsigned long long)n_params);
+// Opens a safetensors file and reads its header: the tensors by name and the offset of the data section.  *out_f is the
+// caller's to close on CS_OK.
+static int32_t open_safetensors(const char* path, FILE** out_f, std::map<std::string, TensorRef>& have, uint64_t& data0) {
     FILE* f = std::fopen(path, "rb");
     if (!f) return fail(CS_ERR_BAD_ARG, "Failed to initialize embedding model: cannot open %s", path);
-    struct Closer { FILE* f; ~Closer() { std::fclose(f); } } closer{f};
+    struct Closer { FILE* f; bool keep = false; ~Closer() { if (!keep) std::fclose(f); } } closer{f};
     unsigned char lenb[8];
     if (std::fread(lenb, 1, 8, f) != 8)
         return fail(CS_ERR_BAD_ARG, "Failed to initialize embedding model: %s is not a safetensors file", path);
@@ -653,7 +648,6 @@ int32_t cs_bert_params_from_safetensors(const char* path, const cs_bert_config* 
     const Json root = jp.value();
     if (!jp.ok || root.kind != Json::Obj)
         return fail(CS_ERR_BAD_ARG, "Failed to initialize embedding model: %s has a malformed header", path);
-    std::map<std::string, TensorRef> have;
     for (const auto& kv : root.obj) {
         if (kv.first == "__metadata__" || kv.second.kind != Json::Obj) continue;
         const Json *dt = kv.second.get("dtype"), *sh = kv.second.get("shape"), *off = kv.second.get("data_offsets");
@@ -675,7 +669,57 @@ int32_t cs_bert_params_from_safetensors(const char* path, const cs_bert_config* 
         if (!sane) continue;
         have[kv.first] = std::move(t);
     }
-    const uint64_t data0 = 8 + hlen;
+    data0 = 8 + hlen;
+    closer.keep = true;
+    *out_f = f;
+    return CS_OK;
+}
+
+// `count` elements of tensor t from element `skip` on, as f32 (F32 / F16 / BF16 files); file_count = the elements its shape implies
+static int32_t read_tensor_f32(FILE* f, uint64_t data0, const TensorRef& t, const char* name, const char* path, uint64_t file_count,
+                               uint64_t skip, uint64_t count, float* dst, std::vector<unsigned char>& raw) {
+    const uint32_t esz = t.dtype == "F32" ? 4 : (t.dtype == "F16" || t.dtype == "BF16") ? 2 : 0;
+    if (!esz)
+        return fail(CS_ERR_UNSUPPORTED, "Failed to initialize embedding model: %s has dtype %s (F32, F16, BF16 only)",
+                    name, t.dtype.c_str());
+    if (t.end < t.begin || t.end - t.begin != file_count * esz)
+        return fail(CS_ERR_BAD_ARG, "Failed to initialize embedding model: %s has inconsistent data_offsets", name);
+    if (fseeko(f, (off_t)(data0 + t.begin + skip * esz), SEEK_SET) != 0)
+        return fail(CS_ERR_BAD_ARG, "Failed to initialize embedding model: %s is truncated", path);
+    if (esz == 4) {
+        if (std::fread(dst, 4, count, f) != count)
+            return fail(CS_ERR_BAD_ARG, "Failed to initialize embedding model: %s is truncated", path);
+    } else {
+        raw.resize(count * 2);
+        if (std::fread(raw.data(), 2, count, f) != count)
+            return fail(CS_ERR_BAD_ARG, "Failed to initialize embedding model: %s is truncated", path);
+        const bool bf = t.dtype == "BF16";
+        for (uint64_t i = 0; i < count; ++i) {
+            const uint16_t v = (uint16_t)(raw[2 * i] | (raw[2 * i + 1] << 8));
+            if (bf) {
+                const uint32_t bits = (uint32_t)v << 16;
+                std::memcpy(dst + i, &bits, 4);
+            } else {
+                dst[i] = half_to_float(v);
+            }
+        }
+    }
+    return CS_OK;
+}
+
+int32_t cs_bert_params_from_safetensors(const char* path, const cs_bert_config* cfg, float* params,
+                                        uint64_t n_params) {
+    if (!path || !cfg || !params) return fail(CS_ERR_BAD_ARG, "null argument");
+    cs_bert_offsets o;
+    cs_bert_layout(cfg, &o);
+    if (n_params != o.total)
+        return fail(CS_ERR_BAD_ARG, "Failed to initialize embedding model: expected %llu parameters, got %llu",
+                    (unsigned long long)o.total, (unsigned long long)n_params);
+    FILE* f = nullptr;
+    std::map<std::string, TensorRef> have;
+    uint64_t data0 = 0;
+    CS_TRY(open_safetensors(path, &f, have, data0));
+    struct Closer { FILE* f; ~Closer() { std::fclose(f); } } closer{f};
     if (cfg->arch == CS_ARCH_MODERN) return modern_params_from_safetensors(f, have, data0, *cfg, params, path);
     std::vector<unsigned char> raw;
     bool jina_first_file = false;
@@ -686,6 +730,7 @@ int32_t cs_bert_params_from_safetensors(const char* path, const cs_bert_config* 
         auto it = have.find(w.name);
         if (it == have.end()) it = have.find("bert." + w.name);
         if (it == have.end()) it = have.find("model." + w.name);
+        if (it == have.end()) it = have.find("roberta." + w.name);  // (RobertaForSequenceClassification: cs_reranker_create_from_dir)
         uint64_t count = 1;
         for (uint64_t d : w.shape) count *= d;
         if (it == have.end()) {
@@ -709,33 +754,7 @@ int32_t cs_bert_params_from_safetensors(const char* path, const cs_bert_config* 
             return fail(CS_ERR_DIM_MISMATCH, "Failed to initialize embedding model: %s has shape [%s], config.json implies [%s]",
                         w.name.c_str(), got.c_str(), exp.c_str());
         }
-        const uint32_t esz = t.dtype == "F32" ? 4 : (t.dtype == "F16" || t.dtype == "BF16") ? 2 : 0;
-        if (!esz)
-            return fail(CS_ERR_UNSUPPORTED, "Failed to initialize embedding model: %s has dtype %s (F32, F16, BF16 only)",
-                        w.name.c_str(), t.dtype.c_str());
-        if (t.end < t.begin || t.end - t.begin != file_count * esz)
-            return fail(CS_ERR_BAD_ARG, "Failed to initialize embedding model: %s has inconsistent data_offsets", w.name.c_str());
-        if (fseeko(f, (off_t)(data0 + t.begin + skip * esz), SEEK_SET) != 0)
-            return fail(CS_ERR_BAD_ARG, "Failed to initialize embedding model: %s is truncated", path);
-        float* dst = params + w.off;
-        if (esz == 4) {
-            if (std::fread(dst, 4, count, f) != count)
-                return fail(CS_ERR_BAD_ARG, "Failed to initialize embedding model: %s is truncated", path);
-        } else {
-            raw.resize(count * 2);
-            if (std::fread(raw.data(), 2, count, f) != count)
-                return fail(CS_ERR_BAD_ARG, "Failed to initialize embedding model: %s is truncated", path);
-            const bool bf = t.dtype == "BF16";
-            for (uint64_t i = 0; i < count; ++i) {
-                const uint16_t v = (uint16_t)(raw[2 * i] | (raw[2 * i + 1] << 8));
-                if (bf) {
-                    const uint32_t bits = (uint32_t)v << 16;
-                    std::memcpy(dst + i, &bits, 4);
-                } else {
-                    dst[i] = half_to_float(v);
-                }
-            }
-        }
+        CS_TRY(read_tensor_f32(f, data0, t, w.name.c_str(), path, file_count, skip, count, params + w.off, raw));
     }
     return CS_OK;
 }
@@ -793,6 +812,101 @@ int32_t cs_embedder_create_from_dir(const char* model_dir, int32_t pooling, int3
     return cs_embedder_create(&cfg, params.data(), 0, device, out);
 }
 
+// ---- a cross-encoder's score head (cs_reranker_*) ----
+// BertForSequenceClassification keeps it as pooler.dense.{weight,bias} (behind the encoder's prefix) + classifier.{weight,bias};
+// RobertaForSequenceClassification as classifier.dense.* + classifier.out_proj.*: the same dense -> tanh -> projection.
+int32_t cs_rerank_head_from_safetensors(const char* path, const cs_bert_config* cfg, float* head, uint64_t n_head) {
+    if (!path || !cfg || !head) return fail(CS_ERR_BAD_ARG, "null argument");
+    const uint64_t H = cfg->hidden;
+    if (n_head != H * H + 2 * H + 1)
+        return fail(CS_ERR_BAD_ARG, "Failed to initialize reranker model: expected %llu head parameters, got %llu",
+                    (unsigned long long)(H * H + 2 * H + 1), (unsigned long long)n_head);
+    FILE* f = nullptr;
+    std::map<std::string, TensorRef> have;
+    uint64_t data0 = 0;
+    CS_TRY(open_safetensors(path, &f, have, data0));
+    struct Closer { FILE* f; ~Closer() { std::fclose(f); } } closer{f};
+    auto find = [&](const std::string& name) -> const TensorRef* {
+        for (const char* prefix : {"", "bert.", "roberta.", "model."}) {
+            auto it = have.find(prefix + name);
+            if (it != have.end()) return &it->second;
+        }
+        return nullptr;
+    };
+    const bool roberta = find("classifier.out_proj.weight") != nullptr;
+    const std::string names[4] = {roberta ? "classifier.dense.weight" : "pooler.dense.weight", roberta ? "classifier.dense.bias" : "pooler.dense.bias",
+                                  roberta ? "classifier.out_proj.weight" : "classifier.weight", roberta ? "classifier.out_proj.bias" : "classifier.bias"};
+    const std::vector<uint64_t> shapes[4] = {{H, H}, {H}, {1, H}, {1}};
+    uint64_t off = 0;
+    std::vector<unsigned char> raw;
+    for (int i = 0; i < 4; ++i) {
+        const TensorRef* t = find(names[i]);
+        if (!t)
+            return fail(CS_ERR_BAD_ARG, "Failed to initialize reranker model: %s holds no score head (tensor %s is missing; "
+                        "pooler.dense + classifier or classifier.dense + classifier.out_proj)", path, names[i].c_str());
+        uint64_t count = 1;
+        for (uint64_t d : shapes[i]) count *= d;
+        if (i >= 2 && t->shape.size() == shapes[i].size() && t->shape[0] != 1 && (i == 3 || t->shape[1] == H))
+            return fail(CS_ERR_UNSUPPORTED, "Failed to initialize reranker model: num_labels %llu (a cross-encoder scores with ONE label)",
+                        (unsigned long long)t->shape[0]);
+        if (t->shape != shapes[i]) {
+            std::string got;
+            for (uint64_t d : t->shape) got += (got.empty() ? "" : ", ") + std::to_string(d);
+            return fail(CS_ERR_DIM_MISMATCH, "Failed to initialize reranker model: %s has shape [%s], hidden size %llu implies another",
+                        names[i].c_str(), got.c_str(), (unsigned long long)H);
+        }
+        CS_TRY(read_tensor_f32(f, data0, *t, names[i].c_str(), path, count, 0, count, head + off, raw));
+        off += count;
+    }
+    return CS_OK;
+}
+
+}  // extern "C"
+
+// The host half of cs_reranker_create_from_dir (reranker.hip): the directory's configuration, encoder parameters and head —
+// everything it refuses is refused here, before a device is asked for.
+int32_t cs::reranker_files_from_dir(const char* model_dir, cs_bert_config* out_cfg, std::vector<float>& params, std::vector<float>& head) {
+    if (!model_dir) return fail(CS_ERR_BAD_ARG, "null model directory");
+    cs_bert_config cfg;
+    CS_TRY(cs_bert_config_from_dir(model_dir, CS_POOL_CLS, &cfg));
+    if (cfg.arch == CS_ARCH_MODERN)
+        return fail(CS_ERR_UNSUPPORTED, "Failed to initialize reranker model: the ModernBERT encoder is not built as a cross-encoder");
+    std::string text;
+    if (read_file(std::string(model_dir) + "/config.json", text, 1 << 24)) {
+        JsonParser jp{text.data(), text.data() + text.size()};
+        const Json root = jp.value();
+        if (jp.ok && root.kind == Json::Obj) {
+            double labels = -1.0;
+            if (const Json* nl = root.get("num_labels")) { if (nl->kind == Json::Num) labels = nl->num; }
+            else if (const Json* il = root.get("id2label")) { if (il->kind == Json::Obj) labels = (double)il->obj.size(); }
+            if (labels >= 0.0 && labels != 1.0)
+                return fail(CS_ERR_UNSUPPORTED, "Failed to initialize reranker model: num_labels %g (a cross-encoder scores with ONE label)", labels);
+        }
+    }
+    bool have_st = false;
+    const std::string file = model_file_in(model_dir, have_st);
+    if (file.empty())
+        return fail(CS_ERR_BAD_ARG, "Failed to initialize reranker model: %s holds no model.safetensors", model_dir);
+    if (!have_st) {
+        if (file.find("quantized") != std::string::npos)
+            return fail(CS_ERR_UNSUPPORTED, "Failed to initialize reranker model: quantised cross-encoders are not built (%s)", file.c_str());
+        return fail(CS_ERR_UNSUPPORTED, "Failed to initialize reranker model: the score head is read from model.safetensors only, "
+                    "not from an ONNX export (%s)", file.c_str());
+    }
+    try {
+        params.resize(cs_bert_param_count(&cfg));
+        head.resize((size_t)cfg.hidden * cfg.hidden + 2 * (size_t)cfg.hidden + 1);
+    } catch (const std::bad_alloc&) {
+        return fail(CS_ERR_OOM, "out of host memory for the model's parameters");
+    }
+    CS_TRY(cs_rerank_head_from_safetensors(file.c_str(), &cfg, head.data(), head.size()));
+    CS_TRY(cs_bert_params_from_safetensors(file.c_str(), &cfg, params.data(), params.size()));
+    *out_cfg = cfg;
+    return CS_OK;
+}
+
+extern "C" {
+
 // ---- tokenizer.json with a SentencePiece-unigram model (the XLM-R vocabulary of the registry's multilingual entries) ----
 // Read into a cs::UnigramSpec (unigram.hpp) — every component must be one unigram.cpp restates, anything else is refused:
 //   model        type Unigram, unk_id, vocab [[piece, score], ...], byte_fallback false
@@ -821,6 +935,44 @@ static bool base64_decode(const std::string& in, std::string& out) {
         }
     }
     return true;
+}
+
+// TemplateProcessing's `pair` for cs_tokenizer_encode_pairs.  `single` is <bos> $A <eos> (both given): the pair must then be
+// <bos> $A <eos> $B <eos> or <bos> $A <eos> <eos> $B <eos>, with whatever type ids the file gives; anything else is refused.
+// A file without `pair`, or whose `single` lacks <bos> or <eos>, or whose `pair` is the bare $A $B the library writes when the
+// file's author gave none, has no pair form (encode_pairs refuses, the handle works as it always did).
+static int32_t template_pair(const Json& pp, const std::string& bos, const std::string& eos, cs::PairForm& out) {
+    out = cs::PairForm();
+    const Json* pair = pp.get("pair");
+    if (!pair || pair->kind != Json::Arr || bos.empty() || eos.empty()) return CS_OK;
+    std::string form;          // one letter per piece: b / e = the specials, A / B = the sequences, ? = anything else
+    std::vector<int32_t> types;
+    for (const Json& e : pair->arr) {
+        const Json* st = e.kind == Json::Obj ? e.get("SpecialToken") : nullptr;
+        const Json* sq = e.kind == Json::Obj ? e.get("Sequence") : nullptr;
+        const Json* in = st && st->kind == Json::Obj ? st : (sq && sq->kind == Json::Obj ? sq : nullptr);
+        const Json* id = in ? in->get("id") : nullptr;
+        const Json* ty = in ? in->get("type_id") : nullptr;
+        char c = '?';
+        if (id && id->kind == Json::Str) {
+            if (in == st) c = id->str == bos ? 'b' : (id->str == eos ? 'e' : '?');
+            else c = id->str == "A" ? 'A' : (id->str == "B" ? 'B' : '?');
+        }
+        if (bos == eos && c == 'b' && !form.empty()) c = 'e';
+        form.push_back(c);
+        types.push_back(ty && ty->kind == Json::Num && ty->num >= 0 && ty->num < 65536.0 ? (int32_t)ty->num : -1);
+    }
+    if (form == "AB") return CS_OK;  // the library's default for a template given without a pair: no pair form
+    if (form == "bAeBe") out.kind = cs::PairForm::BERT;
+    else if (form == "bAeeBe") out.kind = cs::PairForm::ROBERTA;
+    else
+        return fail(CS_ERR_UNSUPPORTED, "Failed to initialize embedding model: TemplateProcessing `pair` is neither <bos> $A <eos> $B <eos> "
+                                        "nor <bos> $A <eos> <eos> $B <eos>");
+    for (size_t i = 0; i < types.size(); ++i) {
+        if (types[i] < 0) return fail(CS_ERR_UNSUPPORTED, "Failed to initialize embedding model: TemplateProcessing `pair` has a piece without a type_id");
+        out.types[i] = types[i];
+    }
+    return CS_OK;
 }
 
 static int32_t unigram_norm(const Json& nz, std::vector<cs::UnigramSpec::Norm>& out) {
@@ -986,6 +1138,7 @@ static int32_t unigram_from_json(const Json& root, const Json& model, const char
             const Json* seq = single->arr[1].kind == Json::Obj ? single->arr[1].get("Sequence") : nullptr;
             if (!special(single->arr[0], bos) || !special(single->arr[2], eos) || !seq)
                 return fail(CS_ERR_UNSUPPORTED, "Failed to initialize embedding model: TemplateProcessing `single` is not <bos> $A <eos>");
+            CS_TRY(template_pair(*pp, bos, eos, spec.pair));
         }
     } else {
         return fail(CS_ERR_UNSUPPORTED, "Failed to initialize embedding model: unigram tokenizer.json without a post_processor");
@@ -1043,7 +1196,7 @@ static int32_t bpe_pre(const Json& pj, std::vector<cs::BpeSpec::Pre>& out) {
     return CS_OK;
 }
 
-static int32_t bpe_post(const Json& pp, std::string& bos, std::string& eos) {
+static int32_t bpe_post(const Json& pp, std::string& bos, std::string& eos, cs::PairForm& pair) {
     if (pp.kind == Json::Null) return CS_OK;
     if (pp.kind != Json::Obj) return fail(CS_ERR_BAD_ARG, "Failed to initialize embedding model: tokenizer.json post_processor is not an object");
     const Json* ty = pp.get("type");
@@ -1052,7 +1205,7 @@ static int32_t bpe_post(const Json& pp, std::string& bos, std::string& eos) {
     if (t == "Sequence") {
         const Json* list = pp.get("processors");
         if (!list || list->kind != Json::Arr) return fail(CS_ERR_BAD_ARG, "Failed to initialize embedding model: post_processor Sequence without a list");
-        for (const Json& e : list->arr) CS_TRY(bpe_post(e, bos, eos));
+        for (const Json& e : list->arr) CS_TRY(bpe_post(e, bos, eos, pair));
         return CS_OK;
     }
     if (t == "RobertaProcessing" || t == "BertProcessing") {
@@ -1064,6 +1217,7 @@ static int32_t bpe_post(const Json& pp, std::string& bos, std::string& eos) {
         };
         if (!first("cls", bos) || !first("sep", eos))
             return fail(CS_ERR_BAD_ARG, "Failed to initialize embedding model: %s without cls / sep", t.c_str());
+        pair = t == "RobertaProcessing" ? cs::PairForm::roberta() : cs::PairForm::bert();
         return CS_OK;
     }
     if (t == "TemplateProcessing") {
@@ -1085,7 +1239,7 @@ static int32_t bpe_post(const Json& pp, std::string& bos, std::string& eos) {
         else if (a.size() == 2 && is_seq(a[0]) && special(a[1], eos)) ok = true;                       // $A <eos>
         else if (a.size() == 3 && special(a[0], bos) && is_seq(a[1]) && special(a[2], eos)) ok = true; // <bos> $A <eos>
         if (!ok) return fail(CS_ERR_UNSUPPORTED, "Failed to initialize embedding model: TemplateProcessing `single` is not [<bos>] $A [<eos>]");
-        return CS_OK;
+        return template_pair(pp, a.size() == 3 ? bos : std::string(), a.size() == 3 ? eos : std::string(), pair);
     }
     return fail(CS_ERR_UNSUPPORTED, "Failed to initialize embedding model: post_processor \"%s\" is not built for BPE tokenizers", t.c_str());
 }
@@ -1171,7 +1325,7 @@ static int32_t bpe_from_json(const Json& root, const Json& model, const char* js
                 spec.added.push_back(std::move(a));
             }
     std::string bos, eos;
-    if (const Json* pp = root.get("post_processor")) CS_TRY(bpe_post(*pp, bos, eos));
+    if (const Json* pp = root.get("post_processor")) CS_TRY(bpe_post(*pp, bos, eos, spec.pair));
     auto id_of = [&](const std::string& tok) -> int32_t {
         if (tok.empty()) return -1;
         auto it = added_ids.find(tok);
@@ -1283,7 +1437,15 @@ int32_t cs_tokenizer_create_from_json(const char* json_path, uint32_t max_length
         else lines += "[unused-id-" + std::to_string(i) + "]";  // a hole in the id space: never produced
         lines.push_back('\n');
     }
-    return cs_tokenizer_create(lines.data(), lines.size(), lowercase, max_length, out);
+    // the pair form: BertProcessing's unless a TemplateProcessing spells one out
+    cs::PairForm pair = cs::PairForm::bert();
+    if (const Json* pp = root.get("post_processor"))
+        if (pp->kind == Json::Obj)
+            if (const Json* ty = pp->get("type"))
+                if (ty->kind == Json::Str && ty->str == "TemplateProcessing") CS_TRY(template_pair(*pp, "[CLS]", "[SEP]", pair));
+    CS_TRY(cs_tokenizer_create(lines.data(), lines.size(), lowercase, max_length, out));
+    cs::tokenizer_set_pair(*out, pair);
+    return CS_OK;
 }
 
 // What fastembed builds its tokenizer from, in a model directory: tokenizer.json when present (truncation at

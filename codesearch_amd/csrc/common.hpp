@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/codesearch_gpu.h"
+#include "pair_form.hpp"
 
 namespace cs {
 
@@ -144,6 +145,18 @@ inline void unpack_keys(const uint64_t* keys, uint32_t nq, uint32_t k, float* ou
 // tokenizer.cpp: per-text id lists ([CLS] ... [SEP], truncated to max_length), texts in parallel
 void tokenize_texts(const cs_tokenizer* t, const char* utf8, const uint64_t* offsets, uint32_t n,
                     uint32_t max_length, std::vector<std::vector<int32_t>>& out);
+
+// tokenizer.cpp: per-pair id and token-type lists under the handle's pair form (cs_tokenizer_encode_pairs); na = n, or 1 =
+// one first text for every pair
+int32_t tokenize_pairs(const cs_tokenizer* t, const char* a_utf8, const uint64_t* a_off, uint32_t na, const char* b_utf8,
+                       const uint64_t* b_off, uint32_t n, uint32_t max_length, std::vector<std::vector<int32_t>>& ids,
+                       std::vector<std::vector<int32_t>>& types);
+// tokenizer.cpp: the pair form of a WordPiece handle whose tokenizer.json spells one out
+void tokenizer_set_pair(cs_tokenizer* t, const PairForm& pair);
+
+// checkpoint.cpp: config.json + model.safetensors of a sequence-classification snapshot -> configuration, encoder parameters
+// and score head on the host (cs_reranker_create_from_dir)
+int32_t reranker_files_from_dir(const char* model_dir, cs_bert_config* cfg, std::vector<float>& params, std::vector<float>& head);
 
 inline uint32_t next_pow2(uint32_t v) {
     uint32_t p = 1;

@@ -31,9 +31,11 @@ uint32_t default_batch(const cs_embedder* h) {
 
 // perm (optional, only with n <= batch): pooled row r of the mini-batch goes to out row perm[r].
 // units (optional, only with n <= batch and CS_GEMM_Q8_DYNAMIC): see UnitSpec.
+// types (optional): token-type ids beside the ids, [n, seq_len]; null = every token has type 0.
+// A result row is out_width(h) floats: hidden, or the one logit of the score head.
 int32_t embed_impl(cs_embedder* h, const int32_t* ids, const int32_t* mask, uint64_t n,
                    uint32_t seq_len, uint32_t batch, float* out, bool out_on_device,
-                   const volatile int32_t* cancel, const uint32_t* perm, const UnitSpec* units) {
+                   const volatile int32_t* cancel, const uint32_t* perm, const UnitSpec* units, const int32_t* types) {
     if (!h) return fail(CS_ERR_BAD_ARG, "null embedder handle");
     if (n == 0) return CS_OK;  // embedder.rs:271-273
     if (!ids || !mask || !out) return fail(CS_ERR_BAD_ARG, "null buffer");
@@ -42,9 +44,20 @@ int32_t embed_impl(cs_embedder* h, const int32_t* ids, const int32_t* mask, uint
                     h->cfg.max_position);
     if (batch == 0) batch = default_batch(h);
     DeviceGuard g(h->device);
-    const uint32_t H = h->cfg.hidden;
+    const uint32_t H = out_width(h);  // floats per result row
     const size_t bmax = n < batch ? (size_t)n : batch;
     CS_TRY(reserve(h, bmax, bmax * seq_len));
+    struct TypesGuard { cs_embedder* e; ~TypesGuard() { e->types_on = false; } } types_guard{h};
+    if (types) {
+        if (h->cfg.arch == CS_ARCH_MODERN)
+            return fail(CS_ERR_UNSUPPORTED, "the ModernBERT encoder has no token-type table: token-type ids cannot be given");
+        if (h->cap_types < h->cap_tokens) {  // first use (or a workspace that has grown since)
+            if (h->d_types) { CS_HIP(hipStreamSynchronize(h->stream)); (void)hipFree(h->d_types); h->d_types = nullptr; h->cap_types = 0; }
+            CS_HIP(hipMalloc(&h->d_types, h->cap_tokens * sizeof(int32_t)));
+            h->cap_types = h->cap_tokens;
+        }
+        h->types_on = true;
+    }
     for (uint64_t done = 0; done < n; done += batch) {
         if (cancel && *cancel)  // embedder.rs:280-282
             return fail(CS_ERR_CANCELLED, "Embedding interrupted by shutdown request");
@@ -55,19 +68,29 @@ int32_t embed_impl(cs_embedder* h, const int32_t* ids, const int32_t* mask, uint
             if (bi[i] < 0 || (uint32_t)bi[i] >= h->cfg.vocab_size)
                 return fail(CS_ERR_BAD_ARG, "Failed to generate embeddings: token id %d outside vocabulary of %u",
                             bi[i], h->cfg.vocab_size);
+        const int32_t* bt = types ? types + done * seq_len : nullptr;
+        for (size_t i = 0; bt && i < tok; ++i)
+            if (bt[i] < 0 || (uint32_t)bt[i] >= h->cfg.type_vocab_size)
+                return fail(CS_ERR_BAD_ARG, "Failed to generate embeddings: token type id %d outside the type table of %u rows",
+                            bt[i], h->cfg.type_vocab_size);
         // a small mini-batch (a query and its variants) goes through 128 KiB of pinned memory: ids | mask in, the range flag and the
         // rows out behind ONE wait — from pageable memory every transfer is staged by the runtime and waits on its own
         constexpr size_t kPinHalf = 64 << 10;
-        const bool pin_in = h->h_pin && tok * 2 * sizeof(int32_t) <= kPinHalf;
+        const bool pin_in = h->h_pin && tok * (bt ? 3 : 2) * sizeof(int32_t) <= kPinHalf;
         if (pin_in) {  // (the stream is idle: the previous mini-batch ended with a wait)
             std::memcpy(h->h_pin, bi, tok * sizeof(int32_t));
             std::memcpy(h->h_pin + tok * sizeof(int32_t), mask + done * seq_len, tok * sizeof(int32_t));
             CS_HIP(hipMemcpyAsync(h->d_ids, h->h_pin, tok * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
             CS_HIP(hipMemcpyAsync(h->d_mask, h->h_pin + tok * sizeof(int32_t), tok * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+            if (bt) {
+                std::memcpy(h->h_pin + 2 * tok * sizeof(int32_t), bt, tok * sizeof(int32_t));
+                CS_HIP(hipMemcpyAsync(h->d_types, h->h_pin + 2 * tok * sizeof(int32_t), tok * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+            }
         } else {
             CS_HIP(hipMemcpyAsync(h->d_ids, bi, tok * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
             CS_HIP(hipMemcpyAsync(h->d_mask, mask + done * seq_len, tok * sizeof(int32_t),
                                   hipMemcpyHostToDevice, h->stream));
+            if (bt) CS_HIP(hipMemcpyAsync(h->d_types, bt, tok * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
         }
         const bool pin_out = h->h_pin && !perm && !out_on_device && (size_t)B * H * sizeof(float) + 64 <= kPinHalf;
         uint32_t* pin_flag = reinterpret_cast<uint32_t*>(h->h_pin + kPinHalf);
@@ -171,6 +194,8 @@ int32_t embed_impl(cs_embedder* h, const int32_t* ids, const int32_t* mask, uint
         } else if (out_on_device) {
             CS_HIP(hipMemcpyAsync(h->d_perm, perm, B * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
             const uint32_t h4 = H / 4;
+            // (float4 rows: logits, one float per row, are scattered on the host below — cs_reranker_* return host memory only)
+            if (H % 4) return fail(CS_ERR_UNSUPPORTED, "rows of %u floats cannot be scattered on the device", H);
             hipLaunchKernelGGL(scatter_rows_kernel, dim3((B * h4 + 255) / 256), dim3(256), 0, h->stream, h->d_pooled,
                                h->d_perm, out, B, h4);
             CS_HIP(hipGetLastError());
@@ -234,6 +259,8 @@ int32_t run_window(cs_embedder* h, const std::vector<SeqView>& seqs, uint32_t ba
                    bool out_on_device, const volatile int32_t* cancel, std::vector<uint32_t>& order,
                    std::vector<int32_t>& ids, std::vector<int32_t>& mask) {
     const uint32_t wn = (uint32_t)seqs.size();
+    const bool typed = wn && seqs[0].types;
+    std::vector<int32_t> types;
     // Length-grouped mini-batches are cut by TOKENS, not by rows: a mini-batch of `batch` short sequences is a fraction
     // of the token rows the dense layers are tuned on (256 x 256 = 65,536 for the 384-d models: whole tile rounds on
     // 256 CUs), so short sequences fill the same budget with more rows (up to 8 x batch).  Sorted ascending, the row
@@ -279,13 +306,16 @@ int32_t run_window(cs_embedder* h, const std::vector<SeqView>& seqs, uint32_t ba
         }
         ids.assign((size_t)B * L, pad);
         mask.assign((size_t)B * L, 0);
+        if (typed) types.assign((size_t)B * L, 0);  // (padding has type 0)
         for (uint32_t r = 0; r < B; ++r) {
             const SeqView& v = seqs[order[b0 + r]];
             std::copy(v.ids, v.ids + v.len, ids.begin() + (size_t)r * L);
             if (v.mask) std::copy(v.mask, v.mask + v.len, mask.begin() + (size_t)r * L);
             else std::fill(mask.begin() + (size_t)r * L, mask.begin() + (size_t)r * L + v.len, 1);
+            if (typed) std::copy(v.types, v.types + v.len, types.begin() + (size_t)r * L);
         }
-        CS_TRY(embed_impl(h, ids.data(), mask.data(), B, L, B, out, out_on_device, nullptr, order.data() + b0));
+        CS_TRY(embed_impl(h, ids.data(), mask.data(), B, L, B, out, out_on_device, nullptr, order.data() + b0, nullptr,
+                          typed ? types.data() : nullptr));
     }
     return CS_OK;
 }
@@ -332,8 +362,8 @@ int32_t embed_texts_impl(cs_embedder* h, const cs_tokenizer* t, const char* utf8
 // (the columns dropped hold padding in every row of the mini-batch) and grouped by length.
 int32_t embed_ids_windowed(cs_embedder* h, const int32_t* ids_in, const int32_t* mask_in, uint64_t n,
                            uint32_t seq_len, uint32_t batch, float* out, bool out_on_device,
-                           const volatile int32_t* cancel) {
-    const uint32_t H = h->cfg.hidden;
+                           const volatile int32_t* cancel, const int32_t* types_in) {
+    const uint32_t H = out_width(h);
     const uint64_t window = (uint64_t)batch * 16;
     std::vector<uint32_t> order;
     std::vector<int32_t> ids, mask;
@@ -345,7 +375,7 @@ int32_t embed_ids_windowed(cs_embedder* h, const int32_t* ids_in, const int32_t*
             const int32_t* m = mask_in + (lo + i) * seq_len;
             uint32_t len = seq_len;
             while (len > 1 && m[len - 1] == 0) --len;
-            seqs.push_back(SeqView{ids_in + (lo + i) * seq_len, m, len});
+            seqs.push_back(SeqView{ids_in + (lo + i) * seq_len, m, len, types_in ? types_in + (lo + i) * seq_len : nullptr});
         }
         CS_TRY(run_window(h, seqs, batch, 0, out + lo * H, out_on_device, cancel, order, ids, mask));
     }
@@ -353,14 +383,14 @@ int32_t embed_ids_windowed(cs_embedder* h, const int32_t* ids_in, const int32_t*
 }
 
 int32_t embed_ids_entry(cs_embedder* h, const int32_t* ids, const int32_t* mask, uint64_t n, uint32_t seq_len,
-                        uint32_t batch, float* out, bool out_on_device, const volatile int32_t* cancel) {
+                        uint32_t batch, float* out, bool out_on_device, const volatile int32_t* cancel, const int32_t* types) {
     if (!h) return fail(CS_ERR_BAD_ARG, "null embedder handle");
     const uint32_t b = batch ? batch : default_batch(h);
     // a single mini-batch runs exactly as given (cs_embedder_last_hidden then has the caller's [n, seq_len] layout)
     if (n <= b || !ids || !mask || !out || seq_len == 0 || seq_len > h->cfg.max_position || !length_sort_enabled() ||
         h->gemm_mode == CS_GEMM_Q8_DYNAMIC)
-        return embed_impl(h, ids, mask, n, seq_len, batch, out, out_on_device, cancel);
-    return embed_ids_windowed(h, ids, mask, n, seq_len, b, out, out_on_device, cancel);
+        return embed_impl(h, ids, mask, n, seq_len, batch, out, out_on_device, cancel, nullptr, nullptr, types);
+    return embed_ids_windowed(h, ids, mask, n, seq_len, b, out, out_on_device, cancel, types);
 }
 }  // namespace emb
 }  // namespace cs

@@ -13,6 +13,7 @@ size_t mid_width(const cs_bert_config& c) { return (size_t)c.intermediate * (cs_
 void free_workspace(cs_embedder* h) {
     if (h->d_ids) (void)hipFree(h->d_ids);
     if (h->d_mask) (void)hipFree(h->d_mask);
+    if (h->d_types) (void)hipFree(h->d_types);
     if (h->d_x) (void)hipFree(h->d_x);
     if (h->d_xs) (void)hipFree(h->d_xs);
     if (h->d_qkv) (void)hipFree(h->d_qkv);
@@ -31,7 +32,8 @@ void free_workspace(cs_embedder* h) {
     h->d_range_pairs = nullptr;
     h->d_seq_unit = h->d_unit_len = h->d_row_slot = h->d_range = nullptr;
     h->d_perm = nullptr;
-    h->d_ids = h->d_mask = nullptr;
+    h->d_ids = h->d_mask = h->d_types = nullptr;
+    h->cap_types = 0;
     h->d_x = h->d_xs = h->d_qkv = h->d_ctx = h->d_mid = h->d_pooled = nullptr;
     h->cap_tokens = h->cap_seqs = 0;
 }
@@ -191,9 +193,10 @@ struct Slice {
         mids = reinterpret_cast<_Float16*>(mid);
         a.ids = h->d_ids + t0; a.mask = mask;
         a.word = P + h->off.word; a.pos = cs_arch_gated(cfg.arch) ? nullptr : P + h->off.pos; a.type0 = P + h->off.type;
+        a.types = h->types_on ? h->d_types + t0 : nullptr; a.ntypes = cfg.type_vocab_size;
         a.g = P + h->off.emb_ln_g; a.b = P + h->off.emb_ln_b;
         a.eps = cfg.layer_norm_eps; a.T = T; a.L = L; a.B = nb; a.vocab = cfg.vocab_size;
-        a.pooling = cfg.pooling; a.x = x; a.out = (h->pooled_dst ? h->pooled_dst : h->d_pooled) + (size_t)b0 * H;
+        a.pooling = cfg.pooling; a.x = x; a.out = (h->pooled_dst ? h->pooled_dst : h->d_pooled) + (size_t)b0 * out_width(h);
         a.xs = mode == CS_GEMM_SPLIT_F16 ? (void*)(h->d_xs + t0 * H) : nullptr;  // q8: the xs buffer holds the quantised rows instead
         a.flag = h->d_flag;
         if (mode == CS_GEMM_Q8_DYNAMIC) a.range_out = h->d_range_pairs;  // LayerNorm leaves its blocks' ranges for the quantising pass that follows
@@ -230,8 +233,13 @@ struct Slice {
         a.g = P + g; a.b = P + b;
         return launch_row_kernel(1, a, H, s);
     }
-    int32_t pool() const {  // E7 + E8
-        CS_TRY(launch_row_kernel(2, a, H, s));
+    // the forward's last launch over the rows `e` describes: E7 + E8, or the score head on the CLS rows (rerank_head.hip)
+    int32_t out_stage(const EncoderLaunch& e) const {
+        if (h->head_on) return launch_rerank_head(e.x, (size_t)e.L * H, h->d_head, e.B, H, e.out, s);
+        return launch_row_kernel(2, e, H, s);
+    }
+    int32_t pool() const {
+        CS_TRY(out_stage(a));
         return mark(CS_STAGE_POOL);
     }
     void layer_begin(uint32_t l) {
@@ -259,6 +267,7 @@ struct Slice {
 // not activated).  The same kernels as every other family; exact-f32 mode included.
 int32_t Slice::run_modern(const ForwardPlan& p) {
     const bool split = mode == CS_GEMM_SPLIT_F16;
+    if (a.types) return fail(CS_ERR_UNSUPPORTED, "the ModernBERT encoder has no token-type table: token-type ids cannot be given");
     a.pos = nullptr; a.type0 = h->d_zero_row;
     CS_TRY(embed());  // E1 (its split copy is layer 0's operand: attn_norm is the identity there)
     EncoderLaunch n = a;   // LayerNorm of the residual stream into the context buffer (+ xs)
@@ -338,7 +347,7 @@ int32_t Slice::run_small(const ForwardPlan& p) {
         if (const char* ph = cs_lab_env("CS_ATTN_PACK_HEADS")) if (ph[0] == '0') hb = 1;
         while (cfg.heads % hb) hb >>= 1;
         SfArgs sa{};
-        sa.ids = a.ids; sa.mask = mask; sa.word = a.word; sa.pos = a.pos; sa.type0 = a.type0; sa.emb_g = a.g; sa.emb_b = a.b;
+        sa.ids = a.ids; sa.mask = mask; sa.word = a.word; sa.pos = a.pos; sa.type0 = a.type0; sa.types = a.types; sa.ntypes = a.ntypes; sa.emb_g = a.g; sa.emb_b = a.b;
         sa.layers = h->d_sf_layers; sa.n_layers = cfg.layers; sa.eps = cfg.layer_norm_eps;
         sa.T = T; sa.L = L; sa.B = nb; sa.vocab = cfg.vocab_size; sa.heads = cfg.heads; sa.hb = hb;
         sa.X = x; sa.XA = xa; sa.Y = y; sa.PARTS = parts; sa.QKVS = qkvs; sa.CTXS = ctxs;
@@ -348,7 +357,7 @@ int32_t Slice::run_small(const ForwardPlan& p) {
         CS_TRY(launch_small_forward(sa, s));
         h->sf_ran = true;
         h->last_hidden_partial = false;
-        CS_TRY(launch_row_kernel(2, a, H, s));  // E7 + E8
+        CS_TRY(out_stage(a));  // E7 + E8
         return CS_OK;
     }
 #endif
@@ -360,7 +369,7 @@ int32_t Slice::run_small(const ForwardPlan& p) {
         const _Float16* ws = h->d_wsplit + (size_t)l * sl.total;
         SpLnGemmArgs g1{};
         g1.Y = y; g1.parts = parts; g1.parts_bias = l ? P + lp.down_b : nullptr; g1.X = x;
-        g1.ids = a.ids; g1.word = a.word; g1.pos = a.pos; g1.type0 = a.type0; g1.L = L; g1.vocab = cfg.vocab_size;
+        g1.ids = a.ids; g1.word = a.word; g1.pos = a.pos; g1.type0 = a.type0; g1.types = a.types; g1.ntypes = a.ntypes; g1.L = L; g1.vocab = cfg.vocab_size;
         g1.ln_g = l ? P + lp.out_ln_g : a.g; g1.ln_b = l ? P + lp.out_ln_b : a.b; g1.eps = cfg.layer_norm_eps;
         g1.Xout = xa; g1.W = ws + sl.qkv; g1.bias = bqkv; g1.Cs = qkvs; g1.T = T; g1.N = 3 * H; g1.flag = h->d_flag;
         CS_TRY(launch_sp_ln_gemm(SH_OUT_SPLIT, l ? 1 : 2, g1, H, s));                                        // (E1 | LN) + E2
@@ -627,7 +636,7 @@ int32_t Slice::run_cls_tail(const ForwardPlan& p, const _Float16* ws) {
     t.g = P + lo.out_ln_g; t.b = P + lo.out_ln_b;
     CS_TRY(launch_row_kernel(1, t, H, s));
     CS_TRY(mark(CS_STAGE_LN_FFN));
-    CS_TRY(launch_row_kernel(2, t, H, s));  // E7 + E8 on the compact rows (L = 1: row b IS the CLS row)
+    CS_TRY(out_stage(t));  // E7 + E8 on the compact rows (L = 1: row b IS the CLS row)
     return mark(CS_STAGE_POOL);
 }
 

@@ -136,6 +136,15 @@ struct cs_embedder {
     size_t cap_tokens = 0, cap_seqs = 0;
     int32_t* d_ids = nullptr;
     int32_t* d_mask = nullptr;
+    // token-type ids of a mini-batch (cross-encoder pairs): allocated by the first call that passes any, cap_types ids;
+    // types_on = the mini-batch on the device carries them (else every kernel reads row 0 of the type table)
+    int32_t* d_types = nullptr;
+    size_t cap_types = 0;
+    bool types_on = false;
+    // a cross-encoder's score head (cs_reranker_*: rerank_head.hip), W_p [H, H] | b_p | w_c | b_c, owned by the reranker handle;
+    // head_on = the call in flight is cs_reranker_score_ids: the head runs in place of the pooling and a result row is ONE float
+    const float* d_head = nullptr;
+    bool head_on = false;
     float* d_x = nullptr;       // [T, H]
     float* d_xs = nullptr;      // [T, H/32, 64] f16: x in split form (same bytes as f32)
     float* d_qkv = nullptr;     // [T, 3H]
@@ -173,6 +182,8 @@ SplitLayer split_layer(const cs_bert_config& c);
 // One mini-batch already on the device (d_ids / d_mask) -> d_pooled [B, H]  (embedder_forward.hip)
 int32_t forward(cs_embedder* h, uint32_t B, uint32_t L, int mode);
 uint32_t default_batch(const cs_embedder* h);
+// Floats per result row: hidden, or 1 while the score head stands in for the pooling
+inline uint32_t out_width(const cs_embedder* h) { return h->head_on ? 1u : h->cfg.hidden; }
 
 // Several quantisation units in ONE mini-batch (dynamic-quantisation mode: calls of the reference embedded together, each
 // still quantised as the tensor it would have been on its own): the unit of every sequence, each unit's own padded length.
@@ -184,12 +195,13 @@ struct UnitSpec {
 // (embedder_embed.hip)
 int32_t embed_impl(cs_embedder* h, const int32_t* ids, const int32_t* mask, uint64_t n, uint32_t seq_len, uint32_t batch,
                    float* out, bool out_on_device, const volatile int32_t* cancel, const uint32_t* perm = nullptr,
-                   const UnitSpec* units = nullptr);
+                   const UnitSpec* units = nullptr, const int32_t* types = nullptr);
 int32_t embed_texts_impl(cs_embedder* h, const cs_tokenizer* t, const char* utf8, const uint64_t* offsets,
                          uint64_t n, uint32_t batch, float* out, bool out_on_device, const volatile int32_t* cancel);
 int32_t embed_ids_entry(cs_embedder* h, const int32_t* ids, const int32_t* mask, uint64_t n, uint32_t seq_len,
-                        uint32_t batch, float* out, bool out_on_device, const volatile int32_t* cancel);
-struct SeqView { const int32_t* ids; const int32_t* mask; uint32_t len; };
+                        uint32_t batch, float* out, bool out_on_device, const volatile int32_t* cancel,
+                        const int32_t* types = nullptr);
+struct SeqView { const int32_t* ids; const int32_t* mask; uint32_t len; const int32_t* types = nullptr; };  // types: all rows of a window or none
 int32_t run_window(cs_embedder* h, const std::vector<SeqView>& seqs, uint32_t batch, int32_t pad, float* out,
                    bool out_on_device, const volatile int32_t* cancel, std::vector<uint32_t>& order,
                    std::vector<int32_t>& ids, std::vector<int32_t>& mask);

@@ -90,6 +90,7 @@ template <int NPL>
 __global__ void __launch_bounds__(256)
 embed_ln_kernel(const int32_t* __restrict__ ids, const float* __restrict__ word,
                 const float* __restrict__ pos, const float* __restrict__ type0,
+                const int32_t* __restrict__ types, uint32_t ntypes,
                 const float* __restrict__ g, const float* __restrict__ b, float eps, uint32_t T,
                 uint32_t L, uint32_t vocab, float* __restrict__ x, _Float16* __restrict__ xs,
                 uint32_t* __restrict__ flag, float* __restrict__ range_out, uint32_t range_rows) {
@@ -102,12 +103,13 @@ embed_ln_kernel(const int32_t* __restrict__ ids, const float* __restrict__ word,
     if (id >= vocab) id = 0;  // host validates; never index out of the table
     const float* we = word + (size_t)id * H;
     const float* pe = pos ? pos + (size_t)(t % L) * H : nullptr;  // null: no position table (CS_ARCH_NOMIC)
+    const float* te = types ? type0 + (size_t)min((uint32_t)types[t], ntypes - 1) * H : type0;  // null: every token has type 0
     float v[NPL];
 #pragma unroll
     for (int p = 0; p < NPL / 2; ++p) {
         const int c = ln_col(lane, 2 * p);
         const float2 w2 = *reinterpret_cast<const float2*>(we + c);
-        const float2 t2 = *reinterpret_cast<const float2*>(type0 + c);
+        const float2 t2 = *reinterpret_cast<const float2*>(te + c);
         const float2 p2 = pe ? *reinterpret_cast<const float2*>(pe + c) : make_float2(0.0f, 0.0f);
         v[2 * p] = (w2.x + t2.x) + p2.x;  // BertEmbeddings: (inputs + token_type) + position
         v[2 * p + 1] = (w2.y + t2.y) + p2.y;
@@ -815,7 +817,7 @@ static void launch_rows(int which, const EncoderLaunch& a, hipStream_t s) {
     const uint32_t T = a.T;
     if (which == 0)
         hipLaunchKernelGGL(embed_ln_kernel<NPL>, dim3((T + 3) / 4), dim3(256), 0, s, a.ids, a.word, a.pos,
-                           a.type0, a.g, a.b, a.eps, T, a.L, a.vocab, a.x, static_cast<_Float16*>(a.xs), a.flag, a.range_out, a.range_rows ? 1u : 0u);
+                           a.type0, a.types, a.ntypes, a.g, a.b, a.eps, T, a.L, a.vocab, a.x, static_cast<_Float16*>(a.xs), a.flag, a.range_out, a.range_rows ? 1u : 0u);
     else if (which == 1)
         hipLaunchKernelGGL(layernorm_kernel<NPL>, dim3((T + 3) / 4), dim3(256), 0, s, a.x, a.g, a.b, a.eps, T,
                            static_cast<_Float16*>(a.xs), a.flag, a.range_out, a.range_rows ? 1u : 0u);

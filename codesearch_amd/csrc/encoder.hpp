@@ -16,6 +16,8 @@ struct EncoderLaunch {
     const float* word = nullptr;
     const float* pos = nullptr;
     const float* type0 = nullptr;
+    const int32_t* types = nullptr;  // which == 0, optional: [T] token-type ids — the row added is type0 + types[t] * H (null: row 0)
+    uint32_t ntypes = 1;             //   rows of the type table (the host validates the ids; the kernel never leaves the table)
     const float* g = nullptr;
     const float* b = nullptr;
     float eps = 1e-12f;
@@ -85,6 +87,8 @@ int32_t launch_gemm_wide_ln(const _Float16* A, const _Float16* W, const float* b
 // stream's CLS rows -> x_cls [B, H] f32 + xs_cls split.
 int32_t launch_attention_cls(const _Float16* q_cls, const _Float16* kv_split, const int32_t* mask, _Float16* ctxs_cls,
                              uint32_t* flag, uint32_t B, uint32_t L, uint32_t H, uint32_t heads, hipStream_t s);
+// rerank_head.hip: logit_b = w_c . tanh(W_p x_b + b_p) + b_c with x_b = x + b * row_stride; head = W_p [H, H] | b_p | w_c | b_c
+int32_t launch_rerank_head(const float* x, size_t row_stride, const float* head, uint32_t B, uint32_t H, float* out, hipStream_t s);
 int32_t launch_gather_cls(const _Float16* xs, float* x_cls, _Float16* xs_cls, uint32_t B, uint32_t L, uint32_t H, hipStream_t s);
 // nomic.hip (CS_ARCH_NOMIC): the rotary position map on the Q and K columns of a QKV tensor, in place — split form
 // [T][3H/32][64] or f32 [T][3H]; rope [L_max][d_h / 2] (cos, sin) — and the feed-forward gate value * silu(gate): up2

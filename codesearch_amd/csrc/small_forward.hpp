@@ -15,6 +15,8 @@ struct SfArgs {
     const int32_t* ids;
     const int32_t* mask;
     const float *word, *pos, *type0, *emb_g, *emb_b;
+    const int32_t* types;  // optional [T] token-type ids (null: row 0 of the type table), ntypes rows in the table
+    uint32_t ntypes;
     const SfLayer* layers;  // device array [n_layers]
     uint32_t n_layers;
     float eps;

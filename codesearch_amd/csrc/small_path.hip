@@ -77,11 +77,12 @@ sp_ln_gemm_kernel(SpLnGemmArgs a) {
             if (id >= a.vocab) id = 0;
             const float* we = a.word + (size_t)id * H;
             const float* pe = a.pos + (size_t)(t % a.L) * H;
+            const float* te = a.types ? a.type0 + (size_t)min((uint32_t)a.types[t], a.ntypes - 1) * H : a.type0;
 #pragma unroll
             for (int p = 0; p < NPL / 2; ++p) {
                 const int c = ln_col(lane, 2 * p);
                 const float2 w2 = *reinterpret_cast<const float2*>(we + c);
-                const float2 t2 = *reinterpret_cast<const float2*>(a.type0 + c);
+                const float2 t2 = *reinterpret_cast<const float2*>(te + c);
                 const float2 p2 = *reinterpret_cast<const float2*>(pe + c);
                 v[rr][2 * p] = (w2.x + t2.x) + p2.x;
                 v[rr][2 * p + 1] = (w2.y + t2.y) + p2.y;

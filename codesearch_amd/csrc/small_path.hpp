@@ -16,6 +16,8 @@ struct SpLnGemmArgs {
     // prologue 2: the embedding gather
     const int32_t* ids;
     const float *word, *pos, *type0;
+    const int32_t* types;  // optional [T] token-type ids (null: row 0 of the type table), ntypes rows in the table
+    uint32_t ntypes;
     uint32_t L, vocab;
     // LayerNorm, and where the block of column tile 0 writes the normalised rows (never the buffer `X` is read from)
     const float *ln_g, *ln_b;

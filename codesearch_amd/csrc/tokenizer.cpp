@@ -142,6 +142,8 @@ struct cs_tokenizer {
     std::shared_ptr<cs::UnigramEngine> unigram;
     // ... or a byte-level BPE tokenizer.json (bpe.cpp): cls / sep are its <bos> / <eos> (-1: the file's template has none)
     std::shared_ptr<cs::BpeEngine> bpe;
+    // how a pair of texts is arranged (cs_tokenizer_encode_pairs): BertProcessing's form unless the file gives another
+    cs::PairForm pair = cs::PairForm::bert();
 
     int32_t find(uint64_t h, const char* a, uint32_t alen, const char* b, uint32_t blen) const {
         // key = a ++ b (a is the optional "##")
@@ -389,6 +391,96 @@ void tokenize_texts(const cs_tokenizer* t, const char* utf8, const uint64_t* off
     for (auto& x : th) x.join();
 }
 
+// The ids of one whole text without the template's tokens (the pair rule below needs both bodies' true lengths)
+static void encode_body(const cs_tokenizer* t, const char* p, size_t n, std::vector<int32_t>& ids) {
+    constexpr uint32_t limit = 0xFFFFFFFFu;
+    ids.clear();
+    if (t->unigram) {
+        t->unigram->encode(p, n, limit, ids);
+        ids.pop_back();
+        ids.erase(ids.begin());
+        return;
+    }
+    if (t->bpe) {
+        t->bpe->encode(p, n, limit, ids);
+        if (t->bpe->eos() >= 0) ids.pop_back();
+        if (t->bpe->bos() >= 0) ids.erase(ids.begin());
+        return;
+    }
+    Encoder enc(*t, ids, limit);
+    enc.encode(reinterpret_cast<const unsigned char*>(p), n);
+}
+
+// Pair i = (first text i, or the one first text when na == 1; second text i) under the handle's pair form, truncated as the
+// `tokenizers` crate truncates by default (TruncationStrategy::LongestFirst, truncate_encodings): with n1 <= n2 the two
+// bodies' lengths and `budget` = max_length - the template's tokens, the shorter body keeps n1 and the longer
+// max(n1, budget - n1) when that fits; otherwise the shorter keeps budget / 2 and the longer the rest; on equal lengths the
+// FIRST body is the "shorter".  Tokens always come off a body's end.
+int32_t tokenize_pairs(const cs_tokenizer* t, const char* a_utf8, const uint64_t* a_off, uint32_t na, const char* b_utf8,
+                       const uint64_t* b_off, uint32_t n, uint32_t max_length, std::vector<std::vector<int32_t>>& ids,
+                       std::vector<std::vector<int32_t>>& types) {
+    if (t->pair.kind == PairForm::NONE)
+        return fail(CS_ERR_UNSUPPORTED, "this tokenizer's post_processor has no pair form that is built ([CLS] A [SEP] B [SEP] or "
+                                        "<s> A </s> </s> B </s>)");
+    if (t->cls < 0 || t->sep < 0)
+        return fail(CS_ERR_UNSUPPORTED, "this tokenizer's template has no <bos> / <eos>: a pair cannot be arranged");
+    const PairForm& pf = t->pair;
+    if (max_length < pf.added() + 2)
+        return fail(CS_ERR_BAD_ARG, "max_length %u leaves no room for the pair template's %u tokens and a token of each text", max_length,
+                    pf.added());
+    const uint32_t budget = max_length - pf.added();
+    ids.assign(n, {});
+    types.assign(n, {});
+    std::vector<int32_t> shared_a;
+    if (na == 1 && n) encode_body(t, a_utf8 + a_off[0], (size_t)(a_off[1] - a_off[0]), shared_a);
+    auto work = [&](uint32_t lo, uint32_t hi) {
+        std::vector<int32_t> own_a, b;
+        for (uint32_t i = lo; i < hi; ++i) {
+            if (na != 1) encode_body(t, a_utf8 + a_off[i], (size_t)(a_off[i + 1] - a_off[i]), own_a);
+            const std::vector<int32_t>& a = na == 1 ? shared_a : own_a;
+            encode_body(t, b_utf8 + b_off[i], (size_t)(b_off[i + 1] - b_off[i]), b);
+            uint32_t n1 = (uint32_t)a.size(), n2 = (uint32_t)b.size();
+            const bool swap = n1 > n2;
+            if (swap) std::swap(n1, n2);
+            n2 = n1 > budget ? n1 : std::max(n1, budget - n1);
+            if (n1 + n2 > budget) { n1 = budget / 2; n2 = n1 + budget % 2; }
+            if (swap) std::swap(n1, n2);
+            const uint32_t ka = std::min<uint32_t>(n1, (uint32_t)a.size()), kb = std::min<uint32_t>(n2, (uint32_t)b.size());
+            std::vector<int32_t>& o = ids[i];
+            std::vector<int32_t>& ty = types[i];
+            int piece = 0;
+            auto special = [&](int32_t id) { o.push_back(id); ty.push_back(pf.types[piece++]); };
+            auto body = [&](const std::vector<int32_t>& v, uint32_t k) {
+                o.insert(o.end(), v.begin(), v.begin() + k);
+                ty.insert(ty.end(), k, pf.types[piece++]);
+            };
+            special(t->cls);
+            body(a, ka);
+            special(t->sep);
+            if (pf.kind == PairForm::ROBERTA) special(t->sep);
+            body(b, kb);
+            special(t->sep);
+        }
+    };
+    const uint32_t nt = tokenizer_threads(n);
+    if (nt <= 1) { work(0, n); return CS_OK; }
+    std::vector<std::thread> th;
+    std::atomic<uint32_t> next{0};
+    const uint32_t grain = 4;
+    for (uint32_t k = 0; k < nt; ++k)
+        th.emplace_back([&] {
+            for (;;) {
+                const uint32_t lo = next.fetch_add(grain);
+                if (lo >= n) break;
+                work(lo, std::min(n, lo + grain));
+            }
+        });
+    for (auto& x : th) x.join();
+    return CS_OK;
+}
+
+void tokenizer_set_pair(cs_tokenizer* t, const PairForm& pair) { t->pair = pair; }
+
 int32_t tokenizer_from_bpe(BpeSpec&& spec, uint32_t max_length, cs_tokenizer** out) {
     if (!out) return fail(CS_ERR_BAD_ARG, "null out pointer");
     *out = nullptr;
@@ -398,6 +490,7 @@ int32_t tokenizer_from_bpe(BpeSpec&& spec, uint32_t max_length, cs_tokenizer** o
     cs_tokenizer* t = new (std::nothrow) cs_tokenizer();
     if (!t) return fail(CS_ERR_OOM, "out of host memory");
     t->bpe = eng;
+    t->pair = eng->pair();
     t->lowercase = false;
     t->max_length = max_length;
     t->size = eng->vocab_size();
@@ -418,6 +511,7 @@ int32_t tokenizer_from_unigram(UnigramSpec&& spec, uint32_t max_length, cs_token
     cs_tokenizer* t = new (std::nothrow) cs_tokenizer();
     if (!t) return fail(CS_ERR_OOM, "out of host memory");
     t->unigram = eng;
+    t->pair = eng->pair();
     t->lowercase = false;
     t->max_length = max_length;
     t->size = eng->vocab_size();
@@ -515,6 +609,37 @@ int32_t cs_tokenizer_encode_batch(const cs_tokenizer* t, const char* utf8, const
             const bool live = j < e.size();
             if (ids) ids[(size_t)i * row_stride + j] = live ? e[j] : t->pad;
             if (mask) mask[(size_t)i * row_stride + j] = live ? 1 : 0;
+        }
+    }
+    return CS_OK;
+}
+
+int32_t cs_tokenizer_encode_pairs(const cs_tokenizer* t, const char* a_utf8, const uint64_t* a_offsets, uint32_t na,
+                                  const char* b_utf8, const uint64_t* b_offsets, uint32_t n, uint32_t max_length, int32_t* ids,
+                                  int32_t* mask, int32_t* types, uint32_t row_stride, uint32_t* out_len) {
+    if (!t) return fail(CS_ERR_BAD_ARG, "null tokenizer handle");
+    if (n && (!a_utf8 || !a_offsets || !b_utf8 || !b_offsets)) return fail(CS_ERR_BAD_ARG, "null text buffer");
+    if (n && na != n && na != 1) return fail(CS_ERR_BAD_ARG, "%u first texts for %u pairs (as many, or one for all)", na, n);
+    if (max_length == 0) max_length = t->max_length;
+    for (uint32_t i = 0; n && i < na; ++i)
+        if (a_offsets[i + 1] < a_offsets[i]) return fail(CS_ERR_BAD_ARG, "text offsets must be non-decreasing");
+    for (uint32_t i = 0; i < n; ++i)
+        if (b_offsets[i + 1] < b_offsets[i]) return fail(CS_ERR_BAD_ARG, "text offsets must be non-decreasing");
+    std::vector<std::vector<int32_t>> enc, ty;
+    CS_TRY(cs::tokenize_pairs(t, a_utf8, a_offsets, na, b_utf8, b_offsets, n, max_length, enc, ty));
+    uint32_t L = 0;
+    for (const auto& e : enc) L = std::max<uint32_t>(L, (uint32_t)e.size());
+    if (out_len) *out_len = L;
+    if (!ids && !mask) return CS_OK;  // length query
+    if (row_stride < L)
+        return fail(CS_ERR_BAD_ARG, "row_stride %u is shorter than the batch's longest sequence %u", row_stride, L);
+    for (uint32_t i = 0; i < n; ++i) {
+        const auto& e = enc[i];
+        for (uint32_t j = 0; j < row_stride; ++j) {
+            const bool live = j < e.size();
+            if (ids) ids[(size_t)i * row_stride + j] = live ? e[j] : t->pad;
+            if (mask) mask[(size_t)i * row_stride + j] = live ? 1 : 0;
+            if (types) types[(size_t)i * row_stride + j] = live ? ty[i][j] : 0;  // padding has type 0
         }
     }
     return CS_OK;

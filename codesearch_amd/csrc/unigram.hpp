@@ -9,6 +9,8 @@
 #include <string>
 #include <vector>
 
+#include "pair_form.hpp"
+
 struct cs_tokenizer;
 
 namespace cs {
@@ -33,6 +35,7 @@ struct UnigramSpec {
     struct Added { std::string text; int32_t id = -1; bool lstrip = false, rstrip = false; };
     std::vector<Added> added;  // matched verbatim in the raw text
     int32_t bos = -1, eos = -1, pad = -1;  // TemplateProcessing "<s> $A </s>", padding id
+    PairForm pair;                         // the post-processor's pair form (cs_tokenizer_encode_pairs)
 };
 
 class UnigramEngine {
@@ -46,6 +49,7 @@ public:
     int32_t pad() const { return spec_.pad; }
     int32_t bos() const { return spec_.bos; }
     int32_t eos() const { return spec_.eos; }
+    const PairForm& pair() const { return spec_.pair; }
 
 private:
     UnigramSpec spec_;

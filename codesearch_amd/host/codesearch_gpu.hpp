@@ -453,6 +453,53 @@ class FastEmbedder {
     const Tokenizer* tok_ = nullptr;
 };
 
+// NeuralReranker — src/rerank/neural.rs:17-122: a cross-encoder scores every (query, document) pair on the device
+// (cs_reranker_*); `rerank` orders by that score, `rerank_and_blend` blends its sigmoid with the min-max-normalised fusion
+// scores, 0.575 / 0.425.  Built from a sequence-classification snapshot directory (config.json, model.safetensors,
+// tokenizer.json or vocab.txt).
+class NeuralReranker {
+  public:
+    static constexpr float RERANK_WEIGHT = 0.575f, RRF_WEIGHT = 0.425f;  // neural.rs:12-13
+    explicit NeuralReranker(const std::string& model_dir, int device = 0, uint32_t max_length = 512) : max_length_(max_length) {
+        check(cs_reranker_create_from_dir(model_dir.c_str(), device, &h_));
+        const int32_t s = cs_tokenizer_create_from_dir(model_dir.c_str(), max_length, &tok_);
+        if (s != CS_OK) { cs_reranker_destroy(h_); h_ = nullptr; check(s); }
+    }
+    ~NeuralReranker() { cs_tokenizer_destroy(tok_); cs_reranker_destroy(h_); }
+    NeuralReranker(const NeuralReranker&) = delete;
+    NeuralReranker& operator=(const NeuralReranker&) = delete;
+
+    // (original index, rerank score), score descending — neural.rs:56-72
+    std::vector<std::pair<size_t, float>> rerank(const std::string& query, const std::vector<std::string>& documents) {
+        return run(query, documents, nullptr);
+    }
+    // (original index, blended score), descending — neural.rs:77-121
+    std::vector<std::pair<size_t, float>> rerank_and_blend(const std::string& query, const std::vector<std::string>& documents,
+                                                           const std::vector<float>& rrf_scores) {
+        if (documents.size() != rrf_scores.size()) throw Error(CS_ERR_BAD_ARG, "Documents and RRF scores must have same length");
+        return run(query, documents, rrf_scores.data());
+    }
+    cs_reranker* handle() const { return h_; }
+
+  private:
+    std::vector<std::pair<size_t, float>> run(const std::string& query, const std::vector<std::string>& documents, const float* rrf) {
+        std::vector<std::pair<size_t, float>> out;
+        if (documents.empty()) return out;  // neural.rs:57-59
+        std::string blob;
+        std::vector<uint64_t> off;
+        Tokenizer::pack(documents, blob, off);
+        std::vector<uint32_t> idx(documents.size());
+        std::vector<float> score(documents.size());
+        check(cs_reranker_rerank_texts(h_, tok_, query.c_str(), blob.data(), off.data(), documents.size(), max_length_, rrf, idx.data(),
+                                       score.data()));
+        for (size_t i = 0; i < idx.size(); ++i) out.emplace_back(idx[i], score[i]);
+        return out;
+    }
+    cs_reranker* h_ = nullptr;
+    cs_tokenizer* tok_ = nullptr;
+    uint32_t max_length_ = 512;
+};
+
 // One encoder replica per GPU inside this process and the index loop of src/index/mod.rs:626-762 over a sharded
 // VectorStore: every replica embeds the chunks whose ids fall on the shards of its own GPU, rows are appended without
 // leaving HBM, no collective (cs_embedders_*).

@@ -157,3 +157,28 @@ def rrf_fusion_with_exact(vector_results: Sequence[SearchResult], fts_results: S
             comb = fs if fs is not None else es
         out.append(FusedResult(cid, float(rrf), vs, comb, vr, fr if fr is not None else er))
     return _sorted_desc(out)
+
+
+# ---- the neural second pass (/root/reference/src/search/mod.rs:712-722, :829-885) ----------------
+
+def rerank_take_count(n_fused: int, max_results: int, rerank: bool, rerank_top: Optional[int] = None,
+                      filter_by_path: bool = False) -> int:
+    """mod.rs:712-722: how many fused results go on — `rerank_top` (default max_results) of them when the reranker is on,
+    else max_results (three times as many under a path filter)."""
+    if rerank:
+        return min(rerank_top if rerank_top is not None else max_results, n_fused)
+    return max_results * (3 if filter_by_path else 1)
+
+
+def rerank_step(reranker, query: str, results: Sequence[SearchResult], max_results: int,
+                filter_path: Optional[str] = None, project_root: str = "") -> List[SearchResult]:
+    """mod.rs:829-885: rerank_and_blend over the results' contents with their (fusion) scores, reorder with the blended
+    score as the new score, the post-reranking path filter, truncate to max_results.  `reranker`: a rerank.NeuralReranker
+    (None, or no results: the results go through unreranked, as when the reference's reranker is off)."""
+    results = list(results)
+    if reranker is not None and results:
+        reranked = reranker.rerank_and_blend(query, [r.content for r in results], [r.score for r in results])
+        results = [dataclasses.replace(results[idx], score=score) for idx, score in reranked]
+    if filter_path is not None:
+        results = [r for r in results if path_matches(r.path, filter_path, project_root, mcp=False)]
+    return results[:max_results]

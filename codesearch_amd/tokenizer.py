@@ -108,6 +108,28 @@ class WordPieceTokenizer:
         ids, mask = np.ascontiguousarray(ids[:, :L.value]), np.ascontiguousarray(mask[:, :L.value])
         return ids, mask
 
+    def encode_pairs(self, first, second: Sequence[str], max_length: int = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(first i, second i) pairs as a cross-encoder reads them -> (ids, mask, types) [n, L] int32.  `first` is one string
+        (a query against every document) or as many strings as `second`.  The arrangement is the handle's post-processor's
+        pair form; truncation is the crate's longest_first (cs_tokenizer_encode_pairs)."""
+        firsts = [first] if isinstance(first, str) else list(first)
+        n = len(second)
+        if not isinstance(first, str) and len(firsts) != n:
+            raise ValueError("as many first texts as second texts, or one string")
+        a_blob, a_off = pack_texts(firsts)
+        b_blob, b_off = pack_texts(second)
+        ml = int(max_length or 0)
+        L = C.c_uint32()
+        stride = ml or self.max_length
+        ids = np.empty((n, stride), np.int32)
+        mask = np.empty((n, stride), np.int32)
+        types = np.empty((n, stride), np.int32)
+        _lib.check(self._lib.cs_tokenizer_encode_pairs(self._h, a_blob, a_off.ctypes.data_as(_lib.u64p), len(firsts), b_blob,
+                                                       b_off.ctypes.data_as(_lib.u64p), n, ml, ids.ctypes.data_as(_lib.i32p),
+                                                       mask.ctypes.data_as(_lib.i32p), types.ctypes.data_as(_lib.i32p), stride,
+                                                       C.byref(L)))
+        return tuple(np.ascontiguousarray(a[:, :L.value]) for a in (ids, mask, types))
+
     def encode(self, text: str) -> List[int]:
         return self.encode_batch([text])[0][0].tolist()
 

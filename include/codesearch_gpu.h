@@ -559,6 +559,9 @@ CS_API int32_t cs_tokenizer_create_from_file(const char* vocab_path, int32_t low
  * GPT-2 pattern) optionally behind Digits; post_processor RobertaProcessing / TemplateProcessing [<bos>] $A [<eos>] /
  * ByteLevel; special added tokens (lstrip / rstrip honoured).  Dropout, word prefixes / suffixes and byte_fallback are
  * refused.  Merges run in the crate's own queue order (lowest rank, then leftmost), so ids equal the crate's. */
+/* A TemplateProcessing post_processor is also read for its `pair` (cs_tokenizer_encode_pairs): where `single` is
+ * <bos> $A <eos>, a `pair` that is neither <bos> $A <eos> $B <eos>, <bos> $A <eos> <eos> $B <eos> nor the crate's bare default
+ * $A $B is refused HERE (CS_ERR_UNSUPPORTED) — such a file loaded for single-text use before pair encoding existed. */
 CS_API int32_t cs_tokenizer_create_from_json(const char* tokenizer_json_path, uint32_t max_length,
                                       cs_tokenizer** out);
 /* A model directory: tokenizer.json when present, else vocab.txt with tokenizer_config.json's
@@ -577,6 +580,26 @@ CS_API int32_t cs_tokenizer_encode_batch(const cs_tokenizer* t, const char* utf8
                                   const uint64_t* offsets, uint32_t n, uint32_t max_length,
                                   int32_t* ids, int32_t* mask, uint32_t row_stride,
                                   uint32_t* out_len);
+
+/* Tokenizer::encode_batch over (first, second) pairs: what a cross-encoder reads (cs_reranker_*).  Pair i is first text i
+ * (a_utf8[a_offsets[i] .. a_offsets[i+1]), na = n texts) — or the ONE first text with na = 1, a query against every
+ * document — and second text i.  The arrangement is the handle's post-processor's:
+ *   vocab.txt / BertProcessing   [CLS] A [SEP] B [SEP], B and its [SEP] with token type 1
+ *   RobertaProcessing            <s> A </s> </s> B </s>, every type 0
+ *   TemplateProcessing           the file's `pair`, which must be one of those two arrangements (with the type ids the
+ *                                file gives); anything else is refused when the handle is created (CS_ERR_UNSUPPORTED).
+ *                                A file without `pair`, with the bare `$A $B` the crate writes when none was given,
+ *                                or whose `single` lacks <bos> or <eos>, creates a handle that refuses this call.
+ * Truncation is the crate's default, longest_first, on the two bodies (tokenizers 0.22.2 truncate_encodings): with
+ * budget = max_length - the template's tokens and n1 <= n2 the bodies' lengths (on equal lengths the FIRST body counts as
+ * the shorter), the shorter keeps n1 and the longer max(n1, budget - n1) when that fits the budget, else the shorter keeps
+ * budget / 2 and the longer the rest; tokens come off a body's end.  max_length 0 = the handle's; a max_length below
+ * the template's tokens + 2 is CS_ERR_BAD_ARG (the crate's behaviour there is degenerate and is not copied).
+ * ids / mask / types: [n, row_stride] i32, padded with [PAD] / 0 / 0; `types` may be NULL; ids and mask both NULL query
+ * *out_len only.  Re-entrant. */
+CS_API int32_t cs_tokenizer_encode_pairs(const cs_tokenizer* t, const char* a_utf8, const uint64_t* a_offsets, uint32_t na,
+                                  const char* b_utf8, const uint64_t* b_offsets, uint32_t n, uint32_t max_length,
+                                  int32_t* ids, int32_t* mask, int32_t* types, uint32_t row_stride, uint32_t* out_len);
 
 /* embed_batch / embed_batch_chunked from strings — embedder.rs:249-295.  Mini-batches of
  * `batch` texts (0 = the 256/128/64 policy, CODESEARCH_BATCH_SIZE honoured), each padded to
@@ -654,6 +677,55 @@ CS_API int32_t cs_embedders_index_texts(cs_embedders* e, const cs_tokenizer* t, 
                                  const volatile int32_t* cancel);
 CS_API int32_t cs_embedders_index_ids(cs_embedders* e, cs_shards* store, const int32_t* ids, const int32_t* mask, uint64_t n,
                                uint32_t seq_len, uint32_t batch, uint32_t* out_ids, const volatile int32_t* cancel);
+
+/* ------------------------------------------------------------------------------------
+ * Cross-encoder reranking — the reference's optional second pass (src/search/mod.rs:829-866, NeuralReranker in
+ * src/rerank/neural.rs: fastembed's TextRerank, JINARerankerV1TurboEn by default).  A cross-encoder is an encoder of this
+ * library (CS_ARCH_BERT, the JinaBert families; not CS_ARCH_MODERN, not a quantised model) with a score head on the CLS row
+ * of its last layer:      logit = w_c . tanh(W_p h_CLS + b_p) + b_c
+ * which is BertForSequenceClassification's pooler + classifier and RobertaClassificationHead's dense -> tanh -> out_proj
+ * alike.  The head runs as one kernel in place of the pooling (csrc/rerank_head.hip; its time is counted under
+ * CS_STAGE_POOL): f32 FMAs in a fixed order, so a pair's logit has the same bits on every run.
+ * Three facts about fastembed are stated from memory and are pinned by no source this project holds: TextRerank truncates
+ * at 512 tokens by default, returns the model's raw logits, and sorts its results by score, descending.
+ * One caller at a time per handle, as cs_embedder_*.
+ * ---------------------------------------------------------------------------------- */
+typedef struct cs_reranker cs_reranker;
+/* Floats of a score head: hidden * hidden + hidden + hidden + 1, in the order W_p [hidden, hidden] (row j = output j) | b_p
+ * | w_c | b_c. */
+CS_API uint64_t cs_rerank_head_count(const cs_bert_config* cfg);
+/* cfg / params / seed as cs_embedder_create (params NULL: synthetic encoder weights from `seed`; cfg->pooling is ignored:
+ * the head reads the CLS row); head: cs_rerank_head_count(cfg) floats of host memory, always given.  Like `params`, `head`
+ * carries no length: a block of another size cannot be detected here — the callers' mirrors check it (rerank.py raises
+ * CS_ERR_DIM_MISMATCH before the call), and cs_rerank_head_from_safetensors checks the file's shapes against cfg. */
+CS_API int32_t cs_reranker_create(const cs_bert_config* cfg, const float* params, const float* head, uint64_t seed,
+                           int32_t device, cs_reranker** out);
+/* The head of a checkpoint: pooler.dense.{weight,bias} + classifier.{weight,bias} (BertForSequenceClassification) or
+ * classifier.dense.* + classifier.out_proj.* (RobertaForSequenceClassification), with or without the encoder's "bert." /
+ * "roberta." prefix.  A file without a head, or with more than one label, is refused.  Pure host code. */
+CS_API int32_t cs_rerank_head_from_safetensors(const char* path, const cs_bert_config* cfg, float* head, uint64_t n_head);
+/* config.json + model.safetensors of a sequence-classification snapshot (the encoder's family is detected as
+ * cs_bert_config_from_dir detects it; num_labels must be 1).  ONNX exports and quantised models are refused. */
+CS_API int32_t cs_reranker_create_from_dir(const char* model_dir, int32_t device, cs_reranker** out);
+CS_API void cs_reranker_destroy(cs_reranker* h);
+/* The encoder inside, borrowed (never destroy it): for cs_embedder_last_hidden, the counters and the profiles, which then
+ * describe the scoring calls.  Embedding through it gives the encoder's CLS embeddings. */
+CS_API cs_embedder* cs_reranker_embedder(cs_reranker* h);
+/* One logit per row.  ids / mask / batch / cancel as cs_embedder_embed_ids; types: [n, seq_len] token-type ids (NULL =
+ * every token has type 0; an id outside the model's type table is CS_ERR_BAD_ARG); out_logits: [n] f32 host memory. */
+CS_API int32_t cs_reranker_score_ids(cs_reranker* h, const int32_t* ids, const int32_t* mask, const int32_t* types, uint64_t n,
+                              uint32_t seq_len, uint32_t batch, float* out_logits, const volatile int32_t* cancel);
+/* NeuralReranker::rerank (rrf_scores NULL) / rerank_and_blend (neural.rs:56-121) from strings: every (query, document i)
+ * pair is encoded with `tok` (cs_tokenizer_encode_pairs; max_length 0 = 512, capped at the model's positions), scored, and
+ * ordered.  out_index / out_score: [n], best first — document indices and their logits, or their blended scores. */
+CS_API int32_t cs_reranker_rerank_texts(cs_reranker* h, const cs_tokenizer* tok, const char* query, const char* docs_utf8,
+                                 const uint64_t* doc_offsets, uint64_t n, uint32_t max_length, const float* rrf_scores,
+                                 uint32_t* out_index, float* out_score);
+/* The host half, usable without a device.  cs_rerank_order: indices and scores by (score descending, index ascending), NaN
+ * last.  cs_rerank_blend: neural.rs:96-118 in f32 — sigmoid(logit) = 1 / (1 + exp(-logit)); rrf min-max normalised with
+ * max(range, 0.0001); 0.575 * rerank + 0.425 * rrf; then the same order.  n == 0: nothing is written, CS_OK. */
+CS_API int32_t cs_rerank_order(const float* scores, uint64_t n, uint32_t* out_index, float* out_score);
+CS_API int32_t cs_rerank_blend(const float* logits, const float* rrf_scores, uint64_t n, uint32_t* out_index, float* out_score);
 
 /* Arithmetic of the dense layers.  CS_GEMM_SPLIT_F16 (default): every f32 operand as two f16
  * values on the f16 MFMA, three MFMAs per product block, f32 accumulation — error per product
