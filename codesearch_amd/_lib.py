@@ -83,6 +83,13 @@ SIGNATURES = {
                                            u32p]),
     "cs_index_search_variants_masked": (C.c_int32, [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, u32p, C.c_uint64, f32p,
                                                     u32p, u32p, i32p]),
+    "cs_index_scope_create": (C.c_int32, [vp, u32p, C.c_uint64, C.POINTER(vp)]),
+    "cs_scope_destroy": (None, [vp]),
+    "cs_scope_info": (C.c_int32, [vp, u64p, u64p, u64p]),
+    "cs_index_search_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p]),
+    "cs_index_search_variants_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p,
+                                                    i32p]),
+    "cs_index_search_scoped_device": (C.c_int32, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]),
     "cs_merge_variants_device": (C.c_int32, [C.c_int32, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]),
     "cs_index_search_status": (C.c_int32, [vp, vp, u32p]),
     "cs_index_release_stream": (C.c_int32, [vp, vp]),
@@ -114,6 +121,10 @@ SIGNATURES = {
                                             u32p]),
     "cs_shards_search_variants_masked": (C.c_int32, [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, u32p, C.c_uint64, f32p,
                                                      u32p, u32p, i32p]),
+    "cs_shards_scope_create": (C.c_int32, [vp, u32p, C.c_uint64, C.POINTER(vp)]),
+    "cs_shards_search_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p]),
+    "cs_shards_search_variants_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p,
+                                                     i32p]),
     "cs_shards_read_rows": (C.c_int32, [vp, C.c_uint64, C.c_uint64, f32p]),
     "cs_index_read_rows": (C.c_int32, [vp, C.c_uint64, C.c_uint64, f32p]),
     "cs_index_debug_counters": (C.c_int32, [vp, u64p, u64p]),

@@ -15,6 +15,7 @@
 
 #include "masked_plan.hpp"
 #include "scan.hpp"
+#include "scope.hpp"
 
 namespace cs {
 
@@ -235,6 +236,10 @@ struct cs_index {
     uint64_t batched_searches = 0, batched_fallbacks = 0, q8_reruns = 0;
     std::vector<uint32_t> h_dead;
     bool built = false;
+    // Build generation: cs_index_build and cs_index_clear advance it.  Every other mutation un-builds the index and a
+    // search needs a build, so whatever a scope derived from the stored rows (its row list, scope.hpp) is current
+    // exactly while the generation is the one it was derived at.
+    std::atomic<uint64_t> build_gen{1};
     // streams of OTHER devices that carry unfinished appends into this corpus (index_append_from: an encoder replica on
     // another GPU writing its rows over xGMI); hipDeviceSynchronize on this device does not wait for them
     // peer appends in flight: ONE event per (source device, stream), re-recorded by every append on that stream (a later
@@ -702,9 +707,30 @@ uint64_t masked_bound(const cs_index* h, const uint32_t* allow, uint64_t allow_b
     return allowed_bound(allow, allow_bits, h->id_base, (uint64_t)h->id_base + h->n_ids, h->n_rows - h->n_removed);
 }
 
+// Everything of a masked or scoped search behind its row list, on `stream`: the optional prime pass and the gathered scan
+// over d_list[0, *d_len), then the shared merge -> the best k per query (outputs as launch_merge's, each optional).
+// `rows` sized the plan: an upper bound of *d_len (a mask's popcount bound) or the length itself (a scope's).
+int32_t run_row_list(cs_index* h, Workspace* w, const ScanPlan& plan, uint64_t rows, const uint32_t* d_list,
+                     const uint32_t* d_len, const float* d_queries, uint32_t nq, uint32_t k, uint64_t* d_keys, float* d_cos,
+                     uint32_t* d_ids, uint32_t* d_counts, hipStream_t stream) {
+    const uint64_t prime_rows = masked_prime_rows(h->route, rows, nq, k, h->dim, h->num_cus, scan_prime_supported(h->dim));
+    const ScanPrime* prime = nullptr;
+    if (prime_rows) {
+        const ScanPlan pp = plan_prime(prime_rows, h->dim, nq, k, h->num_cus);
+        CS_TRY(w->reserve_prime(pp, nq));
+        CS_TRY(launch_scan_masked(pp, h->d_corpus, h->dim, d_list, d_len, d_queries, nq, k, h->row_ids(), nullptr, stream,
+                                  &w->prime, true, prime_rows));
+        prime = &w->prime;
+    }
+    CS_TRY(launch_scan_masked(plan, h->d_corpus, h->dim, d_list, d_len, d_queries, nq, k, h->row_ids(), w->d_partial,
+                              stream, prime));
+    return launch_merge(w->d_partial, plan.blocks, nq, k, false, w->d_tmp_a, w->d_tmp_b, d_keys, d_cos, d_ids, d_counts,
+                        stream);
+}
+
 // A masked search (scan_masked.hip) on `stream`, for a mask whose bound (masked_bound) is > 0 and a plan sized by it: the
-// row list, the optional prime pass and the gathered scan, then the shared merge -> the best k keys per query in
-// d_keys [nq][k].  `allow` is host memory that must stay valid until the stream has passed the search.
+// row list, then run_row_list -> the best k keys per query in d_keys [nq][k].  `allow` is host memory that must stay
+// valid until the stream has passed the search.
 int32_t run_masked(cs_index* h, Workspace* w, const ScanPlan& plan, uint64_t bound, const float* d_queries, uint32_t nq,
                    uint32_t k, const uint32_t* allow, uint64_t allow_bits, uint64_t* d_keys, hipStream_t stream) {
     const MaskWindow win = mask_window(allow_bits, h->id_base, (uint64_t)h->id_base + h->n_ids);
@@ -714,20 +740,54 @@ int32_t run_masked(cs_index* h, Workspace* w, const ScanPlan& plan, uint64_t bou
                           stream));
     CS_TRY(launch_mask_rows(w->d_allow, win.lo, win.hi, h->n_removed ? h->d_dead : nullptr, h->row_ids(), h->n_rows,
                             w->d_mblocks, w->d_list, bound, stream));
-    const uint32_t* d_len = w->d_mblocks + nb;
-    const uint64_t prime_rows = masked_prime_rows(h->route, bound, nq, k, h->dim, h->num_cus, scan_prime_supported(h->dim));
-    const ScanPrime* prime = nullptr;
-    if (prime_rows) {
-        const ScanPlan pp = plan_prime(prime_rows, h->dim, nq, k, h->num_cus);
-        CS_TRY(w->reserve_prime(pp, nq));
-        CS_TRY(launch_scan_masked(pp, h->d_corpus, h->dim, w->d_list, d_len, d_queries, nq, k, h->row_ids(), nullptr, stream,
-                                  &w->prime, true, prime_rows));
-        prime = &w->prime;
-    }
-    CS_TRY(launch_scan_masked(plan, h->d_corpus, h->dim, w->d_list, d_len, d_queries, nq, k, h->row_ids(), w->d_partial,
-                              stream, prime));
-    return launch_merge(w->d_partial, plan.blocks, nq, k, false, w->d_tmp_a, w->d_tmp_b, d_keys, nullptr, nullptr, nullptr,
+    return run_row_list(h, w, plan, bound, w->d_list, w->d_mblocks + nb, d_queries, nq, k, d_keys, nullptr, nullptr, nullptr,
                         stream);
+}
+
+// ---- scopes (scope.hpp) ----------------------------------------------------------------------------
+
+// Frees what the scope owns.  It reads nothing of the index or the shards (sc->index only tells the two kinds apart).
+void scope_free(cs_scope* sc) {
+    for (cs_scope* p : sc->parts) scope_free(p);
+    if (sc->index) {
+        DeviceGuard g(sc->device);
+        if (sc->stream) { (void)hipStreamSynchronize(sc->stream); (void)hipStreamDestroy(sc->stream); }
+        free_bufs(false, sc->d_ids, sc->d_list, sc->d_blocks);
+        free_bufs(true, sc->h_len);
+    }
+    delete sc;
+}
+
+// Makes the scope's row list from its ids for the index as it stands (built), on the scope's stream (a remaking after
+// the device has finished what was enqueued on it), waits for it and publishes length and generation.  The caller holds sc->mu and has the index's device current.
+int32_t scope_make_list(cs_index* h, cs_scope* sc) {
+    const uint64_t gen = h->build_gen.load();
+    uint64_t live = 0;
+    if (sc->n_ids) {
+        const uint32_t nb = scope_list_blocks(sc->n_ids);
+        // a remaking rewrites d_list and d_blocks: a device-form search of the earlier generation that is still only
+        // enqueued on its caller's stream reads them, so the device's work is waited for first (once per build and scope)
+        if (sc->generation) CS_HIP(hipDeviceSynchronize());
+        CS_TRY(launch_scope_rows(sc->d_ids, sc->n_ids, h->n_removed ? h->d_dead : nullptr, h->row_ids(), h->n_rows,
+                                 sc->d_blocks, sc->d_list, sc->n_ids, sc->stream));
+        CS_HIP(hipMemcpyAsync(sc->h_len, sc->d_blocks + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, sc->stream));
+        CS_HIP(hipStreamSynchronize(sc->stream));
+        live = *sc->h_len;
+    }
+    sc->live_rows = live;
+    sc->generation = gen;
+    sc->refreshes += 1;
+    return CS_OK;
+}
+
+// The checks of a scoped search behind check_search's, then the refresh when one is due: *live = the list's length.
+int32_t scope_ready(cs_index* h, cs_scope* sc, uint64_t* live) {
+    if (!sc) return fail(CS_ERR_BAD_ARG, "null scope handle");
+    if (sc->index != h) return fail(CS_ERR_BAD_ARG, "the scope was made for another store");
+    std::lock_guard<std::mutex> lk(sc->mu);
+    if (scope_refresh_due(sc->generation, h->build_gen.load())) CS_TRY(scope_make_list(h, sc));
+    *live = sc->live_rows;
+    return CS_OK;
 }
 
 // The empty answer of a host-buffer search: every slot empty, as unpack_keys leaves it.
@@ -1011,6 +1071,7 @@ int32_t cs_index_build(cs_index* h) {
             h->split_cap = 0;
         }
     }
+    h->build_gen.fetch_add(1);       // scopes remake their row lists
     h->built = true;                 // store.rs:428
     return CS_OK;
 }
@@ -1034,6 +1095,7 @@ int32_t cs_index_clear(cs_index* h) {
     h->q8_searches.store(0);
     h->n_removed = 0;
     h->h_dead.clear();
+    h->build_gen.fetch_add(1);
     h->built = false;  // store.rs:702
     return CS_OK;
 }
@@ -1188,6 +1250,156 @@ int32_t cs_index_search_variants_masked(cs_index* h, const float* queries, uint3
     return s;
 }
 
+int32_t cs_index_scope_create(cs_index* h, const uint32_t* ids, uint64_t n, cs_scope** out) {
+    if (!out) return fail(CS_ERR_BAD_ARG, "out is null");
+    *out = nullptr;
+    if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
+    CS_TRY(check_scope_ids(ids, n));
+    DeviceGuard g(h->device);
+    cs_scope* sc = new cs_scope();
+    sc->index = h;
+    sc->device = h->device;
+    sc->n_ids = n;
+    const int32_t st = [&]() -> int32_t {
+        if (n) {
+            CS_HIP(hipStreamCreateWithFlags(&sc->stream, hipStreamNonBlocking));
+            CS_HIP(realloc_buf(sc->d_ids, (size_t)n));
+            CS_HIP(realloc_buf(sc->d_list, (size_t)n));
+            CS_HIP(realloc_buf(sc->d_blocks, (size_t)scope_list_blocks(n) + 1));
+            CS_HIP(realloc_buf(sc->h_len, 1, true));
+            CS_HIP(hipMemcpyAsync(sc->d_ids, ids, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, sc->stream));
+            CS_HIP(hipStreamSynchronize(sc->stream));  // `ids` is the caller's again
+        }
+        // an index that is not built has rows the device does not know yet (the row -> id table is uploaded by the
+        // build): the list is made by the first search, which needs that build
+        std::lock_guard<std::mutex> lk(sc->mu);
+        return h->built ? scope_make_list(h, sc) : CS_OK;
+    }();
+    if (st != CS_OK) {
+        scope_free(sc);
+        return st;
+    }
+    *out = sc;
+    return CS_OK;
+}
+
+void cs_scope_destroy(cs_scope* scope) {
+    if (scope) scope_free(scope);
+}
+
+int32_t cs_scope_info(const cs_scope* scope, uint64_t* n_ids, uint64_t* live_rows, uint64_t* refreshes) {
+    if (!scope) return fail(CS_ERR_BAD_ARG, "null scope handle");
+    uint64_t n = 0, live = 0, made = 0;
+    auto one = [&](const cs_scope* sc) {
+        std::lock_guard<std::mutex> lk(sc->mu);
+        n += sc->n_ids;
+        live += sc->live_rows;
+        made = std::max(made, sc->refreshes);
+    };
+    if (scope->index) one(scope);
+    for (const cs_scope* p : scope->parts) one(p);
+    if (n_ids) *n_ids = n;
+    if (live_rows) *live_rows = live;
+    if (refreshes) *refreshes = made;
+    return CS_OK;
+}
+
+int32_t cs_index_search_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                               float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
+    CS_TRY(check_search(h, nq, dim, k));
+    if (!queries || !out_cos || !out_ids || !out_counts) return fail(CS_ERR_BAD_ARG, "null buffer");
+    DeviceGuard g(h->device);
+    uint64_t live = 0;
+    CS_TRY(scope_ready(h, scope, &live));
+    if (live == 0) {  // nothing of the scope is stored: no launch
+        fill_empty(nq, k, out_cos, out_ids, out_counts);
+        return CS_OK;
+    }
+    const ScanPlan plan = plan_scan(live, h->dim, nq, k, h->num_cus);  // the grid follows the list's exact length
+    Workspace* w = acquire_pooled(h);
+    if (!w) return fail(CS_ERR_HIP, "could not create a HIP stream");
+    int32_t s = w->reserve(plan, nq, h->dim, k, true);
+    if (s == CS_OK) {
+        s = [&]() -> int32_t {
+            memcpy(w->h_queries, queries, (size_t)nq * h->dim * sizeof(float));
+            CS_HIP(hipMemcpyAsync(w->d_queries, w->h_queries, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice,
+                                  w->stream));
+            CS_TRY(run_row_list(h, w, plan, live, scope->d_list, scope->d_blocks + scope_list_blocks(scope->n_ids),
+                                w->d_queries, nq, k, w->h_keys, nullptr, nullptr, nullptr, w->stream));
+            CS_HIP(hipStreamSynchronize(w->stream));
+            unpack_keys(w->h_keys, nq, k, out_cos, out_ids, out_counts);
+            return CS_OK;
+        }();
+    }
+    release_pooled(h, w);
+    return s;
+}
+
+int32_t cs_index_search_variants_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,
+                                        uint32_t k, float* out_cos, uint32_t* out_ids, uint32_t* out_count,
+                                        int32_t* out_high_confidence) {
+    CS_TRY(check_search(h, nq, dim, k));
+    if (nq > CS_MAX_VARIANTS)
+        return fail(CS_ERR_BAD_ARG, "at most %u query variants per call, got %u", CS_MAX_VARIANTS, nq);
+    if (!queries || !out_cos || !out_ids || !out_count) return fail(CS_ERR_BAD_ARG, "null buffer");
+    DeviceGuard g(h->device);
+    uint64_t live = 0;
+    CS_TRY(scope_ready(h, scope, &live));
+    if (live == 0) {
+        fill_empty(1, k, out_cos, out_ids, nullptr);
+        *out_count = 0;
+        if (out_high_confidence) *out_high_confidence = 0;
+        return CS_OK;
+    }
+    const ScanPlan plan = plan_scan(live, h->dim, nq, k, h->num_cus);
+    Workspace* w = acquire_pooled(h);
+    if (!w) return fail(CS_ERR_HIP, "could not create a HIP stream");
+    int32_t s = w->reserve(plan, nq, h->dim, k, true);
+    if (s == CS_OK) {
+        s = [&]() -> int32_t {
+            if (!w->h_variant_meta) CS_HIP(hipHostMalloc(&w->h_variant_meta, 2 * sizeof(uint32_t)));
+            memcpy(w->h_queries, queries, (size_t)nq * h->dim * sizeof(float));
+            CS_HIP(hipMemcpyAsync(w->d_queries, w->h_queries, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice,
+                                  w->stream));
+            CS_TRY(run_row_list(h, w, plan, live, scope->d_list, scope->d_blocks + scope_list_blocks(scope->n_ids),
+                                w->d_queries, nq, k, w->d_keys, nullptr, nullptr, nullptr, w->stream));
+            CS_TRY(launch_merge_variants(w->d_keys, nq, k, k, w->h_keys, nullptr, nullptr, w->h_variant_meta,
+                                         w->h_variant_meta + 1, w->stream));
+            CS_HIP(hipStreamSynchronize(w->stream));
+            unpack_keys(w->h_keys, 1, k, out_cos, out_ids, nullptr);
+            *out_count = w->h_variant_meta[0];
+            if (out_high_confidence) *out_high_confidence = (int32_t)w->h_variant_meta[1];
+            return CS_OK;
+        }();
+    }
+    release_pooled(h, w);
+    return s;
+}
+
+int32_t cs_index_search_scoped_device(cs_index* h, cs_scope* scope, const float* d_queries, uint32_t nq, uint32_t dim,
+                                      uint32_t k, uint64_t* d_out_keys, float* d_out_cos, uint32_t* d_out_ids,
+                                      uint32_t* d_out_counts, void* stream) {
+    CS_TRY(check_search(h, nq, dim, k));
+    if (!d_queries) return fail(CS_ERR_BAD_ARG, "d_queries is null");
+    DeviceGuard g(h->device);
+    uint64_t live = 0;
+    CS_TRY(scope_ready(h, scope, &live));  // (waits for the device only when the list has to be remade)
+    hipStream_t st = (hipStream_t)stream;
+    if (live == 0) {  // the empty answer, enqueued: keys 0, cosines 0, ids 0xFFFFFFFF, counts 0
+        const size_t on = (size_t)nq * k;
+        if (d_out_keys) CS_HIP(hipMemsetAsync(d_out_keys, 0, on * sizeof(uint64_t), st));
+        if (d_out_cos) CS_HIP(hipMemsetAsync(d_out_cos, 0, on * sizeof(float), st));
+        if (d_out_ids) CS_HIP(hipMemsetAsync(d_out_ids, 0xFF, on * sizeof(uint32_t), st));
+        if (d_out_counts) CS_HIP(hipMemsetAsync(d_out_counts, 0, (size_t)nq * sizeof(uint32_t), st));
+        return CS_OK;
+    }
+    const ScanPlan plan = plan_scan(live, h->dim, nq, k, h->num_cus);
+    Workspace* w = for_stream(h, st);
+    CS_TRY(w->reserve(plan, nq, h->dim, k, false));
+    return run_row_list(h, w, plan, live, scope->d_list, scope->d_blocks + scope_list_blocks(scope->n_ids), d_queries, nq, k,
+                        d_out_keys, d_out_cos, d_out_ids, d_out_counts, st);
+}
+
 int32_t cs_merge_variants_device(int32_t device, const uint64_t* d_keys, uint32_t nv, uint32_t k, uint32_t limit,
                                  uint64_t* d_out_keys, float* d_out_cos, uint32_t* d_out_ids, uint32_t* d_out_count,
                                  uint32_t* d_out_high_confidence, void* stream) {
@@ -1287,6 +1499,12 @@ int32_t cs::index_search_masked_device(cs_index* h, const float* d_queries, uint
     Workspace* w = for_stream(h, stream);
     CS_TRY(w->reserve(plan, nq, h->dim, k, false));
     return run_masked(h, w, plan, bound, d_queries, nq, k, allow, allow_bits, d_out_keys, stream);
+}
+
+int32_t cs::index_scope_live_rows(cs_index* h, cs_scope* scope, uint64_t* live_rows) {
+    if (!h || !h->built) return fail(CS_ERR_NOT_BUILT, "Index not built. Call build_index() after inserting chunks.");
+    DeviceGuard g(h->device);
+    return scope_ready(h, scope, live_rows);
 }
 
 int32_t cs::index_reserve(cs_index* h, uint64_t rows) {

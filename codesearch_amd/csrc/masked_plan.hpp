@@ -138,4 +138,40 @@ inline void shard_mask(const uint32_t* allow, uint64_t allow_bits, uint64_t next
     }
 }
 
+// ---- scopes (index.hip cs_scope, scan_masked.hip launch_scope_rows) -------------------------------
+// A scope is a prepared set of chunk ids kept on the device: its strictly ascending ids and the row list made from
+// them (the live stored rows that hold those ids, ascending), searched any number of times without a mask.  The list is
+// made by one pass over the IDS, kMaskRowsPerBlock of them per block, so its cost follows the scope, not the store.
+
+// ids[0, n) strictly ascending?  -1 when they are, else the first position i >= 1 with ids[i] <= ids[i - 1].
+inline int64_t scope_ids_first_unsorted(const uint32_t* ids, uint64_t n) {
+    for (uint64_t i = 1; i < n; ++i)
+        if (ids[i] <= ids[i - 1]) return (int64_t)i;
+    return -1;
+}
+
+// Blocks of the id-list pass over a scope of n_ids ids.
+inline uint32_t scope_list_blocks(uint64_t n_ids) {
+    return (uint32_t)((n_ids + kMaskRowsPerBlock - 1) / kMaskRowsPerBlock);
+}
+
+// A row list made at build generation `list_generation` of its index (0: not made yet) is remade by the first search
+// that finds the index at another generation: cs_index_build and cs_index_clear advance it, and every other mutation
+// un-builds the index, so no search can run between a mutation and the next advance.
+inline bool scope_refresh_due(uint64_t list_generation, uint64_t index_generation) {
+    return list_generation != index_generation;
+}
+
+// The ascending global ids of a scope over a striped store, restated per shard in its local ids: out[s] stays ascending
+// (a later stripe of a shard has the larger local ids, and ids inside a stripe keep their order).
+inline void shard_scope_ids(const uint32_t* ids, uint64_t n, uint64_t stripe, uint32_t nshards,
+                            std::vector<std::vector<uint32_t>>& out) {
+    out.assign(nshards, std::vector<uint32_t>());
+    if (stripe == 0 || nshards == 0) return;
+    for (uint64_t i = 0; i < n; ++i) {
+        // (a local id never exceeds its global id, so it fits u32)
+        out[shard_of(ids[i], stripe, nshards)].push_back((uint32_t)shard_local_id(ids[i], stripe, nshards));
+    }
+}
+
 }  // namespace cs

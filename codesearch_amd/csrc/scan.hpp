@@ -88,6 +88,16 @@ int32_t launch_scan_masked(const ScanPlan& plan, const float* d_corpus, uint32_t
 int32_t index_search_masked_device(cs_index* h, const float* d_queries, uint32_t nq, uint32_t k, const uint32_t* allow,
                                    uint64_t allow_bits, uint64_t* d_out_keys, hipStream_t stream);
 
+// ---- scopes (index.hip cs_scope; plan: masked_plan.hpp) ------------------------------------------
+// Row list of a scope: for the strictly ascending chunk ids d_scope_ids[0, n_ids), the stored rows [0, n_rows) that hold
+// them and are not tombstoned, ascending, into d_list[0, list_cap); d_blocks[scope_list_blocks(n_ids) + 1] receives
+// the per-block offsets and, last, the list length.  Work and launches follow n_ids, not n_rows.
+int32_t launch_scope_rows(const uint32_t* d_scope_ids, uint64_t n_ids, const uint32_t* d_dead, RowIds ids, uint64_t n_rows,
+                          uint32_t* d_blocks, uint32_t* d_list, uint64_t list_cap, hipStream_t stream);
+// index.hip, for the sharded store: the live rows of a scope of h after the refresh that is due, if one is
+// (scope_refresh_due); the index must be built.
+int32_t index_scope_live_rows(cs_index* h, cs_scope* scope, uint64_t* live_rows);
+
 // corpus[(first_out_row + r) * dim + c] = cs_synth_value(seed, (first_row + r) * dim + c)
 int32_t launch_synth_fill(float* d_rows, uint64_t n, uint32_t dim, uint64_t seed,
                           uint64_t first_row, hipStream_t stream);

@@ -12,6 +12,8 @@
 //      the per-block partial lists go through the same launch_merge.  Other dims: one wave per row, as
 //      scan_topk_generic_kernel.
 //   3. prime pass (PRIME): the streaming scan's, over the first entries of the list.
+//   4. a scope (index.hip cs_scope) keeps its row list on the device and makes it from its id list, not from a bitmap:
+//      the end of this file.  Steps 2 and 3 read it as they read a mask's list.
 // The list holds live rows only, so the scan tests no tombstones.
 #include "scan.hpp"
 #include "masked_plan.hpp"
@@ -391,6 +393,103 @@ int32_t launch_scan_masked(const ScanPlan& plan, const float* d_corpus, uint32_t
         hipLaunchKernelGGL(scan_masked_generic_kernel, dim3(plan.blocks, nq), dim3(kBlock), lds, stream, d_corpus, d_list,
                            d_list_len, dim, d_queries, nq, k, plan.kpad, ids, d_partial);
     }
+    CS_HIP(hipGetLastError());
+    return CS_OK;
+}
+
+// ---- 4. row list of a scope ----------------------------------------------------------------------
+// The same list made from a scope's ascending chunk ids instead of a bitmap over the stored rows: one thread per id
+// decides its row, and the survivors are compacted with the discipline of part 1 (per-block counts over
+// kMaskRowsPerBlock ids, mask_scan_kernel, a ballot-ordered scatter), so ascending ids give ascending rows and the work
+// follows the scope's size.  Lane l of a step reads ids[... + l]: one coalesced 256-byte read per wave.  On a compacted
+// index the row comes from a lower bound over the ascending row -> id table: ~log2(n_rows) dependent loads per id.  The
+// expectation behind leaving it a plain bisection (reasoning, not a measurement: the pass has not been timed on a large
+// compacted index) is that neighbouring lanes hold neighbouring ids and walk the same upper levels, so those loads hit
+// in cache after the first lane's miss, and that sixteen independent steps per thread at full occupancy cover the rest.
+// Both kernels decide with scope_row, as the count and the scatter of part 1 both decide with row_allowed.
+constexpr uint32_t kNoRow = 0xFFFFFFFFu;
+
+__device__ __forceinline__ uint32_t scope_row(uint32_t id, const uint32_t* __restrict__ dead, RowIds ids, uint64_t n_rows) {
+    uint64_t r;
+    if (!ids.ids) {  // never compacted: row = id - id_base
+        if (id < ids.base) return kNoRow;
+        r = (uint64_t)id - ids.base;
+        if (r >= n_rows) return kNoRow;  // not issued (yet)
+    } else {
+        uint64_t lo = 0, hi = n_rows;  // first row whose id is >= id
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi) >> 1;
+            if (ids.ids[mid] < id) lo = mid + 1;
+            else hi = mid;
+        }
+        if (lo >= n_rows || ids.ids[lo] != id) return kNoRow;  // below id_base, not issued, or deleted and reclaimed
+        r = lo;
+    }
+    return row_is_dead(dead, r) ? kNoRow : (uint32_t)r;
+}
+
+// blocks[b] = live rows of ids [b * kMaskRowsPerBlock, +kMaskRowsPerBlock)
+__global__ void __launch_bounds__(kBlock)
+scope_count_kernel(const uint32_t* __restrict__ scope_ids, uint64_t n_ids, const uint32_t* __restrict__ dead, RowIds ids,
+                   uint64_t n_rows, uint32_t* __restrict__ blocks) {
+    __shared__ uint32_t wave_cnt[kWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint64_t i0 = (uint64_t)blockIdx.x * kMaskRowsPerBlock;
+    uint32_t c = 0;
+    for (uint32_t s = 0; s < kMaskIters; ++s) {
+        const uint64_t i = i0 + (uint64_t)s * kBlock + tid;
+        const bool p = i < n_ids && scope_row(scope_ids[i], dead, ids, n_rows) != kNoRow;
+        c += (uint32_t)__popcll(__ballot(p));
+    }
+    if (lane == 0) wave_cnt[wave] = c;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t t = 0;
+        for (int w = 0; w < kWaves; ++w) t += wave_cnt[w];
+        blocks[blockIdx.x] = t;
+    }
+}
+
+// list[blocks[b] + j] = the row of the j-th surviving id of block b; never past list_cap
+__global__ void __launch_bounds__(kBlock)
+scope_scatter_kernel(const uint32_t* __restrict__ scope_ids, uint64_t n_ids, const uint32_t* __restrict__ dead, RowIds ids,
+                     uint64_t n_rows, const uint32_t* __restrict__ blocks, uint32_t* __restrict__ list, uint64_t list_cap) {
+    __shared__ uint32_t wave_cnt[kWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint64_t i0 = (uint64_t)blockIdx.x * kMaskRowsPerBlock;
+    uint64_t pos = blocks[blockIdx.x];
+    const uint64_t below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));  // lanes under this one
+    for (uint32_t s = 0; s < kMaskIters; ++s) {
+        const uint64_t i = i0 + (uint64_t)s * kBlock + tid;
+        const uint32_t r = i < n_ids ? scope_row(scope_ids[i], dead, ids, n_rows) : kNoRow;
+        const bool p = r != kNoRow;
+        const uint64_t b = __ballot(p);
+        if (lane == 0) wave_cnt[wave] = (uint32_t)__popcll(b);
+        __syncthreads();
+        uint32_t off = 0, total = 0;
+        for (int w = 0; w < kWaves; ++w) {
+            off += (w < wave) ? wave_cnt[w] : 0u;
+            total += wave_cnt[w];
+        }
+        const uint64_t at = pos + off + (uint32_t)__popcll(b & below);
+        if (p && at < list_cap) list[at] = r;
+        pos += total;
+        __syncthreads();  // wave_cnt is rewritten by the next step
+    }
+}
+
+int32_t launch_scope_rows(const uint32_t* d_scope_ids, uint64_t n_ids, const uint32_t* d_dead, RowIds ids, uint64_t n_rows,
+                          uint32_t* d_blocks, uint32_t* d_list, uint64_t list_cap, hipStream_t stream) {
+    const uint32_t nb = scope_list_blocks(n_ids);
+    if (nb == 0) {
+        CS_HIP(hipMemsetAsync(d_blocks, 0, sizeof(uint32_t), stream));
+        return CS_OK;
+    }
+    hipLaunchKernelGGL(scope_count_kernel, dim3(nb), dim3(kBlock), 0, stream, d_scope_ids, n_ids, d_dead, ids, n_rows,
+                       d_blocks);
+    hipLaunchKernelGGL(mask_scan_kernel, dim3(1), dim3(1024), 0, stream, d_blocks, nb);
+    hipLaunchKernelGGL(scope_scatter_kernel, dim3(nb), dim3(kBlock), 0, stream, d_scope_ids, n_ids, d_dead, ids, n_rows,
+                       d_blocks, d_list, list_cap);
     CS_HIP(hipGetLastError());
     return CS_OK;
 }

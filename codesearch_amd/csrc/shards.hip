@@ -33,6 +33,7 @@
 
 #include "masked_plan.hpp"
 #include "scan.hpp"
+#include "scope.hpp"
 
 using namespace cs;
 
@@ -193,9 +194,10 @@ int32_t reserve_ctx(cs_shards* h, SearchCtx* c, uint32_t nq, uint32_t k, bool ho
 // (row stride of the gather buffer is the FULL nq).  src != null: the [nq, dim] queries are first brought to the
 // shard's device — from pinned host memory (src_device < 0) or from HBM of device src_device (the root of a
 // device-pointer search; a shard living on that device reads them in place).
-// masks != null: the masked search of that shard (index.hip index_search_masked_device) instead.
+// masks != null: the masked search of that shard (index.hip index_search_masked_device) instead; scope != null: its
+// scoped device search through the scope's part for that shard (cs_index_search_scoped_device).
 int32_t enqueue_shard(cs_shards* h, SearchCtx* c, uint32_t s, uint32_t q0, uint32_t qn, uint32_t nq, uint32_t k,
-                      const float* src, int src_device, const ShardMasks* masks = nullptr) {
+                      const float* src, int src_device, const ShardMasks* masks = nullptr, cs_scope* scope = nullptr) {
     DeviceGuard g(h->devices[s]);
     ShardCtx& x = c->sh[s];
     const size_t qbytes = (size_t)nq * h->dim * sizeof(float);
@@ -215,6 +217,9 @@ int32_t enqueue_shard(cs_shards* h, SearchCtx* c, uint32_t s, uint32_t q0, uint3
     if (masks)
         CS_TRY(index_search_masked_device(h->idx[s], q + (size_t)q0 * h->dim, qn, k, masks->words[s].data(), masks->bits[s],
                                           dst, x.stream));
+    else if (scope)
+        CS_TRY(cs_index_search_scoped_device(h->idx[s], scope->parts[s], q + (size_t)q0 * h->dim, qn, h->dim, k, dst, nullptr,
+                                             nullptr, nullptr, x.stream));
     else
         CS_TRY(cs_index_search_device(h->idx[s], q + (size_t)q0 * h->dim, qn, h->dim, k, dst, nullptr, nullptr,
                                       nullptr, x.stream));
@@ -283,9 +288,10 @@ int32_t check_shards_search(const cs_shards* h, uint32_t nq, uint32_t dim, uint3
 
 // variants != null: after the shard merge the nq lists are merged as query variants (scan.hip merge_variants_kernel) and
 // out_cos / out_ids hold ONE list of k; variants[0] = count, variants[1] = high-confidence flag.
-// masks != null: every shard runs the masked search (never a batched path: nothing to rerun).
+// masks != null / scope != null: every shard runs the masked / scoped search (never a batched path: nothing to rerun).
 int32_t shards_search_impl(cs_shards* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k, float* out_cos,
-                           uint32_t* out_ids, uint32_t* out_counts, uint32_t* variants, const ShardMasks* masks = nullptr) {
+                           uint32_t* out_ids, uint32_t* out_counts, uint32_t* variants, const ShardMasks* masks = nullptr,
+                           cs_scope* scope = nullptr) {
     CS_TRY(check_shards_search(h, nq, dim, k));
     if (!queries || !out_cos || !out_ids || !out_counts) return fail(CS_ERR_BAD_ARG, "null buffer");
     SearchCtx* c = take_ctx(h);
@@ -295,7 +301,7 @@ int32_t shards_search_impl(cs_shards* h, const float* queries, uint32_t nq, uint
         CS_TRY(order_behind_previous(h, c));
         memcpy(c->h_queries, queries, (size_t)nq * h->dim * sizeof(float));
         for (uint32_t s = 0; s < h->n; ++s) {
-            CS_TRY(enqueue_shard(h, c, s, 0, nq, nq, k, c->h_queries, -1, masks));
+            CS_TRY(enqueue_shard(h, c, s, 0, nq, nq, k, c->h_queries, -1, masks, scope));
             DeviceGuard g(h->devices[s]);
             CS_HIP(hipEventRecord(c->sh[s].done, c->sh[s].stream));
         }
@@ -319,7 +325,7 @@ int32_t shards_search_impl(cs_shards* h, const float* queries, uint32_t nq, uint
         CS_TRY(merge());
         c->merged_pending = false;  // every stream of the context is idle now
         bool again = false;
-        if (!masks) CS_TRY(rerun_overflowed(h, c, nq, k, &again));
+        if (!masks && !scope) CS_TRY(rerun_overflowed(h, c, nq, k, &again));
         if (again) CS_TRY(merge());
         if (variants) {
             unpack_keys(c->h_keys, 1, k, out_cos, out_ids, nullptr);
@@ -720,6 +726,87 @@ int32_t cs_shards_search_variants_masked(cs_shards* h, const float* queries, uin
     }
     uint32_t meta[2] = {0, 0};
     CS_TRY(shards_search_impl(h, queries, nq, dim, k, out_cos, out_ids, out_count, meta, &m));
+    *out_count = meta[0];
+    if (out_high_confidence) *out_high_confidence = (int32_t)meta[1];
+    return CS_OK;
+}
+
+}  // extern "C"
+
+// ---- scopes (scope.hpp) ----------------------------------------------------------------------------
+
+namespace {
+
+// Argument checks of a scoped shard search, then every shard's refresh that is due.  *empty: no shard holds a live row
+// of the scope (no launch).
+int32_t prepare_scope(cs_shards* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                      const void* out_a, const void* out_b, const void* out_c, bool* empty) {
+    CS_TRY(check_shards_search(h, nq, dim, k));
+    if (!queries || !out_a || !out_b || !out_c) return fail(CS_ERR_BAD_ARG, "null buffer");
+    if (!scope) return fail(CS_ERR_BAD_ARG, "null scope handle");
+    if (scope->shards != h || scope->parts.size() != h->n) return fail(CS_ERR_BAD_ARG, "the scope was made for another store");
+    *empty = true;
+    for (uint32_t s = 0; s < h->n; ++s) {
+        uint64_t live = 0;
+        CS_TRY(index_scope_live_rows(h->idx[s], scope->parts[s], &live));
+        if (live) *empty = false;
+    }
+    return CS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t cs_shards_scope_create(cs_shards* h, const uint32_t* ids, uint64_t n, cs_scope** out) {
+    if (!out) return fail(CS_ERR_BAD_ARG, "out is null");
+    *out = nullptr;
+    if (!h) return fail(CS_ERR_BAD_ARG, "null shards handle");
+    CS_TRY(check_scope_ids(ids, n));
+    std::vector<std::vector<uint32_t>> local;
+    shard_scope_ids(ids, n, h->stripe, h->n, local);
+    cs_scope* sc = new cs_scope();
+    sc->shards = h;
+    for (uint32_t s = 0; s < h->n; ++s) {
+        cs_scope* part = nullptr;
+        const int32_t st = cs_index_scope_create(h->idx[s], local[s].data(), local[s].size(), &part);
+        if (st != CS_OK) {
+            cs_scope_destroy(sc);
+            return st;
+        }
+        sc->parts.push_back(part);
+    }
+    *out = sc;
+    return CS_OK;
+}
+
+int32_t cs_shards_search_scoped(cs_shards* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                                float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
+    bool empty = true;
+    CS_TRY(prepare_scope(h, scope, queries, nq, dim, k, out_cos, out_ids, out_counts, &empty));
+    if (empty) {
+        fill_empty_lists(nq, k, out_cos, out_ids);
+        memset(out_counts, 0, (size_t)nq * sizeof(uint32_t));
+        return CS_OK;
+    }
+    return shards_search_impl(h, queries, nq, dim, k, out_cos, out_ids, out_counts, nullptr, nullptr, scope);
+}
+
+int32_t cs_shards_search_variants_scoped(cs_shards* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,
+                                         uint32_t k, float* out_cos, uint32_t* out_ids, uint32_t* out_count,
+                                         int32_t* out_high_confidence) {
+    if (nq > CS_MAX_VARIANTS) return fail(CS_ERR_BAD_ARG, "at most %u query variants per call, got %u", CS_MAX_VARIANTS, nq);
+    if (!out_count) return fail(CS_ERR_BAD_ARG, "null buffer");
+    bool empty = true;
+    CS_TRY(prepare_scope(h, scope, queries, nq, dim, k, out_cos, out_ids, out_count, &empty));
+    if (empty) {
+        fill_empty_lists(1, k, out_cos, out_ids);
+        *out_count = 0;
+        if (out_high_confidence) *out_high_confidence = 0;
+        return CS_OK;
+    }
+    uint32_t meta[2] = {0, 0};
+    CS_TRY(shards_search_impl(h, queries, nq, dim, k, out_cos, out_ids, out_count, meta, nullptr, scope));
     *out_count = meta[0];
     if (out_high_confidence) *out_high_confidence = (int32_t)meta[1];
     return CS_OK;

@@ -5,6 +5,7 @@
 // the cs_status and the reference-worded message.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 #include <map>
@@ -248,6 +249,69 @@ class VectorStore {
                                                      mask.data(), bits, cos.data(), ids.data(), &count, &flag)
                   : cs_index_search_variants_masked(h_, q.data(), (uint32_t)nq, (uint32_t)qdim, (uint32_t)limit, mask.data(),
                                                     bits, cos.data(), ids.data(), &count, &flag));
+        if (high_confidence) *high_confidence = flag != 0;
+        return results(cos, ids, count);
+    }
+    // A prepared set of chunk ids of this store (cs_scope): the ids and the row list made from them live on the device,
+    // and a search through it returns what the masked search over the same ids returns, with no mask to build, copy or
+    // compact per call.  The row list follows the store by itself (the first search after a build remakes it); the id
+    // list is fixed.  RAII; a Scope must go before its store.
+    class Scope {
+      public:
+        Scope(const VectorStore& st, std::vector<uint32_t> ids) {
+            std::sort(ids.begin(), ids.end());  // the ABI wants strictly ascending ids
+            ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+            check(st.sh_ ? cs_shards_scope_create(st.sh_, ids.data(), ids.size(), &h_)
+                         : cs_index_scope_create(st.h_, ids.data(), ids.size(), &h_));
+        }
+        ~Scope() { cs_scope_destroy(h_); }
+        Scope(Scope&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+        Scope& operator=(Scope&& o) noexcept {
+            if (this != &o) { cs_scope_destroy(h_); h_ = o.h_; o.h_ = nullptr; }
+            return *this;
+        }
+        Scope(const Scope&) = delete;
+        Scope& operator=(const Scope&) = delete;
+        cs_scope* handle() const { return h_; }
+        // ids held, rows of the list as last made, makings of the list (cs_scope_info)
+        void info(uint64_t* n_ids, uint64_t* live_rows, uint64_t* refreshes) const {
+            check(cs_scope_info(h_, n_ids, live_rows, refreshes));
+        }
+
+      private:
+        cs_scope* h_ = nullptr;
+    };
+    Scope scope(std::vector<uint32_t> ids) const { return Scope(*this, std::move(ids)); }
+    // search / search_variants over a prepared Scope (cs_index_search_scoped / cs_index_search_variants_scoped & the
+    // cs_shards_ forms)
+    std::vector<SearchResult> search(const std::vector<float>& query_embedding, size_t limit, const Scope& scope) const {
+        std::vector<float> cos(limit);
+        std::vector<uint32_t> ids(limit), counts(1);
+        const uint32_t dim = (uint32_t)query_embedding.size();
+        check(sh_ ? cs_shards_search_scoped(sh_, scope.handle(), query_embedding.data(), 1, dim, (uint32_t)limit, cos.data(),
+                                            ids.data(), counts.data())
+                  : cs_index_search_scoped(h_, scope.handle(), query_embedding.data(), 1, dim, (uint32_t)limit, cos.data(),
+                                           ids.data(), counts.data()));
+        return results(cos, ids, counts[0]);
+    }
+    std::vector<SearchResult> search_variants(const std::vector<std::vector<float>>& variants, size_t limit,
+                                              const Scope& scope, bool* high_confidence = nullptr) const {
+        const size_t nq = variants.size();
+        if (nq == 0) return {};
+        const size_t qdim = variants[0].size();
+        std::vector<float> q;
+        for (const auto& v : variants) {
+            if (v.size() != qdim) throw Error(CS_ERR_BAD_ARG, "queries of unequal length");
+            q.insert(q.end(), v.begin(), v.end());
+        }
+        std::vector<float> cos(limit);
+        std::vector<uint32_t> ids(limit);
+        uint32_t count = 0;
+        int32_t flag = 0;
+        check(sh_ ? cs_shards_search_variants_scoped(sh_, scope.handle(), q.data(), (uint32_t)nq, (uint32_t)qdim,
+                                                     (uint32_t)limit, cos.data(), ids.data(), &count, &flag)
+                  : cs_index_search_variants_scoped(h_, scope.handle(), q.data(), (uint32_t)nq, (uint32_t)qdim, (uint32_t)limit,
+                                                    cos.data(), ids.data(), &count, &flag));
         if (high_confidence) *high_confidence = flag != 0;
         return results(cos, ids, count);
     }

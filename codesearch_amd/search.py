@@ -4,9 +4,9 @@
 early-termination predicate.  Rank arithmetic on <= 9 x 200 items — host work by design."""
 from __future__ import annotations
 
-from typing import List, Sequence
+from typing import Dict, List, Optional, Sequence
 
-from .vector_store import SearchResult
+from .vector_store import Scope, SearchResult
 
 HIGH_CONFIDENCE_THRESHOLD = 0.15  # mod.rs:598: distance < 0.15 (cos > 0.7 under arroy's Cosine)
 EARLY_TERMINATION_TOP_N = 5       # mod.rs:599
@@ -64,6 +64,47 @@ def path_matches(path: str, filter_path: str, project_root: str = "", mcp: bool 
     if mcp:
         f = _trim_end(f, "/")
     return p.startswith(f)
+
+
+class ScopeCache:
+    """filter_path -> Scope of one store, for a server that answers the same `filter_path` over and over between two
+    index builds: the directory's chunk ids are looked up and prepared on first use (VectorStore.chunk_ids_under ->
+    VectorStore.scope) and searched from the device afterwards.  A scope's row list follows builds by itself; its ID
+    list does not, so invalidate() after chunks were inserted or deleted — the scopes are dropped and remade lazily."""
+
+    def __init__(self, store, project_root: str = "", mcp: bool = True):
+        self.store, self.project_root, self.mcp = store, project_root, mcp
+        self._scopes: Dict[str, Scope] = {}
+
+    def get(self, filter_path: str) -> Scope:
+        sc = self._scopes.get(filter_path)
+        if sc is None:
+            sc = self.store.scope(self.store.chunk_ids_under(filter_path, self.project_root, self.mcp))
+            self._scopes[filter_path] = sc
+        return sc
+
+    def invalidate(self) -> None:
+        for sc in self._scopes.values():
+            sc.close()
+        self._scopes.clear()
+
+    close = invalidate
+
+    def __len__(self) -> int:
+        return len(self._scopes)
+
+
+def vector_search_step(store, query_embeddings, limit: int, filter_path: Optional[str] = None,
+                       scopes: Optional[ScopeCache] = None, project_root: str = "", mcp: bool = True):
+    """search::search's vector leg (VectorStore.search_variants) narrowed to `filter_path` BEFORE the top-k instead of
+    after it (the reference post-filters the top limit * 3: src/mcp/mod.rs:251-252,400-425): through the caller's
+    ScopeCache where it holds one, else through a one-off masked search over the directory's chunk ids.
+    -> (results, high_confidence)."""
+    if filter_path is None:
+        return store.search_variants(query_embeddings, limit)
+    if scopes is not None:
+        return store.search_variants(query_embeddings, limit, scope=scopes.get(filter_path))
+    return store.search_variants(query_embeddings, limit, chunk_ids=store.chunk_ids_under(filter_path, project_root, mcp))
 
 
 def should_use_vector_only(results: Sequence[SearchResult], vector_only: bool) -> bool:

@@ -15,6 +15,7 @@ import dataclasses
 import hashlib
 import json
 import os
+import weakref
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
 
@@ -140,6 +141,74 @@ def allow_mask(chunk_ids, next_id: int) -> np.ndarray:
     return words
 
 
+def scope_ids(chunk_ids) -> np.ndarray:
+    """The id list of a scope (cs_index_scope_create): `chunk_ids` sorted, de-duplicated, negatives and ids above u32
+    dropped -> strictly ascending u32."""
+    ids = np.asarray(chunk_ids, np.int64).ravel()
+    ids = ids[(ids >= 0) & (ids <= 0xFFFFFFFF)]
+    return np.ascontiguousarray(np.unique(ids), np.uint32)
+
+
+def _one_of(chunk_ids, scope):
+    if chunk_ids is not None and scope is not None:
+        raise ValueError("chunk_ids= and scope= are exclusive: a scope already is a set of chunk ids")
+
+
+class Scope:
+    """A prepared set of chunk ids of one VectorStore (cs_scope): ids and the row list made from them live on the device,
+    and a search with `scope=` returns what the same search with `chunk_ids=` of those ids returns, without building,
+    copying or compacting a mask.  The row list follows the store: the first search after a build remakes it.
+    Made by VectorStore.scope(); a context manager; keeps its store alive."""
+
+    def __init__(self, store: "VectorStore", chunk_ids):
+        self._h = None
+        self.ids = scope_ids(chunk_ids)
+        self.store = store  # (a scope must be destroyed before its store)
+        h = C.c_void_p()
+        _lib.check(store._fn("scope_create")(store._h, self.ids.ctypes.data_as(u32p) if self.ids.size else None,
+                                             self.ids.size, C.byref(h)))
+        self._h = h
+
+    def __len__(self) -> int:
+        return int(self.ids.size)
+
+    def __bool__(self) -> bool:
+        return True  # an empty scope is still a scope: `if scope:` must not turn its search into an unscoped one
+
+    def info(self):
+        """-> (n_ids, live_rows, refreshes): ids held, rows of the list as last made, makings of the list."""
+        if not self._h:
+            raise CsError(_lib.CS_ERR_BAD_ARG, "scope is closed")
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _lib.check(self.store._lib.cs_scope_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            # VectorStore.close() closes its open scopes first, so the store is still there; a scope that the collector
+            # had already dropped from that set gets here after it, and cs_scope_destroy frees only what the scope owns
+            # (its buffers and its stream) without touching the index, so nothing is leaked either way
+            self.store._lib.cs_scope_destroy(self._h)
+            self._h = None
+            self.store._scopes.discard(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 # ---- the store ---------------------------------------------------------------------------------
 
 class VectorStore:
@@ -188,6 +257,7 @@ class VectorStore:
             _lib.check(self._lib.cs_index_create(self.dimensions, capacity, device, id_base, C.byref(handle)))
             self._pfx = "cs_index_"
         self._h = handle
+        self._scopes = weakref.WeakSet()  # open scopes: closed with the store, before it
         self._meta: Dict[int, ChunkMetadata] = {}
         self._removed: set = set()
         self._persisted_rows = 0
@@ -373,6 +443,8 @@ class VectorStore:
     # -- lifecycle
     def close(self):
         if getattr(self, "_h", None):
+            for sc in list(getattr(self, "_scopes", ())):  # a scope is destroyed before its store
+                sc.close()
             self._fn("destroy")(self._h)
             self._h = None
 
@@ -508,9 +580,23 @@ class VectorStore:
         mask = allow_mask(chunk_ids, nxt)
         return (mask.ctypes.data_as(u32p) if mask.size else None), (nxt if mask.size else 0), mask
 
-    def search_raw(self, queries, limit: int, chunk_ids=None):
+    def scope(self, chunk_ids) -> Scope:
+        """A Scope over `chunk_ids` (sorted and de-duplicated here, negatives dropped): prepare once, then pass it as
+        `scope=` to the searches below instead of `chunk_ids=`.  Works over a sharded store too."""
+        sc = Scope(self, chunk_ids)
+        self._scopes.add(sc)
+        return sc
+
+    def _scope_handle(self, scope: Scope):
+        if not scope._h:  # (a scope of another store is the library's to refuse)
+            raise CsError(_lib.CS_ERR_BAD_ARG, "scope is closed")
+        return scope._h
+
+    def search_raw(self, queries, limit: int, chunk_ids=None, scope: Optional[Scope] = None):
         """-> (cos [nq, limit] f32, ids [nq, limit] u32, counts [nq] u32); rows best-first.
-        chunk_ids: only these chunks are searched (cs_index_search_masked: the exact top `limit` among them)."""
+        chunk_ids: only these chunks are searched (cs_index_search_masked: the exact top `limit` among them).
+        scope: the same through a prepared Scope (cs_index_search_scoped); exclusive with chunk_ids."""
+        _one_of(chunk_ids, scope)
         q = np.ascontiguousarray(queries, np.float32)
         if q.ndim == 1:
             q = q[None, :]
@@ -518,7 +604,11 @@ class VectorStore:
         cos = np.zeros((nq, max(limit, 1)), np.float32)
         ids = np.zeros((nq, max(limit, 1)), np.uint32)
         counts = np.zeros(nq, np.uint32)
-        if chunk_ids is None:
+        if scope is not None:
+            _lib.check(self._fn("search_scoped")(self._h, self._scope_handle(scope), q.ctypes.data_as(f32p), nq, dim, limit,
+                                                 cos.ctypes.data_as(f32p), ids.ctypes.data_as(u32p),
+                                                 counts.ctypes.data_as(u32p)))
+        elif chunk_ids is None:
             _lib.check(self._fn("search")(self._h, q.ctypes.data_as(f32p), nq, dim, limit,
                                                  cos.ctypes.data_as(f32p), ids.ctypes.data_as(u32p),
                                                  counts.ctypes.data_as(u32p)))
@@ -529,21 +619,22 @@ class VectorStore:
                                                  counts.ctypes.data_as(u32p)))
         return cos, ids, counts
 
-    def search(self, query_embedding, limit: int, chunk_ids=None) -> List[SearchResult]:
-        """store.rs:431-486.  Results whose metadata is missing are skipped (store.rs:465).  chunk_ids: search_raw."""
-        cos, ids, counts = self.search_raw(query_embedding, limit, chunk_ids=chunk_ids)
+    def search(self, query_embedding, limit: int, chunk_ids=None, scope: Optional[Scope] = None) -> List[SearchResult]:
+        """store.rs:431-486.  Results whose metadata is missing are skipped (store.rs:465).  chunk_ids / scope: search_raw."""
+        cos, ids, counts = self.search_raw(query_embedding, limit, chunk_ids=chunk_ids, scope=scope)
         return self._results(cos[0], ids[0], int(counts[0]))
 
-    def search_batch(self, query_embeddings, limit: int, chunk_ids=None) -> List[List[SearchResult]]:
-        """One call for all query variants (the par_iter of src/search/mod.rs:508-511).  chunk_ids: search_raw."""
-        cos, ids, counts = self.search_raw(query_embeddings, limit, chunk_ids=chunk_ids)
+    def search_batch(self, query_embeddings, limit: int, chunk_ids=None, scope: Optional[Scope] = None) -> List[List[SearchResult]]:
+        """One call for all query variants (the par_iter of src/search/mod.rs:508-511).  chunk_ids / scope: search_raw."""
+        cos, ids, counts = self.search_raw(query_embeddings, limit, chunk_ids=chunk_ids, scope=scope)
         return [self._results(cos[i], ids[i], int(counts[i])) for i in range(len(counts))]
 
-    def search_variants(self, query_embeddings, limit: int, chunk_ids=None):
+    def search_variants(self, query_embeddings, limit: int, chunk_ids=None, scope: Optional[Scope] = None):
         """search::search's vector leg (src/search/mod.rs:508-611) in one call: every variant searched for `limit`
         rows, union with a chunk keeping its best score, best `limit` distinct chunks best-first, merged on
         the device.  -> (results, high_confidence) where high_confidence is the early-termination predicate
-        (top five all distance < 0.15).  chunk_ids: only these chunks are searched (search_raw)."""
+        (top five all distance < 0.15).  chunk_ids / scope: only these chunks are searched (search_raw)."""
+        _one_of(chunk_ids, scope)
         q = np.ascontiguousarray(query_embeddings, np.float32)
         if q.ndim == 1:
             q = q[None, :]
@@ -551,7 +642,11 @@ class VectorStore:
         cos = np.zeros(max(limit, 1), np.float32)
         ids = np.zeros(max(limit, 1), np.uint32)
         count, flag = C.c_uint32(), C.c_int32()
-        if chunk_ids is None:
+        if scope is not None:
+            _lib.check(self._fn("search_variants_scoped")(self._h, self._scope_handle(scope), q.ctypes.data_as(f32p), nq, dim,
+                                                          limit, cos.ctypes.data_as(f32p), ids.ctypes.data_as(u32p),
+                                                          C.byref(count), C.byref(flag)))
+        elif chunk_ids is None:
             _lib.check(self._fn("search_variants")(self._h, q.ctypes.data_as(f32p), nq, dim, limit,
                                                           cos.ctypes.data_as(f32p), ids.ctypes.data_as(u32p),
                                                           C.byref(count), C.byref(flag)))

@@ -198,6 +198,47 @@ CS_API int32_t cs_index_search_variants_masked(cs_index* h, const float* queries
                                         float* out_cos, uint32_t* out_ids, uint32_t* out_count,
                                         int32_t* out_high_confidence);
 
+/* Search scopes — prepared id sets for the masked search.  A caller that narrows to a directory holds a list of chunk
+ * ids and asks the same `filter_path` again and again between two builds; a scope is that list prepared once: it lives
+ * on the device, belongs to ONE store and is searched any number of times with no mask to build, copy or compact.
+ * THE RULE: a scoped search returns, bit for bit (cosines, ids, counts, the variants' count and flag), what the masked
+ * search of the same store returns at that moment for a bitmap holding exactly the scope's ids — after every build,
+ * delete, append and clear.
+ *   ids : absolute chunk ids, STRICTLY ASCENDING; an unsorted or repeated id is CS_ERR_BAD_ARG and the message names
+ *         the first offending position (one host pass).  n == 0 is a valid, empty scope (ids may be NULL).  Ids below
+ *         id_base, never issued or already deleted are legal: they match nothing now and match once they are issued.
+ * Footprint: 8 bytes of HBM per id (the ids, 4 B each, and the row list made from them: the live stored rows that
+ * hold those ids, ascending, 4 B each) plus 4 B per 4,096 ids; the list's length is also kept on the host, read back
+ * once when the list is made, never per search.
+ * Staleness: cs_index_build and cs_index_clear advance the index's build generation (every other mutation un-builds it,
+ * and a search needs a build).  The first scoped search that finds another generation than the list's remakes the list
+ * from the kept ids — a REFRESH: under the scope's own mutex, on a stream of the scope's own, synchronised before the
+ * list is published, so no search that has returned or is running reads a list that is being replaced; a refresh also
+ * waits for the device's work first, which covers a cs_index_search_scoped_device call that was only enqueued.  Mutating
+ * a store while it is searched remains the caller's to exclude, and an enqueued device-form search counts as running
+ * until its stream has passed it: it must have completed before cs_index_build or cs_index_clear.  Per search: no host work proportional to the id space, no mask copy, no row-list launch; a scope
+ * with no live row fills the empty answer and launches nothing.
+ * A scope MUST be destroyed before its store.  Concurrent searches through one scope or through several are safe. */
+typedef struct cs_scope cs_scope;
+CS_API int32_t cs_index_scope_create(cs_index* h, const uint32_t* ids, uint64_t n, cs_scope** out);
+CS_API void    cs_scope_destroy(cs_scope* scope);
+/* *n_ids: ids held; *live_rows: length of the row list as last made; *refreshes: makings of the list — 1 after a create
+ * on a built store (0 on one not built: the first search makes it), +1 per build generation actually searched.  Over a
+ * sharded store the first two are sums over the shards.  Each output optional. */
+CS_API int32_t cs_scope_info(const cs_scope* scope, uint64_t* n_ids, uint64_t* live_rows, uint64_t* refreshes);
+/* cs_index_search_masked / cs_index_search_variants_masked with the scope in place of the mask.  Errors: those of
+ * cs_index_search with the same texts, checked first; then a scope made for another store is CS_ERR_BAD_ARG. */
+CS_API int32_t cs_index_search_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,
+                               uint32_t k, float* out_cos, uint32_t* out_ids, uint32_t* out_counts);
+CS_API int32_t cs_index_search_variants_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,
+                                        uint32_t k, float* out_cos, uint32_t* out_ids, uint32_t* out_count,
+                                        int32_t* out_high_confidence);
+/* Device-pointer form (arguments as cs_index_search_device): only enqueues on `stream`, unless the list has to be
+ * refreshed first.  Always exact: a scoped search takes no batched route, so there is no status to ask for. */
+CS_API int32_t cs_index_search_scoped_device(cs_index* h, cs_scope* scope, const float* d_queries, uint32_t nq, uint32_t dim,
+                                      uint32_t k, uint64_t* d_out_keys, float* d_out_cos, uint32_t* d_out_ids,
+                                      uint32_t* d_out_counts, void* stream);
+
 /* Synchronises `stream` and reports in *overflowed whether any cs_index_search_device call of more
  * than 16 queries issued by this thread on it since the previous status call overflowed a candidate buffer
  * (its results are then incomplete); clears the condition. */
@@ -293,6 +334,16 @@ CS_API int32_t cs_shards_search_masked(cs_shards* h, const float* queries, uint3
 CS_API int32_t cs_shards_search_variants_masked(cs_shards* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
                                          const uint32_t* allow, uint64_t allow_bits,
                                          float* out_cos, uint32_t* out_ids, uint32_t* out_count,
+                                         int32_t* out_high_confidence);
+/* Scopes over the sharded store (cs_index_scope_create & co.): `ids` are global ids, strictly ascending; the scope holds
+ * one scope per shard over that shard's local ids (ascending global ids stay ascending there), every shard runs its
+ * scoped device search on its own stream, and the shard merge returns global ids.  Destroy with cs_scope_destroy,
+ * before the store. */
+CS_API int32_t cs_shards_scope_create(cs_shards* h, const uint32_t* ids, uint64_t n, cs_scope** out);
+CS_API int32_t cs_shards_search_scoped(cs_shards* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,
+                                uint32_t k, float* out_cos, uint32_t* out_ids, uint32_t* out_counts);
+CS_API int32_t cs_shards_search_variants_scoped(cs_shards* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,
+                                         uint32_t k, float* out_cos, uint32_t* out_ids, uint32_t* out_count,
                                          int32_t* out_high_confidence);
 CS_API int32_t cs_shards_read_rows(cs_shards* h, uint64_t first_id, uint64_t n, float* out_rows);
 
