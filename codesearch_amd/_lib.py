@@ -86,6 +86,8 @@ SIGNATURES = {
     "cs_index_scope_create": (C.c_int32, [vp, u32p, C.c_uint64, C.POINTER(vp)]),
     "cs_scope_destroy": (None, [vp]),
     "cs_scope_info": (C.c_int32, [vp, u64p, u64p, u64p]),
+    "cs_scope_set_route": (C.c_int32, [vp, C.c_int32]),
+    "cs_scope_route_info": (C.c_int32, [vp, u64p, u64p, u64p, u64p]),
     "cs_index_search_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p]),
     "cs_index_search_variants_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p,
                                                     i32p]),

@@ -752,7 +752,7 @@ void scope_free(cs_scope* sc) {
     if (sc->index) {
         DeviceGuard g(sc->device);
         if (sc->stream) { (void)hipStreamSynchronize(sc->stream); (void)hipStreamDestroy(sc->stream); }
-        free_bufs(false, sc->d_ids, sc->d_list, sc->d_blocks);
+        free_bufs(false, sc->d_ids, sc->d_list, sc->d_blocks, sc->d_blocked, sc->d_table);
         free_bufs(true, sc->h_len);
     }
     delete sc;
@@ -770,9 +770,35 @@ int32_t scope_make_list(cs_index* h, cs_scope* sc) {
         if (sc->generation) CS_HIP(hipDeviceSynchronize());
         CS_TRY(launch_scope_rows(sc->d_ids, sc->n_ids, h->n_removed ? h->d_dead : nullptr, h->row_ids(), h->n_rows,
                                  sc->d_blocks, sc->d_list, sc->n_ids, sc->stream));
+        // a scope that can ever take the filter (it has a table): the blocked-rows bitmap over the store's rows as they
+        // are now, and the host's view of the list, in the same read-back.  Without room for the bitmap the scope
+        // simply keeps to the gathered scan.
+        sc->filter_state = false;
+        bool state = sc->d_table && h->n_rows > 0;
+        if (state) {
+            const size_t words = (size_t)scope_blocked_words(h->n_rows);
+            if (words > sc->blocked_words) {
+                sc->blocked_words = 0;
+                if (realloc_buf(sc->d_blocked, words) == hipSuccess) sc->blocked_words = words;
+                else { (void)hipGetLastError(); state = false; }
+            }
+        }
+        if (state) {
+            CS_TRY(launch_scope_filter_state(sc->d_list, sc->d_blocks + nb, sc->n_ids, h->n_rows, sc->d_blocked, sc->d_table,
+                                             sc->stream));
+            CS_HIP(hipMemcpyAsync(sc->h_len + 1, sc->d_table, sc->table_words * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                  sc->stream));
+            CS_HIP(hipMemcpyAsync(sc->h_len + 1 + sc->table_words, sc->d_list,
+                                  (size_t)scope_head_entries(sc->n_ids) * sizeof(uint32_t), hipMemcpyDeviceToHost, sc->stream));
+        }
         CS_HIP(hipMemcpyAsync(sc->h_len, sc->d_blocks + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, sc->stream));
         CS_HIP(hipStreamSynchronize(sc->stream));
         live = *sc->h_len;
+        sc->filter_state = state && scope_filter_capable(h->dim, live);
+        if (!sc->filter_state && sc->d_blocked) {  // everything fits phase 0 now: no bitmap is held for it
+            free_bufs(false, sc->d_blocked);
+            sc->blocked_words = 0;
+        }
     }
     sc->live_rows = live;
     sc->generation = gen;
@@ -781,13 +807,67 @@ int32_t scope_make_list(cs_index* h, cs_scope* sc) {
 }
 
 // The checks of a scoped search behind check_search's, then the refresh when one is due: *live = the list's length.
-int32_t scope_ready(cs_index* h, cs_scope* sc, uint64_t* live) {
+// fp != null (the host-buffer searches of nq queries, top-k): the search's route too — fp->ok says that it wants the
+// int8 filter and holds its plan (scoped_filter_plan.hpp; host arithmetic over what the scope keeps, under its mutex).
+int32_t scope_ready(cs_index* h, cs_scope* sc, uint64_t* live, ScopedFilterPlan* fp = nullptr, uint32_t nq = 0,
+                    uint32_t k = 0) {
     if (!sc) return fail(CS_ERR_BAD_ARG, "null scope handle");
     if (sc->index != h) return fail(CS_ERR_BAD_ARG, "the scope was made for another store");
     std::lock_guard<std::mutex> lk(sc->mu);
     if (scope_refresh_due(sc->generation, h->build_gen.load())) CS_TRY(scope_make_list(h, sc));
     *live = sc->live_rows;
+    if (!fp) return CS_OK;
+    *fp = ScopedFilterPlan();
+    ScopedRouteIn in;
+    in.mode = sc->route.load();
+    in.q8_serves = q8_serves(h);
+    if (in.mode == CS_SCOPE_ROUTE_GATHER || !in.q8_serves || !sc->filter_state) return CS_OK;
+    const ScopedFilterPlan plan = plan_scoped_filter(h->dim, h->n_rows, sc->list_view(), nq, k, h->q8_rows, true, cu_count(),
+                                                     filter_knobs());
+    in.plan_ok = plan.ok;
+    in.live = sc->live_rows;
+    in.span = plan.span;
+    const SearchShape shape{nq, k, h->dim, sc->live_rows, h->num_cus, h->normed_rows >= h->n_rows, h->use_split,
+                            batched_supported(h->dim), scan_prime_supported(h->dim), true, 0};
+    if (scoped_wants_filter(h->route, shape, in)) *fp = plan;
     return CS_OK;
+}
+
+// The keys of a host-buffer scoped search, enqueued on the workspace's stream: the best k per query into d_keys [nq][k]
+// (device-addressable).  The queries are in w->h_queries.  With a filter plan whose int8 query planes fit, the index's
+// filter + exact refine runs over the plan's row ranges with the scope's bitmap where the tombstones go; an overflowed
+// candidate buffer is settled here, on the host, by the exact rerun over the scope's list (the unscoped list scan would
+// ignore the scope) — counted per scope, no strike against the int8 copy and no f16-copy stage.  Else the gathered scan.
+int32_t run_scoped(cs_index* h, cs_scope* sc, Workspace* w, const ScanPlan& plan, uint64_t live, const ScopedFilterPlan& fp,
+                   uint32_t nq, uint32_t k, uint64_t* d_keys) {
+    const uint32_t* d_len = sc->d_blocks + scope_list_blocks(sc->n_ids);
+    bool planes = false;
+    if (fp.ok) CS_TRY(w->reserve_split_queries(nq, h->dim, true, &planes));
+    if (!(fp.ok && planes)) {
+        sc->gathered_searches.fetch_add(1);
+        CS_HIP(hipMemcpyAsync(w->d_queries, w->h_queries, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice, w->stream));
+        return run_row_list(h, w, plan, live, sc->d_list, d_len, w->d_queries, nq, k, d_keys, nullptr, nullptr, nullptr, w->stream);
+    }
+    sc->filter_searches.fetch_add(1);
+    CS_TRY(w->reserve_batched(nq, k));
+    w->qw.q_pinned = w->h_queries;  // the prep kernel reads the pinned queries and leaves the device copy
+    w->last_via_q8 = false;         // (this search is no reading of the int8 copy in the strike bookkeeping)
+    Q8View q8;
+    q8.d_q8 = h->d_q8; q8.d_tmeta = h->d_tmeta; q8.d_mu = h->d_mu; q8.rows = h->q8_rows;
+    CS_TRY(launch_scan_split(w->bs, w->qw, h->d_corpus, nullptr, h->n_rows, h->dim, w->d_queries, nq, k, sc->d_blocked,
+                             h->row_ids(), d_keys, nullptr, nullptr, nullptr, w->stream, h->filter_margin, &q8, &fp.plan,
+                             sc->d_list));
+    if (live <= batched_cap(k)) return CS_OK;  // a phase appends at most one candidate per allowed row
+    bool overflow = false;
+    CS_TRY(w->read_overflow(w->stream, &overflow));
+    if (!overflow) return CS_OK;
+    sc->overflow_reruns.fetch_add(1);
+    // The overflow is the scope's alone.  Left in the workspace, word [0] would be folded into the device's count of
+    // overflowed searches by the next filter search's first kernel and surface later as a strike against the int8 copy
+    // (fold_overflows) and in the index's fallback total; word [1] is the sticky word of searches of more than
+    // kGatedMaxQ queries, which no host-buffer search reads.  Both are cleared here, in stream order, behind the read.
+    CS_HIP(hipMemsetAsync(w->bs.d_overflow, 0, 2 * sizeof(uint32_t), w->stream));
+    return run_row_list(h, w, plan, live, sc->d_list, d_len, w->d_queries, nq, k, d_keys, nullptr, nullptr, nullptr, w->stream);
 }
 
 // The empty answer of a host-buffer search: every slot empty, as unpack_keys leaves it.
@@ -811,6 +891,7 @@ RouteKnobs route_knobs_from_env() {
     if (const char* e = std::getenv("CS_SCAN_PRIME_MIN_K")) r.prime_min_k = (uint32_t)std::atol(e);  // 0 = off
     if (const char* e = std::getenv("CS_SCAN_PRIME_MIN_ROWS")) r.prime_min_rows = (uint64_t)std::atoll(e);
     if (const char* e = std::getenv("CS_SCAN_PRIME_ROWS")) r.prime_rows = (uint64_t)std::atoll(e);
+    if (const char* e = std::getenv("CS_SCOPE_FILTER_MAX_SPAN")) r.scope_span_single = r.scope_span_few = r.scope_span_many = std::atof(e);
     return r;
 }
 
@@ -1266,7 +1347,13 @@ int32_t cs_index_scope_create(cs_index* h, const uint32_t* ids, uint64_t n, cs_s
             CS_HIP(realloc_buf(sc->d_ids, (size_t)n));
             CS_HIP(realloc_buf(sc->d_list, (size_t)n));
             CS_HIP(realloc_buf(sc->d_blocks, (size_t)scope_list_blocks(n) + 1));
-            CS_HIP(realloc_buf(sc->h_len, 1, true));
+            // a scope that can ever take the int8 filter keeps the stride table and reads more back per making
+            const bool tables = h->use_q8 && scope_filter_capable(h->dim, n);
+            if (tables) {
+                sc->table_words = 1 + (size_t)scope_stride_entries(n);
+                CS_HIP(realloc_buf(sc->d_table, sc->table_words));
+            }
+            CS_HIP(realloc_buf(sc->h_len, tables ? 1 + sc->table_words + (size_t)scope_head_entries(n) : 1, true));
             CS_HIP(hipMemcpyAsync(sc->d_ids, ids, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, sc->stream));
             CS_HIP(hipStreamSynchronize(sc->stream));  // `ids` is the caller's again
         }
@@ -1304,13 +1391,38 @@ int32_t cs_scope_info(const cs_scope* scope, uint64_t* n_ids, uint64_t* live_row
     return CS_OK;
 }
 
+int32_t cs_scope_set_route(cs_scope* scope, int32_t route) {
+    if (!scope) return fail(CS_ERR_BAD_ARG, "null scope handle");
+    if (!scope->index) return fail(CS_ERR_BAD_ARG, "a scope over a sharded store always takes the gathered scan");
+    if (route != CS_SCOPE_ROUTE_AUTO && route != CS_SCOPE_ROUTE_GATHER && route != CS_SCOPE_ROUTE_FILTER)
+        return fail(CS_ERR_BAD_ARG, "route must be CS_SCOPE_ROUTE_AUTO, _GATHER or _FILTER, got %d", route);
+    scope->route.store(route);
+    return CS_OK;
+}
+
+int32_t cs_scope_route_info(const cs_scope* scope, uint64_t* filter_searches, uint64_t* gathered_searches,
+                            uint64_t* overflow_reruns, uint64_t* extra_bytes) {
+    if (!scope) return fail(CS_ERR_BAD_ARG, "null scope handle");
+    uint64_t extra = 0;
+    if (scope->index) {
+        std::lock_guard<std::mutex> lk(scope->mu);
+        extra = (uint64_t)(scope->blocked_words + scope->table_words) * sizeof(uint32_t);
+    }
+    if (filter_searches) *filter_searches = scope->filter_searches.load();
+    if (gathered_searches) *gathered_searches = scope->gathered_searches.load();
+    if (overflow_reruns) *overflow_reruns = scope->overflow_reruns.load();
+    if (extra_bytes) *extra_bytes = extra;
+    return CS_OK;
+}
+
 int32_t cs_index_search_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
                                float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
     CS_TRY(check_search(h, nq, dim, k));
     if (!queries || !out_cos || !out_ids || !out_counts) return fail(CS_ERR_BAD_ARG, "null buffer");
     DeviceGuard g(h->device);
     uint64_t live = 0;
-    CS_TRY(scope_ready(h, scope, &live));
+    ScopedFilterPlan fp;
+    CS_TRY(scope_ready(h, scope, &live, &fp, nq, k));
     if (live == 0) {  // nothing of the scope is stored: no launch
         fill_empty(nq, k, out_cos, out_ids, out_counts);
         return CS_OK;
@@ -1322,10 +1434,7 @@ int32_t cs_index_search_scoped(cs_index* h, cs_scope* scope, const float* querie
     if (s == CS_OK) {
         s = [&]() -> int32_t {
             memcpy(w->h_queries, queries, (size_t)nq * h->dim * sizeof(float));
-            CS_HIP(hipMemcpyAsync(w->d_queries, w->h_queries, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice,
-                                  w->stream));
-            CS_TRY(run_row_list(h, w, plan, live, scope->d_list, scope->d_blocks + scope_list_blocks(scope->n_ids),
-                                w->d_queries, nq, k, w->h_keys, nullptr, nullptr, nullptr, w->stream));
+            CS_TRY(run_scoped(h, scope, w, plan, live, fp, nq, k, w->h_keys));
             CS_HIP(hipStreamSynchronize(w->stream));
             unpack_keys(w->h_keys, nq, k, out_cos, out_ids, out_counts);
             return CS_OK;
@@ -1344,7 +1453,8 @@ int32_t cs_index_search_variants_scoped(cs_index* h, cs_scope* scope, const floa
     if (!queries || !out_cos || !out_ids || !out_count) return fail(CS_ERR_BAD_ARG, "null buffer");
     DeviceGuard g(h->device);
     uint64_t live = 0;
-    CS_TRY(scope_ready(h, scope, &live));
+    ScopedFilterPlan fp;
+    CS_TRY(scope_ready(h, scope, &live, &fp, nq, k));
     if (live == 0) {
         fill_empty(1, k, out_cos, out_ids, nullptr);
         *out_count = 0;
@@ -1359,10 +1469,8 @@ int32_t cs_index_search_variants_scoped(cs_index* h, cs_scope* scope, const floa
         s = [&]() -> int32_t {
             if (!w->h_variant_meta) CS_HIP(hipHostMalloc(&w->h_variant_meta, 2 * sizeof(uint32_t)));
             memcpy(w->h_queries, queries, (size_t)nq * h->dim * sizeof(float));
-            CS_HIP(hipMemcpyAsync(w->d_queries, w->h_queries, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice,
-                                  w->stream));
-            CS_TRY(run_row_list(h, w, plan, live, scope->d_list, scope->d_blocks + scope_list_blocks(scope->n_ids),
-                                w->d_queries, nq, k, w->d_keys, nullptr, nullptr, nullptr, w->stream));
+            // (an overflow of the filter route is settled inside, before the variants' merge)
+            CS_TRY(run_scoped(h, scope, w, plan, live, fp, nq, k, w->d_keys));
             CS_TRY(launch_merge_variants(w->d_keys, nq, k, k, w->h_keys, nullptr, nullptr, w->h_variant_meta,
                                          w->h_variant_meta + 1, w->stream));
             CS_HIP(hipStreamSynchronize(w->stream));

@@ -94,6 +94,12 @@ int32_t index_search_masked_device(cs_index* h, const float* d_queries, uint32_t
 // the per-block offsets and, last, the list length.  Work and launches follow n_ids, not n_rows.
 int32_t launch_scope_rows(const uint32_t* d_scope_ids, uint64_t n_ids, const uint32_t* d_dead, RowIds ids, uint64_t n_rows,
                           uint32_t* d_blocks, uint32_t* d_list, uint64_t list_cap, hipStream_t stream);
+// What a scope that can take the int8 filter keeps beside its list (scoped_filter_plan.hpp), from d_list[0, *d_len),
+// *d_len <= list_cap: d_blocked[scope_blocked_words(n_rows)] = one bit per stored row, 1 where the row is NOT in the list (the
+// list holds live rows only, so tombstoned rows are blocked too; bits past n_rows are 1), and d_table[0] = the last
+// entry, d_table[1 + j] = d_list[1024 j] (1 + ceil(list_cap / 1024) words).
+int32_t launch_scope_filter_state(const uint32_t* d_list, const uint32_t* d_len, uint64_t list_cap, uint64_t n_rows,
+                                  uint32_t* d_blocked, uint32_t* d_table, hipStream_t stream);
 // index.hip, for the sharded store: the live rows of a scope of h after the refresh that is due, if one is
 // (scope_refresh_due); the index must be built.
 int32_t index_scope_live_rows(cs_index* h, cs_scope* scope, uint64_t* live_rows);
@@ -177,7 +183,11 @@ int32_t launch_corpus_split(const float* d_corpus, const float* d_norms, _Float1
 int32_t launch_scan_split(const BatchedState& st, const SplitQueryWs& qw, const float* d_corpus,
                           const _Float16* d_split, uint64_t n_rows, uint32_t dim, const float* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_dead,
                           RowIds id_base, uint64_t* d_out_keys, float* d_out_cos, uint32_t* d_out_ids,
-                          uint32_t* d_out_counts, hipStream_t stream, float margin, const Q8View* q8 = nullptr);
+                          uint32_t* d_out_counts, hipStream_t stream, float margin, const Q8View* q8 = nullptr,
+                          const FilterPlan* prepared = nullptr, const uint32_t* d_phase0_list = nullptr);
+const FilterKnobs& filter_knobs();  // the plan's laboratory knobs as the launcher reads them (the product: the defaults)
+// prepared (a scoped search, scoped_filter_plan.hpp): launch that plan instead of plan_filter's — its phase 0 re-scores
+// the first prepared->phase0_rows entries of d_phase0_list, and d_dead is the scope's blocked-rows bitmap.
 // Proven bound of |filter cosine - exact cosine| for unit vectors of this width (scan_filter.hip header);
 // `subnormals_exact` = the f16 MFMA consumes subnormal inputs exactly (sh_denorm_selftest).
 float filter_margin(uint32_t dim, bool subnormals_exact);

@@ -850,7 +850,9 @@ score_filter_rw_kernel(const _Float16* __restrict__ corpus_h, uint64_t row_lo, u
 // rows, so the ~500 candidates a k = 200 phase brings per query took 32 us on one CU (9 queries:
 // 9 CUs busy, 247 idle) and take ~3 us on 32.
 constexpr int RK_THREADS = 256;
-template <int J>
+// LIST (phase 0 of a scoped search, scoped_filter_plan.hpp; first_rows != 0): candidate i is row dead[i] — the scope's
+// ascending row list is passed where the tombstone bitmap goes, and it holds live rows only, so no bit is tested.
+template <int J, bool LIST = false>
 __global__ void __launch_bounds__(RK_THREADS)
 rescore_keys_kernel(const float* __restrict__ corpus, const float* __restrict__ queries,
                     const float* __restrict__ qmag, uint64_t* __restrict__ cand,
@@ -881,7 +883,7 @@ rescore_keys_kernel(const float* __restrict__ corpus, const float* __restrict__ 
 #pragma unroll
         for (int u = 0; u < RU; ++u) {
             const uint32_t i = i0 + u * (RK_THREADS / 32) + hw;  // half-wave uniform
-            row[u] = (i < n) ? (first_rows ? i : (uint32_t)slots[i]) : 0u;
+            row[u] = (i < n) ? (first_rows ? (LIST ? dead[i] : i) : (uint32_t)slots[i]) : 0u;
         }
 #pragma unroll
         for (int u = 0; u < RU; ++u) {
@@ -908,7 +910,7 @@ rescore_keys_kernel(const float* __restrict__ corpus, const float* __restrict__ 
                 const float d = half_sum_s(dot);
                 const float c = (qm == 0.0f || xmag == 0.0f) ? 0.0f : d / (qm * xmag);  // batch.rs:320-323
                 // NaN/Inf scores are never returned
-                const bool live = !(first_rows && dead) || !((dead[row[u] >> 5] >> (row[u] & 31)) & 1u);
+                const bool live = LIST || !(first_rows && dead) || !((dead[row[u] >> 5] >> (row[u] & 31)) & 1u);
                 if (l32 == 0)
                     slots[i] = (live && c > -__builtin_huge_valf() && c < __builtin_huge_valf()) ? key_pack(c, id_base.of(row[u])) : 0ull;
             }
@@ -1453,7 +1455,7 @@ int32_t launch_corpus_q8(const float* d_corpus, const float* d_norms, int8_t* d_
 }
 
 // The laboratory knobs of the filter plan (filter_plan.hpp), read once; in the product library they are the defaults.
-static const FilterKnobs& filter_knobs() {
+const FilterKnobs& filter_knobs() {
     static const FilterKnobs kn = [] {
         FilterKnobs d;
         const auto num = [](const char* name, auto& v) {
@@ -1549,7 +1551,7 @@ static int32_t scan_split_impl(const BatchedState& st, const SplitQueryWs& qw, c
                                const _Float16* d_split, uint64_t n_rows, const float* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_dead,
                                RowIds id_base, uint64_t* d_out_keys, float* d_out_cos,
                                uint32_t* d_out_ids, uint32_t* d_out_counts, hipStream_t stream, float margin,
-                               const Q8View* q8) {
+                               const Q8View* q8, const FilterPlan* prepared, const uint32_t* d_phase0_list) {
     constexpr uint32_t dim = 128 * J;
     const uint32_t cap = batched_cap(k);
     static PerDeviceOnce attr_set;  // function attributes are per device
@@ -1565,7 +1567,12 @@ static int32_t scan_split_impl(const BatchedState& st, const SplitQueryWs& qw, c
     }));
     const FilterKnobs& kn = filter_knobs();
     const bool q8_ready = q8 && q8->d_q8 && qw.d_q8q && qw.d_qmeta;
-    const FilterPlan plan = plan_filter(dim, n_rows, nq, k, q8_ready ? q8->rows : 0, qw.d_q8q_hi && qw.d_q8q_lo, cu_count(), kn);
+    // a prepared plan (a scoped search: scoped_filter_plan.hpp) is launched as it stands: its phase 0 are the first
+    // phase0_rows entries of d_phase0_list, and d_dead is the scope's blocked-rows bitmap
+    if (prepared && !(q8_ready && d_phase0_list && d_dead && prepared->use_q8 && (!prepared->two_planes || (qw.d_q8q_hi && qw.d_q8q_lo))))
+        return fail(CS_ERR_BAD_ARG, "a prepared filter plan needs the int8 copy, its query planes, a bitmap and a phase-0 list");
+    const FilterPlan plan = prepared ? *prepared
+                                     : plan_filter(dim, n_rows, nq, k, q8_ready ? q8->rows : 0, qw.d_q8q_hi && qw.d_q8q_lo, cu_count(), kn);
     hipLaunchKernelGGL(prep_queries_kernel<J>, dim3((nq + 7) / 8), dim3(256), 0, stream,
                        qw.q_pinned ? qw.q_pinned : d_queries, qw.q_pinned ? const_cast<float*>(d_queries) : nullptr, nq,
                        qw.d_qmag, qw.d_qsplit, st.d_tau, st.d_cnt, st.d_carry, k, st.d_overflow, plan.phase0_rows,
@@ -1606,10 +1613,14 @@ static int32_t scan_split_impl(const BatchedState& st, const SplitQueryWs& qw, c
         if (ph.tail_hi > ph.tail_lo)  // fewer than 128 rows behind the int8 copy's last complete tile
             hipLaunchKernelGGL(tail_candidates_kernel, dim3(nq), dim3(128), 0, stream, ph.tail_lo, ph.tail_hi, d_dead, cand,
                                st.d_cnt, cap);
-        const bool first = ph.lo == 0, last = ph.hi >= n_rows;
+        const bool first = ph.lo == 0, last = p + 1 == plan.nphases;  // (plan_filter: the phase that reaches n_rows)
         if (ph.hi > ph.lo && !first) CS_HIP(hipGetLastError());
-        hipLaunchKernelGGL(rescore_keys_kernel<J>, dim3(ph.rk_blocks, nq), dim3(RK_THREADS), 0, stream, d_corpus, d_queries,
-                           qw.d_qmag, st.d_cand, st.d_cnt, cap, id_base, first ? (uint32_t)ph.hi : 0u, d_dead);
+        if (first && prepared)
+            hipLaunchKernelGGL((rescore_keys_kernel<J, true>), dim3(ph.rk_blocks, nq), dim3(RK_THREADS), 0, stream, d_corpus,
+                               d_queries, qw.d_qmag, st.d_cand, st.d_cnt, cap, id_base, plan.phase0_rows, d_phase0_list);
+        else
+            hipLaunchKernelGGL(rescore_keys_kernel<J>, dim3(ph.rk_blocks, nq), dim3(RK_THREADS), 0, stream, d_corpus, d_queries,
+                               qw.d_qmag, st.d_cand, st.d_cnt, cap, id_base, first ? (uint32_t)ph.hi : 0u, d_dead);
         CS_HIP(hipGetLastError());
         CS_TRY(launch_select_candidates(st, nq, cap, k, last, d_out_keys, d_out_cos, d_out_ids, d_out_counts, stream));
     }
@@ -1619,11 +1630,12 @@ static int32_t scan_split_impl(const BatchedState& st, const SplitQueryWs& qw, c
 int32_t launch_scan_split(const BatchedState& st, const SplitQueryWs& qw, const float* d_corpus,
                           const _Float16* d_split, uint64_t n_rows, uint32_t dim, const float* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_dead,
                           RowIds id_base, uint64_t* d_out_keys, float* d_out_cos, uint32_t* d_out_ids,
-                          uint32_t* d_out_counts, hipStream_t stream, float margin, const Q8View* q8) {
+                          uint32_t* d_out_counts, hipStream_t stream, float margin, const Q8View* q8,
+                          const FilterPlan* prepared, const uint32_t* d_phase0_list) {
     const auto impl = dim == 384 ? scan_split_impl<3> : dim == 768 ? scan_split_impl<6> : dim == 1024 ? scan_split_impl<8> : nullptr;
     if (!impl) return fail(CS_ERR_UNSUPPORTED, "split scan supports dim 384/768/1024, got %u", dim);
     return impl(st, qw, d_corpus, d_split, n_rows, d_queries, nq, k, d_dead, id_base, d_out_keys, d_out_cos, d_out_ids,
-                d_out_counts, stream, margin, q8);
+                d_out_counts, stream, margin, q8, prepared, d_phase0_list);
 }
 
 }  // namespace cs

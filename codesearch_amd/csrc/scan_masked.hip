@@ -17,6 +17,7 @@
 // The list holds live rows only, so the scan tests no tombstones.
 #include "scan.hpp"
 #include "masked_plan.hpp"
+#include "scoped_filter_plan.hpp"
 #include "scan_wave.hpp"
 
 namespace cs {
@@ -490,6 +491,32 @@ int32_t launch_scope_rows(const uint32_t* d_scope_ids, uint64_t n_ids, const uin
     hipLaunchKernelGGL(mask_scan_kernel, dim3(1), dim3(1024), 0, stream, d_blocks, nb);
     hipLaunchKernelGGL(scope_scatter_kernel, dim3(nb), dim3(kBlock), 0, stream, d_scope_ids, n_ids, d_dead, ids, n_rows,
                        d_blocks, d_list, list_cap);
+    CS_HIP(hipGetLastError());
+    return CS_OK;
+}
+
+// ---- 5. what a scope keeps for the int8 filter (scoped_filter_plan.hpp) -----------------------------
+// The blocked-rows bitmap is the complement of the list's bits: the launcher fills it with ones, then one thread per
+// list entry clears its row's bit.  Entries are distinct, so the result does not depend on the order of the atomics.
+// The same thread leaves every 1,024th entry (and the last) in the table the host reads back once per making.
+__global__ void __launch_bounds__(kBlock)
+scope_unblock_kernel(const uint32_t* __restrict__ list, const uint32_t* __restrict__ len, uint32_t* __restrict__ blocked,
+                     uint32_t* __restrict__ table) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t n = *len;
+    if (i >= n) return;
+    const uint32_t r = list[i];
+    atomicAnd(&blocked[r >> 5], ~(1u << (r & 31)));
+    if ((i & 1023) == 0) table[1 + (i >> 10)] = r;
+    if (i == n - 1) table[0] = r;
+}
+
+int32_t launch_scope_filter_state(const uint32_t* d_list, const uint32_t* d_len, uint64_t list_cap, uint64_t n_rows,
+                                  uint32_t* d_blocked, uint32_t* d_table, hipStream_t stream) {
+    CS_HIP(hipMemsetAsync(d_blocked, 0xFF, (size_t)scope_blocked_words(n_rows) * sizeof(uint32_t), stream));
+    if (list_cap == 0) return CS_OK;
+    hipLaunchKernelGGL(scope_unblock_kernel, dim3((uint32_t)((list_cap + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
+                       d_list, d_len, d_blocked, d_table);
     CS_HIP(hipGetLastError());
     return CS_OK;
 }

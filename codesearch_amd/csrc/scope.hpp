@@ -10,10 +10,14 @@
 
 #include "common.hpp"
 #include "masked_plan.hpp"
+#include "scoped_filter_plan.hpp"
 
 // Over one cs_index (index != null) the scope holds, in HBM of the index's device, 8 bytes per id: its ascending ids and
 // the row list made from them.  Over a sharded store (shards != null) it holds one such scope per shard over that
-// shard's local ids, and nothing else on a device.
+// shard's local ids, and nothing else on a device.  A scope over an index that can ever take the int8 filter (the index
+// keeps an int8 copy, more than kFilterPhase0 ids: scoped_filter_plan.hpp) additionally keeps, made with the list and
+// remade at every refresh: the blocked-rows bitmap (one bit per stored row, HBM), 4 B per 1,024 ids of stride table,
+// and on the host (pinned, read back with the length) the list's head, the stride table and the last entry.
 struct cs_scope {
     cs_index* index = nullptr;
     cs_shards* shards = nullptr;
@@ -23,7 +27,12 @@ struct cs_scope {
     uint32_t* d_ids = nullptr;     // [n_ids] ascending
     uint32_t* d_list = nullptr;    // [n_ids]: the first live_rows entries are the row list
     uint32_t* d_blocks = nullptr;  // [scope_list_blocks(n_ids) + 1]: the id-list pass's offsets; the last word = live_rows
-    uint32_t* h_len = nullptr;     // pinned: where a making of the list reads its length back, once
+    // pinned: where a making of the list reads back, once, [0] its length and, for a scope with filter tables, [1] the
+    // last entry, [2, 1 + table_words) every 1,024th entry, then the first min(n_ids, kScopeHead) entries
+    uint32_t* h_len = nullptr;
+    uint32_t* d_blocked = nullptr; // [blocked_words]: the blocked-rows bitmap, scope_blocked_words(n_rows) of them in use
+    uint32_t* d_table = nullptr;   // [table_words]: the last entry, then every 1,024th (launch_scope_filter_state)
+    size_t blocked_words = 0, table_words = 0;
     hipStream_t stream = nullptr;  // the makings of the list run here
     // mu guards the making of the list and the three words below: a search reads them under it, and a refresh
     // publishes them only after its stream has been synchronised
@@ -31,6 +40,19 @@ struct cs_scope {
     uint64_t generation = 0;       // build generation of the index the list was made at; 0 = not made
     uint64_t live_rows = 0;
     uint64_t refreshes = 0;        // makings of the list
+    bool filter_state = false;     // the bitmap and the host tables are those of `generation` (guarded by mu as well)
+    // the route of the host-buffer searches (cs_scope_set_route) and what they took (cs_scope_route_info)
+    std::atomic<int32_t> route{CS_SCOPE_ROUTE_AUTO};
+    std::atomic<uint64_t> filter_searches{0}, gathered_searches{0}, overflow_reruns{0};
+
+    cs::ScopeListView list_view() const {  // under mu, filter_state set
+        cs::ScopeListView v;
+        v.live = live_rows;
+        v.last = h_len[1];
+        v.stride = h_len + 2;
+        v.head = h_len + 1 + table_words;
+        return v;
+    }
 };
 
 namespace cs {

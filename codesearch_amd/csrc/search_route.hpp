@@ -38,6 +38,15 @@ struct RouteKnobs {
     // 500,000 rows below k = 48 and 100,000 from there on.
     uint32_t prime_min_k = 1;
     uint64_t prime_min_rows = 0, prime_rows = 0;
+    // scoped searches through the int8 filter (scoped_filter_plan.hpp scoped_wants_filter): the filter phases may
+    // stream at most this many rows per live row of the scope, by query count (CS_SCOPE_FILTER_MAX_SPAN sets all three).
+    // Measured over 10M x 384 (profiles/scoped_filter_10m.jsonl), filter / gathered ms at span 2, 4, 10:
+    // one query, k = 10: 0.66 / 1.19, 0.66 / 0.63, 0.63 / 0.29; k = 200: 0.77 / 1.24, 0.75 / 0.69, 0.72 / 0.34 — ahead at 2,
+    // behind at 4; nine variants, k = 200: 0.87 / 4.33, 0.87 / 2.36, 0.91 / 1.12 — ahead at every measured span (the
+    // gathered scan makes three passes, the filter one).  Two to eight queries were not measured: 4 is the byte
+    // break-even of one gathered pass (1 B per element streamed against 4 B), reasoning only.
+    double scope_span_single = 2.0, scope_span_few = 4.0, scope_span_many = 10.0;
+    double scope_filter_max_span(uint32_t nq) const { return nq == 1 ? scope_span_single : nq < 9 ? scope_span_few : scope_span_many; }
 };
 
 // One search as the route sees it.

@@ -277,6 +277,13 @@ class VectorStore {
         void info(uint64_t* n_ids, uint64_t* live_rows, uint64_t* refreshes) const {
             check(cs_scope_info(h_, n_ids, live_rows, refreshes));
         }
+        // CS_SCOPE_ROUTE_AUTO / _GATHER / _FILTER for this scope's host-buffer searches (cs_scope_set_route)
+        void set_route(int32_t route) { check(cs_scope_set_route(h_, route)); }
+        // searches through the filter / by the gathered scan, overflow reruns, HBM bytes beyond 8 per id (cs_scope_route_info)
+        void route_info(uint64_t* filter_searches, uint64_t* gathered_searches, uint64_t* overflow_reruns,
+                        uint64_t* extra_bytes) const {
+            check(cs_scope_route_info(h_, filter_searches, gathered_searches, overflow_reruns, extra_bytes));
+        }
 
       private:
         cs_scope* h_ = nullptr;

@@ -183,6 +183,26 @@ class Scope:
         _lib.check(self.store._lib.cs_scope_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return int(a.value), int(b.value), int(c.value)
 
+    ROUTES = {"auto": 0, "gather": 1, "filter": 2}  # CS_SCOPE_ROUTE_*
+
+    def set_route(self, route):
+        """The route of this scope's host-buffer searches (cs_scope_set_route): "auto" (default), "gather" (always the
+        gathered f32 scan) or "filter" (the int8 filter + exact refine wherever it can serve), or the CS_SCOPE_ROUTE_*
+        value.  The answers' bytes do not depend on it."""
+        if not self._h:
+            raise CsError(_lib.CS_ERR_BAD_ARG, "scope is closed")
+        _lib.check(self.store._lib.cs_scope_set_route(self._h, self.ROUTES.get(route, route)))
+
+    def route_info(self):
+        """-> (filter_searches, gathered_searches, overflow_reruns, extra_bytes): host-buffer searches answered through
+        the filter / by the gathered scan, exact reruns after an overflowed candidate buffer, and the bytes of HBM held
+        beyond 8 per id (cs_scope_route_info)."""
+        if not self._h:
+            raise CsError(_lib.CS_ERR_BAD_ARG, "scope is closed")
+        v = [C.c_uint64() for _ in range(4)]
+        _lib.check(self.store._lib.cs_scope_route_info(self._h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
     @property
     def handle(self):
         return self._h

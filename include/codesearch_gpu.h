@@ -226,6 +226,29 @@ CS_API void    cs_scope_destroy(cs_scope* scope);
  * on a built store (0 on one not built: the first search makes it), +1 per build generation actually searched.  Over a
  * sharded store the first two are sums over the shards.  Each output optional. */
 CS_API int32_t cs_scope_info(const cs_scope* scope, uint64_t* n_ids, uint64_t* live_rows, uint64_t* refreshes);
+/* The route of the host-buffer scoped searches (cs_index_search_scoped, cs_index_search_variants_scoped); the answer's
+ * bytes do not depend on it.  A scope over a store of dim 384 / 768 / 1024 whose list outgrows 3,072 rows additionally
+ * keeps, remade with the list, a blocked-rows bitmap in HBM (one bit per stored row: tombstoned or not in the scope) and
+ * on the host the list's first 4,096 entries and every 1,024th; with them such a search can run through the index's int8
+ * filter + exact refine, its phases planned over the scope's rows, instead of the gathered f32 scan.
+ *   CS_SCOPE_ROUTE_AUTO   (default) the filter when the int8 copy serves, the shape would take the filter over a store of
+ *                         the scope's live rows (CS_FILTER_SINGLE_MIN_ROWS & co.) and the rows streamed are at most 2 (one
+ *                         query), 4 (two to eight) or 10 (nine and more) times the live rows (CS_SCOPE_FILTER_MAX_SPAN
+ *                         sets all three); else the gathered scan.
+ *   CS_SCOPE_ROUTE_GATHER always the gathered scan.
+ *   CS_SCOPE_ROUTE_FILTER the filter whenever it can serve: where the int8 copy does not, the dim has no filter kernels
+ *                         or the whole list fits the first phase, the search quietly takes the gathered scan.
+ * A candidate buffer that overflows is settled by an exact rerun over the scope's list, counted per scope; it is no
+ * strike against the index's int8 copy.  The device-pointer and sharded forms always take the gathered scan; on a
+ * scope over a sharded store the call is CS_ERR_BAD_ARG. */
+enum { CS_SCOPE_ROUTE_AUTO = 0, CS_SCOPE_ROUTE_GATHER = 1, CS_SCOPE_ROUTE_FILTER = 2 };
+CS_API int32_t cs_scope_set_route(cs_scope* scope, int32_t route);
+/* Host-buffer searches answered through the filter / by the gathered scan, exact reruns after an overflow, and the
+ * bytes of HBM the scope holds beyond its 8 per id: the 1,024-stride table (4 B per 1,024 ids, kept by a scope of more
+ * than 3,072 ids over an index with an int8 copy and one of the three dims) and, while its list as last made outgrows
+ * 3,072 rows, the bitmap; 0 for every other scope.  Each output optional.  Over a sharded store all are 0. */
+CS_API int32_t cs_scope_route_info(const cs_scope* scope, uint64_t* filter_searches, uint64_t* gathered_searches,
+                                   uint64_t* overflow_reruns, uint64_t* extra_bytes);
 /* cs_index_search_masked / cs_index_search_variants_masked with the scope in place of the mask.  Errors: those of
  * cs_index_search with the same texts, checked first; then a scope made for another store is CS_ERR_BAD_ARG. */
 CS_API int32_t cs_index_search_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,
