@@ -13,6 +13,7 @@
 
 #include <cstdlib>
 
+#include "grouped_plan.hpp"
 #include "masked_plan.hpp"
 #include "scan.hpp"
 #include "scope.hpp"
@@ -200,6 +201,15 @@ struct cs_index {
     uint32_t compact_dead_pct = 10;
     uint64_t compactions = 0;
     RowIds row_ids() const { return RowIds(id_base, h_ids.empty() ? nullptr : d_ids); }
+    // Groups of the grouped search (scan_grouped.hip): h_groups[id - id_base] for the ids assigned so far (shorter than
+    // n_ids when ids were appended since: those are CS_NO_GROUP), empty = none assigned.  The device copy is brought up to
+    // date under groups_mu by the first grouped search that finds it dirty (ensure_groups); searches read it only.
+    std::vector<uint32_t> h_groups;
+    uint32_t* d_groups = nullptr;
+    uint64_t groups_cap = 0, groups_len = 0;  // elements allocated / valid on the device
+    uint64_t groups_assigned = 0;             // entries != CS_NO_GROUP
+    uint64_t groups_dirty_lo = 0, groups_dirty_hi = 0;  // host entries [lo, hi) the device copy has not seen
+    std::mutex groups_mu;
     float* d_corpus = nullptr;
     uint32_t* d_dead = nullptr;  // bitmap over rows, sized for `capacity`
     float* d_norms = nullptr;    // |row| for rows [0, normed_rows) (batched-query path)
@@ -870,6 +880,45 @@ int32_t run_scoped(cs_index* h, cs_scope* sc, Workspace* w, const ScanPlan& plan
     return run_row_list(h, w, plan, live, sc->d_list, d_len, w->d_queries, nq, k, d_keys, nullptr, nullptr, nullptr, w->stream);
 }
 
+// The group table as this search's kernels read it.  A dirty table is brought up to date first, under groups_mu, with
+// synchronous copies (and after the device has finished what was enqueued, when the table has to move): a concurrent
+// grouped search either waits here or finds it clean.  No group assigned: a null table, every id CS_NO_GROUP.
+int32_t ensure_groups(cs_index* h, uint32_t per_group, GroupView* gv) {
+    std::lock_guard<std::mutex> lk(h->groups_mu);
+    *gv = GroupView{nullptr, 0, h->id_base, per_group};
+    if (h->groups_assigned == 0) return CS_OK;
+    const uint64_t n = h->h_groups.size();
+    if (n > h->groups_cap) {
+        CS_HIP(hipDeviceSynchronize());  // a search that was only enqueued may still read the old table
+        const uint64_t cap = std::max<uint64_t>(n, std::min<uint64_t>(2 * h->groups_cap, 0xffffffffull));
+        h->groups_cap = 0;
+        h->groups_len = 0;
+        CS_HIP(realloc_buf(h->d_groups, (size_t)cap));
+        h->groups_cap = cap;
+        h->groups_dirty_lo = 0;
+        h->groups_dirty_hi = n;
+    }
+    if (h->groups_dirty_hi > h->groups_dirty_lo) {
+        CS_HIP(hipMemcpy(h->d_groups + h->groups_dirty_lo, h->h_groups.data() + h->groups_dirty_lo,
+                         (size_t)(h->groups_dirty_hi - h->groups_dirty_lo) * sizeof(uint32_t), hipMemcpyHostToDevice));
+        h->groups_dirty_lo = h->groups_dirty_hi = 0;
+    }
+    h->groups_len = n;
+    gv->groups = h->d_groups;
+    gv->len = (uint32_t)n;
+    return CS_OK;
+}
+
+// A grouped search (scan_grouped.hip) on `stream`: the capped scan over every stored row, then the capped merge -> the
+// best k keys per query in d_keys [nq][k].
+int32_t run_grouped(cs_index* h, Workspace* w, const GroupedPlan& plan, const GroupView& gv, const float* d_queries,
+                    uint32_t nq, uint32_t k, uint64_t* d_keys, hipStream_t stream) {
+    CS_TRY(launch_scan_grouped(plan, h->d_corpus, h->n_rows, h->dim, d_queries, nq, k, h->n_removed ? h->d_dead : nullptr,
+                               h->row_ids(), gv, w->d_partial, stream));
+    return launch_merge_grouped(plan, w->d_partial, nq, k, gv, w->d_tmp_a, w->d_tmp_b, d_keys, nullptr, nullptr, nullptr,
+                                stream);
+}
+
 // The empty answer of a host-buffer search: every slot empty, as unpack_keys leaves it.
 void fill_empty(uint32_t nq, uint32_t k, float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
     for (size_t i = 0; i < (size_t)nq * k; ++i) { out_cos[i] = 0.0f; out_ids[i] = 0xFFFFFFFFu; }
@@ -991,6 +1040,7 @@ void cs_index_destroy(cs_index* h) {
     if (h->d_tmeta) (void)hipFree(h->d_tmeta);
     if (h->d_mu) (void)hipFree(h->d_mu);
     if (h->d_ids) (void)hipFree(h->d_ids);
+    if (h->d_groups) (void)hipFree(h->d_groups);
     delete h;
 }
 
@@ -1175,6 +1225,11 @@ int32_t cs_index_clear(cs_index* h) {
     h->q8_strikes.store(0);
     h->q8_searches.store(0);
     h->n_removed = 0;
+    {  // the groups go with the ids (the device table keeps its room)
+        std::lock_guard<std::mutex> lk(h->groups_mu);
+        h->h_groups.clear();
+        h->groups_len = h->groups_assigned = h->groups_dirty_lo = h->groups_dirty_hi = 0;
+    }
     h->h_dead.clear();
     h->build_gen.fetch_add(1);
     h->built = false;  // store.rs:702
@@ -1324,6 +1379,78 @@ int32_t cs_index_search_variants_masked(cs_index* h, const float* queries, uint3
             unpack_keys(w->h_keys, 1, k, out_cos, out_ids, nullptr);
             *out_count = w->h_variant_meta[0];
             if (out_high_confidence) *out_high_confidence = (int32_t)w->h_variant_meta[1];
+            return CS_OK;
+        }();
+    }
+    release_pooled(h, w);
+    return s;
+}
+
+int32_t cs_index_set_groups(cs_index* h, const uint32_t* ids, const uint32_t* groups, uint64_t n) {
+    if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
+    if (n == 0) return CS_OK;
+    if (!ids || !groups) return fail(CS_ERR_BAD_ARG, "ids or groups is null");
+    uint32_t top = 0;  // the highest table entry touched
+    for (uint64_t i = 0; i < n; ++i) {
+        if (ids[i] < h->id_base || (uint64_t)ids[i] - h->id_base >= h->n_ids)
+            return fail(CS_ERR_BAD_ARG, "ids[%llu] = %u was never issued (the index has issued ids %u to %llu)",
+                        (unsigned long long)i, ids[i], h->id_base, (unsigned long long)h->id_base + h->n_ids);
+        top = std::max(top, ids[i] - h->id_base);
+    }
+    std::lock_guard<std::mutex> lk(h->groups_mu);
+    if (h->h_groups.size() <= top) h->h_groups.resize((size_t)top + 1, CS_NO_GROUP);
+    uint64_t lo = h->groups_dirty_hi > h->groups_dirty_lo ? h->groups_dirty_lo : ~0ull, hi = h->groups_dirty_hi;
+    if (h->h_groups.size() > h->groups_len) {  // entries the device copy has never held
+        lo = std::min<uint64_t>(lo, h->groups_len);
+        hi = h->h_groups.size();
+    }
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint32_t e = ids[i] - h->id_base;
+        uint32_t& g = h->h_groups[e];
+        if (g == groups[i]) continue;
+        h->groups_assigned += (uint64_t)(groups[i] != CS_NO_GROUP) - (uint64_t)(g != CS_NO_GROUP);
+        g = groups[i];
+        lo = std::min<uint64_t>(lo, e);
+        hi = std::max<uint64_t>(hi, (uint64_t)e + 1);
+    }
+    if (hi > lo) {
+        h->groups_dirty_lo = lo;
+        h->groups_dirty_hi = hi;
+    }
+    return CS_OK;
+}
+
+int32_t cs_index_groups_info(cs_index* h, uint64_t* assigned_ids, uint64_t* table_bytes) {
+    if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
+    std::lock_guard<std::mutex> lk(h->groups_mu);
+    if (assigned_ids) *assigned_ids = h->groups_assigned;
+    if (table_bytes) *table_bytes = h->groups_cap * sizeof(uint32_t);
+    return CS_OK;
+}
+
+int32_t cs_index_search_grouped(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k, uint32_t per_group,
+                                float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
+    CS_TRY(check_search(h, nq, dim, k));
+    if (!queries || !out_cos || !out_ids || !out_counts) return fail(CS_ERR_BAD_ARG, "null buffer");
+    if (per_group == 0) return fail(CS_ERR_BAD_ARG, "per_group must be at least 1");
+    DeviceGuard g(h->device);
+    GroupView gv;
+    CS_TRY(ensure_groups(h, per_group, &gv));
+    const GroupedPlan plan = plan_grouped(h->n_rows, h->dim, nq, k, h->num_cus);
+    ScanPlan room{};  // the workspace's buffers, sized for the grouped plan
+    room.partial_keys = plan.partial_keys;
+    room.merge_keys = plan.merge_keys;
+    Workspace* w = acquire_pooled(h);
+    if (!w) return fail(CS_ERR_HIP, "could not create a HIP stream");
+    int32_t s = w->reserve(room, nq, h->dim, k, true);
+    if (s == CS_OK) {
+        s = [&]() -> int32_t {
+            memcpy(w->h_queries, queries, (size_t)nq * h->dim * sizeof(float));
+            CS_HIP(hipMemcpyAsync(w->d_queries, w->h_queries, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice,
+                                  w->stream));
+            CS_TRY(run_grouped(h, w, plan, gv, w->d_queries, nq, k, w->h_keys, w->stream));
+            CS_HIP(hipStreamSynchronize(w->stream));
+            unpack_keys(w->h_keys, nq, k, out_cos, out_ids, out_counts);
             return CS_OK;
         }();
     }

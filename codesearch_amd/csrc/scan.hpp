@@ -104,6 +104,26 @@ int32_t launch_scope_filter_state(const uint32_t* d_list, const uint32_t* d_len,
 // (scope_refresh_due); the index must be built.
 int32_t index_scope_live_rows(cs_index* h, cs_scope* scope, uint64_t* live_rows);
 
+// ---- grouped search (scan_grouped.hip, plan: grouped_plan.hpp) -----------------------------------
+// The group table of an index as the kernels read it: groups[id - id_base] for ids below id_base + len, CS_NO_GROUP for
+// every other id (and for all of them when groups is null); at most per_group rows of a group are kept.
+struct GroupView {
+    const uint32_t* groups = nullptr;
+    uint32_t len = 0;
+    uint32_t id_base = 0;
+    uint32_t per_group = 0xFFFFFFFFu;
+};
+struct GroupedPlan;
+// The streaming scan's arithmetic with capped per-wave lists: d_partial[q][plan.lists][k], one unsorted list per wave.
+int32_t launch_scan_grouped(const GroupedPlan& plan, const float* d_corpus, uint64_t n_rows, uint32_t dim,
+                            const float* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_dead, RowIds ids,
+                            const GroupView& gv, uint64_t* d_partial, hipStream_t stream);
+// Those lists -> the capped best k per query; every level caps.  Outputs as launch_merge's (each optional); d_tmp_a / d_tmp_b:
+// plan.merge_keys keys each (may be null when plan.merge_levels == 1).
+int32_t launch_merge_grouped(const GroupedPlan& plan, const uint64_t* d_lists, uint32_t nq, uint32_t k, const GroupView& gv,
+                             uint64_t* d_tmp_a, uint64_t* d_tmp_b, uint64_t* d_out_keys, float* d_out_cos,
+                             uint32_t* d_out_ids, uint32_t* d_out_counts, hipStream_t stream);
+
 // corpus[(first_out_row + r) * dim + c] = cs_synth_value(seed, (first_row + r) * dim + c)
 int32_t launch_synth_fill(float* d_rows, uint64_t n, uint32_t dim, uint64_t seed,
                           uint64_t first_row, hipStream_t stream);

@@ -1,0 +1,454 @@
+// scan_grouped.hip — the grouped search: the exact best k live rows such that no group (a chunk's file) contributes more
+// than per_group of them.  The reference caps hits per file only after ranking (src/search/mod.rs:1007-1038 `--per-file`,
+// :947-957 `--compact`): a file with many near-duplicate chunks fills the ranked list before the cap is applied.
+// Host plan, the contract and the merge lemma: grouped_plan.hpp.
+//
+//   1. capped scan: scan_topk_kernel's tile loop and per-row arithmetic (scan.hip; the fmaf order over j,
+//      half_allreduce_sum, the zero guard and the strict `>` are the same, so every cosine is bit-identical), with a u32
+//      group slot beside every key slot of a wave's list.  The fast-path gate stays `c > thr`: a full list whose worst
+//      key the row does not beat holds k cap-valid rows that all beat it.  On the slow path the row's group comes from
+//      the table (one address per wave) and the insert keeps the list the capped top-k of what the wave has met:
+//      wave_list_insert_grouped.  No prime pass, and no block merge: each wave's list goes to HBM as it is.
+//   2. capped merge: every level sorts its keys, ranks each key inside its group and drops ranks >= per_group BEFORE it
+//      keeps the best k: merge_topk_grouped_kernel.
+#include "scan.hpp"
+#include "grouped_plan.hpp"
+#include "scan_wave.hpp"
+
+namespace cs {
+
+static_assert(kNoGroup == CS_NO_GROUP, "grouped_plan.hpp restates the public constant");
+
+__device__ __forceinline__ uint32_t group_of(const GroupView& gv, uint32_t id) {
+    const uint32_t i = id - gv.id_base;  // ids past the table (appended after the last assignment) are ungrouped
+    return (gv.groups && i < gv.len) ? gv.groups[i] : kNoGroup;
+}
+
+typedef volatile uint64_t __attribute__((address_space(3))) lds_vu64;
+typedef volatile uint32_t __attribute__((address_space(3))) lds_vu32;
+
+// thr / wpos of a full list: the worst key and its slot (wave_list_insert's search)
+__device__ __forceinline__ void wave_list_worst(lds_vu64* list, uint32_t k, int lane, float& thr, uint32_t& wpos) {
+    uint64_t mk = ~0ull;
+    uint32_t mp = 0xffffffffu;
+    for (uint32_t i = lane; i < k; i += 64) {
+        const uint64_t v = list[i];
+        if (v < mk) { mk = v; mp = i; }
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+        const uint64_t ok = shfl_xor_u64(mk, s);
+        const uint32_t op = __shfl_xor(mp, s, 64);
+        if (ok < mk || (ok == mk && op < mp)) { mk = ok; mp = op; }
+    }
+    wpos = mp | 0x80000000u;
+    thr = key_cos(mk);  // a full list has no empty slot
+}
+
+// wave_list_insert (scan_wave.hpp) under the cap.  `list` holds the capped top-k of the rows this wave has met, `glist`
+// their groups; thr / wpos as there (wpos < 2^31 counts the filled slots of a list that is not full yet, thr = -inf then).
+// The caller has established c > thr.  Rows arrive in ascending id, so a row that ties a key already there loses to it:
+// packed keys compare that way by themselves (equal cosine, larger id -> smaller key).
+//   group CS_NO_GROUP, or fewer than m slots hold g  -> the ordinary insert: next empty slot, or over the worst key;
+//   m slots hold g                                   -> over the worst key OF GROUP g, and only if the row beats it.
+// The slot search is skipped while fewer than m slots are filled at all: no group can be saturated yet.
+__device__ __forceinline__ void wave_list_insert_grouped(volatile uint64_t* list_generic, volatile uint32_t* glist_generic,
+                                                         uint32_t k, uint32_t m, int lane, float c, uint32_t id, uint32_t g,
+                                                         float& thr, uint32_t& wpos) {
+    constexpr uint32_t kListFull = 0x80000000u;
+    lds_vu64* const list = (lds_vu64*)list_generic;
+    lds_vu32* const glist = (lds_vu32*)glist_generic;
+    const bool full = (wpos & kListFull) != 0;
+    const uint32_t filled = full ? k : wpos;
+    const uint64_t key = key_pack(c, id);
+    if (g != kNoGroup && filled >= m) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        uint32_t cnt = 0;
+        uint64_t wk = ~0ull;
+        uint32_t wp = 0xffffffffu;
+        for (uint32_t i0 = 0; i0 < filled; i0 += 64) {
+            const uint32_t i = i0 + lane;
+            const bool hit = i < filled && glist[i] == g;
+            cnt += (uint32_t)__popcll(__ballot(hit));
+            if (hit) {
+                const uint64_t v = list[i];
+                if (v < wk) { wk = v; wp = i; }
+            }
+        }
+        if (cnt >= m) {  // wave-uniform
+#pragma unroll
+            for (int s = 32; s >= 1; s >>= 1) {
+                const uint64_t ok = shfl_xor_u64(wk, s);
+                const uint32_t op = __shfl_xor(wp, s, 64);
+                if (ok < wk || (ok == wk && op < wp)) { wk = ok; wp = op; }
+            }
+            if (key > wk) {
+                if (lane == 0) list[wp] = key;  // the slot keeps its group
+                if (full) {
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    wave_list_worst(list, k, lane, thr, wpos);
+                }
+            }
+            return;
+        }
+    }
+    const uint32_t slot = wpos & ~kListFull;
+    if (lane == 0) {
+        list[slot] = key;
+        glist[slot] = g;
+    }
+    if (!full && slot + 1 < k) {
+        wpos = slot + 1;
+        return;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    wave_list_worst(list, k, lane, thr, wpos);
+}
+
+// A wave's list -> HBM, unsorted, empty slots as 0: list `blockIdx.x * kWaves + wave` of query q.
+__device__ __forceinline__ void wave_list_store(const uint64_t* list, uint32_t k, int lane, uint64_t* __restrict__ partial,
+                                                uint32_t q, int wave) {
+    uint64_t* out = partial + ((size_t)q * (gridDim.x * kWaves) + (size_t)blockIdx.x * kWaves + wave) * k;
+    for (uint32_t i = lane; i < k; i += 64) out[i] = list[i];
+}
+
+// ---- 1. capped scan ---------------------------------------------------------------------------------
+// scan_topk_kernel (scan.hip) without PRIME, the floor and the gate: see there for J, U and QT.
+template <int J, int U, int QT>
+__global__ void __launch_bounds__(kBlock)
+scan_grouped_topk_kernel(const float* __restrict__ corpus, uint64_t n_rows, const float* __restrict__ queries, uint32_t nq,
+                         uint32_t k, uint32_t kpad, const uint32_t* __restrict__ dead, RowIds id_base, GroupView gv,
+                         uint64_t* __restrict__ partial) {
+    extern __shared__ __attribute__((aligned(16))) uint64_t lds_keys[];  // [QT][kWaves][kpad] keys, then as many u32 groups
+    uint32_t* const lds_groups = reinterpret_cast<uint32_t*>(lds_keys + (size_t)QT * kWaves * kpad);
+    constexpr int DIM = 128 * J;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int half = lane >> 5;
+    const int l32 = lane & 31;
+    const uint32_t q0 = blockIdx.y * QT;
+
+    for (uint32_t i = tid; i < QT * kWaves * kpad; i += kBlock) {
+        lds_keys[i] = 0ull;
+        lds_groups[i] = kNoGroup;
+    }
+
+    // query fragments + magnitudes (mag_a of benchmark_models.rs:325)
+    f32x4 qf[QT][J];
+    float qmag[QT];
+#pragma unroll
+    for (int qi = 0; qi < QT; ++qi) {
+        const uint32_t q = (q0 + qi < nq) ? (q0 + qi) : (nq - 1);
+        const f32x4* qp = reinterpret_cast<const f32x4*>(queries + (size_t)q * DIM) + l32;
+        float s = 0.0f;
+#pragma unroll
+        for (int j = 0; j < J; ++j) {
+            qf[qi][j] = qp[j * 32];
+            s = fmaf(qf[qi][j].x, qf[qi][j].x, s);
+            s = fmaf(qf[qi][j].y, qf[qi][j].y, s);
+            s = fmaf(qf[qi][j].z, qf[qi][j].z, s);
+            s = fmaf(qf[qi][j].w, qf[qi][j].w, s);
+        }
+        qmag[qi] = sqrtf(half_allreduce_sum(s));
+    }
+    float thr[QT];
+    uint32_t wpos[QT];
+#pragma unroll
+    for (int qi = 0; qi < QT; ++qi) {
+        thr[qi] = -__builtin_huge_valf();
+        wpos[qi] = 0;
+    }
+    __syncthreads();
+
+    const uint64_t gw = (uint64_t)blockIdx.x * kWaves + wave;
+    const uint64_t nw = (uint64_t)gridDim.x * kWaves;
+    const uint64_t ntiles = (n_rows + 2 * U - 1) / (2 * U);
+
+    for (uint64_t tile = gw; tile < ntiles; tile += nw) {
+        const uint64_t row0 = tile * (2 * U);
+        f32x4 x[U][J];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            uint64_t r = row0 + 2 * u + half;
+            r = r < n_rows ? r : n_rows - 1;  // tail rows re-read the last row, masked below
+            const f32x4* p = reinterpret_cast<const f32x4*>(corpus + r * DIM) + l32;
+#pragma unroll
+            for (int j = 0; j < J; ++j) x[u][j] = __builtin_nontemporal_load(p + j * 32);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            float ss = 0.0f;
+            float dot[QT];
+#pragma unroll
+            for (int qi = 0; qi < QT; ++qi) dot[qi] = 0.0f;
+#pragma unroll
+            for (int j = 0; j < J; ++j) {
+                const f32x4 v = x[u][j];
+                ss = fmaf(v.x, v.x, ss);
+                ss = fmaf(v.y, v.y, ss);
+                ss = fmaf(v.z, v.z, ss);
+                ss = fmaf(v.w, v.w, ss);
+#pragma unroll
+                for (int qi = 0; qi < QT; ++qi) {
+                    dot[qi] = fmaf(v.x, qf[qi][j].x, dot[qi]);
+                    dot[qi] = fmaf(v.y, qf[qi][j].y, dot[qi]);
+                    dot[qi] = fmaf(v.z, qf[qi][j].z, dot[qi]);
+                    dot[qi] = fmaf(v.w, qf[qi][j].w, dot[qi]);
+                }
+            }
+            const float xmag = sqrtf(half_allreduce_sum(ss));  // mag_b
+            const uint64_t r = row0 + 2 * u + half;
+            const bool valid = r < n_rows;
+#pragma unroll
+            for (int qi = 0; qi < QT; ++qi) {
+                const float d = half_allreduce_sum(dot[qi]);
+                // batch.rs:320-323: zero magnitude -> 0.0, else dot / (mag_a * mag_b)
+                const float c = (qmag[qi] == 0.0f || xmag == 0.0f) ? 0.0f : d / (qmag[qi] * xmag);
+                unsigned long long m = __ballot(valid && l32 == 0 && c > thr[qi]);
+                if (m) {  // wave-uniform slow path; every row takes it until the list is full
+                    volatile uint64_t* list = lds_keys + ((size_t)qi * kWaves + wave) * kpad;
+                    volatile uint32_t* glist = lds_groups + ((size_t)qi * kWaves + wave) * kpad;
+                    while (m) {
+                        const int src = __ffsll((long long)m) - 1;
+                        m &= m - 1;
+                        const float cc = __shfl(c, src, 64);
+                        const uint64_t rr = row0 + 2 * u + (src >> 5);
+                        if (cc > thr[qi] && !row_is_dead(dead, rr)) {
+                            const uint32_t id = id_base.of(rr);
+                            wave_list_insert_grouped(list, glist, k, gv.per_group, lane, cc, id, group_of(gv, id), thr[qi],
+                                                     wpos[qi]);
+                        }
+                    }
+                }
+            }
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+    for (int qi = 0; qi < QT; ++qi) {
+        if (q0 + qi >= nq) break;
+        wave_list_store(lds_keys + ((size_t)qi * kWaves + wave) * kpad, k, lane, partial, q0 + qi, wave);
+    }
+}
+
+// Any other dim: one wave per row, lanes stride over columns (scan_topk_generic_kernel's arithmetic).
+__global__ void __launch_bounds__(kBlock)
+scan_grouped_generic_kernel(const float* __restrict__ corpus, uint64_t n_rows, uint32_t dim, const float* __restrict__ queries,
+                            uint32_t nq, uint32_t k, uint32_t kpad, const uint32_t* __restrict__ dead, RowIds id_base,
+                            GroupView gv, uint64_t* __restrict__ partial) {
+    extern __shared__ __attribute__((aligned(16))) uint64_t lds_keys[];  // [kWaves][kpad] keys, then as many u32 groups
+    uint32_t* const lds_groups = reinterpret_cast<uint32_t*>(lds_keys + (size_t)kWaves * kpad);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t q = blockIdx.y;
+    for (uint32_t i = tid; i < kWaves * kpad; i += kBlock) {
+        lds_keys[i] = 0ull;
+        lds_groups[i] = kNoGroup;
+    }
+    const float* qp = queries + (size_t)q * dim;
+    float s = 0.0f;
+    for (uint32_t c = lane; c < dim; c += 64) s = fmaf(qp[c], qp[c], s);
+    const float qmag = sqrtf(wave_allreduce_sum(s));
+    float thr = -__builtin_huge_valf();
+    uint32_t wpos = 0;
+    __syncthreads();
+    volatile uint64_t* list = lds_keys + (size_t)wave * kpad;
+    volatile uint32_t* glist = lds_groups + (size_t)wave * kpad;
+    const uint64_t gw = (uint64_t)blockIdx.x * kWaves + wave;
+    const uint64_t nw = (uint64_t)gridDim.x * kWaves;
+    for (uint64_t r = gw; r < n_rows; r += nw) {
+        const float* xp = corpus + r * dim;
+        float ss = 0.0f, dot = 0.0f;
+        for (uint32_t c = lane; c < dim; c += 64) {
+            const float v = xp[c];
+            ss = fmaf(v, v, ss);
+            dot = fmaf(v, qp[c], dot);
+        }
+        const float xmag = sqrtf(wave_allreduce_sum(ss));
+        const float d = wave_allreduce_sum(dot);
+        const float c = (qmag == 0.0f || xmag == 0.0f) ? 0.0f : d / (qmag * xmag);
+        if (c > thr && !row_is_dead(dead, r)) {  // wave-uniform
+            const uint32_t id = id_base.of(r);
+            wave_list_insert_grouped(list, glist, k, gv.per_group, lane, c, id, group_of(gv, id), thr, wpos);
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    wave_list_store(lds_keys + (size_t)wave * kpad, k, lane, partial, q, wave);
+}
+
+// ---- 2. capped merge ---------------------------------------------------------------------------------
+// merge_topk_kernel's list layout (scan.hip): list l of query q starts at in + q * q_stride + l * k; block (g, q) takes
+// lists [g * G, min(nlists, (g + 1) * G)) and writes its capped best k to out_keys[q][g][k], best first; with one block
+// per query the result is final and is also decoded to cos / ids / counts.  Per block:
+//   a[] = the keys, sorted: position = rank under (cosine desc, id asc);
+//   b[] = (group << 32 | ~position) images of the non-empty keys, sorted: a group's keys are neighbours, best first, so
+//         a key is past the cap exactly when the image per_group places before it has the same group;
+//   those keys are zeroed in a[], and the survivors — still in key order — are compacted; the first k leave.
+// block_select_topk is not used: it would discard, before the cap, rows that the cap promotes.
+constexpr int kGMergeBlock = 1024;
+constexpr int kGMergePer = kGroupedMergeCap / kGMergeBlock;
+
+__global__ void __launch_bounds__(kGMergeBlock)
+merge_topk_grouped_kernel(const uint64_t* __restrict__ in, uint32_t nlists, uint32_t k, uint32_t G, uint64_t q_stride,
+                          GroupView gv, uint64_t* __restrict__ out_keys, float* __restrict__ out_cos,
+                          uint32_t* __restrict__ out_ids, uint32_t* __restrict__ out_counts) {
+    extern __shared__ __attribute__((aligned(16))) uint64_t a[];  // [nsort] keys, [nsort] images
+    __shared__ uint32_t wave_tot[kGMergeBlock / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t g = blockIdx.x, q = blockIdx.y, ngroups = gridDim.x;
+    const uint32_t lo = g * G;
+    const uint32_t hi = (lo + G < nlists) ? lo + G : nlists;
+    const uint32_t ncand = (hi - lo) * k;  // <= kGroupedMergeCap (the launcher's G)
+    uint32_t nsort = 64;
+    while (nsort < ncand) nsort <<= 1;
+    uint64_t* const b = a + nsort;
+    const uint64_t* src = in + (size_t)q * q_stride + (size_t)lo * k;
+    for (uint32_t i = tid; i < nsort; i += kGMergeBlock) a[i] = (i < ncand) ? src[i] : 0ull;
+    block_bitonic_desc<kGMergeBlock>(a, nsort, tid);
+    for (uint32_t i = tid; i < nsort; i += kGMergeBlock) {
+        const uint64_t key = a[i];
+        b[i] = key ? (((uint64_t)group_of(gv, key_id(key)) << 32) | (uint64_t)(0xffffffffu - i)) : 0ull;
+    }
+    block_bitonic_desc<kGMergeBlock>(b, nsort, tid);
+    const uint32_t m = gv.per_group;
+    for (uint32_t i = tid; i < nsort; i += kGMergeBlock) {
+        const uint64_t v = b[i];
+        const uint32_t grp = (uint32_t)(v >> 32);
+        // images before a non-empty one are non-empty (empty = 0 sorts last)
+        if (v && grp != kNoGroup && i >= m && (uint32_t)(b[i - m] >> 32) == grp) a[0xffffffffu - (uint32_t)v] = 0ull;
+    }
+    __syncthreads();
+    // ordered compaction: thread t owns a[t * kGMergePer, +kGMergePer)
+    uint64_t mine[kGMergePer];
+    uint32_t cnt = 0;
+#pragma unroll
+    for (int j = 0; j < kGMergePer; ++j) {
+        const uint32_t i = (uint32_t)tid * kGMergePer + j;
+        mine[j] = i < nsort ? a[i] : 0ull;
+        cnt += mine[j] != 0ull;
+    }
+    uint32_t x = cnt;  // inclusive scan inside the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = __shfl_up(x, d, 64);
+        if (lane >= d) x += y;
+    }
+    if (lane == 63) wave_tot[wave] = x;
+    __syncthreads();
+    uint32_t pos = x - cnt, total = 0;
+    for (int w = 0; w < kGMergeBlock / 64; ++w) {
+        pos += (w < wave) ? wave_tot[w] : 0u;
+        total += wave_tot[w];
+    }
+    const bool final_pass = (ngroups == 1);
+    const uint32_t kept = total < k ? total : k;
+    uint64_t* const okeys = out_keys ? out_keys + ((size_t)q * ngroups + g) * k : nullptr;
+#pragma unroll
+    for (int j = 0; j < kGMergePer; ++j) {
+        if (mine[j] == 0ull) continue;
+        if (pos < k) {
+            if (okeys) okeys[pos] = mine[j];
+            if (final_pass) {
+                if (out_cos) out_cos[(size_t)q * k + pos] = key_cos(mine[j]);
+                if (out_ids) out_ids[(size_t)q * k + pos] = key_id(mine[j]);
+            }
+        }
+        ++pos;
+    }
+    for (uint32_t i = kept + tid; i < k; i += kGMergeBlock) {  // the slots no survivor fills
+        if (okeys) okeys[i] = 0ull;
+        if (final_pass) {
+            if (out_cos) out_cos[(size_t)q * k + i] = 0.0f;
+            if (out_ids) out_ids[(size_t)q * k + i] = 0xffffffffu;
+        }
+    }
+    if (final_pass && out_counts && tid == 0) out_counts[q] = kept;
+}
+
+// ---- host side ------------------------------------------------------------------------------------------
+
+template <int J, int U, int QT>
+static void launch_grouped_fast(const GroupedPlan& plan, const float* d_corpus, uint64_t n_rows, const float* d_queries,
+                                uint32_t nq, uint32_t k, const uint32_t* d_dead, RowIds ids, const GroupView& gv,
+                                uint64_t* d_partial, hipStream_t stream) {
+    hipLaunchKernelGGL((scan_grouped_topk_kernel<J, U, QT>), dim3(plan.blocks, plan.passes), dim3(kBlock), plan.lds_bytes,
+                       stream, d_corpus, n_rows, d_queries, nq, k, plan.kpad, d_dead, ids, gv, d_partial);
+}
+
+template <int J, int U>
+static void launch_grouped_q(const GroupedPlan& plan, const float* d_corpus, uint64_t n_rows, const float* d_queries,
+                             uint32_t nq, uint32_t k, const uint32_t* d_dead, RowIds ids, const GroupView& gv,
+                             uint64_t* d_partial, hipStream_t stream) {
+    switch (plan.qtile) {
+        case 4: launch_grouped_fast<J, U, 4>(plan, d_corpus, n_rows, d_queries, nq, k, d_dead, ids, gv, d_partial, stream); break;
+        case 2: launch_grouped_fast<J, U, 2>(plan, d_corpus, n_rows, d_queries, nq, k, d_dead, ids, gv, d_partial, stream); break;
+        default: launch_grouped_fast<J, U, 1>(plan, d_corpus, n_rows, d_queries, nq, k, d_dead, ids, gv, d_partial, stream); break;
+    }
+}
+
+int32_t launch_scan_grouped(const GroupedPlan& plan, const float* d_corpus, uint64_t n_rows, uint32_t dim,
+                            const float* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_dead, RowIds ids,
+                            const GroupView& gv, uint64_t* d_partial, hipStream_t stream) {
+    if (gv.per_group == 0) return fail(CS_ERR_BAD_ARG, "per_group must be at least 1");
+    if (plan.lds_bytes > kGroupedLdsBudget || plan.kpad < k)
+        return fail(CS_ERR_BAD_ARG, "grouped scan plan does not fit: %zu B of LDS, kpad %u for k %u", plan.lds_bytes, plan.kpad, k);
+    if (n_rows == 0) {  // nothing to score: all-empty lists
+        CS_HIP(hipMemsetAsync(d_partial, 0, plan.partial_keys * sizeof(uint64_t), stream));
+        return CS_OK;
+    }
+    if (plan.deep && plan.qtile == 1 && grouped_fast_dim(dim)) {  // the streaming scan's deep shapes (scan.hip scan_deep)
+        if (dim == 384) launch_grouped_fast<3, 8, 1>(plan, d_corpus, n_rows, d_queries, nq, k, d_dead, ids, gv, d_partial, stream);
+        else if (dim == 768) launch_grouped_fast<6, 4, 1>(plan, d_corpus, n_rows, d_queries, nq, k, d_dead, ids, gv, d_partial, stream);
+        else launch_grouped_fast<8, 3, 1>(plan, d_corpus, n_rows, d_queries, nq, k, d_dead, ids, gv, d_partial, stream);
+    } else if (dim == 384) launch_grouped_q<3, 4>(plan, d_corpus, n_rows, d_queries, nq, k, d_dead, ids, gv, d_partial, stream);
+    else if (dim == 768) launch_grouped_q<6, 2>(plan, d_corpus, n_rows, d_queries, nq, k, d_dead, ids, gv, d_partial, stream);
+    else if (dim == 1024) launch_grouped_q<8, 2>(plan, d_corpus, n_rows, d_queries, nq, k, d_dead, ids, gv, d_partial, stream);
+    else
+        hipLaunchKernelGGL(scan_grouped_generic_kernel, dim3(plan.blocks, nq), dim3(kBlock), plan.lds_bytes, stream, d_corpus,
+                           n_rows, dim, d_queries, nq, k, plan.kpad, d_dead, ids, gv, d_partial);
+    CS_HIP(hipGetLastError());
+    return CS_OK;
+}
+
+int32_t launch_merge_grouped(const GroupedPlan& plan, const uint64_t* d_lists, uint32_t nq, uint32_t k, const GroupView& gv,
+                             uint64_t* d_tmp_a, uint64_t* d_tmp_b, uint64_t* d_out_keys, float* d_out_cos,
+                             uint32_t* d_out_ids, uint32_t* d_out_counts, hipStream_t stream) {
+    if (gv.per_group == 0) return fail(CS_ERR_BAD_ARG, "per_group must be at least 1");
+    const uint32_t G = plan.merge_group;
+    if (G < 2 || (uint64_t)G * k > kGroupedMergeCap)
+        return fail(CS_ERR_BAD_ARG, "grouped merge takes at most %u keys per block", kGroupedMergeCap);
+    static PerDeviceOnce attr_set;  // function attributes are per device
+    CS_TRY(attr_set.run([&]() -> int32_t {
+        CS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(merge_topk_grouped_kernel),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kGroupedMergeCap * sizeof(uint64_t)));
+        return CS_OK;
+    }));
+    const uint64_t* in = d_lists;
+    uint64_t* bufs[2] = {d_tmp_a, d_tmp_b};
+    int flip = 0;
+    uint32_t nlists = plan.lists;
+    for (;;) {
+        const uint32_t ngroups = (nlists + G - 1) / G;
+        const bool final_pass = ngroups == 1;
+        uint64_t* out = final_pass ? d_out_keys : bufs[flip];
+        if (!final_pass && !out) return fail(CS_ERR_BAD_ARG, "merge scratch missing");
+        const uint32_t take = nlists < G ? nlists : G;
+        uint32_t nsort = 64;
+        while (nsort < take * k) nsort <<= 1;
+        hipLaunchKernelGGL(merge_topk_grouped_kernel, dim3(ngroups, nq), dim3(kGMergeBlock), (size_t)2 * nsort * sizeof(uint64_t),
+                           stream, in, nlists, k, G, (uint64_t)nlists * k, gv, out, d_out_cos, d_out_ids, d_out_counts);
+        CS_HIP(hipGetLastError());
+        if (final_pass) break;
+        in = out;
+        nlists = ngroups;
+        flip ^= 1;
+    }
+    return CS_OK;
+}
+
+}  // namespace cs

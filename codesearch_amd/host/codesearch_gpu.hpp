@@ -193,6 +193,23 @@ class VectorStore {
                                            cos.data(), ids.data(), counts.data()));
         return results(cos, ids, counts[0]);
     }
+    // `--per-file` done exactly (src/search/mod.rs:1007-1038 caps after ranking): the best `limit` chunks with at most
+    // `per_file` of one group, decided on the device (cs_index_search_grouped).  A chunk's group is its file once
+    // set_groups has said so; chunks without a group are never capped.  One index only: no sharded form yet.
+    void set_groups(const std::vector<uint32_t>& ids, const std::vector<uint32_t>& groups) {
+        if (sh_) throw Error(CS_ERR_UNSUPPORTED, "a sharded store has no grouped search");
+        if (ids.size() != groups.size()) throw Error(CS_ERR_BAD_ARG, "ids and groups of unequal length");
+        check(cs_index_set_groups(h_, ids.data(), groups.data(), ids.size()));
+    }
+    std::vector<SearchResult> search_per_file(const std::vector<float>& query_embedding, size_t limit,
+                                              uint32_t per_file) const {
+        if (sh_) throw Error(CS_ERR_UNSUPPORTED, "a sharded store has no grouped search");
+        std::vector<float> cos(limit);
+        std::vector<uint32_t> ids(limit), counts(1);
+        check(cs_index_search_grouped(h_, query_embedding.data(), 1, (uint32_t)query_embedding.size(), (uint32_t)limit,
+                                      per_file, cos.data(), ids.data(), counts.data()));
+        return results(cos, ids, counts[0]);
+    }
     // all query variants in one call (src/search/mod.rs:508-511)
     std::vector<std::vector<SearchResult>> search_batch(const std::vector<std::vector<float>>& queries,
                                                         size_t limit) const {

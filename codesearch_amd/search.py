@@ -6,7 +6,7 @@ from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence
 
-from .vector_store import Scope, SearchResult
+from .vector_store import NO_GROUP, Scope, SearchResult
 
 HIGH_CONFIDENCE_THRESHOLD = 0.15  # mod.rs:598: distance < 0.15 (cos > 0.7 under arroy's Cosine)
 EARLY_TERMINATION_TOP_N = 5       # mod.rs:599
@@ -64,6 +64,44 @@ def path_matches(path: str, filter_path: str, project_root: str = "", mcp: bool 
     if mcp:
         f = _trim_end(f, "/")
     return p.startswith(f)
+
+
+def cap_per_group(cos, ids, groups, k: int, m: int):
+    """The contract of the grouped search (cs_index_search_grouped) on the host: `cos` / `ids` are rows already in
+    (cosine desc, id asc) order and `groups` their groups; walk them, keep a row whose group is NO_GROUP or has fewer
+    than m rows kept, stop at k.  -> (cos, ids) of the kept rows, as lists."""
+    kept_cos, kept_ids, have = [], [], {}
+    for c, i, g in zip(cos, ids, groups):
+        if len(kept_ids) >= k:
+            break
+        g = int(g)
+        if g != NO_GROUP:
+            if have.get(g, 0) >= m:
+                continue
+            have[g] = have.get(g, 0) + 1
+        kept_cos.append(c)
+        kept_ids.append(int(i))
+    return kept_cos, kept_ids
+
+
+def group_results_by_file(results: Sequence[SearchResult], per_file: Optional[int],
+                          max_results: Optional[int] = None) -> List[SearchResult]:
+    """The reference's display order under `--per-file` (src/search/mod.rs:1007-1038): the results grouped by path, the
+    files ordered by their best score (descending; as there the best score counts as at least 0), the hits of a file by
+    score, at most per_file of them.  per_file None or 0, or not below max_results when that is given: the results as
+    they are (mod.rs:1009, :1039-1044).  Equal scores keep the order they came in (the reference's HashMap leaves it open).
+    After VectorStore.search(per_file=...) the truncation drops nothing: the cap was applied before the top-k."""
+    results = list(results)
+    if not per_file or per_file <= 0 or (max_results is not None and per_file >= max_results):
+        return results
+    by_file: Dict[str, List[SearchResult]] = {}
+    for r in results:
+        by_file.setdefault(r.path, []).append(r)
+    files = sorted(by_file.values(), key=lambda rs: -max([0.0] + [r.score for r in rs]))
+    out: List[SearchResult] = []
+    for rs in files:
+        out.extend(sorted(rs, key=lambda r: -r.score)[:per_file])
+    return out
 
 
 class ScopeCache:

@@ -149,7 +149,12 @@ def scope_ids(chunk_ids) -> np.ndarray:
     return np.ascontiguousarray(np.unique(ids), np.uint32)
 
 
-def _one_of(chunk_ids, scope):
+NO_GROUP = 0xFFFFFFFF  # CS_NO_GROUP: an id that carries no group is never capped
+
+
+def _one_of(chunk_ids, scope, per_file=None):
+    if per_file is not None and (chunk_ids is not None or scope is not None):
+        raise ValueError("per_file= is exclusive with chunk_ids= and scope=: the grouped search runs over the whole store")
     if chunk_ids is not None and scope is not None:
         raise ValueError("chunk_ids= and scope= are exclusive: a scope already is a set of chunk ids")
 
@@ -279,6 +284,7 @@ class VectorStore:
         self._h = handle
         self._scopes = weakref.WeakSet()  # open scopes: closed with the store, before it
         self._meta: Dict[int, ChunkMetadata] = {}
+        self._file_groups: Dict[str, int] = {}  # path -> group of the grouped search (per_file=), in order of first sight
         self._removed: set = set()
         self._persisted_rows = 0
         self._persisted_meta_ids: set = set()   # ids whose line is already in chunks.jsonl
@@ -336,6 +342,8 @@ class VectorStore:
                     continue
                 self._meta[cid] = ChunkMetadata(**d)
             self._persisted_meta_ids = set(self._meta)
+            if not self.sharded:  # the groups are not stored: they follow from the sidecar's paths
+                self._assign_file_groups([i for i in sorted(self._meta) if i >= self.id_base])  # (< next_id: above)
         for cid in self._removed:  # deletes committed after the last build (delete_chunks) win over older lines
             if self._meta.pop(cid, None) is not None:
                 self._chunks_rewrite = True
@@ -496,6 +504,8 @@ class VectorStore:
                                           ids.ctypes.data_as(u32p)))
         for i, ch in zip(ids.tolist(), chunks):
             self._meta[i] = ChunkMetadata.from_embedded_chunk(ch)
+        if not self.sharded:
+            self._assign_file_groups(ids.tolist())
         return ids.tolist()
 
     def insert_chunks(self, chunks: Sequence[EmbeddedChunk]) -> int:
@@ -572,6 +582,7 @@ class VectorStore:
         self._writable()
         _lib.check(self._fn("clear")(self._h))
         self._meta.clear()
+        self._file_groups.clear()  # (cs_index_clear drops the groups of the ids)
         self._removed.clear()
         self._persisted_rows = 0
         if self.db_path is not None:
@@ -594,6 +605,38 @@ class VectorStore:
         the deleted rows (cs_index_build, from 10 % dead rows on), more in between."""
         return int(self._fn("stored_rows")(self._h))
 
+    def set_groups(self, ids, groups) -> None:
+        """cs_index_set_groups: groups[i] becomes the group of chunk id ids[i] (NO_GROUP un-assigns it); takes effect at
+        the next search(per_file=...), no rebuild.  An id never issued is an error; a deleted one is accepted.
+        Group numbers are one space: chunks inserted with metadata are given their file's number, counted up from 0 in
+        order of first sight (insert_chunks_with_ids), so a caller who groups other rows by hand and does not mean to
+        join them to a file numbers them from the top down (below NO_GROUP)."""
+        self._writable()
+        if self.sharded:
+            raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no grouped search (per_file): no cs_shards_ form yet")
+        ids = np.ascontiguousarray(ids, np.uint32).ravel()
+        groups = np.ascontiguousarray(groups, np.uint32).ravel()
+        if ids.size != groups.size:
+            raise ValueError("ids and groups must have one entry per id")
+        _lib.check(self._lib.cs_index_set_groups(self._h, ids.ctypes.data_as(u32p), groups.ctypes.data_as(u32p), ids.size))
+
+    def groups_info(self):
+        """-> (ids that carry a group, bytes of HBM the group table holds) (cs_index_groups_info)."""
+        if self.sharded:
+            raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no grouped search (per_file): no cs_shards_ form yet")
+        a, b = C.c_uint64(), C.c_uint64()
+        _lib.check(self._lib.cs_index_groups_info(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def _assign_file_groups(self, ids) -> None:
+        """The chunks' files as groups: one group per distinct path, numbered in order of first sight."""
+        if not len(ids):
+            return
+        groups = [self._file_groups.setdefault(self._meta[i].path, len(self._file_groups)) for i in ids]
+        ids = np.ascontiguousarray(ids, np.uint32)
+        groups = np.ascontiguousarray(groups, np.uint32)
+        _lib.check(self._lib.cs_index_set_groups(self._h, ids.ctypes.data_as(u32p), groups.ctypes.data_as(u32p), ids.size))
+
     def _mask_args(self, chunk_ids):
         """(allow pointer, allow_bits, keep-alive) of a masked search over `chunk_ids`."""
         nxt = self.next_id()
@@ -612,11 +655,13 @@ class VectorStore:
             raise CsError(_lib.CS_ERR_BAD_ARG, "scope is closed")
         return scope._h
 
-    def search_raw(self, queries, limit: int, chunk_ids=None, scope: Optional[Scope] = None):
+    def search_raw(self, queries, limit: int, chunk_ids=None, scope: Optional[Scope] = None, per_file: Optional[int] = None):
         """-> (cos [nq, limit] f32, ids [nq, limit] u32, counts [nq] u32); rows best-first.
         chunk_ids: only these chunks are searched (cs_index_search_masked: the exact top `limit` among them).
-        scope: the same through a prepared Scope (cs_index_search_scoped); exclusive with chunk_ids."""
-        _one_of(chunk_ids, scope)
+        scope: the same through a prepared Scope (cs_index_search_scoped); exclusive with chunk_ids.
+        per_file: at most this many rows of one group (a chunk's file; set_groups for rows without metadata) among the
+        `limit` best, decided on the device (cs_index_search_grouped); exclusive with chunk_ids and scope for now."""
+        _one_of(chunk_ids, scope, per_file)
         q = np.ascontiguousarray(queries, np.float32)
         if q.ndim == 1:
             q = q[None, :]
@@ -624,7 +669,13 @@ class VectorStore:
         cos = np.zeros((nq, max(limit, 1)), np.float32)
         ids = np.zeros((nq, max(limit, 1)), np.uint32)
         counts = np.zeros(nq, np.uint32)
-        if scope is not None:
+        if per_file is not None:
+            if self.sharded:
+                raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no grouped search (per_file): no cs_shards_ form yet")
+            _lib.check(self._lib.cs_index_search_grouped(self._h, q.ctypes.data_as(f32p), nq, dim, limit, int(per_file),
+                                                         cos.ctypes.data_as(f32p), ids.ctypes.data_as(u32p),
+                                                         counts.ctypes.data_as(u32p)))
+        elif scope is not None:
             _lib.check(self._fn("search_scoped")(self._h, self._scope_handle(scope), q.ctypes.data_as(f32p), nq, dim, limit,
                                                  cos.ctypes.data_as(f32p), ids.ctypes.data_as(u32p),
                                                  counts.ctypes.data_as(u32p)))
@@ -639,14 +690,18 @@ class VectorStore:
                                                  counts.ctypes.data_as(u32p)))
         return cos, ids, counts
 
-    def search(self, query_embedding, limit: int, chunk_ids=None, scope: Optional[Scope] = None) -> List[SearchResult]:
-        """store.rs:431-486.  Results whose metadata is missing are skipped (store.rs:465).  chunk_ids / scope: search_raw."""
-        cos, ids, counts = self.search_raw(query_embedding, limit, chunk_ids=chunk_ids, scope=scope)
+    def search(self, query_embedding, limit: int, chunk_ids=None, scope: Optional[Scope] = None,
+               per_file: Optional[int] = None) -> List[SearchResult]:
+        """store.rs:431-486.  Results whose metadata is missing are skipped (store.rs:465).  chunk_ids / scope / per_file:
+        search_raw."""
+        cos, ids, counts = self.search_raw(query_embedding, limit, chunk_ids=chunk_ids, scope=scope, per_file=per_file)
         return self._results(cos[0], ids[0], int(counts[0]))
 
-    def search_batch(self, query_embeddings, limit: int, chunk_ids=None, scope: Optional[Scope] = None) -> List[List[SearchResult]]:
-        """One call for all query variants (the par_iter of src/search/mod.rs:508-511).  chunk_ids / scope: search_raw."""
-        cos, ids, counts = self.search_raw(query_embeddings, limit, chunk_ids=chunk_ids, scope=scope)
+    def search_batch(self, query_embeddings, limit: int, chunk_ids=None, scope: Optional[Scope] = None,
+                     per_file: Optional[int] = None) -> List[List[SearchResult]]:
+        """One call for all query variants (the par_iter of src/search/mod.rs:508-511).  chunk_ids / scope / per_file:
+        search_raw."""
+        cos, ids, counts = self.search_raw(query_embeddings, limit, chunk_ids=chunk_ids, scope=scope, per_file=per_file)
         return [self._results(cos[i], ids[i], int(counts[i])) for i in range(len(counts))]
 
     def search_variants(self, query_embeddings, limit: int, chunk_ids=None, scope: Optional[Scope] = None):

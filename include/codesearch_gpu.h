@@ -262,6 +262,29 @@ CS_API int32_t cs_index_search_scoped_device(cs_index* h, cs_scope* scope, const
                                       uint32_t k, uint64_t* d_out_keys, float* d_out_cos, uint32_t* d_out_ids,
                                       uint32_t* d_out_counts, void* stream);
 
+/* Grouped search — the exact form of the reference's `--per-file` / `--compact`, which rank `max_results` hits first and
+ * cap each file's hits afterwards (src/search/mod.rs:1007-1038, :947-957): a file with many near-duplicate chunks fills
+ * the ranked list before the cap applies, and `--per-file 1 -m 10` shows two or three files.  Every chunk id may carry a
+ * 32-bit group (its file); ids never assigned one are CS_NO_GROUP.
+ * THE RULE, per query: order the live rows by (cosine desc, id asc) — the order and the cosines of cs_index_search on the
+ * streaming route, bit for bit — walk that order, keep a row when its group is CS_NO_GROUP or fewer than per_group rows
+ * of its group have been kept, stop at k kept rows; out_counts[q] = rows kept.  With per_group >= k, or with no group
+ * assigned, the answer is that of cs_index_search on the streaming route.
+ * Groups belong to chunk ids, not to stored rows: they survive cs_index_build (the reclaim of deleted rows included),
+ * apply to the next search without a build, and cs_index_clear drops them.  The index keeps a table of 4 B per id issued
+ * on the host and, from the first grouped search after an assignment, in HBM. */
+#define CS_NO_GROUP 0xFFFFFFFFu
+/* groups[i] becomes the group of ids[i] (CS_NO_GROUP un-assigns it).  An id never issued (below id_base, or at or above
+ * cs_index_next_id) fails with CS_ERR_BAD_ARG and nothing is assigned; an id issued and deleted since is accepted.  Not
+ * to be called while the index is searched. */
+CS_API int32_t cs_index_set_groups(cs_index* h, const uint32_t* ids, const uint32_t* groups, uint64_t n);
+/* *assigned_ids: ids that carry a group other than CS_NO_GROUP; *table_bytes: HBM the table holds.  Each output optional. */
+CS_API int32_t cs_index_groups_info(cs_index* h, uint64_t* assigned_ids, uint64_t* table_bytes);
+/* Errors and limits are those of cs_index_search, with the same texts; per_group == 0 fails with CS_ERR_BAD_ARG.
+ * Concurrent calls, with the same or different per_group, are safe. */
+CS_API int32_t cs_index_search_grouped(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                                       uint32_t per_group, float* out_cos, uint32_t* out_ids, uint32_t* out_counts);
+
 /* Synchronises `stream` and reports in *overflowed whether any cs_index_search_device call of more
  * than 16 queries issued by this thread on it since the previous status call overflowed a candidate buffer
  * (its results are then incomplete); clears the condition. */
