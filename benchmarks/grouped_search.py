@@ -5,7 +5,10 @@ search's median of the same run.  The hog case also records what the reference's
 then cap each file's (src/search/mod.rs:1007-1038) — against the exact grouped answer, for a post-cap over k hits and over
 1,024 (CS_MAX_K: the most a caller could fetch).  One JSON object per line on stdout (and in --out).
 
-    python benchmarks/grouped_search.py [--rows 10000000] [--reps 20] [--out FILE]
+    python benchmarks/grouped_search.py [--rows 10000000] [--dim 384] [--nq 1] [--reps 20] [--out FILE]
+
+--nq N: N queries per call (the case's query, then N - 1 unrelated ones), so that the kernels of two and four queries
+per pass are timed; the recorded answers are query 0's.
 
 The store: synthetic rows, with rows [2/10, 3/10) of it replaced by a hog — 0.9 q0 + 0.1 noise, one group.  The hog case
 searches q0; every other case searches a query unrelated to the hog."""
@@ -27,19 +30,19 @@ from codesearch_amd.synth import synth_rows  # noqa: E402
 
 
 class Caller:
-    def __init__(self, st, dim, k):
-        self.st, self.dim, self.k = st, dim, k
-        self.cos = np.zeros((1, k), np.float32)
-        self.ids = np.zeros((1, k), np.uint32)
-        self.cnt = np.zeros(1, np.uint32)
+    def __init__(self, st, dim, k, nq=1):
+        self.st, self.dim, self.k, self.nq = st, dim, k, nq
+        self.cos = np.zeros((nq, k), np.float32)
+        self.ids = np.zeros((nq, k), np.uint32)
+        self.cnt = np.zeros(nq, np.uint32)
 
     def run(self, q, per_group=None):
         h = self.st.handle
         qp, cp, ip, np_ = q.ctypes.data_as(f32p), self.cos.ctypes.data_as(f32p), self.ids.ctypes.data_as(u32p), self.cnt.ctypes.data_as(u32p)
         if per_group is None:
-            s = self.st._lib.cs_index_search(h, qp, 1, self.dim, self.k, cp, ip, np_)
+            s = self.st._lib.cs_index_search(h, qp, self.nq, self.dim, self.k, cp, ip, np_)
         else:
-            s = self.st._lib.cs_index_search_grouped(h, qp, 1, self.dim, self.k, per_group, cp, ip, np_)
+            s = self.st._lib.cs_index_search_grouped(h, qp, self.nq, self.dim, self.k, per_group, cp, ip, np_)
         _lib.check(s)
         n = int(self.cnt[0])
         return self.cos[0][:n].copy(), self.ids[0][:n].copy()
@@ -60,6 +63,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=10_000_000)
     ap.add_argument("--dim", type=int, default=384)
+    ap.add_argument("--nq", type=int, default=1)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
@@ -73,6 +77,7 @@ def main():
             out.flush()
 
     n, dim = a.rows, a.dim
+    more = synth_rows(0x9E6, 0, max(a.nq - 1, 1), dim)[:a.nq - 1]
     hog_lo, hog_n = n // 5, n // 10
     qs = np.ascontiguousarray(synth_rows(0x9E5, 0, 2, dim))
     q_hog, q_other = qs[0:1], qs[1:2]
@@ -100,11 +105,12 @@ def main():
         ("hog", hog, q_hog),                    # one group holds a tenth of the store and every near-duplicate of the query
     ]
     for cname, groups, q in cases:
+        q = np.ascontiguousarray(np.concatenate([q, more]))
         t0 = time.perf_counter()
         st.set_groups(ids, groups)
         set_ms = (time.perf_counter() - t0) * 1e3
         for k in (10, 200):
-            call = Caller(st, dim, k)
+            call = Caller(st, dim, k, a.nq)
             for m in (1, 3):
                 t0 = time.perf_counter()
                 call.run(q, m)  # the first search after an assignment uploads the table
@@ -115,7 +121,7 @@ def main():
                 t2 = timed(lambda: call.run(q, m), a.reps)
                 gc, gi = call.run(q, m)
                 med = lambda t: round(float(np.median(t)), 4)  # noqa: E731
-                rec = {"case": cname, "rows": n, "k": k, "m": m, "grouped_ms": med(t1 + t2), "grouped_before_ms": med(t1),
+                rec = {"case": cname, "rows": n, "dim": dim, "nq": a.nq, "k": k, "m": m, "grouped_ms": med(t1 + t2), "grouped_before_ms": med(t1),
                        "grouped_after_ms": med(t2), "stream_ms": med(ts), "reps": a.reps,
                        "count": int(gi.size), "set_groups_ms": round(set_ms, 1), "first_search_ms": round(first_ms, 2)}
                 rec["ratio_vs_stream"] = round(rec["grouped_ms"] / rec["stream_ms"], 4)
@@ -123,7 +129,7 @@ def main():
                 exact = set(gi.tolist())
                 for depth, name in ((k, "postcap_k"), (1024, "postcap_1024")):
                     c2 = Caller(st, dim, depth)
-                    pc, pi = c2.run(q)
+                    pc, pi = c2.run(q[0:1])
                     post = cap_per_group(pc, pi, groups[pi], k, m)[1]
                     rec[name + "_hits"] = len(post)
                     rec[name + "_exact_found"] = len(exact & set(post))

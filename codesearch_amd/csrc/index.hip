@@ -142,10 +142,11 @@ struct Workspace {
         return reserve_buf(bs.d_carry, carry_cap, (size_t)nq * k);
     }
 
-    int32_t reserve(const ScanPlan& p, uint32_t nq, uint32_t dim, uint32_t k, bool host_io) {
-        CS_TRY(reserve_buf(d_partial, partial_cap, p.partial_keys));
-        CS_TRY(reserve_buf(d_tmp_a, tmp_a_cap, p.merge_keys));
-        CS_TRY(reserve_buf(d_tmp_b, tmp_b_cap, p.merge_keys));
+    // partial_keys / merge_keys: the room the search kind's plan asks for (ScanPlan, GroupedPlan)
+    int32_t reserve(size_t partial_keys, size_t merge_keys, uint32_t nq, uint32_t dim, uint32_t k, bool host_io) {
+        CS_TRY(reserve_buf(d_partial, partial_cap, partial_keys));
+        CS_TRY(reserve_buf(d_tmp_a, tmp_a_cap, merge_keys));
+        CS_TRY(reserve_buf(d_tmp_b, tmp_b_cap, merge_keys));
         if (!host_io) return CS_OK;
         const size_t qn = (size_t)nq * dim, on = (size_t)nq * k;
         CS_TRY(reserve_buf(d_queries, q_cap, qn));
@@ -712,6 +713,12 @@ int32_t run_search(cs_index* h, Workspace* w, const ScanPlan& plan, const float*
     return settle_overflow(h, w, a, via_q8, may_sync, timed ? &ev : nullptr);
 }
 
+// The pinned queries of a host-buffer search -> w->d_queries, on the workspace's stream.
+int32_t upload_queries(const cs_index* h, Workspace* w, uint32_t nq) {
+    CS_HIP(hipMemcpyAsync(w->d_queries, w->h_queries, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice, w->stream));
+    return CS_OK;
+}
+
 // Upper bound of the live rows a mask allows (masked_plan.hpp allowed_bound): 0 = the search launches nothing.
 uint64_t masked_bound(const cs_index* h, const uint32_t* allow, uint64_t allow_bits) {
     return allowed_bound(allow, allow_bits, h->id_base, (uint64_t)h->id_base + h->n_ids, h->n_rows - h->n_removed);
@@ -855,7 +862,7 @@ int32_t run_scoped(cs_index* h, cs_scope* sc, Workspace* w, const ScanPlan& plan
     if (fp.ok) CS_TRY(w->reserve_split_queries(nq, h->dim, true, &planes));
     if (!(fp.ok && planes)) {
         sc->gathered_searches.fetch_add(1);
-        CS_HIP(hipMemcpyAsync(w->d_queries, w->h_queries, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice, w->stream));
+        CS_TRY(upload_queries(h, w, nq));
         return run_row_list(h, w, plan, live, sc->d_list, d_len, w->d_queries, nq, k, d_keys, nullptr, nullptr, nullptr, w->stream);
     }
     sc->filter_searches.fetch_add(1);
@@ -919,12 +926,6 @@ int32_t run_grouped(cs_index* h, Workspace* w, const GroupedPlan& plan, const Gr
                                 stream);
 }
 
-// The empty answer of a host-buffer search: every slot empty, as unpack_keys leaves it.
-void fill_empty(uint32_t nq, uint32_t k, float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
-    for (size_t i = 0; i < (size_t)nq * k; ++i) { out_cos[i] = 0.0f; out_ids[i] = 0xFFFFFFFFu; }
-    if (out_counts) memset(out_counts, 0, (size_t)nq * sizeof(uint32_t));
-}
-
 // The route's thresholds of a new index: RouteKnobs' defaults, or what the environment sets.
 RouteKnobs route_knobs_from_env() {
     RouteKnobs r;
@@ -957,6 +958,105 @@ int32_t check_search(const cs_index* h, uint32_t nq, uint32_t dim, uint32_t k) {
     if (k == 0 || k > CS_MAX_K)
         return fail(CS_ERR_BAD_ARG, "k must be in 1..%u, got %u", CS_MAX_K, k);
     return CS_OK;
+}
+
+// ---- the host-buffer searches' frame ------------------------------------------------------------------
+// Where a host-buffer search leaves its answer: nq lists [nq][k] with counts[nq], or (variants) the nq lists merged into
+// one list [k] with counts[0] = its length and the optional high-confidence flag (cs_index_search_variants).
+struct HostAnswer {
+    float* cos; uint32_t* ids; uint32_t* counts; int32_t* high_confidence;
+    bool variants;
+};
+
+// The argument checks every host-buffer search starts with, in this order.
+int32_t check_host_search(const cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k, const HostAnswer& out) {
+    CS_TRY(check_search(h, nq, dim, k));
+    if (out.variants && nq > CS_MAX_VARIANTS)
+        return fail(CS_ERR_BAD_ARG, "at most %u query variants per call, got %u", CS_MAX_VARIANTS, nq);
+    if (!queries || !out.cos || !out.ids || !out.counts) return fail(CS_ERR_BAD_ARG, "null buffer");
+    return CS_OK;
+}
+
+// The empty answer (nothing the kind may return is stored: no launch, no workspace): every slot as unpack_keys leaves an
+// empty one.
+int32_t empty_answer(uint32_t nq, uint32_t k, const HostAnswer& out) {
+    const size_t lists = out.variants ? 1 : nq;
+    for (size_t i = 0; i < lists * k; ++i) { out.cos[i] = 0.0f; out.ids[i] = 0xFFFFFFFFu; }
+    memset(out.counts, 0, lists * sizeof(uint32_t));
+    if (out.variants && out.high_confidence) *out.high_confidence = 0;
+    return CS_OK;
+}
+
+// One host-buffer search on a pooled workspace (own stream), for arguments that passed the checks: room for the kind's
+// plan, the queries into w->h_queries, then enqueue(w, keys) puts the kind's launches on w->stream — the best k keys per
+// query go to `keys`, and whether the queries are copied to the device is the kind's business.  Lists: keys = the pinned
+// w->h_keys, the last kernel writes the packed keys straight into it (device-addressable, coherent): no D2H copy call.
+// Variants: the per-variant lists stay in HBM (w->d_keys) and the merge kernel writes the <= k survivors and the two
+// scalars into pinned memory.  One stream sync either way, then the host unpacks.  A template, not std::function: nothing
+// on this path allocates.
+template <class Enqueue>
+int32_t host_search(cs_index* h, const float* queries, uint32_t nq, uint32_t k, size_t partial_keys, size_t merge_keys,
+                    const HostAnswer& out, Enqueue&& enqueue) {
+    Workspace* w = acquire_pooled(h);
+    if (!w) return fail(CS_ERR_HIP, "could not create a HIP stream");
+    const int32_t s = [&]() -> int32_t {
+        CS_TRY(w->reserve(partial_keys, merge_keys, nq, h->dim, k, true));
+        if (out.variants && !w->h_variant_meta) CS_HIP(hipHostMalloc(&w->h_variant_meta, 2 * sizeof(uint32_t)));
+        memcpy(w->h_queries, queries, (size_t)nq * h->dim * sizeof(float));
+        CS_TRY(enqueue(w, out.variants ? w->d_keys : w->h_keys));
+        if (out.variants)
+            CS_TRY(launch_merge_variants(w->d_keys, nq, k, k, w->h_keys, nullptr, nullptr, w->h_variant_meta,
+                                         w->h_variant_meta + 1, w->stream));
+        CS_HIP(hipStreamSynchronize(w->stream));
+        unpack_keys(w->h_keys, out.variants ? 1 : nq, k, out.cos, out.ids, out.variants ? nullptr : out.counts);
+        if (out.variants) {
+            *out.counts = w->h_variant_meta[0];
+            if (out.high_confidence) *out.high_confidence = (int32_t)w->h_variant_meta[1];
+        }
+        return CS_OK;
+    }();
+    release_pooled(h, w);
+    return s;
+}
+
+// The plain search.  Variants: exact without a host round trip (<= 16 queries carry the gated rerun).
+int32_t search_all(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k, const HostAnswer& out) {
+    CS_TRY(check_host_search(h, queries, nq, dim, k, out));
+    DeviceGuard g(h->device);
+    const ScanPlan plan = plan_scan(h->n_rows, h->dim, nq, k, h->num_cus);
+    return host_search(h, queries, nq, k, plan.partial_keys, plan.merge_keys, out, [&](Workspace* w, uint64_t* keys) {
+        return run_search(h, w, plan, w->d_queries, nq, k, keys, nullptr, nullptr, nullptr, w->stream, w->h_queries,
+                          /*may_sync=*/!out.variants);
+    });
+}
+
+int32_t search_masked(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k, const uint32_t* allow,
+                      uint64_t allow_bits, const HostAnswer& out) {
+    CS_TRY(check_host_search(h, queries, nq, dim, k, out));
+    if (!allow && allow_bits) return fail(CS_ERR_BAD_ARG, "allow is null");
+    const uint64_t bound = masked_bound(h, allow, allow_bits);
+    if (bound == 0) return empty_answer(nq, k, out);  // nothing allowed is stored
+    DeviceGuard g(h->device);
+    const ScanPlan plan = plan_scan(bound, h->dim, nq, k, h->num_cus);  // the grid follows the allowed rows
+    return host_search(h, queries, nq, k, plan.partial_keys, plan.merge_keys, out, [&](Workspace* w, uint64_t* keys) {
+        CS_TRY(upload_queries(h, w, nq));
+        return run_masked(h, w, plan, bound, w->d_queries, nq, k, allow, allow_bits, keys, w->stream);
+    });
+}
+
+int32_t search_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                      const HostAnswer& out) {
+    CS_TRY(check_host_search(h, queries, nq, dim, k, out));
+    DeviceGuard g(h->device);
+    uint64_t live = 0;
+    ScopedFilterPlan fp;
+    CS_TRY(scope_ready(h, scope, &live, &fp, nq, k));
+    if (live == 0) return empty_answer(nq, k, out);  // nothing of the scope is stored
+    const ScanPlan plan = plan_scan(live, h->dim, nq, k, h->num_cus);  // the grid follows the list's exact length
+    // (an overflow of the filter route is settled inside run_scoped, before a variants' merge)
+    return host_search(h, queries, nq, k, plan.partial_keys, plan.merge_keys, out, [&](Workspace* w, uint64_t* keys) {
+        return run_scoped(h, scope, w, plan, live, fp, nq, k, keys);
+    });
 }
 
 }  // namespace
@@ -1245,28 +1345,7 @@ int32_t cs_index_device(const cs_index* h) { return h ? h->device : -1; }
 
 int32_t cs_index_search(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
                         float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
-    CS_TRY(check_search(h, nq, dim, k));
-    if (!queries || !out_cos || !out_ids || !out_counts)
-        return fail(CS_ERR_BAD_ARG, "null buffer");
-    DeviceGuard g(h->device);
-    const ScanPlan plan = plan_scan(h->n_rows, h->dim, nq, k, h->num_cus);
-    Workspace* w = acquire_pooled(h);
-    if (!w) return fail(CS_ERR_HIP, "could not create a HIP stream");
-    int32_t s = w->reserve(plan, nq, h->dim, k, true);
-    if (s == CS_OK) {
-        s = [&]() -> int32_t {
-            memcpy(w->h_queries, queries, (size_t)nq * h->dim * sizeof(float));
-            // the last kernel of the search writes the packed keys straight into the pinned host buffer
-            // (device-addressable, coherent): no D2H copy call, one stream sync
-            CS_TRY(run_search(h, w, plan, w->d_queries, nq, k, w->h_keys, nullptr, nullptr, nullptr, w->stream,
-                              w->h_queries));
-            CS_HIP(hipStreamSynchronize(w->stream));
-            unpack_keys(w->h_keys, nq, k, out_cos, out_ids, out_counts);
-            return CS_OK;
-        }();
-    }
-    release_pooled(h, w);
-    return s;
+    return search_all(h, queries, nq, dim, k, HostAnswer{out_cos, out_ids, out_counts, nullptr, false});
 }
 
 int32_t cs_index_search_device(cs_index* h, const float* d_queries, uint32_t nq, uint32_t dim,
@@ -1277,7 +1356,7 @@ int32_t cs_index_search_device(cs_index* h, const float* d_queries, uint32_t nq,
     DeviceGuard g(h->device);
     const ScanPlan plan = plan_scan(h->n_rows, h->dim, nq, k, h->num_cus);
     Workspace* w = for_stream(h, (hipStream_t)stream);
-    CS_TRY(w->reserve(plan, nq, h->dim, k, false));
+    CS_TRY(w->reserve(plan.partial_keys, plan.merge_keys, nq, h->dim, k, false));
     return run_search(h, w, plan, d_queries, nq, k, d_out_keys, d_out_cos, d_out_ids, d_out_counts,
                       (hipStream_t)stream, nullptr, /*may_sync=*/false);
 }
@@ -1285,105 +1364,20 @@ int32_t cs_index_search_device(cs_index* h, const float* d_queries, uint32_t nq,
 int32_t cs_index_search_variants(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
                                  float* out_cos, uint32_t* out_ids, uint32_t* out_count,
                                  int32_t* out_high_confidence) {
-    CS_TRY(check_search(h, nq, dim, k));
-    if (nq > CS_MAX_VARIANTS)
-        return fail(CS_ERR_BAD_ARG, "at most %u query variants per call, got %u", CS_MAX_VARIANTS, nq);
-    if (!queries || !out_cos || !out_ids || !out_count) return fail(CS_ERR_BAD_ARG, "null buffer");
-    DeviceGuard g(h->device);
-    const ScanPlan plan = plan_scan(h->n_rows, h->dim, nq, k, h->num_cus);
-    Workspace* w = acquire_pooled(h);
-    if (!w) return fail(CS_ERR_HIP, "could not create a HIP stream");
-    int32_t s = w->reserve(plan, nq, h->dim, k, true);
-    if (s == CS_OK) {
-        s = [&]() -> int32_t {
-            if (!w->h_variant_meta) CS_HIP(hipHostMalloc(&w->h_variant_meta, 2 * sizeof(uint32_t)));
-            memcpy(w->h_queries, queries, (size_t)nq * h->dim * sizeof(float));
-            // per-variant lists stay in HBM (exact without a host round trip: <= 16 queries carry the gated rerun),
-            // the merge kernel writes the <= k survivors and the two scalars straight into pinned host memory
-            CS_TRY(run_search(h, w, plan, w->d_queries, nq, k, w->d_keys, nullptr, nullptr, nullptr, w->stream,
-                              w->h_queries, /*may_sync=*/false));
-            CS_TRY(launch_merge_variants(w->d_keys, nq, k, k, w->h_keys, nullptr, nullptr, w->h_variant_meta,
-                                         w->h_variant_meta + 1, w->stream));
-            CS_HIP(hipStreamSynchronize(w->stream));
-            unpack_keys(w->h_keys, 1, k, out_cos, out_ids, nullptr);
-            *out_count = w->h_variant_meta[0];
-            if (out_high_confidence) *out_high_confidence = (int32_t)w->h_variant_meta[1];
-            return CS_OK;
-        }();
-    }
-    release_pooled(h, w);
-    return s;
+    return search_all(h, queries, nq, dim, k, HostAnswer{out_cos, out_ids, out_count, out_high_confidence, true});
 }
 
 int32_t cs_index_search_masked(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
                                const uint32_t* allow, uint64_t allow_bits, float* out_cos, uint32_t* out_ids,
                                uint32_t* out_counts) {
-    CS_TRY(check_search(h, nq, dim, k));
-    if (!queries || !out_cos || !out_ids || !out_counts) return fail(CS_ERR_BAD_ARG, "null buffer");
-    if (!allow && allow_bits) return fail(CS_ERR_BAD_ARG, "allow is null");
-    const uint64_t bound = masked_bound(h, allow, allow_bits);
-    if (bound == 0) {  // nothing allowed is stored: no launch
-        fill_empty(nq, k, out_cos, out_ids, out_counts);
-        return CS_OK;
-    }
-    DeviceGuard g(h->device);
-    const ScanPlan plan = plan_scan(bound, h->dim, nq, k, h->num_cus);  // the grid follows the allowed rows
-    Workspace* w = acquire_pooled(h);
-    if (!w) return fail(CS_ERR_HIP, "could not create a HIP stream");
-    int32_t s = w->reserve(plan, nq, h->dim, k, true);
-    if (s == CS_OK) {
-        s = [&]() -> int32_t {
-            memcpy(w->h_queries, queries, (size_t)nq * h->dim * sizeof(float));
-            CS_HIP(hipMemcpyAsync(w->d_queries, w->h_queries, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice,
-                                  w->stream));
-            CS_TRY(run_masked(h, w, plan, bound, w->d_queries, nq, k, allow, allow_bits, w->h_keys, w->stream));
-            CS_HIP(hipStreamSynchronize(w->stream));
-            unpack_keys(w->h_keys, nq, k, out_cos, out_ids, out_counts);
-            return CS_OK;
-        }();
-    }
-    release_pooled(h, w);
-    return s;
+    return search_masked(h, queries, nq, dim, k, allow, allow_bits, HostAnswer{out_cos, out_ids, out_counts, nullptr, false});
 }
 
 int32_t cs_index_search_variants_masked(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
                                         const uint32_t* allow, uint64_t allow_bits, float* out_cos, uint32_t* out_ids,
                                         uint32_t* out_count, int32_t* out_high_confidence) {
-    CS_TRY(check_search(h, nq, dim, k));
-    if (nq > CS_MAX_VARIANTS)
-        return fail(CS_ERR_BAD_ARG, "at most %u query variants per call, got %u", CS_MAX_VARIANTS, nq);
-    if (!queries || !out_cos || !out_ids || !out_count) return fail(CS_ERR_BAD_ARG, "null buffer");
-    if (!allow && allow_bits) return fail(CS_ERR_BAD_ARG, "allow is null");
-    const uint64_t bound = masked_bound(h, allow, allow_bits);
-    if (bound == 0) {
-        fill_empty(1, k, out_cos, out_ids, nullptr);
-        *out_count = 0;
-        if (out_high_confidence) *out_high_confidence = 0;
-        return CS_OK;
-    }
-    DeviceGuard g(h->device);
-    const ScanPlan plan = plan_scan(bound, h->dim, nq, k, h->num_cus);
-    Workspace* w = acquire_pooled(h);
-    if (!w) return fail(CS_ERR_HIP, "could not create a HIP stream");
-    int32_t s = w->reserve(plan, nq, h->dim, k, true);
-    if (s == CS_OK) {
-        s = [&]() -> int32_t {
-            if (!w->h_variant_meta) CS_HIP(hipHostMalloc(&w->h_variant_meta, 2 * sizeof(uint32_t)));
-            memcpy(w->h_queries, queries, (size_t)nq * h->dim * sizeof(float));
-            CS_HIP(hipMemcpyAsync(w->d_queries, w->h_queries, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice,
-                                  w->stream));
-            CS_TRY(run_masked(h, w, plan, bound, w->d_queries, nq, k, allow, allow_bits, w->d_keys, w->stream));
-            CS_TRY(launch_merge_variants(w->d_keys, nq, k, k, w->h_keys, nullptr, nullptr, w->h_variant_meta,
-                                         w->h_variant_meta + 1, w->stream));
-            CS_HIP(hipStreamSynchronize(w->stream));
-            unpack_keys(w->h_keys, 1, k, out_cos, out_ids, nullptr);
-            *out_count = w->h_variant_meta[0];
-            if (out_high_confidence) *out_high_confidence = (int32_t)w->h_variant_meta[1];
-            return CS_OK;
-        }();
-    }
-    release_pooled(h, w);
-    return s;
+    return search_masked(h, queries, nq, dim, k, allow, allow_bits,
+                         HostAnswer{out_cos, out_ids, out_count, out_high_confidence, true});
 }
 
 int32_t cs_index_set_groups(cs_index* h, const uint32_t* ids, const uint32_t* groups, uint64_t n) {
@@ -1430,32 +1424,17 @@ int32_t cs_index_groups_info(cs_index* h, uint64_t* assigned_ids, uint64_t* tabl
 
 int32_t cs_index_search_grouped(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k, uint32_t per_group,
                                 float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
-    CS_TRY(check_search(h, nq, dim, k));
-    if (!queries || !out_cos || !out_ids || !out_counts) return fail(CS_ERR_BAD_ARG, "null buffer");
+    const HostAnswer out{out_cos, out_ids, out_counts, nullptr, false};
+    CS_TRY(check_host_search(h, queries, nq, dim, k, out));
     if (per_group == 0) return fail(CS_ERR_BAD_ARG, "per_group must be at least 1");
     DeviceGuard g(h->device);
     GroupView gv;
     CS_TRY(ensure_groups(h, per_group, &gv));
     const GroupedPlan plan = plan_grouped(h->n_rows, h->dim, nq, k, h->num_cus);
-    ScanPlan room{};  // the workspace's buffers, sized for the grouped plan
-    room.partial_keys = plan.partial_keys;
-    room.merge_keys = plan.merge_keys;
-    Workspace* w = acquire_pooled(h);
-    if (!w) return fail(CS_ERR_HIP, "could not create a HIP stream");
-    int32_t s = w->reserve(room, nq, h->dim, k, true);
-    if (s == CS_OK) {
-        s = [&]() -> int32_t {
-            memcpy(w->h_queries, queries, (size_t)nq * h->dim * sizeof(float));
-            CS_HIP(hipMemcpyAsync(w->d_queries, w->h_queries, (size_t)nq * h->dim * sizeof(float), hipMemcpyHostToDevice,
-                                  w->stream));
-            CS_TRY(run_grouped(h, w, plan, gv, w->d_queries, nq, k, w->h_keys, w->stream));
-            CS_HIP(hipStreamSynchronize(w->stream));
-            unpack_keys(w->h_keys, nq, k, out_cos, out_ids, out_counts);
-            return CS_OK;
-        }();
-    }
-    release_pooled(h, w);
-    return s;
+    return host_search(h, queries, nq, k, plan.partial_keys, plan.merge_keys, out, [&](Workspace* w, uint64_t* keys) {
+        CS_TRY(upload_queries(h, w, nq));
+        return run_grouped(h, w, plan, gv, w->d_queries, nq, k, keys, w->stream);
+    });
 }
 
 int32_t cs_index_scope_create(cs_index* h, const uint32_t* ids, uint64_t n, cs_scope** out) {
@@ -1544,71 +1523,13 @@ int32_t cs_scope_route_info(const cs_scope* scope, uint64_t* filter_searches, ui
 
 int32_t cs_index_search_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
                                float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
-    CS_TRY(check_search(h, nq, dim, k));
-    if (!queries || !out_cos || !out_ids || !out_counts) return fail(CS_ERR_BAD_ARG, "null buffer");
-    DeviceGuard g(h->device);
-    uint64_t live = 0;
-    ScopedFilterPlan fp;
-    CS_TRY(scope_ready(h, scope, &live, &fp, nq, k));
-    if (live == 0) {  // nothing of the scope is stored: no launch
-        fill_empty(nq, k, out_cos, out_ids, out_counts);
-        return CS_OK;
-    }
-    const ScanPlan plan = plan_scan(live, h->dim, nq, k, h->num_cus);  // the grid follows the list's exact length
-    Workspace* w = acquire_pooled(h);
-    if (!w) return fail(CS_ERR_HIP, "could not create a HIP stream");
-    int32_t s = w->reserve(plan, nq, h->dim, k, true);
-    if (s == CS_OK) {
-        s = [&]() -> int32_t {
-            memcpy(w->h_queries, queries, (size_t)nq * h->dim * sizeof(float));
-            CS_TRY(run_scoped(h, scope, w, plan, live, fp, nq, k, w->h_keys));
-            CS_HIP(hipStreamSynchronize(w->stream));
-            unpack_keys(w->h_keys, nq, k, out_cos, out_ids, out_counts);
-            return CS_OK;
-        }();
-    }
-    release_pooled(h, w);
-    return s;
+    return search_scoped(h, scope, queries, nq, dim, k, HostAnswer{out_cos, out_ids, out_counts, nullptr, false});
 }
 
 int32_t cs_index_search_variants_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,
                                         uint32_t k, float* out_cos, uint32_t* out_ids, uint32_t* out_count,
                                         int32_t* out_high_confidence) {
-    CS_TRY(check_search(h, nq, dim, k));
-    if (nq > CS_MAX_VARIANTS)
-        return fail(CS_ERR_BAD_ARG, "at most %u query variants per call, got %u", CS_MAX_VARIANTS, nq);
-    if (!queries || !out_cos || !out_ids || !out_count) return fail(CS_ERR_BAD_ARG, "null buffer");
-    DeviceGuard g(h->device);
-    uint64_t live = 0;
-    ScopedFilterPlan fp;
-    CS_TRY(scope_ready(h, scope, &live, &fp, nq, k));
-    if (live == 0) {
-        fill_empty(1, k, out_cos, out_ids, nullptr);
-        *out_count = 0;
-        if (out_high_confidence) *out_high_confidence = 0;
-        return CS_OK;
-    }
-    const ScanPlan plan = plan_scan(live, h->dim, nq, k, h->num_cus);
-    Workspace* w = acquire_pooled(h);
-    if (!w) return fail(CS_ERR_HIP, "could not create a HIP stream");
-    int32_t s = w->reserve(plan, nq, h->dim, k, true);
-    if (s == CS_OK) {
-        s = [&]() -> int32_t {
-            if (!w->h_variant_meta) CS_HIP(hipHostMalloc(&w->h_variant_meta, 2 * sizeof(uint32_t)));
-            memcpy(w->h_queries, queries, (size_t)nq * h->dim * sizeof(float));
-            // (an overflow of the filter route is settled inside, before the variants' merge)
-            CS_TRY(run_scoped(h, scope, w, plan, live, fp, nq, k, w->d_keys));
-            CS_TRY(launch_merge_variants(w->d_keys, nq, k, k, w->h_keys, nullptr, nullptr, w->h_variant_meta,
-                                         w->h_variant_meta + 1, w->stream));
-            CS_HIP(hipStreamSynchronize(w->stream));
-            unpack_keys(w->h_keys, 1, k, out_cos, out_ids, nullptr);
-            *out_count = w->h_variant_meta[0];
-            if (out_high_confidence) *out_high_confidence = (int32_t)w->h_variant_meta[1];
-            return CS_OK;
-        }();
-    }
-    release_pooled(h, w);
-    return s;
+    return search_scoped(h, scope, queries, nq, dim, k, HostAnswer{out_cos, out_ids, out_count, out_high_confidence, true});
 }
 
 int32_t cs_index_search_scoped_device(cs_index* h, cs_scope* scope, const float* d_queries, uint32_t nq, uint32_t dim,
@@ -1630,7 +1551,7 @@ int32_t cs_index_search_scoped_device(cs_index* h, cs_scope* scope, const float*
     }
     const ScanPlan plan = plan_scan(live, h->dim, nq, k, h->num_cus);
     Workspace* w = for_stream(h, st);
-    CS_TRY(w->reserve(plan, nq, h->dim, k, false));
+    CS_TRY(w->reserve(plan.partial_keys, plan.merge_keys, nq, h->dim, k, false));
     return run_row_list(h, w, plan, live, scope->d_list, scope->d_blocks + scope_list_blocks(scope->n_ids), d_queries, nq, k,
                         d_out_keys, d_out_cos, d_out_ids, d_out_counts, st);
 }
@@ -1732,7 +1653,7 @@ int32_t cs::index_search_masked_device(cs_index* h, const float* d_queries, uint
     }
     const ScanPlan plan = plan_scan(bound, h->dim, nq, k, h->num_cus);
     Workspace* w = for_stream(h, stream);
-    CS_TRY(w->reserve(plan, nq, h->dim, k, false));
+    CS_TRY(w->reserve(plan.partial_keys, plan.merge_keys, nq, h->dim, k, false));
     return run_masked(h, w, plan, bound, d_queries, nq, k, allow, allow_bits, d_out_keys, stream);
 }
 

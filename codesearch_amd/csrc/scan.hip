@@ -13,7 +13,7 @@
 // Algorithmic bytes per row = dim*4 (1536 B at dim 384).
 #include "scan.hpp"
 #include "block_select.hpp"
-#include "scan_wave.hpp"  // f32x4, kBlock, the wave / block helpers (shared with scan_masked.hip)
+#include "scan_wave.hpp"  // f32x4, kBlock, the scans' shared body
 
 #include "../../include/cs_synth.h"
 
@@ -24,6 +24,8 @@ constexpr int kMergeCap = 4096;  // keys a merge block can sort (2048 used up to
 
 // ---- S1+S2: the streaming scan ----------------------------------------------------------
 //
+// What scores a row and what merges a block's lists is scan_wave.hpp's, shared with scan_masked.hip and scan_grouped.hip;
+// this kernel adds the consecutive-row tiles, the choice of loads, the gate and the tombstone test.
 // J  = float4 chunks per lane per row (dim = 128*J);  U = row pairs in flight per wave
 // (a wave tile is 2U consecutive rows: half-wave h takes row 2u+h);  QT = queries scored
 // per pass from registers;  NT = non-temporal corpus loads.
@@ -38,7 +40,8 @@ constexpr int kMergeCap = 4096;  // keys a merge block can sort (2048 used up to
 // EQUAL to the bound must still pass the `>`; a bound in the denormal range becomes -FLT_MIN so
 // the test never depends on the denormal mode).  The full scan then starts every list with
 // thr = floor instead of -inf and inserts ~10 rows per wave instead of ~650; results are
-// bit-identical because only rows that cannot be among the best k are skipped.
+// bit-identical because only rows that cannot be among the best k are skipped.  The pass's end — maxima to HBM, the last
+// block's selection — is prime_pass_tail (scan_wave.hpp).
 template <int J, int U, int QT, bool NT, bool PRIME = false>
 __global__ void __launch_bounds__(kBlock)
 scan_topk_kernel(const float* __restrict__ corpus, uint64_t n_rows,
@@ -61,24 +64,11 @@ scan_topk_kernel(const float* __restrict__ corpus, uint64_t n_rows,
 
     for (uint32_t i = tid; i < QT * kWaves * kpad; i += kBlock) lds_keys[i] = 0ull;
 
-    // query fragments + magnitudes (mag_a of benchmark_models.rs:325)
-    f32x4 qf[QT][J];
+    f32x4 qf[QT][J];  // a pass past the last query re-reads query nq - 1 (its results are never stored)
     float qmag[QT];
 #pragma unroll
-    for (int qi = 0; qi < QT; ++qi) {
-        const uint32_t q = (q0 + qi < nq) ? (q0 + qi) : (nq - 1);
-        const f32x4* qp = reinterpret_cast<const f32x4*>(queries + (size_t)q * DIM) + l32;
-        float s = 0.0f;
-#pragma unroll
-        for (int j = 0; j < J; ++j) {
-            qf[qi][j] = qp[j * 32];
-            s = fmaf(qf[qi][j].x, qf[qi][j].x, s);
-            s = fmaf(qf[qi][j].y, qf[qi][j].y, s);
-            s = fmaf(qf[qi][j].z, qf[qi][j].z, s);
-            s = fmaf(qf[qi][j].w, qf[qi][j].w, s);
-        }
-        qmag[qi] = sqrtf(half_allreduce_sum(s));
-    }
+    for (int qi = 0; qi < QT; ++qi)
+        qmag[qi] = load_query_fragment<J>(queries, (q0 + qi < nq) ? (q0 + qi) : (nq - 1), l32, qf[qi]);
     float thr[QT], floor[QT];
     uint32_t wpos[QT];
 #pragma unroll
@@ -115,33 +105,14 @@ scan_topk_kernel(const float* __restrict__ corpus, uint64_t n_rows,
         const uint64_t row0 = tile * (2 * U);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            float ss = 0.0f;
             float dot[QT];
-#pragma unroll
-            for (int qi = 0; qi < QT; ++qi) dot[qi] = 0.0f;
-#pragma unroll
-            for (int j = 0; j < J; ++j) {
-                const f32x4 v = x[u][j];
-                ss = fmaf(v.x, v.x, ss);
-                ss = fmaf(v.y, v.y, ss);
-                ss = fmaf(v.z, v.z, ss);
-                ss = fmaf(v.w, v.w, ss);
-#pragma unroll
-                for (int qi = 0; qi < QT; ++qi) {
-                    dot[qi] = fmaf(v.x, qf[qi][j].x, dot[qi]);
-                    dot[qi] = fmaf(v.y, qf[qi][j].y, dot[qi]);
-                    dot[qi] = fmaf(v.z, qf[qi][j].z, dot[qi]);
-                    dot[qi] = fmaf(v.w, qf[qi][j].w, dot[qi]);
-                }
-            }
-            const float xmag = sqrtf(half_allreduce_sum(ss));  // mag_b
+            const float xmag = row_products<J, QT>(x[u], qf, dot);
             const uint64_t r = row0 + 2 * u + half;
             const bool valid = r < n_rows;
 #pragma unroll
             for (int qi = 0; qi < QT; ++qi) {
                 const float d = half_allreduce_sum(dot[qi]);
-                // batch.rs:320-323: zero magnitude -> 0.0, else dot / (mag_a * mag_b)
-                const float c = (qmag[qi] == 0.0f || xmag == 0.0f) ? 0.0f : d / (qmag[qi] * xmag);
+                const float c = cosine_of(d, qmag[qi], xmag);
                 if constexpr (PRIME) {
                     if (valid && c > thr[qi] && !row_is_dead(dead, r)) thr[qi] = c;
                     continue;
@@ -168,52 +139,7 @@ scan_topk_kernel(const float* __restrict__ corpus, uint64_t n_rows,
         score_tile(x, tile);
     }
     if constexpr (PRIME) {
-        // wave maxima -> HBM; the last block of this pass selects the k-th largest per query
-        const uint32_t nwaves = gridDim.x * kWaves;
-#pragma unroll
-        for (int qi = 0; qi < QT; ++qi) {
-            const float m = fmaxf(__shfl(thr[qi], 0, 64), __shfl(thr[qi], 32, 64));
-            if (lane == 0 && q0 + qi < nq)
-                __hip_atomic_store(wave_max + (size_t)(q0 + qi) * nwaves + gw, m, __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __shared__ uint32_t is_last;
-        __threadfence();
-        __syncthreads();
-        if (tid == 0) {
-            const uint32_t prev = __hip_atomic_fetch_add(done_ctr + blockIdx.y, 1u, __ATOMIC_ACQ_REL,
-                                                         __HIP_MEMORY_SCOPE_AGENT);
-            is_last = (prev == gridDim.x - 1);
-        }
-        __syncthreads();
-        if (!is_last) return;
-        __threadfence();
-        uint32_t nsort = 64;
-        while (nsort < nwaves) nsort <<= 1;  // host keeps nsort <= kWaves * kpad (the LDS size)
-#pragma unroll 1
-        for (int qi = 0; qi < QT; ++qi) {
-            if (q0 + qi >= nq) break;
-            __syncthreads();
-            for (uint32_t i = tid; i < nsort; i += kBlock) {
-                float m = -__builtin_huge_valf();
-                if (i < nwaves)
-                    m = __hip_atomic_load(wave_max + (size_t)(q0 + qi) * nwaves + i, __ATOMIC_RELAXED,
-                                          __HIP_MEMORY_SCOPE_AGENT);
-                lds_keys[i] = (m == -__builtin_huge_valf()) ? 0ull : key_pack(m, 0u);
-            }
-            block_bitonic_desc<kBlock>(lds_keys, nsort, tid);
-            if (tid == 0) {
-                const uint64_t key = (k <= nsort) ? lds_keys[k - 1] : 0ull;
-                float t = -__builtin_huge_valf();
-                if (key) {
-                    const uint32_t o = (uint32_t)(key >> 32) - 1u;  // next float below the bound
-                    t = key_cos((uint64_t)o << 32);
-                    if (fabsf(t) < 1.17549435e-38f) t = -1.17549435e-38f;
-                }
-                floor_out[q0 + qi] = t;
-            }
-        }
-        if (tid == 0) __hip_atomic_store(done_ctr + blockIdx.y, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        prime_pass_tail<QT>(thr, q0, nq, k, gw, tid, lane, lds_keys, wave_max, done_ctr, floor_out);
         return;
     }
     __syncthreads();
@@ -223,15 +149,12 @@ scan_topk_kernel(const float* __restrict__ corpus, uint64_t n_rows,
 #pragma unroll 1
     for (int qi = 0; qi < QT; ++qi) {
         if (q0 + qi >= nq) break;
-        uint64_t* a = lds_keys + (size_t)qi * nsort;
-        block_bitonic_desc<kBlock>(a, nsort, tid);
-        uint64_t* out = partial + ((size_t)(q0 + qi) * gridDim.x + blockIdx.x) * k;
-        for (uint32_t i = tid; i < k; i += kBlock) out[i] = a[i];
+        block_merge_store(lds_keys + (size_t)qi * nsort, kpad, k, q0 + qi, tid, partial);
     }
 }
 
 // Any-dim fallback (e.g. the reference's own 4-d unit test, store.rs:846-893): one wave
-// per row, lanes stride over columns.  Not a tuned path.
+// per row, lanes stride over columns (wave_row_cosine, scan_wave.hpp).  Not a tuned path.
 __global__ void __launch_bounds__(kBlock)
 scan_topk_generic_kernel(const float* __restrict__ corpus, uint64_t n_rows, uint32_t dim,
                          const float* __restrict__ queries, uint32_t nq, uint32_t k,
@@ -243,9 +166,7 @@ scan_topk_generic_kernel(const float* __restrict__ corpus, uint64_t n_rows, uint
     const uint32_t q = blockIdx.y;
     for (uint32_t i = tid; i < kWaves * kpad; i += kBlock) lds_keys[i] = 0ull;
     const float* qp = queries + (size_t)q * dim;
-    float s = 0.0f;
-    for (uint32_t c = lane; c < dim; c += 64) s = fmaf(qp[c], qp[c], s);
-    const float qmag = sqrtf(wave_allreduce_sum(s));
+    const float qmag = wave_query_mag(qp, dim, lane);
     float thr = -__builtin_huge_valf();
     uint32_t wpos = 0;
     __syncthreads();
@@ -254,23 +175,12 @@ scan_topk_generic_kernel(const float* __restrict__ corpus, uint64_t n_rows, uint
     const uint64_t nw = (uint64_t)gridDim.x * kWaves;
     for (uint64_t r = gw; r < n_rows; r += nw) {
         const float* xp = corpus + r * dim;
-        float ss = 0.0f, dot = 0.0f;
-        for (uint32_t c = lane; c < dim; c += 64) {
-            const float v = xp[c];
-            ss = fmaf(v, v, ss);
-            dot = fmaf(v, qp[c], dot);
-        }
-        const float xmag = sqrtf(wave_allreduce_sum(ss));
-        const float d = wave_allreduce_sum(dot);
-        const float c = (qmag == 0.0f || xmag == 0.0f) ? 0.0f : d / (qmag * xmag);
+        const float c = wave_row_cosine(xp, qp, dim, lane, qmag);
         if (c > thr && !row_is_dead(dead, r))  // wave-uniform
             wave_list_insert(list, k, lane, c, id_base.of(r), thr, wpos);
     }
     __syncthreads();
-    const uint32_t nsort = kWaves * kpad;
-    block_bitonic_desc<kBlock>(lds_keys, nsort, tid);
-    uint64_t* out = partial + ((size_t)q * gridDim.x + blockIdx.x) * k;
-    for (uint32_t i = tid; i < k; i += kBlock) out[i] = lds_keys[i];
+    block_merge_store(lds_keys, kpad, k, q, tid, partial);
 }
 
 // ---- S2/S4: key-list merge ----------------------------------------------------------------

@@ -3,8 +3,8 @@
 // :947-957 `--compact`): a file with many near-duplicate chunks fills the ranked list before the cap is applied.
 // Host plan, the contract and the merge lemma: grouped_plan.hpp.
 //
-//   1. capped scan: scan_topk_kernel's tile loop and per-row arithmetic (scan.hip; the fmaf order over j,
-//      half_allreduce_sum, the zero guard and the strict `>` are the same, so every cosine is bit-identical), with a u32
+//   1. capped scan: scan_topk_kernel's tile loop (scan.hip), a row scored by the functions that score it there
+//      (scan_wave.hpp: load_query_fragment, row_products, cosine_of — so every cosine is bit-identical), with a u32
 //      group slot beside every key slot of a wave's list.  The fast-path gate stays `c > thr`: a full list whose worst
 //      key the row does not beat holds k cap-valid rows that all beat it.  On the slow path the row's group comes from
 //      the table (one address per wave) and the insert keeps the list the capped top-k of what the wave has met:
@@ -24,26 +24,7 @@ __device__ __forceinline__ uint32_t group_of(const GroupView& gv, uint32_t id) {
     return (gv.groups && i < gv.len) ? gv.groups[i] : kNoGroup;
 }
 
-typedef volatile uint64_t __attribute__((address_space(3))) lds_vu64;
 typedef volatile uint32_t __attribute__((address_space(3))) lds_vu32;
-
-// thr / wpos of a full list: the worst key and its slot (wave_list_insert's search)
-__device__ __forceinline__ void wave_list_worst(lds_vu64* list, uint32_t k, int lane, float& thr, uint32_t& wpos) {
-    uint64_t mk = ~0ull;
-    uint32_t mp = 0xffffffffu;
-    for (uint32_t i = lane; i < k; i += 64) {
-        const uint64_t v = list[i];
-        if (v < mk) { mk = v; mp = i; }
-    }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        const uint64_t ok = shfl_xor_u64(mk, s);
-        const uint32_t op = __shfl_xor(mp, s, 64);
-        if (ok < mk || (ok == mk && op < mp)) { mk = ok; mp = op; }
-    }
-    wpos = mp | 0x80000000u;
-    thr = key_cos(mk);  // a full list has no empty slot
-}
 
 // wave_list_insert (scan_wave.hpp) under the cap.  `list` holds the capped top-k of the rows this wave has met, `glist`
 // their groups; thr / wpos as there (wpos < 2^31 counts the filled slots of a list that is not full yet, thr = -inf then).
@@ -88,7 +69,7 @@ __device__ __forceinline__ void wave_list_insert_grouped(volatile uint64_t* list
                 if (full) {
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
-                    wave_list_worst(list, k, lane, thr, wpos);
+                    wave_list_worst<true>(list, k, lane, thr, wpos);  // a full list has no empty slot
                 }
             }
             return;
@@ -105,7 +86,7 @@ __device__ __forceinline__ void wave_list_insert_grouped(volatile uint64_t* list
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    wave_list_worst(list, k, lane, thr, wpos);
+    wave_list_worst<true>(list, k, lane, thr, wpos);  // a full list has no empty slot
 }
 
 // A wave's list -> HBM, unsorted, empty slots as 0: list `blockIdx.x * kWaves + wave` of query q.
@@ -137,24 +118,11 @@ scan_grouped_topk_kernel(const float* __restrict__ corpus, uint64_t n_rows, cons
         lds_groups[i] = kNoGroup;
     }
 
-    // query fragments + magnitudes (mag_a of benchmark_models.rs:325)
-    f32x4 qf[QT][J];
+    f32x4 qf[QT][J];  // a pass past the last query re-reads query nq - 1 (its results are never stored)
     float qmag[QT];
 #pragma unroll
-    for (int qi = 0; qi < QT; ++qi) {
-        const uint32_t q = (q0 + qi < nq) ? (q0 + qi) : (nq - 1);
-        const f32x4* qp = reinterpret_cast<const f32x4*>(queries + (size_t)q * DIM) + l32;
-        float s = 0.0f;
-#pragma unroll
-        for (int j = 0; j < J; ++j) {
-            qf[qi][j] = qp[j * 32];
-            s = fmaf(qf[qi][j].x, qf[qi][j].x, s);
-            s = fmaf(qf[qi][j].y, qf[qi][j].y, s);
-            s = fmaf(qf[qi][j].z, qf[qi][j].z, s);
-            s = fmaf(qf[qi][j].w, qf[qi][j].w, s);
-        }
-        qmag[qi] = sqrtf(half_allreduce_sum(s));
-    }
+    for (int qi = 0; qi < QT; ++qi)
+        qmag[qi] = load_query_fragment<J>(queries, (q0 + qi < nq) ? (q0 + qi) : (nq - 1), l32, qf[qi]);
     float thr[QT];
     uint32_t wpos[QT];
 #pragma unroll
@@ -181,33 +149,14 @@ scan_grouped_topk_kernel(const float* __restrict__ corpus, uint64_t n_rows, cons
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            float ss = 0.0f;
             float dot[QT];
-#pragma unroll
-            for (int qi = 0; qi < QT; ++qi) dot[qi] = 0.0f;
-#pragma unroll
-            for (int j = 0; j < J; ++j) {
-                const f32x4 v = x[u][j];
-                ss = fmaf(v.x, v.x, ss);
-                ss = fmaf(v.y, v.y, ss);
-                ss = fmaf(v.z, v.z, ss);
-                ss = fmaf(v.w, v.w, ss);
-#pragma unroll
-                for (int qi = 0; qi < QT; ++qi) {
-                    dot[qi] = fmaf(v.x, qf[qi][j].x, dot[qi]);
-                    dot[qi] = fmaf(v.y, qf[qi][j].y, dot[qi]);
-                    dot[qi] = fmaf(v.z, qf[qi][j].z, dot[qi]);
-                    dot[qi] = fmaf(v.w, qf[qi][j].w, dot[qi]);
-                }
-            }
-            const float xmag = sqrtf(half_allreduce_sum(ss));  // mag_b
+            const float xmag = row_products<J, QT>(x[u], qf, dot);
             const uint64_t r = row0 + 2 * u + half;
             const bool valid = r < n_rows;
 #pragma unroll
             for (int qi = 0; qi < QT; ++qi) {
                 const float d = half_allreduce_sum(dot[qi]);
-                // batch.rs:320-323: zero magnitude -> 0.0, else dot / (mag_a * mag_b)
-                const float c = (qmag[qi] == 0.0f || xmag == 0.0f) ? 0.0f : d / (qmag[qi] * xmag);
+                const float c = cosine_of(d, qmag[qi], xmag);
                 unsigned long long m = __ballot(valid && l32 == 0 && c > thr[qi]);
                 if (m) {  // wave-uniform slow path; every row takes it until the list is full
                     volatile uint64_t* list = lds_keys + ((size_t)qi * kWaves + wave) * kpad;
@@ -236,7 +185,7 @@ scan_grouped_topk_kernel(const float* __restrict__ corpus, uint64_t n_rows, cons
     }
 }
 
-// Any other dim: one wave per row, lanes stride over columns (scan_topk_generic_kernel's arithmetic).
+// Any other dim: one wave per row, lanes stride over columns.
 __global__ void __launch_bounds__(kBlock)
 scan_grouped_generic_kernel(const float* __restrict__ corpus, uint64_t n_rows, uint32_t dim, const float* __restrict__ queries,
                             uint32_t nq, uint32_t k, uint32_t kpad, const uint32_t* __restrict__ dead, RowIds id_base,
@@ -250,6 +199,8 @@ scan_grouped_generic_kernel(const float* __restrict__ corpus, uint64_t n_rows, u
         lds_groups[i] = kNoGroup;
     }
     const float* qp = queries + (size_t)q * dim;
+    // (this kernel keeps its own text of wave_query_mag / wave_row_cosine, scan_wave.hpp: with either helper, or cosine_of,
+    // it compiles 2 instructions longer; the arithmetic is the same, line for line)
     float s = 0.0f;
     for (uint32_t c = lane; c < dim; c += 64) s = fmaf(qp[c], qp[c], s);
     const float qmag = sqrtf(wave_allreduce_sum(s));

@@ -6,12 +6,13 @@
 //      rows into a list in ASCENDING row order — per-block counts, one exclusive scan, a scatter.  No atomic append: the
 //      per-wave lists of the scan resolve a tie with the worst slot in favour of the row already there (wave_list_insert),
 //      which is the (cosine desc, id asc) order only while every wave meets its rows in ascending id.
-//   2. gathered scan: scan_topk_kernel's per-row arithmetic with one change, half-wave h of tile t reads row
-//      list[t * 2U + 2u + h] instead of t * 2U + 2u + h.  The fmaf order over j, half_allreduce_sum, the zero guard and
-//      the strict `>` are the same, so every cosine is bit-identical to the one the full scan computes for that row, and
-//      the per-block partial lists go through the same launch_merge.  Other dims: one wave per row, as
-//      scan_topk_generic_kernel.
-//   3. prime pass (PRIME): the streaming scan's, over the first entries of the list.
+//   2. gathered scan: scan_topk_kernel's tile loop with one change, half-wave h of tile t reads row
+//      list[t * 2U + 2u + h] instead of t * 2U + 2u + h.  A row is scored by the functions that score it in the streaming
+//      scan (scan_wave.hpp: load_query_fragment, row_products, cosine_of) and enters a list through the same
+//      wave_list_insert, so every cosine is bit-identical to the one the full scan computes for that row, and the
+//      per-block partial lists (block_merge_store) go through the same launch_merge.  Other dims: one wave per row,
+//      wave_row_cosine.  (One instantiation, <8,2,4>, carries those three functions' lines as its own text: kOwnText.)
+//   3. prime pass (PRIME): the streaming scan's (prime_pass_tail), over the first entries of the list.
 //   4. a scope (index.hip cs_scope) keeps its row list on the device and makes it from its id list, not from a bitmap:
 //      the end of this file.  Steps 2 and 3 read it as they read a mask's list.
 // The list holds live rows only, so the scan tests no tombstones.
@@ -155,22 +156,31 @@ scan_masked_topk_kernel(const float* __restrict__ corpus, const uint32_t* __rest
 
     for (uint32_t i = tid; i < QT * kWaves * kpad; i += kBlock) lds_keys[i] = 0ull;
 
-    f32x4 qf[QT][J];
+    // 1,024-d, four queries per pass, not the prime pass: this ONE instantiation carries the lines of load_query_fragment,
+    // row_products and cosine_of as its own text.  Through the functions the compiler makes it 204 instructions shorter and
+    // 0.5 - 0.9 % slower over short row lists (profiles/scan_shared_body.log); with all three inline here it is the code it
+    // was before the functions existed.  The arithmetic is theirs, line for line.
+    constexpr bool kOwnText = J == 8 && QT == 4 && !PRIME;
+    f32x4 qf[QT][J];  // a pass past the last query re-reads query nq - 1 (its results are never stored)
     float qmag[QT];
 #pragma unroll
     for (int qi = 0; qi < QT; ++qi) {
         const uint32_t q = (q0 + qi < nq) ? (q0 + qi) : (nq - 1);
-        const f32x4* qp = reinterpret_cast<const f32x4*>(queries + (size_t)q * DIM) + l32;
-        float s = 0.0f;
+        if constexpr (kOwnText) {
+            const f32x4* qp = reinterpret_cast<const f32x4*>(queries + (size_t)q * DIM) + l32;
+            float s = 0.0f;
 #pragma unroll
-        for (int j = 0; j < J; ++j) {
-            qf[qi][j] = qp[j * 32];
-            s = fmaf(qf[qi][j].x, qf[qi][j].x, s);
-            s = fmaf(qf[qi][j].y, qf[qi][j].y, s);
-            s = fmaf(qf[qi][j].z, qf[qi][j].z, s);
-            s = fmaf(qf[qi][j].w, qf[qi][j].w, s);
+            for (int j = 0; j < J; ++j) {
+                qf[qi][j] = qp[j * 32];
+                s = fmaf(qf[qi][j].x, qf[qi][j].x, s);
+                s = fmaf(qf[qi][j].y, qf[qi][j].y, s);
+                s = fmaf(qf[qi][j].z, qf[qi][j].z, s);
+                s = fmaf(qf[qi][j].w, qf[qi][j].w, s);
+            }
+            qmag[qi] = sqrtf(half_allreduce_sum(s));
+        } else {
+            qmag[qi] = load_query_fragment<J>(queries, q, l32, qf[qi]);
         }
-        qmag[qi] = sqrtf(half_allreduce_sum(s));
     }
     float thr[QT], floor[QT];
     uint32_t wpos[QT];
@@ -204,31 +214,38 @@ scan_masked_topk_kernel(const float* __restrict__ corpus, const uint32_t* __rest
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            float ss = 0.0f;
             float dot[QT];
+            float xmag;
+            if constexpr (kOwnText) {
+                float ss = 0.0f;
 #pragma unroll
-            for (int qi = 0; qi < QT; ++qi) dot[qi] = 0.0f;
+                for (int qi = 0; qi < QT; ++qi) dot[qi] = 0.0f;
 #pragma unroll
-            for (int j = 0; j < J; ++j) {
-                const f32x4 v = x[u][j];
-                ss = fmaf(v.x, v.x, ss);
-                ss = fmaf(v.y, v.y, ss);
-                ss = fmaf(v.z, v.z, ss);
-                ss = fmaf(v.w, v.w, ss);
+                for (int j = 0; j < J; ++j) {
+                    const f32x4 v = x[u][j];
+                    ss = fmaf(v.x, v.x, ss);
+                    ss = fmaf(v.y, v.y, ss);
+                    ss = fmaf(v.z, v.z, ss);
+                    ss = fmaf(v.w, v.w, ss);
 #pragma unroll
-                for (int qi = 0; qi < QT; ++qi) {
-                    dot[qi] = fmaf(v.x, qf[qi][j].x, dot[qi]);
-                    dot[qi] = fmaf(v.y, qf[qi][j].y, dot[qi]);
-                    dot[qi] = fmaf(v.z, qf[qi][j].z, dot[qi]);
-                    dot[qi] = fmaf(v.w, qf[qi][j].w, dot[qi]);
+                    for (int qi = 0; qi < QT; ++qi) {
+                        dot[qi] = fmaf(v.x, qf[qi][j].x, dot[qi]);
+                        dot[qi] = fmaf(v.y, qf[qi][j].y, dot[qi]);
+                        dot[qi] = fmaf(v.z, qf[qi][j].z, dot[qi]);
+                        dot[qi] = fmaf(v.w, qf[qi][j].w, dot[qi]);
+                    }
                 }
+                xmag = sqrtf(half_allreduce_sum(ss));
+            } else {
+                xmag = row_products<J, QT>(x[u], qf, dot);
             }
-            const float xmag = sqrtf(half_allreduce_sum(ss));
             const bool valid = e0 + 2 * u + half < n_list;
 #pragma unroll
             for (int qi = 0; qi < QT; ++qi) {
                 const float d = half_allreduce_sum(dot[qi]);
-                const float c = (qmag[qi] == 0.0f || xmag == 0.0f) ? 0.0f : d / (qmag[qi] * xmag);
+                float c;
+                if constexpr (kOwnText) c = (qmag[qi] == 0.0f || xmag == 0.0f) ? 0.0f : d / (qmag[qi] * xmag);
+                else c = cosine_of(d, qmag[qi], xmag);
                 if constexpr (PRIME) {
                     if (valid && c > thr[qi]) thr[qi] = c;
                     continue;
@@ -248,65 +265,19 @@ scan_masked_topk_kernel(const float* __restrict__ corpus, const uint32_t* __rest
         }
     }
     if constexpr (PRIME) {
-        // wave maxima -> HBM; the last block of this pass selects the k-th largest per query (scan_topk_kernel)
-        const uint32_t nwaves = gridDim.x * kWaves;
-#pragma unroll
-        for (int qi = 0; qi < QT; ++qi) {
-            const float m = fmaxf(__shfl(thr[qi], 0, 64), __shfl(thr[qi], 32, 64));
-            if (lane == 0 && q0 + qi < nq)
-                __hip_atomic_store(wave_max + (size_t)(q0 + qi) * nwaves + gw, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __shared__ uint32_t is_last;
-        __threadfence();
-        __syncthreads();
-        if (tid == 0) {
-            const uint32_t prev = __hip_atomic_fetch_add(done_ctr + blockIdx.y, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-            is_last = (prev == gridDim.x - 1);
-        }
-        __syncthreads();
-        if (!is_last) return;
-        __threadfence();
-        uint32_t nsort = 64;
-        while (nsort < nwaves) nsort <<= 1;  // host keeps nsort <= kWaves * kpad (the LDS size)
-#pragma unroll 1
-        for (int qi = 0; qi < QT; ++qi) {
-            if (q0 + qi >= nq) break;
-            __syncthreads();
-            for (uint32_t i = tid; i < nsort; i += kBlock) {
-                float m = -__builtin_huge_valf();
-                if (i < nwaves)
-                    m = __hip_atomic_load(wave_max + (size_t)(q0 + qi) * nwaves + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                lds_keys[i] = (m == -__builtin_huge_valf()) ? 0ull : key_pack(m, 0u);
-            }
-            block_bitonic_desc<kBlock>(lds_keys, nsort, tid);
-            if (tid == 0) {
-                const uint64_t key = (k <= nsort) ? lds_keys[k - 1] : 0ull;
-                float t = -__builtin_huge_valf();
-                if (key) {
-                    const uint32_t o = (uint32_t)(key >> 32) - 1u;  // next float below the bound
-                    t = key_cos((uint64_t)o << 32);
-                    if (fabsf(t) < 1.17549435e-38f) t = -1.17549435e-38f;
-                }
-                floor_out[q0 + qi] = t;
-            }
-        }
-        if (tid == 0) __hip_atomic_store(done_ctr + blockIdx.y, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        prime_pass_tail<QT>(thr, q0, nq, k, gw, tid, lane, lds_keys, wave_max, done_ctr, floor_out);
         return;
     }
     __syncthreads();
-
     const uint32_t nsort = kWaves * kpad;
 #pragma unroll 1
     for (int qi = 0; qi < QT; ++qi) {
         if (q0 + qi >= nq) break;
-        uint64_t* a = lds_keys + (size_t)qi * nsort;
-        block_bitonic_desc<kBlock>(a, nsort, tid);
-        uint64_t* out = partial + ((size_t)(q0 + qi) * gridDim.x + blockIdx.x) * k;
-        for (uint32_t i = tid; i < k; i += kBlock) out[i] = a[i];
+        block_merge_store(lds_keys + (size_t)qi * nsort, kpad, k, q0 + qi, tid, partial);
     }
 }
 
-// Any other dim: one wave per list entry, lanes stride over columns (scan_topk_generic_kernel's arithmetic).
+// Any other dim: one wave per list entry, lanes stride over columns (wave_row_cosine, scan_wave.hpp).
 __global__ void __launch_bounds__(kBlock)
 scan_masked_generic_kernel(const float* __restrict__ corpus, const uint32_t* __restrict__ rows,
                            const uint32_t* __restrict__ rows_len, uint32_t dim, const float* __restrict__ queries,
@@ -317,9 +288,7 @@ scan_masked_generic_kernel(const float* __restrict__ corpus, const uint32_t* __r
     const uint64_t n_list = *rows_len;
     for (uint32_t i = tid; i < kWaves * kpad; i += kBlock) lds_keys[i] = 0ull;
     const float* qp = queries + (size_t)q * dim;
-    float s = 0.0f;
-    for (uint32_t c = lane; c < dim; c += 64) s = fmaf(qp[c], qp[c], s);
-    const float qmag = sqrtf(wave_allreduce_sum(s));
+    const float qmag = wave_query_mag(qp, dim, lane);
     float thr = -__builtin_huge_valf();
     uint32_t wpos = 0;
     __syncthreads();
@@ -329,22 +298,11 @@ scan_masked_generic_kernel(const float* __restrict__ corpus, const uint32_t* __r
     for (uint64_t e = gw; e < n_list; e += nw) {
         const uint32_t r = rows[e];
         const float* xp = corpus + (uint64_t)r * dim;
-        float ss = 0.0f, dot = 0.0f;
-        for (uint32_t c = lane; c < dim; c += 64) {
-            const float v = xp[c];
-            ss = fmaf(v, v, ss);
-            dot = fmaf(v, qp[c], dot);
-        }
-        const float xmag = sqrtf(wave_allreduce_sum(ss));
-        const float d = wave_allreduce_sum(dot);
-        const float c = (qmag == 0.0f || xmag == 0.0f) ? 0.0f : d / (qmag * xmag);
+        const float c = wave_row_cosine(xp, qp, dim, lane, qmag);
         if (c > thr) wave_list_insert(list, k, lane, c, row_ids.of(r), thr, wpos);  // wave-uniform
     }
     __syncthreads();
-    const uint32_t nsort = kWaves * kpad;
-    block_bitonic_desc<kBlock>(lds_keys, nsort, tid);
-    uint64_t* out = partial + ((size_t)q * gridDim.x + blockIdx.x) * k;
-    for (uint32_t i = tid; i < k; i += kBlock) out[i] = lds_keys[i];
+    block_merge_store(lds_keys, kpad, k, q, tid, partial);
 }
 
 template <int J, int U, int QT>

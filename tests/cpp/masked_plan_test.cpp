@@ -64,6 +64,18 @@ static void check_prime() {
     CHECK(masked_prime_rows(kn, 10000000, 1, 200, 100, 256, false) == 0);  // no prime kernel for this dim
     kn.prime_min_k = 0;
     CHECK(masked_prime_rows(kn, 10000000, 1, 200, 384, 256, true) == 0);
+    // the knobs of tests/test_gpu_scan.py::test_every_scan_kind_returns_the_streaming_scan_bits: its masked and scoped
+    // searches over 12,000 allowed rows (11,880 after its deletions) do take the prime pass, over 2,400 list entries
+    RouteKnobs forced;
+    forced.prime_min_k = 1;
+    forced.prime_min_rows = 1;
+    forced.prime_rows = 2400;
+    for (uint64_t bound : {12000ull, 11880ull})
+        for (uint32_t nq : {1u, 2u, 4u})
+            for (uint32_t k : {10u, 200u}) {
+                for (uint32_t dim : {384u, 768u, 1024u}) CHECK(masked_prime_rows(forced, bound, nq, k, dim, 256, true) == 2400);
+                CHECK(masked_prime_rows(forced, bound, nq, k, 100, 256, false) == 0);
+            }
 }
 
 static void check_shards() {

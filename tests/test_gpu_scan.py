@@ -779,6 +779,51 @@ def test_primed_scan_is_bit_identical(VS, oracle, dim, monkeypatch):
     assert_topk_equal(c0[0], i0[0], ecos, eids, rows, qs[0], oracle)
 
 
+@pytest.mark.parametrize("dim", [384, 768, 1024, 100])
+def test_every_scan_kind_returns_the_streaming_scan_bits(VS, dim, monkeypatch):
+    """The masked, scoped (gathered) and grouped searches score rows with the streaming scan's own functions
+    (scan_wave.hpp), so over the same rows they return its ids, counts and cosine bytes: every id allowed, a scope of
+    every id, a cap that never binds.  The prime pass is forced on, which is what takes the masked and scoped searches
+    through their prime pass at this size; 12,000 rows is no multiple of a tile, and the store holds exact duplicates
+    in and outside the sample, zero rows and (after the second build) tombstones; one query of the four is zero."""
+    n = 12000
+    rows = synth_rows(91, 0, n, dim)
+    rows[5] = rows[2]; rows[900] = rows[2]; rows[4000] = rows[2] * 3.0   # exact ties, in and out of the sample
+    rows[10:200] = 0.0                                                    # cosine exactly 0 inside the sample
+    rows[3000:3300] = 0.0
+    qs = np.stack([rows[2], synth_rows(92, 0, 1, dim)[0], np.zeros(dim, np.float32), synth_rows(92, 5, 1, dim)[0]])
+    monkeypatch.setenv("CS_INDEX_SPLIT", "0")                            # 2..4 queries stay on the exact scans
+    monkeypatch.setenv("CS_SCAN_PRIME_MIN_K", "1")
+    monkeypatch.setenv("CS_SCAN_PRIME_MIN_ROWS", "1")
+    monkeypatch.setenv("CS_SCAN_PRIME_ROWS", "2400")
+    st = VS(None, dim)
+    st.insert_embeddings(rows)
+    st.build_index()
+    st.set_single_query_route(st.ROUTE_STREAM)
+    every_id = np.arange(n)
+    st.set_groups(every_id, every_id % 7)
+    scope = st.scope(every_id)
+    scope.set_route("gather")
+    for dead in (False, True):
+        if dead:
+            gone = list(range(0, 100)) + [900, 4000, 5000] + list(range(11000, 11017))   # 1 % of the rows
+            assert st.delete_chunks(gone) == len(gone)
+            st.build_index()
+            assert st.stored_rows() == n                                  # tombstones, not a compacted store
+        for k in (10, 200):
+            one = [st.search_raw(q, k) for q in qs]                       # the streaming search, one query per call
+            for nq in (1, 2, 4):
+                want = tuple(np.concatenate([o[j] for o in one[:nq]]) for j in range(3))
+                kinds = {"masked": st.search_raw(qs[:nq], k, chunk_ids=every_id),
+                         "scoped": st.search_raw(qs[:nq], k, scope=scope),
+                         "grouped": st.search_raw(qs[:nq], k, per_file=k)}
+                for kind, (c, i, cnt) in kinds.items():
+                    assert cnt.tolist() == want[2].tolist(), (kind, k, nq, dead)
+                    assert i.tolist() == want[1].tolist(), (kind, k, nq, dead)
+                    assert c.tobytes() == want[0].tobytes(), (kind, k, nq, dead)
+    assert scope.route_info()[1] > 0                                      # the scope did take the gathered scan
+
+
 @pytest.mark.parametrize("dim", [384, 768, 100])
 def test_large_k_up_to_cs_max_k(VS, oracle, dim, monkeypatch):
     """retrieval_limit = max(5 * max_results, 200) (src/search/mod.rs:494-502) passes 200 at the
