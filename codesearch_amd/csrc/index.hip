@@ -194,14 +194,19 @@ struct cs_index {
     // Reclaiming deleted rows (store.rs:548-610: arroy drops deleted items at the next build; the incremental `index` deletes a
     // changed file's chunks and re-inserts them, src/index/mod.rs:525,544 — a store re-indexed daily would otherwise only grow):
     // when at least compact_dead_pct % of the stored rows are tombstones, cs_index_build rewrites corpus (norms and the filter
-    // copies are rebuilt from it) without them.  Ids stay what they were: h_ids / d_ids = the id of each stored row,
-    // ascending; empty = never compacted, id = id_base + row.  (CS_INDEX_COMPACT_DEAD_PCT, default 10; 0 = never.)
+    // copies are rebuilt from it) without them.  Ids stay what they were: once `compacted`, h_ids / d_ids = the id of each
+    // stored row, ascending; until then id = id_base + row and both are empty.  (CS_INDEX_COMPACT_DEAD_PCT, default 10;
+    // 0 = never.)  The flag, not h_ids.empty(), says which numbering holds: a reclaim of an index whose rows are all
+    // deleted leaves no row and so an empty table, yet the ids it has issued are spent (never reused, store.rs:101) and the
+    // rows appended next continue from n_ids, not from row 0.  Only cs_index_clear returns to the identity numbering.
+    bool compacted = false;
     std::vector<uint32_t> h_ids;
     uint32_t* d_ids = nullptr;
     uint64_t ids_cap = 0, ids_uploaded = 0;
     uint32_t compact_dead_pct = 10;
     uint64_t compactions = 0;
-    RowIds row_ids() const { return RowIds(id_base, h_ids.empty() ? nullptr : d_ids); }
+    // (d_ids of a compacted index is null only while it stores no row: cs_index_build uploads the table before any search)
+    RowIds row_ids() const { return RowIds(id_base, compacted ? d_ids : nullptr); }
     // Groups of the grouped search (scan_grouped.hip): h_groups[id - id_base] for the ids assigned so far (shorter than
     // n_ids when ids were appended since: those are CS_NO_GROUP), empty = none assigned.  The device copy is brought up to
     // date under groups_mu by the first grouped search that finds it dirty (ensure_groups); searches read it only.
@@ -466,7 +471,7 @@ int32_t compact(cs_index* h) {
     nid.reserve((size_t)live);
     std::vector<uint32_t> idx;
     idx.reserve((size_t)chunk);
-    const bool ident = h->h_ids.empty();
+    const bool ident = !h->compacted;
     uint64_t dst = 0;
     for (uint64_t c0 = 0; c0 < h->n_rows; c0 += chunk) {
         const uint64_t c1 = std::min(h->n_rows, c0 + chunk);
@@ -495,7 +500,8 @@ int32_t compact(cs_index* h) {
     h->n_removed = 0;
     h->h_dead.assign((size_t)((live + 31) / 32), 0u);
     if (h->d_dead && h->capacity) CS_HIP(hipMemset(h->d_dead, 0, (size_t)((h->capacity + 31) / 32) * sizeof(uint32_t)));
-    h->h_ids.swap(nid);
+    h->h_ids.swap(nid);  // (empty when every row was deleted: `compacted` keeps the ids spent)
+    h->compacted = true;
     h->ids_uploaded = 0;
     // everything derived from the rows is rebuilt over the new storage order by the build that follows
     h->normed_rows = 0;
@@ -519,7 +525,7 @@ void finish_append(cs_index* h, uint64_t n, uint32_t* out_ids) {
     const uint32_t start = h->id_base + (uint32_t)h->n_ids;   // ids are never reused (store.rs:101)
     if (out_ids)
         for (uint64_t i = 0; i < n; ++i) out_ids[i] = start + (uint32_t)i;  // store.rs:684
-    if (!h->h_ids.empty())  // a compacted index: the new rows' ids join the row -> id table (uploaded by the next build)
+    if (h->compacted)  // a compacted index: the new rows' ids join the row -> id table (uploaded by the next build)
         for (uint64_t i = 0; i < n; ++i) h->h_ids.push_back(start + (uint32_t)i);
     h->n_ids += n;
     h->n_rows += n;
@@ -1214,7 +1220,7 @@ int32_t cs_index_remove(cs_index* h, const uint32_t* ids, uint64_t n, uint64_t* 
     for (uint64_t i = 0; i < n; ++i) {
         if (ids[i] < h->id_base) continue;
         uint64_t row = (uint64_t)ids[i] - h->id_base;
-        if (!h->h_ids.empty()) {  // compacted: the id's row by bisection of the ascending row -> id table
+        if (h->compacted) {  // compacted: the id's row by bisection of the ascending row -> id table
             const auto it = std::lower_bound(h->h_ids.begin(), h->h_ids.end(), ids[i]);
             if (it == h->h_ids.end() || *it != ids[i]) continue;  // never issued, or deleted and reclaimed: not counted
             row = (uint64_t)(it - h->h_ids.begin());
@@ -1242,7 +1248,7 @@ int32_t cs_index_build(cs_index* h) {
     DeviceGuard g(h->device);
     CS_TRY(drain_appends(h));  // appended rows (incl. async device appends) are now visible
     if (h->compact_dead_pct && h->n_removed && h->n_removed * 100 >= (uint64_t)h->compact_dead_pct * h->n_rows) CS_TRY(compact(h));
-    if (!h->h_ids.empty() && h->ids_uploaded < h->n_rows) {  // the row -> id table of a compacted index, for the rows that are new
+    if (h->compacted && h->ids_uploaded < h->n_rows) {  // the row -> id table of a compacted index, for the rows that are new
         if (h->ids_cap < h->n_rows) {
             uint32_t* nt = nullptr;
             const uint64_t cap = std::max<uint64_t>(h->capacity, h->n_rows);
@@ -1316,6 +1322,7 @@ int32_t cs_index_clear(cs_index* h) {
     h->n_rows = 0;  // store.rs:701 next_id = 0
     h->n_ids = 0;
     h->h_ids.clear();
+    h->compacted = false;  // ids restart at id_base: the identity numbering again
     h->ids_uploaded = 0;
     h->normed_rows = 0;
     h->split_rows = 0;
@@ -1741,7 +1748,7 @@ int32_t cs_index_read_rows(cs_index* h, uint64_t first_row, uint64_t n, float* o
     if (n == 0) return CS_OK;
     DeviceGuard g(h->device);
     CS_TRY(drain_appends(h));
-    if (!h->h_ids.empty()) {  // compacted: rows are named by their ids (first_row = id - id_base); runs of neighbours in one copy
+    if (h->compacted) {  // compacted: rows are named by their ids (first_row = id - id_base); runs of neighbours in one copy
         uint64_t i = 0;
         while (i < n) {
             const uint32_t id = h->id_base + (uint32_t)(first_row + i);
