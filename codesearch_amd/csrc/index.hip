@@ -14,6 +14,7 @@
 #include <cstdlib>
 
 #include "grouped_plan.hpp"
+#include "index_ledger.hpp"
 #include "masked_plan.hpp"
 #include "scan.hpp"
 #include "scope.hpp"
@@ -186,35 +187,21 @@ struct cs_index {
     int device = 0;
     int num_cus = 256;
     uint32_t dim = 0;
-    uint32_t id_base = 0;
     uint64_t capacity = 0;   // rows allocated
-    uint64_t n_rows = 0;     // rows in storage
-    uint64_t n_ids = 0;      // ids issued (next_id - id_base): n_rows until cs_index_build first reclaims deleted rows
-    uint64_t n_removed = 0;  // tombstoned rows still in storage
-    // Reclaiming deleted rows (store.rs:548-610: arroy drops deleted items at the next build; the incremental `index` deletes a
-    // changed file's chunks and re-inserts them, src/index/mod.rs:525,544 — a store re-indexed daily would otherwise only grow):
-    // when at least compact_dead_pct % of the stored rows are tombstones, cs_index_build rewrites corpus (norms and the filter
-    // copies are rebuilt from it) without them.  Ids stay what they were: once `compacted`, h_ids / d_ids = the id of each
-    // stored row, ascending; until then id = id_base + row and both are empty.  (CS_INDEX_COMPACT_DEAD_PCT, default 10;
-    // 0 = never.)  The flag, not h_ids.empty(), says which numbering holds: a reclaim of an index whose rows are all
-    // deleted leaves no row and so an empty table, yet the ids it has issued are spent (never reused, store.rs:101) and the
-    // rows appended next continue from n_ids, not from row 0.  Only cs_index_clear returns to the identity numbering.
-    bool compacted = false;
-    std::vector<uint32_t> h_ids;
+    // ids, stored rows and tombstones (index_ledger.hpp): the host's side of everything below that is numbered by them
+    IndexLedger ledger;
+    // the device copy of the ledger's row -> id table, once it is compacted: cs_index_build uploads the rows that are new
     uint32_t* d_ids = nullptr;
     uint64_t ids_cap = 0, ids_uploaded = 0;
-    uint32_t compact_dead_pct = 10;
+    uint32_t compact_dead_pct = 10;  // cs_index_build reclaims from this share of tombstones on (CS_INDEX_COMPACT_DEAD_PCT; 0 = never)
     uint64_t compactions = 0;
     // (d_ids of a compacted index is null only while it stores no row: cs_index_build uploads the table before any search)
-    RowIds row_ids() const { return RowIds(id_base, compacted ? d_ids : nullptr); }
-    // Groups of the grouped search (scan_grouped.hip): h_groups[id - id_base] for the ids assigned so far (shorter than
-    // n_ids when ids were appended since: those are CS_NO_GROUP), empty = none assigned.  The device copy is brought up to
-    // date under groups_mu by the first grouped search that finds it dirty (ensure_groups); searches read it only.
-    std::vector<uint32_t> h_groups;
+    RowIds row_ids() const { return RowIds(ledger.id_base(), ledger.compacted() ? d_ids : nullptr); }
+    // Groups of the grouped search (scan_grouped.hip).  The device copy is brought up to date under groups_mu by the
+    // first grouped search that finds it dirty (ensure_groups); searches read it only.
+    GroupTable groups;
     uint32_t* d_groups = nullptr;
-    uint64_t groups_cap = 0, groups_len = 0;  // elements allocated / valid on the device
-    uint64_t groups_assigned = 0;             // entries != CS_NO_GROUP
-    uint64_t groups_dirty_lo = 0, groups_dirty_hi = 0;  // host entries [lo, hi) the device copy has not seen
+    uint64_t groups_cap = 0;  // elements allocated on the device
     std::mutex groups_mu;
     float* d_corpus = nullptr;
     uint32_t* d_dead = nullptr;  // bitmap over rows, sized for `capacity`
@@ -250,7 +237,6 @@ struct cs_index {
     float filter_margin = 0.0f;  // scan_filter.hip: bound of the f16 filter's error for this dim
     RouteKnobs route;  // search_route.hpp: the thresholds of plan_route (route_knobs_from_env)
     uint64_t batched_searches = 0, batched_fallbacks = 0, q8_reruns = 0;
-    std::vector<uint32_t> h_dead;
     bool built = false;
     // Build generation: cs_index_build and cs_index_clear advance it.  Every other mutation un-builds the index and a
     // search needs a build, so whatever a scope derived from the stored rows (its row list, scope.hpp) is current
@@ -331,7 +317,7 @@ static bool grow_fault(int stage, const cs_index* h) {
 int32_t grow(cs_index* h, uint64_t need_rows) {
     if (need_rows <= h->capacity) return CS_OK;
     // drain the device before the old buffers are copied and freed, or rows of an unfinished append would be lost
-    if (h->n_rows) CS_TRY(drain_appends(h));
+    if (h->ledger.stored()) CS_TRY(drain_appends(h));
     uint64_t cap = h->capacity ? h->capacity * 2 : 1024;
     if (cap < need_rows) cap = need_rows;
     GrowBuffers nb;
@@ -374,9 +360,10 @@ int32_t grow(cs_index* h, uint64_t need_rows) {
     CS_GROW_COPY(3, hipMemset(nb.nd, 0, words * sizeof(uint32_t)));
     if (h->normed_rows)
         CS_GROW_COPY(4, hipMemcpy(nb.nn, h->d_norms, (size_t)h->normed_rows * sizeof(float), hipMemcpyDeviceToDevice));
-    if (h->n_rows) {
-        CS_GROW_COPY(5, hipMemcpy(nb.nc, h->d_corpus, (size_t)h->n_rows * h->dim * sizeof(float), hipMemcpyDeviceToDevice));
-        CS_GROW_COPY(6, hipMemcpy(nb.nd, h->h_dead.data(), h->h_dead.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (h->ledger.stored()) {
+        const std::vector<uint32_t>& dead = h->ledger.dead_words();
+        CS_GROW_COPY(5, hipMemcpy(nb.nc, h->d_corpus, (size_t)h->ledger.stored() * h->dim * sizeof(float), hipMemcpyDeviceToDevice));
+        CS_GROW_COPY(6, hipMemcpy(nb.nd, dead.data(), dead.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     // ---- commit: nothing below can fail ----
     if (h->d_split) {
@@ -418,8 +405,8 @@ bool q8_serves(const cs_index* h) {
 bool ensure_f16(cs_index* h) {
     if (!h->use_split) return false;
     std::lock_guard<std::mutex> lk(h->filter_mu);
-    if (h->d_split && h->split_rows >= h->n_rows) return true;
-    if (h->f16_failed || h->normed_rows < h->n_rows) return false;
+    if (h->d_split && h->split_rows >= h->ledger.stored()) return true;
+    if (h->f16_failed || h->normed_rows < h->ledger.stored()) return false;
     const size_t cap256 = ((size_t)h->capacity + 255) / 256 * 256;
     if (!h->d_split || h->split_cap < cap256) {
         if (h->d_split) (void)hipFree(h->d_split);
@@ -432,13 +419,13 @@ bool ensure_f16(cs_index* h) {
         }
         h->split_cap = cap256;
     }
-    if (launch_corpus_split(h->d_corpus, h->d_norms, h->d_split, h->split_rows, h->n_rows - h->split_rows, h->dim, nullptr) != CS_OK ||
+    if (launch_corpus_split(h->d_corpus, h->d_norms, h->d_split, h->split_rows, h->ledger.stored() - h->split_rows, h->dim, nullptr) != CS_OK ||
         hipStreamSynchronize(nullptr) != hipSuccess) {
         (void)hipGetLastError();
         h->f16_failed = true;
         return false;
     }
-    h->split_rows = h->n_rows;
+    h->split_rows = h->ledger.stored();
     return true;
 }
 
@@ -458,29 +445,22 @@ gather_rows_kernel(const float* __restrict__ src, const uint32_t* __restrict__ i
 // derived from the rows (norms, mean unit row, int8 / f16 filter copies) is rebuilt by the build that called this.  A search
 // afterwards streams only live rows, and returns what it returned before: the same ids, the same cosines, bit for bit.
 int32_t compact(cs_index* h) {
-    const uint64_t live = h->n_rows - h->n_removed;
+    const uint64_t live = h->ledger.live(), stored = h->ledger.stored();
     constexpr uint64_t CH = 1u << 18;  // rows per chunk (staging: 403 MB at dim 384)
-    const uint64_t chunk = std::min<uint64_t>(CH, h->n_rows);
+    const uint64_t chunk = std::min<uint64_t>(CH, stored);
     struct Tmp {
         float* rows = nullptr; uint32_t* idx = nullptr;
         ~Tmp() { if (rows) (void)hipFree(rows); if (idx) (void)hipFree(idx); }
     } t;
     CS_HIP(hipMalloc(&t.rows, (size_t)chunk * h->dim * sizeof(float)));
     CS_HIP(hipMalloc(&t.idx, (size_t)chunk * sizeof(uint32_t)));
-    std::vector<uint32_t> nid;
-    nid.reserve((size_t)live);
     std::vector<uint32_t> idx;
     idx.reserve((size_t)chunk);
-    const bool ident = !h->compacted;
     uint64_t dst = 0;
-    for (uint64_t c0 = 0; c0 < h->n_rows; c0 += chunk) {
-        const uint64_t c1 = std::min(h->n_rows, c0 + chunk);
+    for (uint64_t c0 = 0; c0 < stored; c0 += chunk) {
+        const uint64_t c1 = std::min(stored, c0 + chunk);
         idx.clear();
-        for (uint64_t r = c0; r < c1; ++r)
-            if (!((h->h_dead[(size_t)(r >> 5)] >> (r & 31)) & 1u)) {
-                idx.push_back((uint32_t)(r - c0));
-                nid.push_back(ident ? h->id_base + (uint32_t)r : h->h_ids[(size_t)r]);
-            }
+        h->ledger.survivors(c0, c1, idx);
         const uint64_t cnt = idx.size();
         if (cnt == 0) continue;
         if (dst == c0 && cnt == c1 - c0) { dst += cnt; continue; }  // nothing deleted up to here: the rows are in place
@@ -496,12 +476,8 @@ int32_t compact(cs_index* h) {
         dst += cnt;
     }
     if (dst != live) return fail(CS_ERR_HIP, "compaction moved %llu rows, expected %llu", (unsigned long long)dst, (unsigned long long)live);
-    h->n_rows = live;
-    h->n_removed = 0;
-    h->h_dead.assign((size_t)((live + 31) / 32), 0u);
+    h->ledger.commit_reclaim();
     if (h->d_dead && h->capacity) CS_HIP(hipMemset(h->d_dead, 0, (size_t)((h->capacity + 31) / 32) * sizeof(uint32_t)));
-    h->h_ids.swap(nid);  // (empty when every row was deleted: `compacted` keeps the ids spent)
-    h->compacted = true;
     h->ids_uploaded = 0;
     // everything derived from the rows is rebuilt over the new storage order by the build that follows
     h->normed_rows = 0;
@@ -516,20 +492,15 @@ int32_t check_append(cs_index* h, uint64_t n, uint32_t dim) {
     if (dim != h->dim)  // store.rs:667-671
         return fail(CS_ERR_DIM_MISMATCH, "Embedding dimension mismatch: expected %u, got %u",
                     h->dim, dim);
-    if ((uint64_t)h->id_base + h->n_ids + n > 0xffffffffull)
+    if (!h->ledger.can_append(n))
         return fail(CS_ERR_BAD_ARG, "id space exhausted: ids are u32 (store.rs:97)");
     return CS_OK;
 }
 
 void finish_append(cs_index* h, uint64_t n, uint32_t* out_ids) {
-    const uint32_t start = h->id_base + (uint32_t)h->n_ids;   // ids are never reused (store.rs:101)
+    const uint32_t start = h->ledger.append(n);
     if (out_ids)
         for (uint64_t i = 0; i < n; ++i) out_ids[i] = start + (uint32_t)i;  // store.rs:684
-    if (h->compacted)  // a compacted index: the new rows' ids join the row -> id table (uploaded by the next build)
-        for (uint64_t i = 0; i < n; ++i) h->h_ids.push_back(start + (uint32_t)i);
-    h->n_ids += n;
-    h->n_rows += n;
-    h->h_dead.resize((size_t)((h->n_rows + 31) / 32), 0u);
     if (n) h->built = false;  // store.rs:682
 }
 
@@ -607,14 +578,14 @@ void fold_overflows(cs_index* h, Workspace* w) {
 
 // the exact list-based scan and its merge (gate: launch_scan)
 int32_t list_scan(cs_index* h, Workspace* w, const SearchArgs& a, const uint32_t* gate) {
-    CS_TRY(launch_scan(a.plan, h->d_corpus, h->n_rows, h->dim, a.d_queries, a.nq, a.k, a.d_dead, h->row_ids(), w->d_partial,
+    CS_TRY(launch_scan(a.plan, h->d_corpus, h->ledger.stored(), h->dim, a.d_queries, a.nq, a.k, a.d_dead, h->row_ids(), w->d_partial,
                        a.stream, nullptr, false, gate));
     return launch_merge(w->d_partial, a.plan.blocks, a.nq, a.k, false, w->d_tmp_a, w->d_tmp_b, a.d_keys, a.d_cos, a.d_ids,
                         a.d_counts, a.stream, gate);
 }
 
 int32_t split_filter(cs_index* h, Workspace* w, const SearchArgs& a, const Q8View* q8) {
-    return launch_scan_split(w->bs, w->qw, h->d_corpus, h->d_split, h->n_rows, h->dim, a.d_queries, a.nq, a.k, a.d_dead,
+    return launch_scan_split(w->bs, w->qw, h->d_corpus, h->d_split, h->ledger.stored(), h->dim, a.d_queries, a.nq, a.k, a.d_dead,
                              h->row_ids(), a.d_keys, a.d_cos, a.d_ids, a.d_counts, a.stream, h->filter_margin, q8);
 }
 
@@ -622,7 +593,7 @@ int32_t split_filter(cs_index* h, Workspace* w, const SearchArgs& a, const Q8Vie
 // most one per row, so it can only overflow over more rows than that (adversarial row order; thousands of near-duplicate
 // rows).  Then the exact answer comes from a rerun.
 int32_t settle_overflow(cs_index* h, Workspace* w, const SearchArgs& a, bool via_q8, bool may_sync, const EventTriple* ev) {
-    const bool can_overflow = h->n_rows > batched_cap(a.k);
+    const bool can_overflow = h->ledger.stored() > batched_cap(a.k);
     bool overflow = false, reran = false;
     if (!may_sync) {
         // Device API: never wait for the device.  Up to kGatedMaxQ queries, the exact list-based scan and
@@ -665,7 +636,7 @@ int32_t run_search(cs_index* h, Workspace* w, const ScanPlan& plan, const float*
     EventTriple ev{};
     const bool timed = take_events(h, w, &ev);
     if (timed) CS_HIP(hipEventRecord(ev.e0, stream));
-    const SearchShape shape{nq, k, h->dim, h->n_rows, h->num_cus, h->n_rows > 0 && h->normed_rows >= h->n_rows, h->use_split,
+    const SearchShape shape{nq, k, h->dim, h->ledger.stored(), h->num_cus, h->ledger.stored() > 0 && h->normed_rows >= h->ledger.stored(), h->use_split,
                             batched_supported(h->dim), scan_prime_supported(h->dim), h_queries_pinned != nullptr,
                             (uint64_t)plan.blocks * plan.passes};
     // Which copy filters: the int8 one when it serves; else the f16 one, built here, once, if it is not there yet; with
@@ -685,7 +656,7 @@ int32_t run_search(cs_index* h, Workspace* w, const ScanPlan& plan, const float*
     if (route.queries == QuerySource::Copy)
         CS_HIP(hipMemcpyAsync(const_cast<float*>(d_queries), h_queries_pinned, (size_t)nq * h->dim * sizeof(float),
                               hipMemcpyHostToDevice, stream));
-    const SearchArgs a{plan, d_queries, nq, k, d_keys, d_cos, d_ids, d_counts, stream, h->n_removed ? h->d_dead : nullptr};
+    const SearchArgs a{plan, d_queries, nq, k, d_keys, d_cos, d_ids, d_counts, stream, h->ledger.removed() ? h->d_dead : nullptr};
     if (route.path == SearchPath::Stream) {
         const ScanPrime* prime = nullptr;
         if (route.prime_rows) {
@@ -695,7 +666,7 @@ int32_t run_search(cs_index* h, Workspace* w, const ScanPlan& plan, const float*
                                stream, &w->prime, true));
             prime = &w->prime;
         }
-        CS_TRY(launch_scan(plan, h->d_corpus, h->n_rows, h->dim, d_queries, nq, k, a.d_dead, h->row_ids(), w->d_partial,
+        CS_TRY(launch_scan(plan, h->d_corpus, h->ledger.stored(), h->dim, d_queries, nq, k, a.d_dead, h->row_ids(), w->d_partial,
                            stream, prime));
         if (timed) CS_HIP(hipEventRecord(ev.e1, stream));
         CS_TRY(launch_merge(w->d_partial, plan.blocks, nq, k, false, w->d_tmp_a, w->d_tmp_b, d_keys, d_cos, d_ids, d_counts,
@@ -712,7 +683,7 @@ int32_t run_search(cs_index* h, Workspace* w, const ScanPlan& plan, const float*
         }
         CS_TRY(split_filter(h, w, a, &q8));
     } else {
-        CS_TRY(launch_scan_batched(w->bs, h->d_corpus, h->d_norms, h->n_rows, h->dim, d_queries, nq, k, a.d_dead, h->row_ids(),
+        CS_TRY(launch_scan_batched(w->bs, h->d_corpus, h->d_norms, h->ledger.stored(), h->dim, d_queries, nq, k, a.d_dead, h->row_ids(),
                                    h->num_cus, d_keys, d_cos, d_ids, d_counts, stream));
     }
     if (timed) CS_HIP(hipEventRecord(ev.e1, stream));
@@ -727,7 +698,7 @@ int32_t upload_queries(const cs_index* h, Workspace* w, uint32_t nq) {
 
 // Upper bound of the live rows a mask allows (masked_plan.hpp allowed_bound): 0 = the search launches nothing.
 uint64_t masked_bound(const cs_index* h, const uint32_t* allow, uint64_t allow_bits) {
-    return allowed_bound(allow, allow_bits, h->id_base, (uint64_t)h->id_base + h->n_ids, h->n_rows - h->n_removed);
+    return allowed_bound(allow, allow_bits, h->ledger.id_base(), h->ledger.next_id(), h->ledger.live());
 }
 
 // Everything of a masked or scoped search behind its row list, on `stream`: the optional prime pass and the gathered scan
@@ -756,12 +727,12 @@ int32_t run_row_list(cs_index* h, Workspace* w, const ScanPlan& plan, uint64_t r
 // valid until the stream has passed the search.
 int32_t run_masked(cs_index* h, Workspace* w, const ScanPlan& plan, uint64_t bound, const float* d_queries, uint32_t nq,
                    uint32_t k, const uint32_t* allow, uint64_t allow_bits, uint64_t* d_keys, hipStream_t stream) {
-    const MaskWindow win = mask_window(allow_bits, h->id_base, (uint64_t)h->id_base + h->n_ids);
-    const uint32_t nb = mask_list_blocks(h->n_rows);
+    const MaskWindow win = mask_window(allow_bits, h->ledger.id_base(), h->ledger.next_id());
+    const uint32_t nb = mask_list_blocks(h->ledger.stored());
     CS_TRY(w->reserve_masked(win.words, bound, nb));
-    CS_HIP(hipMemcpyAsync(w->d_allow, allow + (win.lo >> 5), (size_t)win.words * sizeof(uint32_t), hipMemcpyHostToDevice,
+    CS_HIP(hipMemcpyAsync(w->d_allow, allow + win.first_word, (size_t)win.words * sizeof(uint32_t), hipMemcpyHostToDevice,
                           stream));
-    CS_TRY(launch_mask_rows(w->d_allow, win.lo, win.hi, h->n_removed ? h->d_dead : nullptr, h->row_ids(), h->n_rows,
+    CS_TRY(launch_mask_rows(w->d_allow, win.lo, win.hi, h->ledger.removed() ? h->d_dead : nullptr, h->row_ids(), h->ledger.stored(),
                             w->d_mblocks, w->d_list, bound, stream));
     return run_row_list(h, w, plan, bound, w->d_list, w->d_mblocks + nb, d_queries, nq, k, d_keys, nullptr, nullptr, nullptr,
                         stream);
@@ -791,15 +762,15 @@ int32_t scope_make_list(cs_index* h, cs_scope* sc) {
         // a remaking rewrites d_list and d_blocks: a device-form search of the earlier generation that is still only
         // enqueued on its caller's stream reads them, so the device's work is waited for first (once per build and scope)
         if (sc->generation) CS_HIP(hipDeviceSynchronize());
-        CS_TRY(launch_scope_rows(sc->d_ids, sc->n_ids, h->n_removed ? h->d_dead : nullptr, h->row_ids(), h->n_rows,
+        CS_TRY(launch_scope_rows(sc->d_ids, sc->n_ids, h->ledger.removed() ? h->d_dead : nullptr, h->row_ids(), h->ledger.stored(),
                                  sc->d_blocks, sc->d_list, sc->n_ids, sc->stream));
         // a scope that can ever take the filter (it has a table): the blocked-rows bitmap over the store's rows as they
         // are now, and the host's view of the list, in the same read-back.  Without room for the bitmap the scope
         // simply keeps to the gathered scan.
         sc->filter_state = false;
-        bool state = sc->d_table && h->n_rows > 0;
+        bool state = sc->d_table && h->ledger.stored() > 0;
         if (state) {
-            const size_t words = (size_t)scope_blocked_words(h->n_rows);
+            const size_t words = (size_t)scope_blocked_words(h->ledger.stored());
             if (words > sc->blocked_words) {
                 sc->blocked_words = 0;
                 if (realloc_buf(sc->d_blocked, words) == hipSuccess) sc->blocked_words = words;
@@ -807,7 +778,7 @@ int32_t scope_make_list(cs_index* h, cs_scope* sc) {
             }
         }
         if (state) {
-            CS_TRY(launch_scope_filter_state(sc->d_list, sc->d_blocks + nb, sc->n_ids, h->n_rows, sc->d_blocked, sc->d_table,
+            CS_TRY(launch_scope_filter_state(sc->d_list, sc->d_blocks + nb, sc->n_ids, h->ledger.stored(), sc->d_blocked, sc->d_table,
                                              sc->stream));
             CS_HIP(hipMemcpyAsync(sc->h_len + 1, sc->d_table, sc->table_words * sizeof(uint32_t), hipMemcpyDeviceToHost,
                                   sc->stream));
@@ -845,12 +816,12 @@ int32_t scope_ready(cs_index* h, cs_scope* sc, uint64_t* live, ScopedFilterPlan*
     in.mode = sc->route.load();
     in.q8_serves = q8_serves(h);
     if (in.mode == CS_SCOPE_ROUTE_GATHER || !in.q8_serves || !sc->filter_state) return CS_OK;
-    const ScopedFilterPlan plan = plan_scoped_filter(h->dim, h->n_rows, sc->list_view(), nq, k, h->q8_rows, true, cu_count(),
+    const ScopedFilterPlan plan = plan_scoped_filter(h->dim, h->ledger.stored(), sc->list_view(), nq, k, h->q8_rows, true, cu_count(),
                                                      filter_knobs());
     in.plan_ok = plan.ok;
     in.live = sc->live_rows;
     in.span = plan.span;
-    const SearchShape shape{nq, k, h->dim, sc->live_rows, h->num_cus, h->normed_rows >= h->n_rows, h->use_split,
+    const SearchShape shape{nq, k, h->dim, sc->live_rows, h->num_cus, h->normed_rows >= h->ledger.stored(), h->use_split,
                             batched_supported(h->dim), scan_prime_supported(h->dim), true, 0};
     if (scoped_wants_filter(h->route, shape, in)) *fp = plan;
     return CS_OK;
@@ -877,7 +848,7 @@ int32_t run_scoped(cs_index* h, cs_scope* sc, Workspace* w, const ScanPlan& plan
     w->last_via_q8 = false;         // (this search is no reading of the int8 copy in the strike bookkeeping)
     Q8View q8;
     q8.d_q8 = h->d_q8; q8.d_tmeta = h->d_tmeta; q8.d_mu = h->d_mu; q8.rows = h->q8_rows;
-    CS_TRY(launch_scan_split(w->bs, w->qw, h->d_corpus, nullptr, h->n_rows, h->dim, w->d_queries, nq, k, sc->d_blocked,
+    CS_TRY(launch_scan_split(w->bs, w->qw, h->d_corpus, nullptr, h->ledger.stored(), h->dim, w->d_queries, nq, k, sc->d_blocked,
                              h->row_ids(), d_keys, nullptr, nullptr, nullptr, w->stream, h->filter_margin, &q8, &fp.plan,
                              sc->d_list));
     if (live <= batched_cap(k)) return CS_OK;  // a phase appends at most one candidate per allowed row
@@ -898,25 +869,21 @@ int32_t run_scoped(cs_index* h, cs_scope* sc, Workspace* w, const ScanPlan& plan
 // grouped search either waits here or finds it clean.  No group assigned: a null table, every id CS_NO_GROUP.
 int32_t ensure_groups(cs_index* h, uint32_t per_group, GroupView* gv) {
     std::lock_guard<std::mutex> lk(h->groups_mu);
-    *gv = GroupView{nullptr, 0, h->id_base, per_group};
-    if (h->groups_assigned == 0) return CS_OK;
-    const uint64_t n = h->h_groups.size();
+    *gv = GroupView{nullptr, 0, h->ledger.id_base(), per_group};
+    if (h->groups.assigned() == 0) return CS_OK;
+    const uint64_t n = h->groups.size();
     if (n > h->groups_cap) {
         CS_HIP(hipDeviceSynchronize());  // a search that was only enqueued may still read the old table
         const uint64_t cap = std::max<uint64_t>(n, std::min<uint64_t>(2 * h->groups_cap, 0xffffffffull));
         h->groups_cap = 0;
-        h->groups_len = 0;
+        h->groups.uploaded(0);  // the new table holds nothing yet
         CS_HIP(realloc_buf(h->d_groups, (size_t)cap));
         h->groups_cap = cap;
-        h->groups_dirty_lo = 0;
-        h->groups_dirty_hi = n;
     }
-    if (h->groups_dirty_hi > h->groups_dirty_lo) {
-        CS_HIP(hipMemcpy(h->d_groups + h->groups_dirty_lo, h->h_groups.data() + h->groups_dirty_lo,
-                         (size_t)(h->groups_dirty_hi - h->groups_dirty_lo) * sizeof(uint32_t), hipMemcpyHostToDevice));
-        h->groups_dirty_lo = h->groups_dirty_hi = 0;
-    }
-    h->groups_len = n;
+    uint64_t lo = 0, hi = 0;
+    if (h->groups.pending(&lo, &hi))
+        CS_HIP(hipMemcpy(h->d_groups + lo, h->groups.data() + lo, (size_t)(hi - lo) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    h->groups.uploaded(n);
     gv->groups = h->d_groups;
     gv->len = (uint32_t)n;
     return CS_OK;
@@ -926,7 +893,7 @@ int32_t ensure_groups(cs_index* h, uint32_t per_group, GroupView* gv) {
 // best k keys per query in d_keys [nq][k].
 int32_t run_grouped(cs_index* h, Workspace* w, const GroupedPlan& plan, const GroupView& gv, const float* d_queries,
                     uint32_t nq, uint32_t k, uint64_t* d_keys, hipStream_t stream) {
-    CS_TRY(launch_scan_grouped(plan, h->d_corpus, h->n_rows, h->dim, d_queries, nq, k, h->n_removed ? h->d_dead : nullptr,
+    CS_TRY(launch_scan_grouped(plan, h->d_corpus, h->ledger.stored(), h->dim, d_queries, nq, k, h->ledger.removed() ? h->d_dead : nullptr,
                                h->row_ids(), gv, w->d_partial, stream));
     return launch_merge_grouped(plan, w->d_partial, nq, k, gv, w->d_tmp_a, w->d_tmp_b, d_keys, nullptr, nullptr, nullptr,
                                 stream);
@@ -1029,7 +996,7 @@ int32_t host_search(cs_index* h, const float* queries, uint32_t nq, uint32_t k, 
 int32_t search_all(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k, const HostAnswer& out) {
     CS_TRY(check_host_search(h, queries, nq, dim, k, out));
     DeviceGuard g(h->device);
-    const ScanPlan plan = plan_scan(h->n_rows, h->dim, nq, k, h->num_cus);
+    const ScanPlan plan = plan_scan(h->ledger.stored(), h->dim, nq, k, h->num_cus);
     return host_search(h, queries, nq, k, plan.partial_keys, plan.merge_keys, out, [&](Workspace* w, uint64_t* keys) {
         return run_search(h, w, plan, w->d_queries, nq, k, keys, nullptr, nullptr, nullptr, w->stream, w->h_queries,
                           /*may_sync=*/!out.variants);
@@ -1095,7 +1062,7 @@ int32_t cs_index_create(uint32_t dim, uint64_t capacity_rows, int32_t device, ui
     h->device = device;
     h->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     h->dim = dim;
-    h->id_base = id_base;
+    h->ledger = IndexLedger(id_base);
     {
         const char* env = std::getenv("CS_INDEX_SPLIT");  // "0": keep the batched path on the exact-f32 MFMA
         h->use_split = split_scan_supported(dim) && !(env && env[0] == '0');
@@ -1155,8 +1122,8 @@ int32_t cs_index_add(cs_index* h, const float* rows, uint64_t n, uint32_t dim, u
     if (n == 0) return CS_OK;  // store.rs:655-657
     if (!rows) return fail(CS_ERR_BAD_ARG, "rows is null");
     DeviceGuard g(h->device);
-    CS_TRY(grow(h, h->n_rows + n));
-    CS_HIP(hipMemcpy(h->d_corpus + (size_t)h->n_rows * h->dim, rows,
+    CS_TRY(grow(h, h->ledger.stored() + n));
+    CS_HIP(hipMemcpy(h->d_corpus + (size_t)h->ledger.stored() * h->dim, rows,
                      (size_t)n * h->dim * sizeof(float), hipMemcpyHostToDevice));
     finish_append(h, n, out_ids);
     return CS_OK;
@@ -1168,8 +1135,8 @@ int32_t cs_index_add_device(cs_index* h, const float* d_rows, uint64_t n, uint32
     if (n == 0) return CS_OK;
     if (!d_rows) return fail(CS_ERR_BAD_ARG, "d_rows is null");
     DeviceGuard g(h->device);
-    CS_TRY(grow(h, h->n_rows + n));
-    CS_HIP(hipMemcpyAsync(h->d_corpus + (size_t)h->n_rows * h->dim, d_rows,
+    CS_TRY(grow(h, h->ledger.stored() + n));
+    CS_HIP(hipMemcpyAsync(h->d_corpus + (size_t)h->ledger.stored() * h->dim, d_rows,
                           (size_t)n * h->dim * sizeof(float), hipMemcpyDeviceToDevice,
                           (hipStream_t)stream));
     finish_append(h, n, out_ids);
@@ -1184,16 +1151,16 @@ int32_t cs_index_reserve_rows(cs_index* h, uint64_t n, uint32_t dim, float** d_r
     CS_TRY(check_append(h, n, dim));
     if (!d_rows) return fail(CS_ERR_BAD_ARG, "d_rows is null");
     DeviceGuard g(h->device);
-    CS_TRY(grow(h, h->n_rows + n));
-    *d_rows = h->d_corpus + (size_t)h->n_rows * h->dim;
+    CS_TRY(grow(h, h->ledger.stored() + n));
+    *d_rows = h->d_corpus + (size_t)h->ledger.stored() * h->dim;
     return CS_OK;
 }
 
 int32_t cs_index_commit_rows(cs_index* h, uint64_t n, uint32_t* out_ids) {
     CS_TRY(check_append(h, n, h ? h->dim : 0));
-    if (h->n_rows + n > h->capacity)
+    if (h->ledger.stored() + n > h->capacity)
         return fail(CS_ERR_BAD_ARG, "cs_index_commit_rows: %llu rows were not reserved (capacity %llu, stored %llu)", (unsigned long long)n,
-                    (unsigned long long)h->capacity, (unsigned long long)h->n_rows);
+                    (unsigned long long)h->capacity, (unsigned long long)h->ledger.stored());
     finish_append(h, n, out_ids);
     return CS_OK;
 }
@@ -1202,11 +1169,11 @@ int32_t cs_index_add_synthetic(cs_index* h, uint64_t n, uint64_t seed, uint64_t 
                                uint32_t* out_first_id) {
     CS_TRY(check_append(h, n, h ? h->dim : 0));
     DeviceGuard g(h->device);
-    CS_TRY(grow(h, h->n_rows + n));
-    CS_TRY(launch_synth_fill(h->d_corpus + (size_t)h->n_rows * h->dim, n, h->dim, seed, first_row,
+    CS_TRY(grow(h, h->ledger.stored() + n));
+    CS_TRY(launch_synth_fill(h->d_corpus + (size_t)h->ledger.stored() * h->dim, n, h->dim, seed, first_row,
                              nullptr));
     CS_HIP(hipStreamSynchronize(nullptr));
-    if (out_first_id) *out_first_id = h->id_base + (uint32_t)h->n_ids;
+    if (out_first_id) *out_first_id = h->ledger.next_id();
     finish_append(h, n, nullptr);
     return CS_OK;
 }
@@ -1216,28 +1183,12 @@ int32_t cs_index_remove(cs_index* h, const uint32_t* ids, uint64_t n, uint64_t* 
     if (removed) *removed = 0;
     if (n == 0) return CS_OK;  // store.rs:585-587
     if (!ids) return fail(CS_ERR_BAD_ARG, "ids is null");
-    uint64_t cnt = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        if (ids[i] < h->id_base) continue;
-        uint64_t row = (uint64_t)ids[i] - h->id_base;
-        if (h->compacted) {  // compacted: the id's row by bisection of the ascending row -> id table
-            const auto it = std::lower_bound(h->h_ids.begin(), h->h_ids.end(), ids[i]);
-            if (it == h->h_ids.end() || *it != ids[i]) continue;  // never issued, or deleted and reclaimed: not counted
-            row = (uint64_t)(it - h->h_ids.begin());
-        }
-        if (row >= h->n_rows) continue;  // del_item fails -> not counted (store.rs:594)
-        uint32_t& w = h->h_dead[(size_t)(row >> 5)];
-        const uint32_t bit = 1u << (row & 31);
-        if (w & bit) continue;
-        w |= bit;
-        ++cnt;
-    }
+    const uint64_t cnt = h->ledger.remove(ids, n);
     if (cnt) {
-        DeviceGuard g(h->device);
-        CS_HIP(hipMemcpy(h->d_dead, h->h_dead.data(), h->h_dead.size() * sizeof(uint32_t),
-                         hipMemcpyHostToDevice));
-        h->n_removed += cnt;
         h->built = false;  // store.rs:604-606
+        DeviceGuard g(h->device);
+        const std::vector<uint32_t>& dead = h->ledger.dead_words();
+        CS_HIP(hipMemcpy(h->d_dead, dead.data(), dead.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     if (removed) *removed = cnt;
     return CS_OK;
@@ -1247,35 +1198,35 @@ int32_t cs_index_build(cs_index* h) {
     if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
     DeviceGuard g(h->device);
     CS_TRY(drain_appends(h));  // appended rows (incl. async device appends) are now visible
-    if (h->compact_dead_pct && h->n_removed && h->n_removed * 100 >= (uint64_t)h->compact_dead_pct * h->n_rows) CS_TRY(compact(h));
-    if (h->compacted && h->ids_uploaded < h->n_rows) {  // the row -> id table of a compacted index, for the rows that are new
-        if (h->ids_cap < h->n_rows) {
+    if (h->ledger.wants_reclaim(h->compact_dead_pct)) CS_TRY(compact(h));
+    if (h->ledger.compacted() && h->ids_uploaded < h->ledger.stored()) {  // the row -> id table of a compacted index, for the rows that are new
+        if (h->ids_cap < h->ledger.stored()) {
             uint32_t* nt = nullptr;
-            const uint64_t cap = std::max<uint64_t>(h->capacity, h->n_rows);
+            const uint64_t cap = std::max<uint64_t>(h->capacity, h->ledger.stored());
             CS_HIP(hipMalloc(&nt, (size_t)cap * sizeof(uint32_t)));
             if (h->d_ids) (void)hipFree(h->d_ids);
             h->d_ids = nt;
             h->ids_cap = cap;
             h->ids_uploaded = 0;
         }
-        CS_HIP(hipMemcpy(h->d_ids + h->ids_uploaded, h->h_ids.data() + h->ids_uploaded,
-                         (size_t)(h->n_rows - h->ids_uploaded) * sizeof(uint32_t), hipMemcpyHostToDevice));
-        h->ids_uploaded = h->n_rows;
+        CS_HIP(hipMemcpy(h->d_ids + h->ids_uploaded, h->ledger.ids_data() + h->ids_uploaded,
+                         (size_t)(h->ledger.stored() - h->ids_uploaded) * sizeof(uint32_t), hipMemcpyHostToDevice));
+        h->ids_uploaded = h->ledger.stored();
     }
-    if ((batched_supported(h->dim) || h->use_split) && h->normed_rows < h->n_rows) {
-        CS_TRY(launch_row_norms(h->d_corpus, h->normed_rows, h->n_rows - h->normed_rows, h->dim,
+    if ((batched_supported(h->dim) || h->use_split) && h->normed_rows < h->ledger.stored()) {
+        CS_TRY(launch_row_norms(h->d_corpus, h->normed_rows, h->ledger.stored() - h->normed_rows, h->dim,
                                 h->d_norms, nullptr));
         CS_HIP(hipDeviceSynchronize());
-        h->normed_rows = h->n_rows;
+        h->normed_rows = h->ledger.stored();
     }
-    if (h->use_q8 && h->d_q8 && h->q8_rows / 128 < h->n_rows / 128) {  // tiles that became complete
+    if (h->use_q8 && h->d_q8 && h->q8_rows / 128 < h->ledger.stored() / 128) {  // tiles that became complete
         if (!h->d_mu) CS_HIP(hipMalloc(&h->d_mu, h->dim * sizeof(float)));
         if (h->q8_rows == 0)  // first tiles of this copy: centre it on the mean unit row of what is there now
-            CS_TRY(launch_unit_mean(h->d_corpus, h->d_norms, std::min<uint64_t>(h->n_rows, 1u << 20), h->dim, h->d_mu, nullptr));
+            CS_TRY(launch_unit_mean(h->d_corpus, h->d_norms, std::min<uint64_t>(h->ledger.stored(), 1u << 20), h->dim, h->d_mu, nullptr));
         CS_TRY(launch_corpus_q8(h->d_corpus, h->d_norms, h->d_q8, h->d_tmeta, h->q8_rows / 128,
-                                h->n_rows / 128 - h->q8_rows / 128, h->dim, h->d_mu, nullptr));
+                                h->ledger.stored() / 128 - h->q8_rows / 128, h->dim, h->d_mu, nullptr));
         CS_HIP(hipDeviceSynchronize());
-        h->q8_rows = h->n_rows / 128 * 128;
+        h->q8_rows = h->ledger.stored() / 128 * 128;
         // outlier coordinates: the tile scale is the tile's largest |u - mu|; where the typical tile's is far above what
         // evenly spread coordinates give (4.3 / sqrt(dim) for Gaussian rows), the band (it grows with the square) lets
         // through more rows than the candidate buffers hold — the f16 copy serves the filter then
@@ -1319,10 +1270,7 @@ int32_t cs_index_clear(cs_index* h) {
     CS_TRY(drain_appends(h));
     if (h->d_dead && h->capacity)
         CS_HIP(hipMemset(h->d_dead, 0, (size_t)((h->capacity + 31) / 32) * sizeof(uint32_t)));
-    h->n_rows = 0;  // store.rs:701 next_id = 0
-    h->n_ids = 0;
-    h->h_ids.clear();
-    h->compacted = false;  // ids restart at id_base: the identity numbering again
+    h->ledger.clear();  // store.rs:701 next_id = 0: ids restart at id_base, the identity numbering again
     h->ids_uploaded = 0;
     h->normed_rows = 0;
     h->split_rows = 0;
@@ -1331,22 +1279,19 @@ int32_t cs_index_clear(cs_index* h) {
     h->q8_active.store(true);
     h->q8_strikes.store(0);
     h->q8_searches.store(0);
-    h->n_removed = 0;
     {  // the groups go with the ids (the device table keeps its room)
         std::lock_guard<std::mutex> lk(h->groups_mu);
-        h->h_groups.clear();
-        h->groups_len = h->groups_assigned = h->groups_dirty_lo = h->groups_dirty_hi = 0;
+        h->groups.clear();
     }
-    h->h_dead.clear();
     h->build_gen.fetch_add(1);
     h->built = false;  // store.rs:702
     return CS_OK;
 }
 
 int32_t cs_index_is_built(const cs_index* h) { return h && h->built ? 1 : 0; }
-uint64_t cs_index_len(const cs_index* h) { return h ? h->n_rows - h->n_removed : 0; }
-uint64_t cs_index_stored_rows(const cs_index* h) { return h ? h->n_rows : 0; }
-uint32_t cs_index_next_id(const cs_index* h) { return h ? h->id_base + (uint32_t)h->n_ids : 0; }
+uint64_t cs_index_len(const cs_index* h) { return h ? h->ledger.live() : 0; }
+uint64_t cs_index_stored_rows(const cs_index* h) { return h ? h->ledger.stored() : 0; }
+uint32_t cs_index_next_id(const cs_index* h) { return h ? h->ledger.next_id() : 0; }
 uint32_t cs_index_dim(const cs_index* h) { return h ? h->dim : 0; }
 int32_t cs_index_device(const cs_index* h) { return h ? h->device : -1; }
 
@@ -1361,7 +1306,7 @@ int32_t cs_index_search_device(cs_index* h, const float* d_queries, uint32_t nq,
     CS_TRY(check_search(h, nq, dim, k));
     if (!d_queries) return fail(CS_ERR_BAD_ARG, "d_queries is null");
     DeviceGuard g(h->device);
-    const ScanPlan plan = plan_scan(h->n_rows, h->dim, nq, k, h->num_cus);
+    const ScanPlan plan = plan_scan(h->ledger.stored(), h->dim, nq, k, h->num_cus);
     Workspace* w = for_stream(h, (hipStream_t)stream);
     CS_TRY(w->reserve(plan.partial_keys, plan.merge_keys, nq, h->dim, k, false));
     return run_search(h, w, plan, d_queries, nq, k, d_out_keys, d_out_cos, d_out_ids, d_out_counts,
@@ -1391,40 +1336,18 @@ int32_t cs_index_set_groups(cs_index* h, const uint32_t* ids, const uint32_t* gr
     if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
     if (n == 0) return CS_OK;
     if (!ids || !groups) return fail(CS_ERR_BAD_ARG, "ids or groups is null");
-    uint32_t top = 0;  // the highest table entry touched
-    for (uint64_t i = 0; i < n; ++i) {
-        if (ids[i] < h->id_base || (uint64_t)ids[i] - h->id_base >= h->n_ids)
-            return fail(CS_ERR_BAD_ARG, "ids[%llu] = %u was never issued (the index has issued ids %u to %llu)",
-                        (unsigned long long)i, ids[i], h->id_base, (unsigned long long)h->id_base + h->n_ids);
-        top = std::max(top, ids[i] - h->id_base);
-    }
     std::lock_guard<std::mutex> lk(h->groups_mu);
-    if (h->h_groups.size() <= top) h->h_groups.resize((size_t)top + 1, CS_NO_GROUP);
-    uint64_t lo = h->groups_dirty_hi > h->groups_dirty_lo ? h->groups_dirty_lo : ~0ull, hi = h->groups_dirty_hi;
-    if (h->h_groups.size() > h->groups_len) {  // entries the device copy has never held
-        lo = std::min<uint64_t>(lo, h->groups_len);
-        hi = h->h_groups.size();
-    }
-    for (uint64_t i = 0; i < n; ++i) {
-        const uint32_t e = ids[i] - h->id_base;
-        uint32_t& g = h->h_groups[e];
-        if (g == groups[i]) continue;
-        h->groups_assigned += (uint64_t)(groups[i] != CS_NO_GROUP) - (uint64_t)(g != CS_NO_GROUP);
-        g = groups[i];
-        lo = std::min<uint64_t>(lo, e);
-        hi = std::max<uint64_t>(hi, (uint64_t)e + 1);
-    }
-    if (hi > lo) {
-        h->groups_dirty_lo = lo;
-        h->groups_dirty_hi = hi;
-    }
+    const int64_t bad = h->groups.set(ids, groups, n, h->ledger);
+    if (bad >= 0)
+        return fail(CS_ERR_BAD_ARG, "ids[%llu] = %u was never issued (the index has issued ids %u to %llu)",
+                    (unsigned long long)bad, ids[bad], h->ledger.id_base(), (unsigned long long)h->ledger.next_id());
     return CS_OK;
 }
 
 int32_t cs_index_groups_info(cs_index* h, uint64_t* assigned_ids, uint64_t* table_bytes) {
     if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
     std::lock_guard<std::mutex> lk(h->groups_mu);
-    if (assigned_ids) *assigned_ids = h->groups_assigned;
+    if (assigned_ids) *assigned_ids = h->groups.assigned();
     if (table_bytes) *table_bytes = h->groups_cap * sizeof(uint32_t);
     return CS_OK;
 }
@@ -1437,7 +1360,7 @@ int32_t cs_index_search_grouped(cs_index* h, const float* queries, uint32_t nq, 
     DeviceGuard g(h->device);
     GroupView gv;
     CS_TRY(ensure_groups(h, per_group, &gv));
-    const GroupedPlan plan = plan_grouped(h->n_rows, h->dim, nq, k, h->num_cus);
+    const GroupedPlan plan = plan_grouped(h->ledger.stored(), h->dim, nq, k, h->num_cus);
     return host_search(h, queries, nq, k, plan.partial_keys, plan.merge_keys, out, [&](Workspace* w, uint64_t* keys) {
         CS_TRY(upload_queries(h, w, nq));
         return run_grouped(h, w, plan, gv, w->d_queries, nq, k, keys, w->stream);
@@ -1681,9 +1604,9 @@ int32_t cs::index_append_from(cs_index* h, const float* d_rows, int src_device, 
     if (n == 0) return CS_OK;
     {
         DeviceGuard g(h->device);
-        CS_TRY(grow(h, h->n_rows + n));
+        CS_TRY(grow(h, h->ledger.stored() + n));
     }
-    float* dst = h->d_corpus + (size_t)h->n_rows * h->dim;
+    float* dst = h->d_corpus + (size_t)h->ledger.stored() * h->dim;
     const size_t bytes = (size_t)n * h->dim * sizeof(float);
     DeviceGuard g(src_device);  // `stream` belongs to the source device
     if (src_device == h->device) CS_HIP(hipMemcpyAsync(dst, d_rows, bytes, hipMemcpyDeviceToDevice, stream));
@@ -1741,31 +1664,23 @@ extern "C" {
 
 int32_t cs_index_read_rows(cs_index* h, uint64_t first_row, uint64_t n, float* out_rows) {
     if (!h || !out_rows) return fail(CS_ERR_BAD_ARG, "null argument");
-    if (first_row + n > h->n_ids)
+    if (first_row + n > h->ledger.issued_ids())
         return fail(CS_ERR_BAD_ARG, "rows [%llu, %llu) out of range (have %llu)",
                     (unsigned long long)first_row, (unsigned long long)(first_row + n),
-                    (unsigned long long)h->n_ids);
+                    (unsigned long long)h->ledger.issued_ids());
     if (n == 0) return CS_OK;
     DeviceGuard g(h->device);
     CS_TRY(drain_appends(h));
-    if (h->compacted) {  // compacted: rows are named by their ids (first_row = id - id_base); runs of neighbours in one copy
-        uint64_t i = 0;
-        while (i < n) {
-            const uint32_t id = h->id_base + (uint32_t)(first_row + i);
-            const auto it = std::lower_bound(h->h_ids.begin(), h->h_ids.end(), id);
-            if (it == h->h_ids.end() || *it != id)
-                return fail(CS_ERR_BAD_ARG, "row of id %u was deleted and reclaimed by cs_index_build", id);
-            const uint64_t row = (uint64_t)(it - h->h_ids.begin());
-            uint64_t run = 1;
-            while (i + run < n && row + run < h->n_rows && h->h_ids[(size_t)(row + run)] == id + run) ++run;
-            CS_HIP(hipMemcpy(out_rows + (size_t)i * h->dim, h->d_corpus + (size_t)row * h->dim, (size_t)run * h->dim * sizeof(float),
-                             hipMemcpyDeviceToHost));
-            i += run;
-        }
-        return CS_OK;
+    // rows are named by their ids (first_row = id - id_base): runs of neighbours in one copy (all of them, until a reclaim)
+    for (uint64_t i = 0; i < n;) {
+        const IndexLedger::Run run = h->ledger.id_run(first_row + i, n - i);
+        if (run.row == kNoRow)
+            return fail(CS_ERR_BAD_ARG, "row of id %u was deleted and reclaimed by cs_index_build",
+                        h->ledger.id_base() + (uint32_t)(first_row + i));
+        CS_HIP(hipMemcpy(out_rows + (size_t)i * h->dim, h->d_corpus + (size_t)run.row * h->dim,
+                         (size_t)run.len * h->dim * sizeof(float), hipMemcpyDeviceToHost));
+        i += run.len;
     }
-    CS_HIP(hipMemcpy(out_rows, h->d_corpus + (size_t)first_row * h->dim,
-                     (size_t)n * h->dim * sizeof(float), hipMemcpyDeviceToHost));
     return CS_OK;
 }
 

@@ -40,10 +40,10 @@ inline uint64_t popcount_range(const uint32_t* allow, uint64_t lo, uint64_t hi) 
 }
 
 // The part of the mask a search reads: ids [lo, hi) with lo a multiple of 32 (the copy starts on a word), hi = the
-// smaller of allow_bits and next_id.  The device copy holds words [lo / 32, lo / 32 + words).
+// smaller of allow_bits and next_id.  The device copy holds words [first_word, first_word + words) of the mask.
 struct MaskWindow {
     uint64_t lo = 0, hi = 0;
-    uint64_t words = 0;
+    uint64_t first_word = 0, words = 0;
 };
 
 inline MaskWindow mask_window(uint64_t allow_bits, uint64_t first_id, uint64_t next_id) {
@@ -54,6 +54,7 @@ inline MaskWindow mask_window(uint64_t allow_bits, uint64_t first_id, uint64_t n
         m.lo = m.hi = 0;
         return m;
     }
+    m.first_word = m.lo >> 5;
     m.words = (m.hi - m.lo + 31) >> 5;
     return m;
 }

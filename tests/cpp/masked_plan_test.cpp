@@ -48,11 +48,11 @@ static void check_popcount() {
 
 static void check_window() {
     MaskWindow m = mask_window(1000, 0, 600);
-    CHECK(m.lo == 0 && m.hi == 600 && m.words == 19);
+    CHECK(m.lo == 0 && m.hi == 600 && m.first_word == 0 && m.words == 19);
     m = mask_window(1000, 70, 600);  // id_base 70: the copy starts at the word holding id 64
-    CHECK(m.lo == 64 && m.hi == 600 && m.words == 17);
+    CHECK(m.lo == 64 && m.hi == 600 && m.first_word == 2 && m.words == 17);
     m = mask_window(50, 70, 600);  // the mask ends below the first id
-    CHECK(m.words == 0 && m.lo == 0 && m.hi == 0);
+    CHECK(m.words == 0 && m.first_word == 0 && m.lo == 0 && m.hi == 0);
     CHECK(mask_list_blocks(0) == 0 && mask_list_blocks(1) == 1 && mask_list_blocks(4096) == 1 && mask_list_blocks(4097) == 2);
 }
 
