@@ -91,6 +91,12 @@ SIGNATURES = {
     "cs_index_set_groups": (C.c_int32, [vp, u32p, u32p, C.c_uint64]),
     "cs_index_groups_info": (C.c_int32, [vp, u64p, u64p]),
     "cs_index_search_grouped": (C.c_int32, [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p]),
+    "cs_index_search_grouped_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p,
+                                                   u32p]),
+    "cs_index_search_variants_grouped": (C.c_int32, [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p,
+                                                     i32p]),
+    "cs_index_search_variants_grouped_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32p,
+                                                            u32p, u32p, i32p]),
     "cs_index_search_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p]),
     "cs_index_search_variants_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p,
                                                     i32p]),

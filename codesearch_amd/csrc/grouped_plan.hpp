@@ -15,6 +15,24 @@
 //
 // No prime pass: the k-th largest wave maximum bounds the k-th best cosine from below only because the maxima belong to
 // k different rows; under a cap those rows may share a group and the capped k-th can lie below it.
+//
+// A scope (cs_index_search_grouped_scoped) changes the rows in play, not the rule: the scan walks the scope's row list
+// (live rows only, ascending) and plan_grouped is called with the list's length where the stored rows go.  The list needs
+// no other answer from the plan: the same LDS and partial-list budgets, the same merge levels.
+//
+// Query variants under the cap (cs_index_search_variants_grouped): a row's key is s(c) = the best of its keys over the
+// set V of variants, and the answer is the capped top-k under s.  Why per-variant capped lists can be merged: let s(c) be
+// reached in variant v, and let c be missing from v's capped top-k.  Then, in v's order, either per_group rows of c's
+// group beat c — under s each of them keeps a key at least as large, and s(c) is c's key in v, so they beat c under s —
+// or k cap-valid rows beat c in v: their s-keys beat c too, and the greedy capped walk over the rows that beat c keeps
+// at least as many rows per group as any cap-valid subset of them does, so it has kept k rows before it reaches c.
+// Either way c is not in the capped top-k under s.  The same argument holds for s restricted to any subset of V that
+// contains v, so the merge may run in levels over groups of variants, PROVIDED EVERY level de-duplicates, keeps the best
+// key per id and caps (a row that enters a later level with less than its best key is one the answer does not hold: the
+// rows that shut it out under its best key shut it out under a smaller one).  The per-variant lists must themselves be
+// capped: the plain top-k of a variant can consist of one group's rows, and the row the cap promotes is then in no
+// list (tests/cpp/grouped_variants_test.cpp shows one).  capped_variants_merge_block below is one block of
+// merge_variants_grouped_kernel on the host.
 #pragma once
 
 #include <algorithm>
@@ -59,6 +77,17 @@ inline uint32_t grouped_merge_levels(uint32_t lists, uint32_t k) {
     uint32_t levels = 1;
     while ((lists = (lists + G - 1) / G) > 1) ++levels;
     return levels;
+}
+
+// The capped variants merge (merge_variants_grouped_kernel): a block takes the lists of grouped_merge_group(k) variants,
+// so nine lists of more than 455 keys take two levels.  One ping-pong buffer of a multi-level merge, in keys (0: one
+// level): the first level's output, ceil(nv / G) lists of k.
+inline uint32_t grouped_variants_levels(uint32_t nv, uint32_t k) { return grouped_merge_levels(nv, k); }
+
+inline size_t grouped_variants_tmp_keys(uint32_t nv, uint32_t k) {
+    const uint32_t G = grouped_merge_group(k);
+    const uint32_t first = (nv + G - 1) / G;
+    return first > 1 ? (size_t)first * k : 0;
 }
 
 inline GroupedPlan plan_grouped(uint64_t n_rows, uint32_t dim, uint32_t nq, uint32_t k, int num_cus) {
@@ -160,6 +189,24 @@ inline std::vector<GroupedRow> capped_merge_block(std::vector<GroupedRow> rows, 
     for (size_t i = 0; i < rows.size() && out.size() < k; ++i)
         if (!cut[i]) out.push_back(rows[i]);
     return out;
+}
+
+// One block of the capped variants merge (merge_variants_grouped_kernel) on the host, step by step as the kernel takes
+// them.  `rows` = the keys of the block's variants, one after the other; a packed key carries ~id in its low word, so the
+// same id may come with several keys.  The table keeps the largest key of every id (the kernel's LDS hash: one slot per
+// id, a 64-bit atomic max), its entries are sorted by key, and from there it is capped_merge_block: the (group, position)
+// image sort, the cut, the survivors in key order up to `limit`.
+inline std::vector<GroupedRow> capped_variants_merge_block(const std::vector<GroupedRow>& rows, uint32_t limit, uint32_t m) {
+    std::vector<GroupedRow> table;  // slot = first sight of the id
+    for (const GroupedRow& r : rows) {
+        if (r.key == 0) continue;  // an empty slot of a list
+        const uint32_t id = ~(uint32_t)r.key;
+        size_t slot = 0;
+        while (slot < table.size() && ~(uint32_t)table[slot].key != id) ++slot;
+        if (slot == table.size()) table.push_back(r);
+        else if (r.key > table[slot].key) table[slot] = r;
+    }
+    return capped_merge_block(table, limit, m);
 }
 
 }  // namespace cs

@@ -899,6 +899,17 @@ int32_t run_grouped(cs_index* h, Workspace* w, const GroupedPlan& plan, const Gr
                                 stream);
 }
 
+// run_grouped over a scope's row list d_list[0, *d_len) (live rows only; the plan was made for the list's length): the
+// gathered capped scan, then the same capped merge.
+int32_t run_grouped_list(cs_index* h, Workspace* w, const GroupedPlan& plan, const GroupView& gv, const uint32_t* d_list,
+                         const uint32_t* d_len, const float* d_queries, uint32_t nq, uint32_t k, uint64_t* d_keys,
+                         hipStream_t stream) {
+    CS_TRY(launch_scan_grouped_list(plan, h->d_corpus, h->dim, d_list, d_len, d_queries, nq, k, h->row_ids(), gv, w->d_partial,
+                                    stream));
+    return launch_merge_grouped(plan, w->d_partial, nq, k, gv, w->d_tmp_a, w->d_tmp_b, d_keys, nullptr, nullptr, nullptr,
+                                stream);
+}
+
 // The route's thresholds of a new index: RouteKnobs' defaults, or what the environment sets.
 RouteKnobs route_knobs_from_env() {
     RouteKnobs r;
@@ -936,9 +947,12 @@ int32_t check_search(const cs_index* h, uint32_t nq, uint32_t dim, uint32_t k) {
 // ---- the host-buffer searches' frame ------------------------------------------------------------------
 // Where a host-buffer search leaves its answer: nq lists [nq][k] with counts[nq], or (variants) the nq lists merged into
 // one list [k] with counts[0] = its length and the optional high-confidence flag (cs_index_search_variants).
+// `capped` (a grouped variants search): the group table the variants are merged under — every per-variant list is a capped
+// list and the merge caps again (launch_merge_variants_grouped); null: the plain variants merge.
 struct HostAnswer {
     float* cos; uint32_t* ids; uint32_t* counts; int32_t* high_confidence;
     bool variants;
+    const GroupView* capped = nullptr;
 };
 
 // The argument checks every host-buffer search starts with, in this order.
@@ -964,8 +978,8 @@ int32_t empty_answer(uint32_t nq, uint32_t k, const HostAnswer& out) {
 // plan, the queries into w->h_queries, then enqueue(w, keys) puts the kind's launches on w->stream — the best k keys per
 // query go to `keys`, and whether the queries are copied to the device is the kind's business.  Lists: keys = the pinned
 // w->h_keys, the last kernel writes the packed keys straight into it (device-addressable, coherent): no D2H copy call.
-// Variants: the per-variant lists stay in HBM (w->d_keys) and the merge kernel writes the <= k survivors and the two
-// scalars into pinned memory.  One stream sync either way, then the host unpacks.  A template, not std::function: nothing
+// Variants: the per-variant lists stay in HBM (w->d_keys) and the merge kernel — the kind's: the plain variants merge, or
+// the capped one when the answer carries a group table — writes the <= k survivors and the two scalars into pinned memory.  One stream sync either way, then the host unpacks.  A template, not std::function: nothing
 // on this path allocates.
 template <class Enqueue>
 int32_t host_search(cs_index* h, const float* queries, uint32_t nq, uint32_t k, size_t partial_keys, size_t merge_keys,
@@ -977,7 +991,10 @@ int32_t host_search(cs_index* h, const float* queries, uint32_t nq, uint32_t k, 
         if (out.variants && !w->h_variant_meta) CS_HIP(hipHostMalloc(&w->h_variant_meta, 2 * sizeof(uint32_t)));
         memcpy(w->h_queries, queries, (size_t)nq * h->dim * sizeof(float));
         CS_TRY(enqueue(w, out.variants ? w->d_keys : w->h_keys));
-        if (out.variants)
+        if (out.variants && out.capped)
+            CS_TRY(launch_merge_variants_grouped(w->d_keys, nq, k, *out.capped, w->d_tmp_a, w->d_tmp_b, w->h_keys, nullptr,
+                                                 nullptr, w->h_variant_meta, w->h_variant_meta + 1, w->stream));
+        else if (out.variants)
             CS_TRY(launch_merge_variants(w->d_keys, nq, k, k, w->h_keys, nullptr, nullptr, w->h_variant_meta,
                                          w->h_variant_meta + 1, w->stream));
         CS_HIP(hipStreamSynchronize(w->stream));
@@ -1029,6 +1046,33 @@ int32_t search_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32
     // (an overflow of the filter route is settled inside run_scoped, before a variants' merge)
     return host_search(h, queries, nq, k, plan.partial_keys, plan.merge_keys, out, [&](Workspace* w, uint64_t* keys) {
         return run_scoped(h, scope, w, plan, live, fp, nq, k, keys);
+    });
+}
+
+// The grouped searches: over the whole store (scope_given false: the capped scan over every stored row) or over a scope's
+// row list (the gathered capped scan, always: the int8 filter's threshold is the uncapped k-th, so no filter plan is asked
+// for), one list per query or the variants merged under the cap.
+int32_t search_grouped(cs_index* h, bool scope_given, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                       uint32_t per_group, HostAnswer out) {
+    CS_TRY(check_host_search(h, queries, nq, dim, k, out));
+    if (per_group == 0) return fail(CS_ERR_BAD_ARG, "per_group must be at least 1");
+    DeviceGuard g(h->device);
+    uint64_t rows = h->ledger.stored();
+    if (scope_given) {
+        CS_TRY(scope_ready(h, scope, &rows));
+        if (rows == 0) return empty_answer(nq, k, out);  // nothing of the scope is stored
+    }
+    GroupView gv;
+    CS_TRY(ensure_groups(h, per_group, &gv));
+    if (out.variants) out.capped = &gv;
+    const GroupedPlan plan = plan_grouped(rows, h->dim, nq, k, h->num_cus);  // a scope: the grid follows the list's length
+    const size_t merge_keys = std::max(plan.merge_keys, out.variants ? grouped_variants_tmp_keys(nq, k) : (size_t)0);
+    return host_search(h, queries, nq, k, plan.partial_keys, merge_keys, out, [&](Workspace* w, uint64_t* keys) {
+        CS_TRY(upload_queries(h, w, nq));
+        if (!scope_given) return run_grouped(h, w, plan, gv, w->d_queries, nq, k, keys, w->stream);
+        scope->gathered_searches.fetch_add(1);
+        return run_grouped_list(h, w, plan, gv, scope->d_list, scope->d_blocks + scope_list_blocks(scope->n_ids), w->d_queries, nq,
+                                k, keys, w->stream);
     });
 }
 
@@ -1354,17 +1398,14 @@ int32_t cs_index_groups_info(cs_index* h, uint64_t* assigned_ids, uint64_t* tabl
 
 int32_t cs_index_search_grouped(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k, uint32_t per_group,
                                 float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
-    const HostAnswer out{out_cos, out_ids, out_counts, nullptr, false};
-    CS_TRY(check_host_search(h, queries, nq, dim, k, out));
-    if (per_group == 0) return fail(CS_ERR_BAD_ARG, "per_group must be at least 1");
-    DeviceGuard g(h->device);
-    GroupView gv;
-    CS_TRY(ensure_groups(h, per_group, &gv));
-    const GroupedPlan plan = plan_grouped(h->ledger.stored(), h->dim, nq, k, h->num_cus);
-    return host_search(h, queries, nq, k, plan.partial_keys, plan.merge_keys, out, [&](Workspace* w, uint64_t* keys) {
-        CS_TRY(upload_queries(h, w, nq));
-        return run_grouped(h, w, plan, gv, w->d_queries, nq, k, keys, w->stream);
-    });
+    return search_grouped(h, false, nullptr, queries, nq, dim, k, per_group, HostAnswer{out_cos, out_ids, out_counts, nullptr, false});
+}
+
+int32_t cs_index_search_variants_grouped(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                                         uint32_t per_group, float* out_cos, uint32_t* out_ids, uint32_t* out_count,
+                                         int32_t* out_high_confidence) {
+    return search_grouped(h, false, nullptr, queries, nq, dim, k, per_group,
+                          HostAnswer{out_cos, out_ids, out_count, out_high_confidence, true});
 }
 
 int32_t cs_index_scope_create(cs_index* h, const uint32_t* ids, uint64_t n, cs_scope** out) {
@@ -1460,6 +1501,18 @@ int32_t cs_index_search_variants_scoped(cs_index* h, cs_scope* scope, const floa
                                         uint32_t k, float* out_cos, uint32_t* out_ids, uint32_t* out_count,
                                         int32_t* out_high_confidence) {
     return search_scoped(h, scope, queries, nq, dim, k, HostAnswer{out_cos, out_ids, out_count, out_high_confidence, true});
+}
+
+int32_t cs_index_search_grouped_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                                       uint32_t per_group, float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
+    return search_grouped(h, true, scope, queries, nq, dim, k, per_group, HostAnswer{out_cos, out_ids, out_counts, nullptr, false});
+}
+
+int32_t cs_index_search_variants_grouped_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,
+                                                uint32_t k, uint32_t per_group, float* out_cos, uint32_t* out_ids,
+                                                uint32_t* out_count, int32_t* out_high_confidence) {
+    return search_grouped(h, true, scope, queries, nq, dim, k, per_group,
+                          HostAnswer{out_cos, out_ids, out_count, out_high_confidence, true});
 }
 
 int32_t cs_index_search_scoped_device(cs_index* h, cs_scope* scope, const float* d_queries, uint32_t nq, uint32_t dim,

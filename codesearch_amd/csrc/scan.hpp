@@ -124,6 +124,19 @@ int32_t launch_merge_grouped(const GroupedPlan& plan, const uint64_t* d_lists, u
                              uint64_t* d_tmp_a, uint64_t* d_tmp_b, uint64_t* d_out_keys, float* d_out_cos,
                              uint32_t* d_out_ids, uint32_t* d_out_counts, hipStream_t stream);
 
+// launch_scan_grouped over the live rows d_list[0, *d_list_len) (a scope's row list, ascending; plan: plan_grouped of the
+// length): the same per-wave capped lists, for launch_merge_grouped.  The list holds live rows only: no tombstone test.
+int32_t launch_scan_grouped_list(const GroupedPlan& plan, const float* d_corpus, uint32_t dim, const uint32_t* d_list,
+                                 const uint32_t* d_list_len, const float* d_queries, uint32_t nq, uint32_t k, RowIds ids,
+                                 const GroupView& gv, uint64_t* d_partial, hipStream_t stream);
+// launch_merge_variants under the cap: capped per-variant lists d_keys [nv][k] -> the capped best k distinct ids (a chunk
+// keeps its best key), best first, + count + the high-confidence predicate on the list returned.  Every level
+// de-duplicates and caps (grouped_plan.hpp); d_tmp_a / d_tmp_b: grouped_variants_tmp_keys(nv, k) keys each (may be null
+// when that is 0).
+int32_t launch_merge_variants_grouped(const uint64_t* d_keys, uint32_t nv, uint32_t k, const GroupView& gv, uint64_t* d_tmp_a,
+                                      uint64_t* d_tmp_b, uint64_t* d_out_keys, float* d_out_cos, uint32_t* d_out_ids,
+                                      uint32_t* d_out_count, uint32_t* d_out_high_confidence, hipStream_t stream);
+
 // corpus[(first_out_row + r) * dim + c] = cs_synth_value(seed, (first_row + r) * dim + c)
 int32_t launch_synth_fill(float* d_rows, uint64_t n, uint32_t dim, uint64_t seed,
                           uint64_t first_row, hipStream_t stream);

@@ -339,6 +339,41 @@ class VectorStore {
         if (high_confidence) *high_confidence = flag != 0;
         return results(cos, ids, count);
     }
+    // `--per-file` inside a Scope, and over the merged query variants with or without one (cs_index_search_grouped_scoped,
+    // cs_index_search_variants_grouped, cs_index_search_variants_grouped_scoped): the cap is applied on the device, to the
+    // scope's rows and to the merged order; the flag is the predicate on the capped list.  One index only.
+    std::vector<SearchResult> search_per_file(const std::vector<float>& query_embedding, size_t limit, uint32_t per_file,
+                                              const Scope& scope) const {
+        if (sh_) throw Error(CS_ERR_UNSUPPORTED, "a sharded store has no grouped search");
+        std::vector<float> cos(limit);
+        std::vector<uint32_t> ids(limit), counts(1);
+        check(cs_index_search_grouped_scoped(h_, scope.handle(), query_embedding.data(), 1, (uint32_t)query_embedding.size(),
+                                             (uint32_t)limit, per_file, cos.data(), ids.data(), counts.data()));
+        return results(cos, ids, counts[0]);
+    }
+    std::vector<SearchResult> search_variants_per_file(const std::vector<std::vector<float>>& variants, size_t limit,
+                                                       uint32_t per_file, const Scope* scope = nullptr,
+                                                       bool* high_confidence = nullptr) const {
+        if (sh_) throw Error(CS_ERR_UNSUPPORTED, "a sharded store has no grouped search");
+        const size_t nq = variants.size();
+        if (nq == 0) return {};
+        const size_t qdim = variants[0].size();
+        std::vector<float> q;
+        for (const auto& v : variants) {
+            if (v.size() != qdim) throw Error(CS_ERR_BAD_ARG, "queries of unequal length");
+            q.insert(q.end(), v.begin(), v.end());
+        }
+        std::vector<float> cos(limit);
+        std::vector<uint32_t> ids(limit);
+        uint32_t count = 0;
+        int32_t flag = 0;
+        check(scope ? cs_index_search_variants_grouped_scoped(h_, scope->handle(), q.data(), (uint32_t)nq, (uint32_t)qdim,
+                                                              (uint32_t)limit, per_file, cos.data(), ids.data(), &count, &flag)
+                    : cs_index_search_variants_grouped(h_, q.data(), (uint32_t)nq, (uint32_t)qdim, (uint32_t)limit, per_file,
+                                                       cos.data(), ids.data(), &count, &flag));
+        if (high_confidence) *high_confidence = flag != 0;
+        return results(cos, ids, count);
+    }
     std::vector<SearchResult> search_variants(const std::vector<std::vector<float>>& variants, size_t limit,
                                               bool* high_confidence = nullptr) const {
         const size_t nq = variants.size();

@@ -84,6 +84,29 @@ def cap_per_group(cos, ids, groups, k: int, m: int):
     return kept_cos, kept_ids
 
 
+def merge_variants_capped(lists, group_of, k: int, m: int):
+    """The contract of the grouped variants search (cs_index_search_variants_grouped[_scoped]) on the host.  `lists`: per
+    query variant a (cos, ids) pair over the rows in play — the variant's full order, or any list that holds every row
+    that matters; `group_of(ids)` -> their groups.  A chunk keeps its best cosine over the variants (the best packed key:
+    cosine desc, then id asc, so of one id simply the largest cosine), the chunks are ordered by (that cosine desc, id asc)
+    and capped by cap_per_group.  -> (cos, ids) of the kept rows, as lists."""
+    best = {}
+    for cos, ids in lists:
+        for c, i in zip(cos, ids):
+            i = int(i)
+            if i not in best or c > best[i]:
+                best[i] = c
+    order = sorted(best, key=lambda i: (-float(best[i]), i))
+    return cap_per_group([best[i] for i in order], order, group_of(order) if order else [], k, m)
+
+
+def high_confidence(cos, top_n: int = 5, max_distance: float = 0.15) -> bool:
+    """The early-termination predicate of the variants searches on a returned list's cosines (src/search/mod.rs:595-611):
+    the list is not empty and its first top_n entries all have distance (1 - cos) / 2 < max_distance, in float32."""
+    c = np.asarray(cos, np.float32)[:top_n]
+    return bool(len(c)) and bool(((np.float32(1.0) - c) * np.float32(0.5) < np.float32(max_distance)).all())
+
+
 def group_results_by_file(results: Sequence[SearchResult], per_file: Optional[int],
                           max_results: Optional[int] = None) -> List[SearchResult]:
     """The reference's display order under `--per-file` (src/search/mod.rs:1007-1038): the results grouped by path, the

@@ -159,6 +159,12 @@ def _one_of(chunk_ids, scope, per_file=None):
         raise ValueError("chunk_ids= and scope= are exclusive: a scope already is a set of chunk ids")
 
 
+def _filters_ok(chunk_ids, scope, per_file):
+    """The argument check of the searches: per_file= may come with scope= (the grouped scoped search); every other pair is
+    _one_of's to refuse — per_file= with chunk_ids= (no masked grouped form), chunk_ids= with scope=."""
+    _one_of(chunk_ids, None if (per_file is not None and chunk_ids is None) else scope, per_file)
+
+
 class Scope:
     """A prepared set of chunk ids of one VectorStore (cs_scope): ids and the row list made from them live on the device,
     and a search with `scope=` returns what the same search with `chunk_ids=` of those ids returns, without building,
@@ -660,8 +666,9 @@ class VectorStore:
         chunk_ids: only these chunks are searched (cs_index_search_masked: the exact top `limit` among them).
         scope: the same through a prepared Scope (cs_index_search_scoped); exclusive with chunk_ids.
         per_file: at most this many rows of one group (a chunk's file; set_groups for rows without metadata) among the
-        `limit` best, decided on the device (cs_index_search_grouped); exclusive with chunk_ids and scope for now."""
-        _one_of(chunk_ids, scope, per_file)
+        `limit` best, decided on the device (cs_index_search_grouped); with scope=, among the scope's rows
+        (cs_index_search_grouped_scoped); exclusive with chunk_ids."""
+        _filters_ok(chunk_ids, scope, per_file)
         q = np.ascontiguousarray(queries, np.float32)
         if q.ndim == 1:
             q = q[None, :]
@@ -672,9 +679,14 @@ class VectorStore:
         if per_file is not None:
             if self.sharded:
                 raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no grouped search (per_file): no cs_shards_ form yet")
-            _lib.check(self._lib.cs_index_search_grouped(self._h, q.ctypes.data_as(f32p), nq, dim, limit, int(per_file),
-                                                         cos.ctypes.data_as(f32p), ids.ctypes.data_as(u32p),
-                                                         counts.ctypes.data_as(u32p)))
+            if scope is not None:
+                _lib.check(self._lib.cs_index_search_grouped_scoped(self._h, self._scope_handle(scope), q.ctypes.data_as(f32p),
+                                                                    nq, dim, limit, int(per_file), cos.ctypes.data_as(f32p),
+                                                                    ids.ctypes.data_as(u32p), counts.ctypes.data_as(u32p)))
+            else:
+                _lib.check(self._lib.cs_index_search_grouped(self._h, q.ctypes.data_as(f32p), nq, dim, limit, int(per_file),
+                                                             cos.ctypes.data_as(f32p), ids.ctypes.data_as(u32p),
+                                                             counts.ctypes.data_as(u32p)))
         elif scope is not None:
             _lib.check(self._fn("search_scoped")(self._h, self._scope_handle(scope), q.ctypes.data_as(f32p), nq, dim, limit,
                                                  cos.ctypes.data_as(f32p), ids.ctypes.data_as(u32p),
@@ -704,12 +716,23 @@ class VectorStore:
         cos, ids, counts = self.search_raw(query_embeddings, limit, chunk_ids=chunk_ids, scope=scope, per_file=per_file)
         return [self._results(cos[i], ids[i], int(counts[i])) for i in range(len(counts))]
 
-    def search_variants(self, query_embeddings, limit: int, chunk_ids=None, scope: Optional[Scope] = None):
+    def search_variants(self, query_embeddings, limit: int, chunk_ids=None, scope: Optional[Scope] = None,
+                        per_file: Optional[int] = None):
         """search::search's vector leg (src/search/mod.rs:508-611) in one call: every variant searched for `limit`
         rows, union with a chunk keeping its best score, best `limit` distinct chunks best-first, merged on
         the device.  -> (results, high_confidence) where high_confidence is the early-termination predicate
-        (top five all distance < 0.15).  chunk_ids / scope: only these chunks are searched (search_raw)."""
-        _one_of(chunk_ids, scope)
+        (top five all distance < 0.15).  chunk_ids / scope: only these chunks are searched (search_raw).
+        per_file: at most this many chunks of one file among the `limit` returned, the cap applied to the merged order
+        on the device (cs_index_search_variants_grouped, with scope= cs_index_search_variants_grouped_scoped); the flag
+        is then the predicate on the capped list.  Exclusive with chunk_ids."""
+        cos, ids, count, flag = self.search_variants_raw(query_embeddings, limit, chunk_ids=chunk_ids, scope=scope,
+                                                         per_file=per_file)
+        return self._results(cos, ids, count), flag
+
+    def search_variants_raw(self, query_embeddings, limit: int, chunk_ids=None, scope: Optional[Scope] = None,
+                            per_file: Optional[int] = None):
+        """search_variants without the metadata join -> (cos [limit] f32, ids [limit] u32, count, high_confidence)."""
+        _filters_ok(chunk_ids, scope, per_file)
         q = np.ascontiguousarray(query_embeddings, np.float32)
         if q.ndim == 1:
             q = q[None, :]
@@ -717,7 +740,18 @@ class VectorStore:
         cos = np.zeros(max(limit, 1), np.float32)
         ids = np.zeros(max(limit, 1), np.uint32)
         count, flag = C.c_uint32(), C.c_int32()
-        if scope is not None:
+        if per_file is not None:
+            if self.sharded:
+                raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no grouped search (per_file): no cs_shards_ form yet")
+            out = (cos.ctypes.data_as(f32p), ids.ctypes.data_as(u32p), C.byref(count), C.byref(flag))
+            if scope is not None:
+                _lib.check(self._lib.cs_index_search_variants_grouped_scoped(self._h, self._scope_handle(scope),
+                                                                             q.ctypes.data_as(f32p), nq, dim, limit,
+                                                                             int(per_file), *out))
+            else:
+                _lib.check(self._lib.cs_index_search_variants_grouped(self._h, q.ctypes.data_as(f32p), nq, dim, limit,
+                                                                      int(per_file), *out))
+        elif scope is not None:
             _lib.check(self._fn("search_variants_scoped")(self._h, self._scope_handle(scope), q.ctypes.data_as(f32p), nq, dim,
                                                           limit, cos.ctypes.data_as(f32p), ids.ctypes.data_as(u32p),
                                                           C.byref(count), C.byref(flag)))
@@ -730,7 +764,7 @@ class VectorStore:
             _lib.check(self._fn("search_variants_masked")(self._h, q.ctypes.data_as(f32p), nq, dim, limit, allow, bits,
                                                           cos.ctypes.data_as(f32p), ids.ctypes.data_as(u32p),
                                                           C.byref(count), C.byref(flag)))
-        return self._results(cos, ids, int(count.value)), bool(flag.value)
+        return cos, ids, int(count.value), bool(flag.value)
 
     def chunk_ids_under(self, filter_path: str, project_root: str = "", mcp: bool = True) -> List[int]:
         """Ids of the chunks whose metadata path passes the reference's filter_path rule (search.path_matches; MCP or

@@ -284,6 +284,34 @@ CS_API int32_t cs_index_groups_info(cs_index* h, uint64_t* assigned_ids, uint64_
  * Concurrent calls, with the same or different per_group, are safe. */
 CS_API int32_t cs_index_search_grouped(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
                                        uint32_t per_group, float* out_cos, uint32_t* out_ids, uint32_t* out_counts);
+/* Grouped search inside a scope and across query variants — the three features at once, as one reference search is
+ * (`codesearch search -m 10 --per-file 1` under an MCP `filter_path`: nine variants, a directory and a cap).
+ * GROUPED SCOPED, per query: order the live rows whose id is in the scope by (cosine desc, id asc) — cosine bits those of
+ * the streaming scan — walk that order, keep a row when its group is CS_NO_GROUP or fewer than per_group rows of its group
+ * have been kept, stop at k; out_counts[q] = rows kept.  Bit for bit (cosines, ids, counts) it equals
+ * cs_index_search_grouped when the scope holds every id, and cs_index_search_scoped when per_group >= k or no group is
+ * assigned.
+ * GROUPED VARIANTS: a live row's key is the best of its (cosine, id) keys over the nq variants (what
+ * cs_index_search_variants keeps for a chunk); order the rows by that key, apply the same capped walk, stop at k.
+ * *out_count = rows kept; *out_high_confidence = the predicate of cs_index_search_variants on the list returned (its top
+ * five all with distance < 0.15).  With per_group >= k or no group assigned it equals cs_index_search_variants bit for
+ * bit, and the scoped form equals cs_index_search_variants_scoped.  nq <= CS_MAX_VARIANTS.
+ * On the device every variant's list is itself a capped list and the merge de-duplicates and caps at every level
+ * (scan_grouped.hip); capping a merged uncapped list on the host is not the same thing and can lose rows.
+ * Errors, texts and their order: those of cs_index_search (for the variants forms, of cs_index_search_variants), then
+ * per_group == 0 (CS_ERR_BAD_ARG), then the scope's (a null scope, a scope made for another store: CS_ERR_BAD_ARG).  A
+ * scope with no live row gives the empty answer and launches nothing.  The scoped forms always take the gathered scan
+ * (counted in cs_scope_route_info's gathered_searches), whatever cs_scope_set_route says: the int8 filter's threshold is
+ * the uncapped k-th.  Concurrent calls are safe.  No cs_shards_, masked (bitmap) or device-pointer form yet. */
+CS_API int32_t cs_index_search_grouped_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,
+                                              uint32_t k, uint32_t per_group, float* out_cos, uint32_t* out_ids,
+                                              uint32_t* out_counts);
+CS_API int32_t cs_index_search_variants_grouped(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                                                uint32_t per_group, float* out_cos, uint32_t* out_ids, uint32_t* out_count,
+                                                int32_t* out_high_confidence);
+CS_API int32_t cs_index_search_variants_grouped_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq,
+                                                       uint32_t dim, uint32_t k, uint32_t per_group, float* out_cos,
+                                                       uint32_t* out_ids, uint32_t* out_count, int32_t* out_high_confidence);
 
 /* Synchronises `stream` and reports in *overflowed whether any cs_index_search_device call of more
  * than 16 queries issued by this thread on it since the previous status call overflowed a candidate buffer
