@@ -1,0 +1,155 @@
+"""Similar-chunk search (cs_index_search_similar) against what a caller can do without it — read the source's row back
+(cs_index_read_rows), search with it on the streaming route at k + 1 (cs_index_search) and drop the source on the host —
+over the same 10M x 384 store, in one process, alternated (new, baseline, new again, --reps calls each).  The baseline is
+exact for "self" only: for "file" it is the rank-then-filter method the feature replaces, and its answer is recorded beside
+the exact one.  Per source kind, k (10, 200), sources per call (1, 9), mode (none, self, file) and bound (none, 0.9): the
+median wall time of the host-buffer call over both new series, each series' own median, the baseline's median and the
+ratio.  One JSON object per line on stdout (and in --out).
+
+The baseline of several sources (baseline_ms) is one read and one one-query streaming search PER SOURCE: cs_index_search
+has no streaming route for nine queries in one call.  What one call of nine rows costs is recorded beside it, measured
+once per shape and not alternated with the new call: on the library's default route (the int8 filter + exact refine: baseline_one_call_default_ms) and
+with the filter switched off (five or more queries then take the exact-f32 MFMA path: baseline_one_call_nofilter_ms).
+
+    python benchmarks/similar_search.py [--rows 10000000] [--dim 384] [--reps 20] [--out FILE] [--tree DIR]
+
+The store: synthetic rows in files of 8 ids, with rows [2/10, 3/10) of it replaced by one file of near-duplicates of its
+first row (0.95 s + 0.05 noise).  The "hog" source is that first row; the "ordinary" source is a row far from the file.
+With 9 sources per call the other 8 are ordinary rows.
+
+--tree DIR: load the package and the library of another checkout (the parent commit's, built): the entry point it lacks is
+not timed, so the same script gives the baseline's times under the parent's library."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+
+def timed(fn, reps):
+    """-> the wall times of `reps` calls after one untimed call, ms."""
+    fn()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return ts
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=10_000_000)
+    ap.add_argument("--dim", type=int, default=384)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--out", default="")
+    ap.add_argument("--tree", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    a = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(a.tree))
+    from codesearch_amd import VectorStore, _lib
+    from codesearch_amd._lib import f32p, u32p
+    from codesearch_amd.synth import synth_rows
+
+    out = open(a.out, "w") if a.out else None
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if out:
+            out.write(line + "\n")
+            out.flush()
+
+    n, dim, seed = a.rows, a.dim, 0x5EA4C5
+    hog_lo, hog_n = n // 5, n // 10
+    st = VectorStore(None, dim, capacity=n)
+    st.insert_synthetic(hog_lo, seed, 0)
+    s_row = synth_rows(seed, hog_lo, 1, dim)
+    st.insert_embeddings(s_row)
+    rng = np.random.default_rng(2)
+    scale = float(np.linalg.norm(s_row)) / np.sqrt(dim)
+    step = 100_000
+    for lo in range(1, hog_n, step):
+        cnt = min(step, hog_n - lo)
+        noise = rng.standard_normal((cnt, dim), dtype=np.float32) * np.float32(scale)
+        st.insert_embeddings(np.float32(0.95) * s_row + np.float32(0.05) * noise)
+    st.insert_synthetic(n - hog_lo - hog_n, seed, hog_lo + hog_n)
+    st.build_index()
+    st.set_single_query_route(st.ROUTE_STREAM)
+    assert st.next_id() == n
+    lib, h = st._lib, st.handle
+    has_new = "cs_index_search_similar" in _lib.SIGNATURES
+    ids = np.arange(n, dtype=np.uint32)
+    groups = ids // 8
+    groups[hog_lo:hog_lo + hog_n] = 0xFFFFFFF0
+    st.set_groups(ids, groups)
+    others = (np.arange(8, dtype=np.uint32) * 1000 + n // 2 + 17).astype(np.uint32)
+    kinds = [("ordinary", np.uint32(n - n // 7)), ("hog", np.uint32(hog_lo))]
+    modes = {"none": 0, "self": 1, "file": 2}
+    med = lambda t: round(float(np.median(t)), 4)  # noqa: E731
+    for kind, src in kinds:
+        for nq in (1, 9):
+            srcs = np.ascontiguousarray(np.concatenate([[src], others[:nq - 1]]), np.uint32)
+            rows = np.zeros((nq, dim), np.float32)
+            for k in (10, 200):
+                cos, idb, cnt = np.zeros((nq, k), np.float32), np.zeros((nq, k), np.uint32), np.zeros(nq, np.uint32)
+                bcos, bid, bcnt = np.zeros((nq, k + 1), np.float32), np.zeros((nq, k + 1), np.uint32), np.zeros(nq, np.uint32)
+
+                def baseline():  # the streaming route: one query per call (set_single_query_route above)
+                    for q in range(nq):
+                        _lib.check(lib.cs_index_read_rows(h, int(srcs[q]), 1, rows[q:q + 1].ctypes.data_as(f32p)))
+                        _lib.check(lib.cs_index_search(h, rows[q:q + 1].ctypes.data_as(f32p), 1, dim, k + 1,
+                                                       bcos[q:q + 1].ctypes.data_as(f32p), bid[q:q + 1].ctypes.data_as(u32p),
+                                                       bcnt[q:q + 1].ctypes.data_as(u32p)))
+
+                def one_call():  # the sources are not neighbours: one read per source, then all rows in one search
+                    for q in range(nq):
+                        _lib.check(lib.cs_index_read_rows(h, int(srcs[q]), 1, rows[q:q + 1].ctypes.data_as(f32p)))
+                    _lib.check(lib.cs_index_search(h, rows.ctypes.data_as(f32p), nq, dim, k + 1, bcos.ctypes.data_as(f32p),
+                                                   bid.ctypes.data_as(u32p), bcnt.ctypes.data_as(u32p)))
+
+                base_first = timed(baseline, a.reps)
+                one_default = one_nofilter = None
+                if nq > 1:
+                    one_default = med(timed(one_call, a.reps))
+                    st.set_filter_min_queries(1 << 20)
+                    one_nofilter = med(timed(one_call, a.reps))
+                    st.set_filter_min_queries(2)
+                for mname, mode in modes.items():
+                    for bound in (None, 0.9):
+                        rec = {"source": kind, "rows": n, "dim": dim, "nq": nq, "k": k, "mode": mname, "min_cos": bound,
+                               "reps": a.reps, "library": "new" if has_new else "parent"}
+                        if has_new:
+                            def similar():
+                                _lib.check(lib.cs_index_search_similar(h, srcs.ctypes.data_as(u32p), nq, k, mode,
+                                                                       float("-inf") if bound is None else bound,
+                                                                       cos.ctypes.data_as(f32p), idb.ctypes.data_as(u32p),
+                                                                       cnt.ctypes.data_as(u32p)))
+
+                            t1 = timed(similar, a.reps)
+                            tb = timed(baseline, a.reps)
+                            t2 = timed(similar, a.reps)
+                            rec.update({"similar_ms": med(t1 + t2), "similar_before_ms": med(t1), "similar_after_ms": med(t2),
+                                        "baseline_ms": med(tb), "count": int(cnt[0])})
+                            rec["ratio_vs_baseline"] = round(rec["similar_ms"] / rec["baseline_ms"], 4)
+                            # what the baseline's ranked list holds of the exact answer once the mode's rows are dropped
+                            baseline()
+                            kept = [int(i) for i, c in zip(bid[0][:bcnt[0]], bcos[0][:bcnt[0]])
+                                    if (mode == 0 or i != src) and (mode != 2 or groups[i] != groups[src])
+                                    and (bound is None or c > bound)][:k]
+                            rec["baseline_hits"] = len(kept)
+                            rec["baseline_exact_found"] = len(set(kept) & set(idb[0][:cnt[0]].tolist()))
+                        else:
+                            rec["baseline_ms"] = med(timed(baseline, a.reps))
+                        rec["baseline_first_series_ms"] = med(base_first)
+                        if nq > 1:
+                            rec["baseline_one_call_default_ms"] = one_default
+                            rec["baseline_one_call_nofilter_ms"] = one_nofilter
+                        emit(rec)
+    if out:
+        out.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -19,6 +19,7 @@ CS_ERR_CANCELLED, CS_ERR_OOM, CS_ERR_HIP, CS_ERR_UNSUPPORTED = 4, 5, 6, 7
 CS_GEMM_F32, CS_GEMM_SPLIT_F16, CS_GEMM_Q8_DYNAMIC = 0, 1, 2
 CS_MAX_K = 1024
 CS_MAX_QUERIES = 4096
+CS_SIMILAR_EXCLUDE_NONE, CS_SIMILAR_EXCLUDE_SELF, CS_SIMILAR_EXCLUDE_GROUP = 0, 1, 2
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
@@ -97,6 +98,7 @@ SIGNATURES = {
                                                      i32p]),
     "cs_index_search_variants_grouped_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32p,
                                                             u32p, u32p, i32p]),
+    "cs_index_search_similar": (C.c_int32, [vp, u32p, C.c_uint32, C.c_uint32, C.c_int32, C.c_float, f32p, u32p, u32p]),
     "cs_index_search_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p]),
     "cs_index_search_variants_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p,
                                                     i32p]),

@@ -18,6 +18,7 @@
 #include "masked_plan.hpp"
 #include "scan.hpp"
 #include "scope.hpp"
+#include "similar_sources.hpp"
 
 namespace cs {
 
@@ -82,6 +83,10 @@ struct Workspace {
     // row-list pass's per-block offsets (+ the list length)
     uint32_t* d_allow = nullptr; uint32_t* d_list = nullptr; uint32_t* d_mblocks = nullptr;
     size_t allow_cap = 0, list_cap = 0, mblocks_cap = 0;
+    // similar-chunk searches (search_similar): per query the source's stored row, its excluded id and its excluded group,
+    // [3][nq] — resolved on the host into the pinned copy, one copy to the device
+    uint32_t* h_similar = nullptr; uint32_t* d_similar = nullptr;
+    size_t h_similar_cap = 0, d_similar_cap = 0;
     std::vector<EventTriple> free_events;
     BatchedState bs;
     size_t cnt_cap = 0, tau_cap = 0, cand_cap = 0, carry_cap = 0;
@@ -127,6 +132,11 @@ struct Workspace {
         return reserve_buf(d_mblocks, mblocks_cap, (size_t)list_blocks + 1);
     }
 
+    int32_t reserve_similar(uint32_t nq) {
+        CS_TRY(reserve_buf(h_similar, h_similar_cap, 3 * (size_t)nq, true));
+        return reserve_buf(d_similar, d_similar_cap, 3 * (size_t)nq);
+    }
+
     int32_t reserve_batched(uint32_t nq, uint32_t k) {
         if (!h_overflow) {
             CS_HIP(realloc_buf(h_overflow, 4, true));
@@ -170,8 +180,8 @@ struct Workspace {
     void release_all() {
         free_bufs(false, d_partial, d_tmp_a, d_tmp_b, d_queries, d_keys, d_cos, d_ids, d_counts, prime.d_wave_max, prime.d_done,
                   prime.d_floor, bs.d_cand, bs.d_cnt, bs.d_tau, bs.d_carry, bs.d_overflow, qw.d_qsplit, qw.d_qmag, qw.d_q8q,
-                  qw.d_q8q_hi, qw.d_qmeta, d_allow, d_list, d_mblocks);
-        free_bufs(true, h_keys, h_queries, h_overflow, h_variant_meta);
+                  qw.d_q8q_hi, qw.d_qmeta, d_allow, d_list, d_mblocks, d_similar);
+        free_bufs(true, h_keys, h_queries, h_overflow, h_variant_meta, h_similar);
         for (auto& t : free_events) {
             (void)hipEventDestroy(t.e0); (void)hipEventDestroy(t.e1); (void)hipEventDestroy(t.e2);
         }
@@ -976,7 +986,8 @@ int32_t empty_answer(uint32_t nq, uint32_t k, const HostAnswer& out) {
 
 // One host-buffer search on a pooled workspace (own stream), for arguments that passed the checks: room for the kind's
 // plan, the queries into w->h_queries, then enqueue(w, keys) puts the kind's launches on w->stream — the best k keys per
-// query go to `keys`, and whether the queries are copied to the device is the kind's business.  Lists: keys = the pinned
+// query go to `keys`, and whether the queries are copied to the device is the kind's business.  queries == null: the kind's
+// enqueue step produces the queries on the device (w->d_queries) itself, and w->h_queries is left alone.  Lists: keys = the pinned
 // w->h_keys, the last kernel writes the packed keys straight into it (device-addressable, coherent): no D2H copy call.
 // Variants: the per-variant lists stay in HBM (w->d_keys) and the merge kernel — the kind's: the plain variants merge, or
 // the capped one when the answer carries a group table — writes the <= k survivors and the two scalars into pinned memory.  One stream sync either way, then the host unpacks.  A template, not std::function: nothing
@@ -989,7 +1000,7 @@ int32_t host_search(cs_index* h, const float* queries, uint32_t nq, uint32_t k, 
     const int32_t s = [&]() -> int32_t {
         CS_TRY(w->reserve(partial_keys, merge_keys, nq, h->dim, k, true));
         if (out.variants && !w->h_variant_meta) CS_HIP(hipHostMalloc(&w->h_variant_meta, 2 * sizeof(uint32_t)));
-        memcpy(w->h_queries, queries, (size_t)nq * h->dim * sizeof(float));
+        if (queries) memcpy(w->h_queries, queries, (size_t)nq * h->dim * sizeof(float));
         CS_TRY(enqueue(w, out.variants ? w->d_keys : w->h_keys));
         if (out.variants && out.capped)
             CS_TRY(launch_merge_variants_grouped(w->d_keys, nq, k, *out.capped, w->d_tmp_a, w->d_tmp_b, w->h_keys, nullptr,
@@ -1073,6 +1084,45 @@ int32_t search_grouped(cs_index* h, bool scope_given, cs_scope* scope, const flo
         scope->gathered_searches.fetch_add(1);
         return run_grouped_list(h, w, plan, gv, scope->d_list, scope->d_blocks + scope_list_blocks(scope->n_ids), w->d_queries, nq,
                                 k, keys, w->stream);
+    });
+}
+
+// The similar-chunk search (scan_similar.hip): the sources resolved on the host (similar_sources.hpp), their rows gathered
+// into w->d_queries on the device, the streaming scan's arithmetic under the per-query exclusions, the ordinary merge.
+int32_t search_similar(cs_index* h, const uint32_t* ids, uint32_t nq, uint32_t k, int32_t exclude, float min_cos,
+                       const HostAnswer& out) {
+    if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
+    CS_TRY(check_search(h, nq, h->dim, k));
+    if (!ids || !out.cos || !out.ids || !out.counts) return fail(CS_ERR_BAD_ARG, "null buffer");
+    if (!similar_mode_ok(exclude))
+        return fail(CS_ERR_BAD_ARG, "exclude must be CS_SIMILAR_EXCLUDE_NONE, _SELF or _GROUP (0..2), got %d", exclude);
+    if (min_cos != min_cos) return fail(CS_ERR_BAD_ARG, "min_cos is NaN");
+    DeviceGuard g(h->device);
+    GroupView gv{nullptr, 0, h->ledger.id_base(), 0xFFFFFFFFu};
+    {
+        std::lock_guard<std::mutex> lk(h->groups_mu);  // (ensure_groups below moves the table's upload marks under it)
+        const SourceCheck sc = resolve_similar_sources(h->ledger, h->groups, ids, nq, exclude, nullptr, nullptr, nullptr);
+        if (sc.fault == SourceFault::NeverIssued)
+            return fail(CS_ERR_BAD_ARG, "ids[%u] = %u was never issued (the index has issued ids %u to %llu)", sc.at, ids[sc.at],
+                        h->ledger.id_base(), (unsigned long long)h->ledger.next_id());
+        if (sc.fault == SourceFault::Deleted)
+            return fail(CS_ERR_BAD_ARG, "ids[%u] = %u: the chunk was deleted", sc.at, ids[sc.at]);
+    }
+    if (exclude == CS_SIMILAR_EXCLUDE_GROUP) CS_TRY(ensure_groups(h, 0xFFFFFFFFu, &gv));
+    const ScanPlan plan = plan_scan(h->ledger.stored(), h->dim, nq, k, h->num_cus);
+    return host_search(h, nullptr, nq, k, plan.partial_keys, plan.merge_keys, out, [&](Workspace* w, uint64_t* keys) {
+        CS_TRY(w->reserve_similar(nq));
+        {
+            std::lock_guard<std::mutex> lk(h->groups_mu);
+            resolve_similar_sources(h->ledger, h->groups, ids, nq, exclude, w->h_similar, w->h_similar + nq, w->h_similar + 2 * (size_t)nq);
+        }
+        CS_HIP(hipMemcpyAsync(w->d_similar, w->h_similar, 3 * (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice, w->stream));
+        CS_TRY(launch_gather_sources(h->d_corpus, h->dim, w->d_similar, nq, w->d_queries, w->stream));
+        const SimilarView sv{w->d_similar + nq, w->d_similar + 2 * (size_t)nq, min_cos};
+        CS_TRY(launch_scan_similar(plan, h->d_corpus, h->ledger.stored(), h->dim, w->d_queries, nq, k,
+                                   h->ledger.removed() ? h->d_dead : nullptr, h->row_ids(), gv, sv, w->d_partial, w->stream));
+        return launch_merge(w->d_partial, plan.blocks, nq, k, false, w->d_tmp_a, w->d_tmp_b, keys, nullptr, nullptr, nullptr,
+                            w->stream);
     });
 }
 
@@ -1406,6 +1456,11 @@ int32_t cs_index_search_variants_grouped(cs_index* h, const float* queries, uint
                                          int32_t* out_high_confidence) {
     return search_grouped(h, false, nullptr, queries, nq, dim, k, per_group,
                           HostAnswer{out_cos, out_ids, out_count, out_high_confidence, true});
+}
+
+int32_t cs_index_search_similar(cs_index* h, const uint32_t* ids, uint32_t nq, uint32_t k, int32_t exclude, float min_cos,
+                                float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
+    return search_similar(h, ids, nq, k, exclude, min_cos, HostAnswer{out_cos, out_ids, out_counts, nullptr, false});
 }
 
 int32_t cs_index_scope_create(cs_index* h, const uint32_t* ids, uint64_t n, cs_scope** out) {

@@ -137,6 +137,24 @@ int32_t launch_merge_variants_grouped(const uint64_t* d_keys, uint32_t nv, uint3
                                       uint64_t* d_tmp_b, uint64_t* d_out_keys, float* d_out_cos, uint32_t* d_out_ids,
                                       uint32_t* d_out_count, uint32_t* d_out_high_confidence, hipStream_t stream);
 
+// ---- similar-chunk search (scan_similar.hip, sources: similar_sources.hpp) -------------------------------
+// What a similar-chunk search may not return, per query, and its bound: query q never gets the row whose id is
+// d_ex_ids[q] (an id no row carries: nothing) nor a row whose group is d_ex_groups[q] (CS_NO_GROUP: nothing); only rows
+// with cosine > min_cos are kept (-inf: all; never NaN).
+struct SimilarView {
+    const uint32_t* d_ex_ids = nullptr;     // [nq]
+    const uint32_t* d_ex_groups = nullptr;  // [nq]
+    float min_cos = -__builtin_huge_valf();
+};
+// d_queries[q] = the stored row d_rows[q] of d_corpus, verbatim, for q < nq (every d_rows[q] a stored row).
+int32_t launch_gather_sources(const float* d_corpus, uint32_t dim, const uint32_t* d_rows, uint32_t nq, float* d_queries,
+                              hipStream_t stream);
+// The streaming scan's arithmetic under those exclusions (plan: plan_scan): the same per-block partial lists as
+// launch_scan, for launch_merge.  gv.per_group is not read.
+int32_t launch_scan_similar(const ScanPlan& plan, const float* d_corpus, uint64_t n_rows, uint32_t dim, const float* d_queries,
+                            uint32_t nq, uint32_t k, const uint32_t* d_dead, RowIds ids, const GroupView& gv,
+                            const SimilarView& sv, uint64_t* d_partial, hipStream_t stream);
+
 // corpus[(first_out_row + r) * dim + c] = cs_synth_value(seed, (first_row + r) * dim + c)
 int32_t launch_synth_fill(float* d_rows, uint64_t n, uint32_t dim, uint64_t seed,
                           uint64_t first_row, hipStream_t stream);

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
+#include <limits>
 #include <map>
 #include <optional>
 #include <stdexcept>
@@ -208,6 +209,17 @@ class VectorStore {
         std::vector<uint32_t> ids(limit), counts(1);
         check(cs_index_search_grouped(h_, query_embedding.data(), 1, (uint32_t)query_embedding.size(), (uint32_t)limit,
                                       per_file, cos.data(), ids.data(), counts.data()));
+        return results(cos, ids, counts[0]);
+    }
+    // "More like this": the `limit` stored chunks nearest to chunk `id`'s stored row, never the chunk itself; other_files:
+    // none of its group (its file, set_groups) either.  The row is gathered and the exclusion applied on the device
+    // (cs_index_search_similar), not on a ranked list.  One index only: no sharded form yet.
+    std::vector<SearchResult> similar(uint32_t id, size_t limit, bool other_files = false) const {
+        if (sh_) throw Error(CS_ERR_UNSUPPORTED, "a sharded store has no similar-chunk search");
+        std::vector<float> cos(limit);
+        std::vector<uint32_t> ids(limit), counts(1);
+        check(cs_index_search_similar(h_, &id, 1, (uint32_t)limit, other_files ? CS_SIMILAR_EXCLUDE_GROUP : CS_SIMILAR_EXCLUDE_SELF,
+                                      -std::numeric_limits<float>::infinity(), cos.data(), ids.data(), counts.data()));
         return results(cos, ids, counts[0]);
     }
     // all query variants in one call (src/search/mod.rs:508-511)

@@ -84,6 +84,30 @@ def cap_per_group(cos, ids, groups, k: int, m: int):
     return kept_cos, kept_ids
 
 
+def drop_excluded(cos, ids, groups, src_id: int, src_group: int, mode: str, min_cos, k: int):
+    """The contract of the similar-chunk search (cs_index_search_similar) on the host: `cos` / `ids` are the live rows in
+    (cosine desc, id asc) order for the source's stored row as the query, `groups` their groups.  mode "none" drops
+    nothing, "self" the source chunk, "file" the source chunk and — when src_group is not NO_GROUP — every row of that
+    group; then rows whose cosine is not strictly greater than min_cos go (None or -inf: no bound) and the first k stay.
+    -> (cos, ids) of the kept rows, as lists."""
+    if mode not in ("none", "self", "file"):
+        raise ValueError(f'mode must be "none", "self" or "file", got {mode!r}')
+    src_id, src_group = int(src_id), int(src_group)
+    kept_cos, kept_ids = [], []
+    for c, i, g in zip(cos, ids, groups):
+        if len(kept_ids) >= k:
+            break
+        if mode != "none" and int(i) == src_id:
+            continue
+        if mode == "file" and src_group != NO_GROUP and int(g) == src_group:
+            continue
+        if min_cos is not None and not (c > min_cos):
+            continue
+        kept_cos.append(c)
+        kept_ids.append(int(i))
+    return kept_cos, kept_ids
+
+
 def merge_variants_capped(lists, group_of, k: int, m: int):
     """The contract of the grouped variants search (cs_index_search_variants_grouped[_scoped]) on the host.  `lists`: per
     query variant a (cos, ids) pair over the rows in play — the variant's full order, or any list that holds every row

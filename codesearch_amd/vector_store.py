@@ -130,6 +130,11 @@ def cos_to_score(cos):
     return np.float32(1.0) - cos_to_distance(cos)
 
 
+def score_to_cos(score):
+    """The inverse of cos_to_score: score = 1 - (1 - cos) / 2, so cos = 2 score - 1."""
+    return np.float32(2.0) * np.asarray(score, np.float32) - np.float32(1.0)
+
+
 def allow_mask(chunk_ids, next_id: int) -> np.ndarray:
     """The mask of a masked search (cs_index_search_masked): a bitmap over chunk ids [0, next_id), bit i = bit i & 31 of
     word i >> 5, set for every id in `chunk_ids`.  Ids outside [0, next_id) are dropped."""
@@ -765,6 +770,43 @@ class VectorStore:
                                                           cos.ctypes.data_as(f32p), ids.ctypes.data_as(u32p),
                                                           C.byref(count), C.byref(flag)))
         return cos, ids, int(count.value), bool(flag.value)
+
+    _SIMILAR_MODES = {"none": _lib.CS_SIMILAR_EXCLUDE_NONE, "self": _lib.CS_SIMILAR_EXCLUDE_SELF,
+                      "file": _lib.CS_SIMILAR_EXCLUDE_GROUP}
+
+    def similar_raw(self, chunk_ids, limit: int, exclude: str = "self", min_cos: Optional[float] = None):
+        """cs_index_search_similar: per source chunk id, the `limit` stored chunks nearest to that chunk's stored row —
+        the rows are gathered on the device, no vector crosses the bus — without what `exclude` names: "none" nothing
+        (the source comes back first), "self" the source chunk, "file" the source chunk and every chunk of its group
+        (its file; set_groups for rows without metadata).  The exclusion is part of the selection, not a filter on a ranked
+        list.  min_cos: only chunks whose cosine is strictly greater are returned (None: no bound).
+        -> (cos [n, limit] f32, ids [n, limit] u32, counts [n] u32); more than CS_MAX_QUERIES sources go in several calls."""
+        if self.sharded:
+            raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no similar-chunk search: no cs_shards_ form yet")
+        if exclude not in self._SIMILAR_MODES:
+            raise ValueError(f'exclude must be "self", "file" or "none", got {exclude!r}')
+        src = np.ascontiguousarray(chunk_ids, np.uint32).ravel()
+        n = src.size
+        bound = np.float32(-np.inf) if min_cos is None else np.float32(min_cos)
+        cos = np.zeros((n, max(limit, 1)), np.float32)
+        ids = np.zeros((n, max(limit, 1)), np.uint32)
+        counts = np.zeros(n, np.uint32)
+        for lo in range(0, max(n, 1), _lib.CS_MAX_QUERIES):  # (n == 0: one call, refused by the library like nq == 0)
+            hi = min(n, lo + _lib.CS_MAX_QUERIES)
+            part = src[lo:hi]
+            _lib.check(self._lib.cs_index_search_similar(self._h, part.ctypes.data_as(u32p), hi - lo, limit,
+                                                         self._SIMILAR_MODES[exclude], float(bound),
+                                                         cos[lo:hi].ctypes.data_as(f32p), ids[lo:hi].ctypes.data_as(u32p),
+                                                         counts[lo:hi].ctypes.data_as(u32p)))
+        return cos, ids, counts
+
+    def similar(self, chunk_id: int, limit: int, other_files: bool = False, min_score: Optional[float] = None) -> List[SearchResult]:
+        """The `limit` chunks most similar to chunk `chunk_id`, best first, never the chunk itself; other_files=True: none
+        of its file either (the files assigned at insert).  min_score: only chunks whose score — the reference's scale,
+        cos_to_score — is above it.  Results whose metadata is missing are skipped, as in search()."""
+        min_cos = None if min_score is None else score_to_cos(min_score)
+        cos, ids, counts = self.similar_raw([int(chunk_id)], limit, exclude="file" if other_files else "self", min_cos=min_cos)
+        return self._results(cos[0], ids[0], int(counts[0]))
 
     def chunk_ids_under(self, filter_path: str, project_root: str = "", mcp: bool = True) -> List[int]:
         """Ids of the chunks whose metadata path passes the reference's filter_path rule (search.path_matches; MCP or

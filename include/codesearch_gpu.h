@@ -313,6 +313,35 @@ CS_API int32_t cs_index_search_variants_grouped_scoped(cs_index* h, cs_scope* sc
                                                        uint32_t dim, uint32_t k, uint32_t per_group, float* out_cos,
                                                        uint32_t* out_ids, uint32_t* out_count, int32_t* out_high_confidence);
 
+/* Similar-chunk search — "which stored chunks are nearest to this stored chunk": more like this, clone and near-duplicate
+ * detection, "where else is this function copied".  The queries are chunk ids, not vectors: the source rows are gathered
+ * on the device and never leave HBM.  A caller who reads the row back, searches with it and filters the ranked list on
+ * the host gets the chunk itself first and its own file next; a vendored or generated file of near-duplicates fills all
+ * CS_MAX_K slots before anything from another file appears.  Here the exclusion is part of the selection.
+ * THE RULE, for source ids[q]: the query is that chunk's stored row, its f32 values as stored, wherever a reclaiming build
+ * has moved it; order the live rows by (cosine desc, id asc) — the order and the cosine bits of cs_index_search on the
+ * streaming route when handed that row as its query; drop the rows the mode excludes; drop the rows whose cosine is not
+ * strictly greater than min_cos (-INFINITY: no bound); keep the first k.  out_counts[q] = rows kept; the unused slots hold
+ * what every search leaves there (cosine 0, id 0xFFFFFFFF).  out_cos / out_ids: [nq][k].
+ *   - CS_SIMILAR_EXCLUDE_NONE with no bound equals cs_index_search of the row read back, bit for bit: the source comes back
+ *     first unless an identical row carries a lower id.
+ *   - CS_SIMILAR_EXCLUDE_GROUP with no group assigned equals CS_SIMILAR_EXCLUDE_SELF; so it does for a source whose group
+ *     is CS_NO_GROUP.
+ *   - Groups are the table of cs_index_set_groups: ids past its end are CS_NO_GROUP, it survives builds and applies without
+ *     one.
+ *   - Duplicate source ids are allowed (each gets its own list).  Concurrent calls are safe.
+ * Errors, in this order: those of cs_index_search with the same texts (null handle, not built, nq in 1..CS_MAX_QUERIES, k
+ * in 1..CS_MAX_K; there is no dim argument); a null buffer; exclude outside 0..2; a NaN min_cos; then the ids, the first
+ * offending one named in the text — an id never issued is CS_ERR_BAD_ARG, and so is an id issued and deleted since, with a
+ * text that says the chunk was deleted, whether its row is only tombstoned or already reclaimed.  A failing call writes
+ * nothing and launches nothing.  No cs_shards_, scoped or device-pointer form yet. */
+#define CS_SIMILAR_EXCLUDE_NONE  0   /* nothing excluded: the source chunk comes back first */
+#define CS_SIMILAR_EXCLUDE_SELF  1   /* the source chunk itself */
+#define CS_SIMILAR_EXCLUDE_GROUP 2   /* the source chunk, and every chunk of its group when that group is not CS_NO_GROUP */
+CS_API int32_t cs_index_search_similar(cs_index* h, const uint32_t* ids, uint32_t nq, uint32_t k,
+                                       int32_t exclude, float min_cos,
+                                       float* out_cos, uint32_t* out_ids, uint32_t* out_counts);
+
 /* Synchronises `stream` and reports in *overflowed whether any cs_index_search_device call of more
  * than 16 queries issued by this thread on it since the previous status call overflowed a candidate buffer
  * (its results are then incomplete); clears the condition. */
