@@ -226,6 +226,8 @@ DIAG_SIGNATURES = {
                                            C.c_uint32, u32p, C.c_uint32, f32p, i32p]),
     "cs_debug_gemm": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, f32p, f32p, f32p, f32p, f32p,
                                   C.c_uint32, C.c_uint32, C.c_uint32, u32p]),
+    "cs_debug_attention": (C.c_int32, [C.c_int32, f32p, i32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32p, C.c_uint32,
+                                       u32p, u32p, C.c_uint32, f32p, f32p, f32p, f32p, f32p, C.c_uint32, u32p, u32p]),
 }
 
 _LIB = None

@@ -554,7 +554,11 @@ attention_shx_body(char* smem, const MQ& mq, const MO& mo, const _Float16* qkvs,
         }
     }
     lsum += __shfl_xor(lsum, 32, 64);
-    const float inv = 1.0f / lsum;
+    // A query row whose wave walked no key tile (POS = 2: a padded row further than the window behind the sequence's last
+    // valid tile) has lsum = 0 and zero accumulators: it stores zeros — 0 * (1 / 0) would store NaN, which sh_split reports
+    // as out of range and the embedder answers by running the whole mini-batch again on the exact-f32 kernels.  Every row
+    // that saw a tile has lsum > 0 (its largest term is 2^(max - m) >= 1, an all-masked tile's terms are 2^0) and keeps its bits.
+    const float inv = lsum > 0.0f ? 1.0f / lsum : 0.0f;
     float rlo = 0.0f, rhi = 0.0f;  // range of what this wave stores, zero included
     if (wave_live && query < L) {
 #pragma unroll

@@ -350,6 +350,108 @@ int32_t cs_debug_gemm_q8_units(int32_t device, int32_t epilogue, const float* A,
     return st;
 }
 
+// Diagnostics: the attention kernels (E3) alone on host buffers — launch_attention_sh2 as the encoder calls it, or (proj_w
+// given) attention inside the out-projection, launch_sp_attn_proj.  Buffers hold exactly B * L token rows (the kernels
+// clamp their reads to the last one).  Contract in include/codesearch_gpu_diag.h.
+int32_t cs_debug_attention(int32_t device, const float* qkv, const int32_t* mask, uint32_t B, uint32_t L, uint32_t H,
+                           uint32_t heads, const float* alibi_slopes, uint32_t window, const uint32_t* seq_unit,
+                           const uint32_t* unit_len, uint32_t units, const float* proj_w, const float* proj_bias,
+                           const float* proj_resid, float* out, float* range_pairs_out, uint32_t range_pairs_cap,
+                           uint32_t* range_pairs, uint32_t* range_flag) {
+    if (!qkv || !mask || !out) return fail(CS_ERR_BAD_ARG, "null buffer");
+    if (B == 0 || L == 0 || H == 0 || heads == 0) return fail(CS_ERR_BAD_ARG, "cs_debug_attention needs B, L, H, heads > 0");
+    if (H % heads || (H / heads != 32 && H / heads != 64))
+        return fail(CS_ERR_UNSUPPORTED, "head_dim %u not supported (32 or 64)", H / heads);
+    if (L > 8192 || (uint64_t)B * L > (1u << 20)) return fail(CS_ERR_UNSUPPORTED, "cs_debug_attention: L <= 8192, B * L <= 2^20");
+    if ((units != 0) != (seq_unit != nullptr) || (units != 0) != (unit_len != nullptr))
+        return fail(CS_ERR_BAD_ARG, "seq_unit, unit_len and units go together");
+    for (uint32_t b = 0; b < B && units; ++b)
+        if (seq_unit[b] >= units) return fail(CS_ERR_BAD_ARG, "seq_unit[%u] = %u: only %u units", b, seq_unit[b], units);
+    if ((range_pairs_out != nullptr) != (range_pairs != nullptr) || (range_pairs_out && range_pairs_cap == 0))
+        return fail(CS_ERR_BAD_ARG, "range_pairs_out, its capacity and range_pairs go together");
+    const uint32_t T = B * L;
+    if (!proj_w != !proj_bias || !proj_w != !proj_resid) return fail(CS_ERR_BAD_ARG, "proj_w, proj_bias and proj_resid go together");
+    if (proj_w) {
+        if (alibi_slopes || window || units || range_pairs_out)
+            return fail(CS_ERR_BAD_ARG, "attention inside the out-projection takes no ALiBi, window, units or range pairs");
+        if (!sp_attn_proj_supported(H, heads, T, L))
+            return fail(CS_ERR_UNSUPPORTED, "attention + out-projection in one launch: %u rows of %u tokens, hidden %u, %u heads not built", T, L, H, heads);
+    }
+    int ndev = 0;
+    CS_HIP(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(CS_ERR_HIP, "HIP device %d not available (%d visible)", device, ndev);
+    DeviceGuard g(device);
+    const size_t q_n = (size_t)T * 3 * H, c_n = (size_t)T * H;
+    // the most pairs a launch writes: one head per block (launch_attention_sh2)
+    const size_t pair_cap = (size_t)heads * B * ((L + 127) / 128) * 4;
+    float *dQ = nullptr, *dW = nullptr, *dB = nullptr, *dR = nullptr, *dC = nullptr, *dAl = nullptr, *dRp = nullptr;
+    _Float16 *sQ = nullptr, *sW = nullptr, *sC = nullptr;
+    int32_t* dM = nullptr;
+    uint32_t *dF = nullptr, *dSu = nullptr, *dUl = nullptr;
+    auto run = [&]() -> int32_t {
+        CS_HIP(hipMalloc(&dQ, q_n * 4)); CS_HIP(hipMalloc(&sQ, q_n * 4)); CS_HIP(hipMalloc(&dM, (size_t)T * 4)); CS_HIP(hipMalloc(&dF, 4));
+        CS_HIP(hipMemcpy(dQ, qkv, q_n * 4, hipMemcpyHostToDevice));
+        CS_HIP(hipMemcpy(dM, mask, (size_t)T * 4, hipMemcpyHostToDevice));
+        CS_HIP(hipMemset(dF, 0, 4));
+        CS_TRY(launch_split_rows(dQ, sQ, T, 3 * H, dF, nullptr));
+        if (proj_w) {
+            CS_HIP(hipMalloc(&dW, (size_t)H * H * 4)); CS_HIP(hipMalloc(&sW, (size_t)H * H * 4)); CS_HIP(hipMalloc(&dB, (size_t)H * 4));
+            CS_HIP(hipMalloc(&dR, c_n * 4)); CS_HIP(hipMalloc(&dC, c_n * 4));
+            CS_HIP(hipMemcpy(dW, proj_w, (size_t)H * H * 4, hipMemcpyHostToDevice));
+            CS_HIP(hipMemcpy(dB, proj_bias, (size_t)H * 4, hipMemcpyHostToDevice));
+            CS_HIP(hipMemcpy(dR, proj_resid, c_n * 4, hipMemcpyHostToDevice));
+            CS_TRY(launch_split_rows(dW, sW, H, H, dF, nullptr));
+            CS_TRY(launch_sp_attn_proj(sQ, dM, sW, dB, dR, dC, T, L, H, heads, dF, nullptr));
+            CS_HIP(hipDeviceSynchronize());
+            CS_HIP(hipMemcpy(out, dC, c_n * 4, hipMemcpyDeviceToHost));
+            if (range_flag) CS_HIP(hipMemcpy(range_flag, dF, 4, hipMemcpyDeviceToHost));
+            return CS_OK;
+        }
+        CS_HIP(hipMalloc(&sC, c_n * 4));
+        CS_HIP(hipMemset(sC, 0, c_n * 4));
+        if (alibi_slopes) {  // [2][heads]: the slopes, then the slopes times log2 e in f32 (embedder.hip)
+            std::vector<float> sl(2 * (size_t)heads);
+            for (uint32_t i = 0; i < heads; ++i) { sl[i] = alibi_slopes[i]; sl[heads + i] = sl[i] * 1.4426950408889634f; }
+            CS_HIP(hipMalloc(&dAl, sl.size() * 4));
+            CS_HIP(hipMemcpy(dAl, sl.data(), sl.size() * 4, hipMemcpyHostToDevice));
+        }
+        if (units) {
+            CS_HIP(hipMalloc(&dSu, (size_t)B * 4)); CS_HIP(hipMalloc(&dUl, (size_t)units * 4));
+            CS_HIP(hipMemcpy(dSu, seq_unit, (size_t)B * 4, hipMemcpyHostToDevice));
+            CS_HIP(hipMemcpy(dUl, unit_len, (size_t)units * 4, hipMemcpyHostToDevice));
+        }
+        if (range_pairs_out) {
+            CS_HIP(hipMalloc(&dRp, pair_cap * 8));
+            CS_HIP(hipMemset(dRp, 0, pair_cap * 8));
+        }
+        uint32_t pairs = 0;
+        CS_TRY(launch_attention_sh2(sQ, dM, sC, dF, B, L, H, heads, nullptr, dRp, range_pairs_out ? &pairs : nullptr, dSu, dUl, dAl, window));
+        CS_HIP(hipDeviceSynchronize());
+        if (range_pairs_out) {
+            *range_pairs = pairs;
+            if (pairs > pair_cap) return fail(CS_ERR_HIP, "attention reported %u range pairs, more than one per wave (%zu)", pairs, pair_cap);
+            if (pairs > range_pairs_cap) return fail(CS_ERR_BAD_ARG, "range_pairs_out holds %u pairs, the launch wrote %u", range_pairs_cap, pairs);
+            CS_HIP(hipMemcpy(range_pairs_out, dRp, (size_t)pairs * 8, hipMemcpyDeviceToHost));
+        }
+        std::vector<_Float16> hs(c_n * 2);
+        CS_HIP(hipMemcpy(hs.data(), sC, c_n * 4, hipMemcpyDeviceToHost));
+        const size_t nch = H / 32;
+        for (size_t m = 0; m < T; ++m)
+            for (size_t n = 0; n < H; ++n) {
+                const _Float16* line = hs.data() + (m * nch + n / 32) * 64;
+                out[m * H + n] = (float)line[n % 32] + (float)line[32 + n % 32] * (1.0f / 2048.0f);
+            }
+        if (range_flag) CS_HIP(hipMemcpy(range_flag, dF, 4, hipMemcpyDeviceToHost));
+        return CS_OK;
+    };
+    const int32_t st = run();
+    if (st != CS_OK) (void)hipDeviceSynchronize();
+    for (void* p : {(void*)dQ, (void*)dW, (void*)dB, (void*)dR, (void*)dC, (void*)dAl, (void*)dRp, (void*)sQ, (void*)sW, (void*)sC,
+                    (void*)dM, (void*)dF, (void*)dSu, (void*)dUl})
+        if (p) (void)hipFree(p);
+    return st;
+}
+
 // Diagnostics: device time of one dense layer on synthetic operands already in HBM (no PCIe, no allocation inside the
 // timed region).  mode as cs_debug_gemm (0 f32 MFMA, 1 split-f16 128 x 128 / skinny kernels, 2 split-f16 wide kernel);
 // epilogue 0 f32 store, 1 GELU -> split store, 2 + residual, 3 LayerNorm-fused (mode 2, N = 384), 4 bias -> split store

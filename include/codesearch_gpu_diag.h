@@ -2,7 +2,7 @@
  * codesearch_gpu_diag.h — operator-level diagnostics of libcsgpu, exported ONLY by codesearch_amd/libcsgpu_diag.so (the
  * product library built once more with -DCS_DIAGNOSTICS: it additionally holds csrc/diagnostics.hip, the ablation
  * instantiations of the wide GEMM kernel and its in-kernel clock stamps).  Used by tests/test_gpu_gemm_split.py,
- * tests/test_gpu_quantized.py (operator parity) and benchmarks/ (A/B timing); nothing in INTEGRATION.md binds it and a
+ * tests/test_gpu_quantized.py, tests/test_gpu_attention.py (operator parity) and benchmarks/ (A/B timing); nothing in INTEGRATION.md binds it and a
  * deployment does not ship it.  The diagnostic library exports every symbol of include/codesearch_gpu.h as well, so a
  * process may use it in place of libcsgpu.so.
  */
@@ -57,6 +57,29 @@ CS_API int32_t cs_debug_gemm_q8_units(int32_t device, int32_t epilogue, const fl
  * into this library only and taken with CS_SMALL_FORWARD=1: how many mini-batches took it, and how many of those gave up at
  * a grid barrier and were re-run kernel by kernel. */
 CS_API int32_t cs_debug_small_forward_counters(cs_embedder* h, uint64_t* forwards, uint64_t* fallbacks);
+
+/* Diagnostics: the attention kernels (E3, csrc/attention_split.hip) alone on host buffers, for unit parity against a float64
+ * softmax (tests/test_gpu_attention.py).  qkv [B*L, 3H] f32, a row = Q heads | K heads | V heads, head h at columns h * dh
+ * (dh = H / heads = 32 or 64); mask [B, L], non-zero = a token.  The rows are split (launch_split_rows) and handed to
+ * launch_attention_sh2 exactly as the encoder hands them; out [B*L, H] receives the split context read back as
+ * hi + lo / 2048, padded query rows included.  Buffers hold exactly B * L rows.
+ * alibi_slopes [heads] (optional): JinaBert's ALiBi, -slope_h |i - j| on every score; the kernel receives the slopes and the
+ * slopes times log2 e in f32, as cs_embedder_create builds the table.  window (0: none): ModernBERT's local layers, keys with
+ * |i - j| > window are masked.  Both together: the launcher's CS_ERR_BAD_ARG.
+ * seq_unit [B], unit_len [units], units (all null / 0: one unit): the quantisation units of a queued device batch — query
+ * rows at or beyond unit_len[seq_unit[b]] stay out of the range pairs.
+ * range_pairs_out (optional, with range_pairs): the raw (lo, hi) float pairs every wave reports of what it stored, as the
+ * quantised path reads them; *range_pairs = how many the launcher reported, CS_ERR_BAD_ARG when that exceeds
+ * range_pairs_cap (heads * B * ceil(L / 128) * 4 always suffices).
+ * proj_w [H, H], proj_bias [H], proj_resid [B*L, H] (all or none): attention INSIDE the out-projection instead
+ * (launch_sp_attn_proj: H = 384, 12 heads, L <= 32, B * L <= 256; no ALiBi, window, units or pairs) — out [B*L, H] is then
+ * attention(qkv) proj_w^T + proj_bias + proj_resid in f32.
+ * *range_flag (optional) is set when a split-f16 value (an input or a stored context value) left the f16 range or was NaN. */
+CS_API int32_t cs_debug_attention(int32_t device, const float* qkv, const int32_t* mask, uint32_t B, uint32_t L, uint32_t H,
+                           uint32_t heads, const float* alibi_slopes, uint32_t window, const uint32_t* seq_unit,
+                           const uint32_t* unit_len, uint32_t units, const float* proj_w, const float* proj_bias,
+                           const float* proj_resid, float* out, float* range_pairs_out, uint32_t range_pairs_cap,
+                           uint32_t* range_pairs, uint32_t* range_flag);
 
 /* Diagnostics: device milliseconds per launch of one dense layer on synthetic operands resident in HBM.
  * mode 0 exact-f32 MFMA, 1 split-f16 (128 x 128 / skinny kernels), 2 split-f16 wide kernel (N % 384 == 0);

@@ -106,10 +106,37 @@ def test_padded_rows_stay_finite_and_do_not_leak(FE, oracle):
     emb = FE(cfg, seed=wseed)
     got = emb.embed_ids(ids, mask)
     assert np.isfinite(got).all()
+    assert np.isfinite(emb.last_hidden(3 * L)).all()   # padded rows included
+    # ... and on the split-f16 kernels: a NaN stored for a padded row would raise the range flag and send the whole
+    # mini-batch to the exact-f32 kernels, which the pooled output cannot show
+    assert emb.debug_counters()[:2] == (1, 0)
     alone = emb.embed_ids(ids[1:2, :20], mask[1:2, :20])
     np.testing.assert_allclose(got[1], alone[0], atol=2e-6)
     ref = oracle.bert_forward(cfg, synth_params(cfg, wseed), ids, mask)["pooled"]
     np.testing.assert_allclose(got, ref, atol=TOL_ORACLE)
+    assert emb.debug_counters()[1] == 0
+    emb.close()
+
+
+@pytest.mark.parametrize("hidden,heads,window", [(384, 12, 16), (1024, 16, 64)])
+def test_published_lengths_with_ragged_rows(FE, oracle, hidden, heads, window):
+    """The lengths the published model runs to (L = 300, 512), three layers (global, local, local), one full row, one that
+    crosses 256 tokens and one short row: beyond 256 tokens a block of the local layers skips the 128-key super-tiles no
+    query of it can see, and the short row leaves whole query blocks without a visible key."""
+    cfg = BertConfig(vocab_size=1024, hidden=hidden, layers=3, heads=heads, intermediate=1536, max_position=512, type_vocab_size=1,
+                     pooling=POOL_MEAN, arch=ARCH_MODERN, layer_norm_eps=1e-5, rotary_base=160000.0, rotary_base_local=10000.0,
+                     global_every=3, local_window=window)
+    wseed = 700 + hidden
+    params = synth_params(cfg, wseed)
+    emb = FE(cfg, seed=wseed)
+    for n, (L, lens) in enumerate(((300, [300, 270, 30]), (512, [512, 290, 40]))):
+        ids, mask = token_batch_with_lens(cfg, 800 + L, lens, L)
+        got = emb.embed_ids(ids, mask)
+        ref = oracle.bert_forward(cfg, params, ids, mask)["pooled"]
+        print("modern %d x %d heads, window %d, L %d: max |gpu - oracle| %.2e" % (hidden, heads, window, L, np.abs(got - ref).max()))
+        np.testing.assert_allclose(got, ref, atol=TOL_ORACLE)
+        np.testing.assert_allclose(np.linalg.norm(got, axis=1), 1.0, atol=1e-5)
+        assert emb.debug_counters()[:2] == (n + 1, 0)
     emb.close()
 
 
