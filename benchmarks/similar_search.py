@@ -11,14 +11,21 @@ has no streaming route for nine queries in one call.  What one call of nine rows
 once per shape and not alternated with the new call: on the library's default route (the int8 filter + exact refine: baseline_one_call_default_ms) and
 with the filter switched off (five or more queries then take the exact-f32 MFMA path: baseline_one_call_nofilter_ms).
 
-    python benchmarks/similar_search.py [--rows 10000000] [--dim 384] [--reps 20] [--out FILE] [--tree DIR]
+    python benchmarks/similar_search.py [--rows 10000000] [--dim 384] [--reps 20] [--out FILE] [--tree DIR] [--scoped]
 
 The store: synthetic rows in files of 8 ids, with rows [2/10, 3/10) of it replaced by one file of near-duplicates of its
 first row (0.95 s + 0.05 noise).  The "hog" source is that first row; the "ordinary" source is a row far from the file.
 With 9 sources per call the other 8 are ordinary rows.
 
 --tree DIR: load the package and the library of another checkout (the parent commit's, built): the entry point it lacks is
-not timed, so the same script gives the baseline's times under the parent's library."""
+not timed, so the same script gives the baseline's times under the parent's library.
+
+--scoped: the scoped cases instead (cs_index_search_similar_scoped) over the same store: scopes of every id, a random 10 %, a
+random 1 % and the near-duplicate file plus a random 1 %; the source is the file's first row for the last scope and the
+ordinary row for the others, which does not lie in the random scopes' ids unless drawn.  The baseline is what a caller can
+do without the call: one read per source (cs_index_read_rows), then ONE cs_index_search_scoped of those rows with the
+scope on CS_SCOPE_ROUTE_GATHER at k + 1, the excluded rows dropped on the host — exact for "self" only.  The same
+alternation, and baseline_exact_found as above."""
 import argparse
 import json
 import os
@@ -39,6 +46,64 @@ def timed(fn, reps):
     return ts
 
 
+def scoped_cases(a, st, lib, h, _lib, emit, sources, others, groups, hog_lo, hog_n, modes, med):
+    from codesearch_amd._lib import f32p, u32p
+
+    n, dim = a.rows, a.dim
+    has_new = "cs_index_search_similar_scoped" in _lib.SIGNATURES
+    rng = np.random.default_rng(3)
+    tenth, hundredth = np.sort(rng.choice(n, n // 10, replace=False)), np.sort(rng.choice(n, n // 100, replace=False))
+    hog = np.union1d(np.arange(hog_lo, hog_lo + hog_n), np.sort(rng.choice(n, n // 100, replace=False)))
+    for sname, ids, kind in (("all", np.arange(n), "ordinary"), ("10%", tenth, "ordinary"), ("1%", hundredth, "ordinary"),
+                             ("hog+1%", hog, "hog")):
+        sc = st.scope(ids)
+        sc.set_route("gather")
+        in_scope = np.zeros(n, bool)
+        in_scope[ids] = True
+        src = sources[kind]
+        for nq in (1, 9):
+            srcs = np.ascontiguousarray(np.concatenate([[src], others[:nq - 1]]), np.uint32)
+            rows = np.zeros((nq, dim), np.float32)
+            for k in (10, 200):
+                cos, idb, cnt = np.zeros((nq, k), np.float32), np.zeros((nq, k), np.uint32), np.zeros(nq, np.uint32)
+                bcos, bid, bcnt = np.zeros((nq, k + 1), np.float32), np.zeros((nq, k + 1), np.uint32), np.zeros(nq, np.uint32)
+
+                def baseline():
+                    for q in range(nq):
+                        _lib.check(lib.cs_index_read_rows(h, int(srcs[q]), 1, rows[q:q + 1].ctypes.data_as(f32p)))
+                    _lib.check(lib.cs_index_search_scoped(h, sc.handle, rows.ctypes.data_as(f32p), nq, dim, k + 1,
+                                                          bcos.ctypes.data_as(f32p), bid.ctypes.data_as(u32p),
+                                                          bcnt.ctypes.data_as(u32p)))
+
+                for mname, mode in modes.items():
+                    for bound in (None, 0.9):
+                        rec = {"scope": sname, "scope_ids": int(ids.size), "source": kind, "source_in_scope": bool(in_scope[src]),
+                               "rows": n, "dim": dim, "nq": nq, "k": k, "mode": mname, "min_cos": bound, "reps": a.reps,
+                               "library": "new" if has_new else "parent"}
+                        if has_new:
+                            def similar():
+                                _lib.check(lib.cs_index_search_similar_scoped(h, sc.handle, srcs.ctypes.data_as(u32p), nq, k, mode,
+                                                                              float("-inf") if bound is None else bound,
+                                                                              cos.ctypes.data_as(f32p), idb.ctypes.data_as(u32p),
+                                                                              cnt.ctypes.data_as(u32p)))
+
+                            t1 = timed(similar, a.reps)
+                            tb = timed(baseline, a.reps)
+                            t2 = timed(similar, a.reps)
+                            rec.update({"similar_ms": med(t1 + t2), "similar_before_ms": med(t1), "similar_after_ms": med(t2),
+                                        "baseline_ms": med(tb), "count": int(cnt[0])})
+                            rec["ratio_vs_baseline"] = round(rec["similar_ms"] / rec["baseline_ms"], 4)
+                            kept = [int(i) for i, c in zip(bid[0][:bcnt[0]], bcos[0][:bcnt[0]])
+                                    if (mode == 0 or i != src) and (mode != 2 or groups[i] != groups[src])
+                                    and (bound is None or c > bound)][:k]
+                            rec["baseline_hits"] = len(kept)
+                            rec["baseline_exact_found"] = len(set(kept) & set(idb[0][:cnt[0]].tolist()))
+                        else:
+                            rec["baseline_ms"] = med(timed(baseline, a.reps))
+                        emit(rec)
+        sc.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=10_000_000)
@@ -46,6 +111,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default="")
     ap.add_argument("--tree", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    ap.add_argument("--scoped", action="store_true")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.tree))
     from codesearch_amd import VectorStore, _lib
@@ -88,6 +154,9 @@ def main():
     kinds = [("ordinary", np.uint32(n - n // 7)), ("hog", np.uint32(hog_lo))]
     modes = {"none": 0, "self": 1, "file": 2}
     med = lambda t: round(float(np.median(t)), 4)  # noqa: E731
+    if a.scoped:
+        scoped_cases(a, st, lib, h, _lib, emit, dict(kinds), others, groups, hog_lo, hog_n, modes, med)
+        kinds = []
     for kind, src in kinds:
         for nq in (1, 9):
             srcs = np.ascontiguousarray(np.concatenate([[src], others[:nq - 1]]), np.uint32)

@@ -99,6 +99,8 @@ SIGNATURES = {
     "cs_index_search_variants_grouped_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32p,
                                                             u32p, u32p, i32p]),
     "cs_index_search_similar": (C.c_int32, [vp, u32p, C.c_uint32, C.c_uint32, C.c_int32, C.c_float, f32p, u32p, u32p]),
+    "cs_index_search_similar_scoped": (C.c_int32, [vp, vp, u32p, C.c_uint32, C.c_uint32, C.c_int32, C.c_float, f32p, u32p,
+                                                   u32p]),
     "cs_index_search_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p]),
     "cs_index_search_variants_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p,
                                                     i32p]),

@@ -810,13 +810,19 @@ int32_t scope_make_list(cs_index* h, cs_scope* sc) {
     return CS_OK;
 }
 
+// The handle-level checks of a scoped search: they read nothing that a refresh writes and take no lock.
+int32_t check_scope_handle(const cs_index* h, const cs_scope* sc) {
+    if (!sc) return fail(CS_ERR_BAD_ARG, "null scope handle");
+    if (sc->index != h) return fail(CS_ERR_BAD_ARG, "the scope was made for another store");
+    return CS_OK;
+}
+
 // The checks of a scoped search behind check_search's, then the refresh when one is due: *live = the list's length.
 // fp != null (the host-buffer searches of nq queries, top-k): the search's route too — fp->ok says that it wants the
 // int8 filter and holds its plan (scoped_filter_plan.hpp; host arithmetic over what the scope keeps, under its mutex).
 int32_t scope_ready(cs_index* h, cs_scope* sc, uint64_t* live, ScopedFilterPlan* fp = nullptr, uint32_t nq = 0,
                     uint32_t k = 0) {
-    if (!sc) return fail(CS_ERR_BAD_ARG, "null scope handle");
-    if (sc->index != h) return fail(CS_ERR_BAD_ARG, "the scope was made for another store");
+    CS_TRY(check_scope_handle(h, sc));
     std::lock_guard<std::mutex> lk(sc->mu);
     if (scope_refresh_due(sc->generation, h->build_gen.load())) CS_TRY(scope_make_list(h, sc));
     *live = sc->live_rows;
@@ -1087,16 +1093,20 @@ int32_t search_grouped(cs_index* h, bool scope_given, cs_scope* scope, const flo
     });
 }
 
-// The similar-chunk search (scan_similar.hip): the sources resolved on the host (similar_sources.hpp), their rows gathered
-// into w->d_queries on the device, the streaming scan's arithmetic under the per-query exclusions, the ordinary merge.
-int32_t search_similar(cs_index* h, const uint32_t* ids, uint32_t nq, uint32_t k, int32_t exclude, float min_cos,
-                       const HostAnswer& out) {
+// The similar-chunk searches (scan_similar.hip): the sources resolved on the host (similar_sources.hpp), their rows gathered
+// into w->d_queries on the device, the scan's arithmetic under the per-query exclusions, the ordinary merge.  Over the whole
+// store (scope_given false: the streaming scan over every stored row) or over a scope's row list (the gathered scan, always,
+// as for the grouped search).  Every check, the scope's handle-level ones before the ids, comes before the scope's list is
+// refreshed; groups_mu is released before the scope's mutex is taken.
+int32_t search_similar(cs_index* h, bool scope_given, cs_scope* scope, const uint32_t* ids, uint32_t nq, uint32_t k,
+                       int32_t exclude, float min_cos, const HostAnswer& out) {
     if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
     CS_TRY(check_search(h, nq, h->dim, k));
     if (!ids || !out.cos || !out.ids || !out.counts) return fail(CS_ERR_BAD_ARG, "null buffer");
     if (!similar_mode_ok(exclude))
         return fail(CS_ERR_BAD_ARG, "exclude must be CS_SIMILAR_EXCLUDE_NONE, _SELF or _GROUP (0..2), got %d", exclude);
     if (min_cos != min_cos) return fail(CS_ERR_BAD_ARG, "min_cos is NaN");
+    if (scope_given) CS_TRY(check_scope_handle(h, scope));
     DeviceGuard g(h->device);
     GroupView gv{nullptr, 0, h->ledger.id_base(), 0xFFFFFFFFu};
     {
@@ -1108,8 +1118,13 @@ int32_t search_similar(cs_index* h, const uint32_t* ids, uint32_t nq, uint32_t k
         if (sc.fault == SourceFault::Deleted)
             return fail(CS_ERR_BAD_ARG, "ids[%u] = %u: the chunk was deleted", sc.at, ids[sc.at]);
     }
+    uint64_t rows = h->ledger.stored();
+    if (scope_given) {
+        CS_TRY(scope_ready(h, scope, &rows));
+        if (rows == 0) return empty_answer(nq, k, out);  // nothing of the scope is stored
+    }
     if (exclude == CS_SIMILAR_EXCLUDE_GROUP) CS_TRY(ensure_groups(h, 0xFFFFFFFFu, &gv));
-    const ScanPlan plan = plan_scan(h->ledger.stored(), h->dim, nq, k, h->num_cus);
+    const ScanPlan plan = plan_scan(rows, h->dim, nq, k, h->num_cus);  // a scope: the grid follows the list's length
     return host_search(h, nullptr, nq, k, plan.partial_keys, plan.merge_keys, out, [&](Workspace* w, uint64_t* keys) {
         CS_TRY(w->reserve_similar(nq));
         {
@@ -1119,8 +1134,14 @@ int32_t search_similar(cs_index* h, const uint32_t* ids, uint32_t nq, uint32_t k
         CS_HIP(hipMemcpyAsync(w->d_similar, w->h_similar, 3 * (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice, w->stream));
         CS_TRY(launch_gather_sources(h->d_corpus, h->dim, w->d_similar, nq, w->d_queries, w->stream));
         const SimilarView sv{w->d_similar + nq, w->d_similar + 2 * (size_t)nq, min_cos};
-        CS_TRY(launch_scan_similar(plan, h->d_corpus, h->ledger.stored(), h->dim, w->d_queries, nq, k,
-                                   h->ledger.removed() ? h->d_dead : nullptr, h->row_ids(), gv, sv, w->d_partial, w->stream));
+        if (scope_given) {
+            scope->gathered_searches.fetch_add(1);
+            CS_TRY(launch_scan_similar_list(plan, h->d_corpus, h->dim, scope->d_list, scope->d_blocks + scope_list_blocks(scope->n_ids),
+                                            w->d_queries, nq, k, h->row_ids(), gv, sv, w->d_partial, w->stream));
+        } else {
+            CS_TRY(launch_scan_similar(plan, h->d_corpus, h->ledger.stored(), h->dim, w->d_queries, nq, k,
+                                       h->ledger.removed() ? h->d_dead : nullptr, h->row_ids(), gv, sv, w->d_partial, w->stream));
+        }
         return launch_merge(w->d_partial, plan.blocks, nq, k, false, w->d_tmp_a, w->d_tmp_b, keys, nullptr, nullptr, nullptr,
                             w->stream);
     });
@@ -1460,7 +1481,12 @@ int32_t cs_index_search_variants_grouped(cs_index* h, const float* queries, uint
 
 int32_t cs_index_search_similar(cs_index* h, const uint32_t* ids, uint32_t nq, uint32_t k, int32_t exclude, float min_cos,
                                 float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
-    return search_similar(h, ids, nq, k, exclude, min_cos, HostAnswer{out_cos, out_ids, out_counts, nullptr, false});
+    return search_similar(h, false, nullptr, ids, nq, k, exclude, min_cos, HostAnswer{out_cos, out_ids, out_counts, nullptr, false});
+}
+
+int32_t cs_index_search_similar_scoped(cs_index* h, cs_scope* scope, const uint32_t* ids, uint32_t nq, uint32_t k,
+                                       int32_t exclude, float min_cos, float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
+    return search_similar(h, true, scope, ids, nq, k, exclude, min_cos, HostAnswer{out_cos, out_ids, out_counts, nullptr, false});
 }
 
 int32_t cs_index_scope_create(cs_index* h, const uint32_t* ids, uint64_t n, cs_scope** out) {

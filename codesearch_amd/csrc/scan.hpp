@@ -154,6 +154,12 @@ int32_t launch_gather_sources(const float* d_corpus, uint32_t dim, const uint32_
 int32_t launch_scan_similar(const ScanPlan& plan, const float* d_corpus, uint64_t n_rows, uint32_t dim, const float* d_queries,
                             uint32_t nq, uint32_t k, const uint32_t* d_dead, RowIds ids, const GroupView& gv,
                             const SimilarView& sv, uint64_t* d_partial, hipStream_t stream);
+// launch_scan_similar over the live rows d_list[0, *d_list_len) (a scope's row list, ascending; plan: plan_scan of the
+// length): the gathered scan's arithmetic under those exclusions, the same per-block partial lists, for launch_merge.  The
+// list holds live rows only: no tombstone test.
+int32_t launch_scan_similar_list(const ScanPlan& plan, const float* d_corpus, uint32_t dim, const uint32_t* d_list,
+                                 const uint32_t* d_list_len, const float* d_queries, uint32_t nq, uint32_t k, RowIds ids,
+                                 const GroupView& gv, const SimilarView& sv, uint64_t* d_partial, hipStream_t stream);
 
 // corpus[(first_out_row + r) * dim + c] = cs_synth_value(seed, (first_row + r) * dim + c)
 int32_t launch_synth_fill(float* d_rows, uint64_t n, uint32_t dim, uint64_t seed,

@@ -15,6 +15,9 @@
 //      inserted.  The queries of one tile carry different exclusions.
 //   3. merge: a wave's list holds only rows the answer may contain, so no level needs a cap: the block merge
 //      (block_merge_store) and the ordinary launch_merge finish it, on plan_scan's geometry.
+//   4. inside a scope (cs_index_search_similar_scoped): step 2 over the scope's row list instead of every stored row —
+//      the gathered scan's tile loop (scan_masked.hip part 2) with this file's list state and slow path: the end of the
+//      kernels below.  Steps 1 and 3 are the same.
 #include "scan.hpp"
 #include "grouped_plan.hpp"  // kNoGroup
 #include "scan_wave.hpp"
@@ -167,6 +170,146 @@ scan_similar_generic_kernel(const float* __restrict__ corpus, uint64_t n_rows, u
     block_merge_store(lds_keys, kpad, k, q, tid, partial);
 }
 
+// ---- 4. scan over a scope's row list ------------------------------------------------------------------------
+// scan_masked_topk_kernel's tile loop (scan_masked.hip part 2, not its prime pass) under scan_similar_topk_kernel's list
+// state and slow path: half-wave h of tile t scores row rows[t * 2U + 2u + h] of the list rows[0, *rows_len).  The list
+// holds live rows only (launch_scope_rows), in ascending row order, so there is no tombstone read and a wave still meets
+// its rows in ascending id.  A row that beats the threshold resolves its id, is tested against the query's exclusions and
+// only then inserted.
+//
+// Registers: plan_scan sizes the grid to be fully resident from the streaming scan's occupancy, and at 384-d with four queries
+// per pass that is three blocks per CU: 168 VGPRs.  The unscoped kernel has 167 and the masked scan 168; this one came out
+// at 169, which the allocation granule of 8 turns into two blocks per CU and a grid with a second round of blocks (DESIGN.md
+// §8d).  That shape alone therefore declares the three waves per SIMD it is launched for; every other shape is launched at
+// one or two blocks per CU and fits as it is.
+template <int J, int QT>
+constexpr int similar_list_waves_per_simd() { return (J == 3 && QT == 4) ? 3 : 1; }
+
+template <int J, int U, int QT>
+__global__ void __launch_bounds__(kBlock, (similar_list_waves_per_simd<J, QT>()))
+scan_similar_list_kernel(const float* __restrict__ corpus, const uint32_t* __restrict__ rows,
+                         const uint32_t* __restrict__ rows_len, const float* __restrict__ queries, uint32_t nq, uint32_t k,
+                         uint32_t kpad, RowIds row_ids, GroupView gv, const uint32_t* __restrict__ ex_ids,
+                         const uint32_t* __restrict__ ex_groups, float min_cos, uint64_t* __restrict__ partial) {
+    extern __shared__ __attribute__((aligned(16))) uint64_t lds_keys[];  // [QT][kWaves][kpad]
+    constexpr int DIM = 128 * J;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int half = lane >> 5;
+    const int l32 = lane & 31;
+    const uint32_t q0 = blockIdx.y * QT;
+    const uint64_t n_list = *rows_len;
+
+    for (uint32_t i = tid; i < QT * kWaves * kpad; i += kBlock) lds_keys[i] = 0ull;
+
+    f32x4 qf[QT][J];  // a pass past the last query re-reads query nq - 1 (its results are never stored)
+    float qmag[QT];
+    float thr[QT], floor[QT];
+    uint32_t wpos[QT], ex_id[QT], ex_group[QT];
+#pragma unroll
+    for (int qi = 0; qi < QT; ++qi) {
+        const uint32_t q = (q0 + qi < nq) ? (q0 + qi) : (nq - 1);
+        qmag[qi] = load_query_fragment<J>(queries, q, l32, qf[qi]);
+        ex_id[qi] = ex_ids[q];
+        ex_group[qi] = ex_groups[q];
+        floor[qi] = min_cos;
+        thr[qi] = floor[qi];
+        wpos[qi] = 0;
+    }
+    __syncthreads();
+
+    const uint64_t gw = (uint64_t)blockIdx.x * kWaves + wave;
+    const uint64_t nw = (uint64_t)gridDim.x * kWaves;
+    const uint64_t ntiles = (n_list + 2 * U - 1) / (2 * U);
+
+    for (uint64_t tile = gw; tile < ntiles; tile += nw) {
+        const uint64_t e0 = tile * (2 * U);  // list entries of this tile
+        f32x4 x[U][J];
+        uint32_t row[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            uint64_t e = e0 + 2 * u + half;
+            e = e < n_list ? e : n_list - 1;  // tail entries re-read the last entry, masked below
+            row[u] = rows[e];
+            const f32x4* p = reinterpret_cast<const f32x4*>(corpus + (uint64_t)row[u] * DIM) + l32;
+#pragma unroll
+            for (int j = 0; j < J; ++j) x[u][j] = __builtin_nontemporal_load(p + j * 32);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            float dot[QT];
+            const float xmag = row_products<J, QT>(x[u], qf, dot);
+            const bool valid = e0 + 2 * u + half < n_list;
+#pragma unroll
+            for (int qi = 0; qi < QT; ++qi) {
+                const float d = half_allreduce_sum(dot[qi]);
+                const float c = cosine_of(d, qmag[qi], xmag);
+                unsigned long long m = __ballot(valid && l32 == 0 && c > thr[qi]);
+                if (m) {  // rare: wave-uniform slow path; half 0 (the lower list entry) first
+                    volatile uint64_t* list = lds_keys + ((size_t)qi * kWaves + wave) * kpad;
+                    while (m) {
+                        const int src = __ffsll((long long)m) - 1;
+                        m &= m - 1;
+                        const float cc = __shfl(c, src, 64);
+                        const uint32_t rr = __shfl(row[u], src, 64);
+                        if (cc > thr[qi]) {
+                            const uint32_t id = row_ids.of(rr);
+                            if (similar_keeps(gv, id, ex_id[qi], ex_group[qi]))
+                                wave_list_insert(list, k, lane, cc, id, thr[qi], wpos[qi], floor[qi]);
+                        }
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+
+    const uint32_t nsort = kWaves * kpad;
+#pragma unroll 1
+    for (int qi = 0; qi < QT; ++qi) {
+        if (q0 + qi >= nq) break;
+        block_merge_store(lds_keys + (size_t)qi * nsort, kpad, k, q0 + qi, tid, partial);
+    }
+}
+
+// Any other dim: one wave per list entry, lanes stride over columns (wave_row_cosine, scan_wave.hpp).  A template only to
+// be emitted with the instantiations, behind every kernel this file already had: their labels keep their numbers, so their
+// device code stays the same text (benchmarks/compare_device_code.py).
+template <int = 0>
+__global__ void __launch_bounds__(kBlock)
+scan_similar_list_generic_kernel(const float* __restrict__ corpus, const uint32_t* __restrict__ rows,
+                                 const uint32_t* __restrict__ rows_len, uint32_t dim, const float* __restrict__ queries,
+                                 uint32_t nq, uint32_t k, uint32_t kpad, RowIds row_ids, GroupView gv,
+                                 const uint32_t* __restrict__ ex_ids, const uint32_t* __restrict__ ex_groups, float min_cos,
+                                 uint64_t* __restrict__ partial) {
+    extern __shared__ __attribute__((aligned(16))) uint64_t lds_keys[];  // [kWaves][kpad]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t q = blockIdx.y;
+    const uint64_t n_list = *rows_len;
+    for (uint32_t i = tid; i < kWaves * kpad; i += kBlock) lds_keys[i] = 0ull;
+    const float* qp = queries + (size_t)q * dim;
+    const float qmag = wave_query_mag(qp, dim, lane);
+    const uint32_t ex_id = ex_ids[q], ex_group = ex_groups[q];
+    float thr = min_cos;
+    uint32_t wpos = 0;
+    __syncthreads();
+    volatile uint64_t* list = lds_keys + (size_t)wave * kpad;
+    const uint64_t gw = (uint64_t)blockIdx.x * kWaves + wave;
+    const uint64_t nw = (uint64_t)gridDim.x * kWaves;
+    for (uint64_t e = gw; e < n_list; e += nw) {
+        const uint32_t r = rows[e];
+        const float* xp = corpus + (uint64_t)r * dim;
+        const float c = wave_row_cosine(xp, qp, dim, lane, qmag);
+        if (c > thr) {  // wave-uniform
+            const uint32_t id = row_ids.of(r);
+            if (similar_keeps(gv, id, ex_id, ex_group)) wave_list_insert(list, k, lane, c, id, thr, wpos, min_cos);
+        }
+    }
+    __syncthreads();
+    block_merge_store(lds_keys, kpad, k, q, tid, partial);
+}
+
 // ---- host side ------------------------------------------------------------------------------------------
 
 int32_t launch_gather_sources(const float* d_corpus, uint32_t dim, const uint32_t* d_rows, uint32_t nq, float* d_queries,
@@ -221,6 +364,53 @@ int32_t launch_scan_similar(const ScanPlan& plan, const float* d_corpus, uint64_
         const size_t lds = (size_t)kWaves * plan.kpad * sizeof(uint64_t);
         hipLaunchKernelGGL(scan_similar_generic_kernel, dim3(plan.blocks, nq), dim3(kBlock), lds, stream, d_corpus, n_rows, dim,
                            d_queries, nq, k, plan.kpad, d_dead, ids, gv, sv.d_ex_ids, sv.d_ex_groups, sv.min_cos, d_partial);
+    }
+    CS_HIP(hipGetLastError());
+    return CS_OK;
+}
+
+template <int J, int U, int QT>
+static void launch_similar_list_fast(const ScanPlan& plan, const float* d_corpus, const uint32_t* d_list, const uint32_t* d_len,
+                                     const float* d_queries, uint32_t nq, uint32_t k, RowIds ids, const GroupView& gv,
+                                     const SimilarView& sv, uint64_t* d_partial, hipStream_t stream) {
+    const size_t lds = (size_t)QT * kWaves * plan.kpad * sizeof(uint64_t);
+    hipLaunchKernelGGL((scan_similar_list_kernel<J, U, QT>), dim3(plan.blocks, plan.passes), dim3(kBlock), lds, stream,
+                       d_corpus, d_list, d_len, d_queries, nq, k, plan.kpad, ids, gv, sv.d_ex_ids, sv.d_ex_groups, sv.min_cos,
+                       d_partial);
+}
+
+template <int J, int U>
+static void launch_similar_list_q(const ScanPlan& plan, const float* d_corpus, const uint32_t* d_list, const uint32_t* d_len,
+                                  const float* d_queries, uint32_t nq, uint32_t k, RowIds ids, const GroupView& gv,
+                                  const SimilarView& sv, uint64_t* d_partial, hipStream_t stream) {
+    switch (plan.qtile) {
+        case 4: launch_similar_list_fast<J, U, 4>(plan, d_corpus, d_list, d_len, d_queries, nq, k, ids, gv, sv, d_partial, stream); break;
+        case 2: launch_similar_list_fast<J, U, 2>(plan, d_corpus, d_list, d_len, d_queries, nq, k, ids, gv, sv, d_partial, stream); break;
+        default: launch_similar_list_fast<J, U, 1>(plan, d_corpus, d_list, d_len, d_queries, nq, k, ids, gv, sv, d_partial, stream); break;
+    }
+}
+
+int32_t launch_scan_similar_list(const ScanPlan& plan, const float* d_corpus, uint32_t dim, const uint32_t* d_list,
+                                 const uint32_t* d_list_len, const float* d_queries, uint32_t nq, uint32_t k, RowIds ids,
+                                 const GroupView& gv, const SimilarView& sv, uint64_t* d_partial, hipStream_t stream) {
+    if (!sv.d_ex_ids || !sv.d_ex_groups || sv.min_cos != sv.min_cos)
+        return fail(CS_ERR_BAD_ARG, "similar scan needs its exclusion arrays and a bound that is a number");
+    if (!d_list || !d_list_len) return fail(CS_ERR_BAD_ARG, "similar scan over a row list needs the list and its length");
+    if (plan.kpad < k || plan.qtile < 1 || (size_t)plan.qtile * kWaves * plan.kpad * sizeof(uint64_t) > 64 * 1024)
+        return fail(CS_ERR_BAD_ARG, "similar scan plan does not fit: qtile %u, kpad %u for k %u", plan.qtile, plan.kpad, k);
+    const bool fast = dim == 384 || dim == 768 || dim == 1024;
+    if (fast && plan.deep && plan.qtile == 1) {  // the streaming scan's deep shapes (scan.hip scan_deep)
+        if (dim == 384) launch_similar_list_fast<3, 8, 1>(plan, d_corpus, d_list, d_list_len, d_queries, nq, k, ids, gv, sv, d_partial, stream);
+        else if (dim == 768) launch_similar_list_fast<6, 4, 1>(plan, d_corpus, d_list, d_list_len, d_queries, nq, k, ids, gv, sv, d_partial, stream);
+        else launch_similar_list_fast<8, 3, 1>(plan, d_corpus, d_list, d_list_len, d_queries, nq, k, ids, gv, sv, d_partial, stream);
+    } else if (dim == 384) launch_similar_list_q<3, 4>(plan, d_corpus, d_list, d_list_len, d_queries, nq, k, ids, gv, sv, d_partial, stream);
+    else if (dim == 768) launch_similar_list_q<6, 2>(plan, d_corpus, d_list, d_list_len, d_queries, nq, k, ids, gv, sv, d_partial, stream);
+    else if (dim == 1024) launch_similar_list_q<8, 2>(plan, d_corpus, d_list, d_list_len, d_queries, nq, k, ids, gv, sv, d_partial, stream);
+    else {
+        const size_t lds = (size_t)kWaves * plan.kpad * sizeof(uint64_t);
+        hipLaunchKernelGGL(scan_similar_list_generic_kernel<>, dim3(plan.blocks, nq), dim3(kBlock), lds, stream, d_corpus, d_list,
+                           d_list_len, dim, d_queries, nq, k, plan.kpad, ids, gv, sv.d_ex_ids, sv.d_ex_groups, sv.min_cos,
+                           d_partial);
     }
     CS_HIP(hipGetLastError());
     return CS_OK;

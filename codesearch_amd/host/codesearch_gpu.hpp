@@ -363,6 +363,17 @@ class VectorStore {
                                              (uint32_t)limit, per_file, cos.data(), ids.data(), counts.data()));
         return results(cos, ids, counts[0]);
     }
+    // similar() among the chunks of a Scope only (cs_index_search_similar_scoped): "where else under src/ is this copied".
+    // Chunk `id` itself need not be in the scope.  One index only.
+    std::vector<SearchResult> similar(uint32_t id, size_t limit, bool other_files, const Scope& scope) const {
+        if (sh_) throw Error(CS_ERR_UNSUPPORTED, "a sharded store has no similar-chunk search");
+        std::vector<float> cos(limit);
+        std::vector<uint32_t> ids(limit), counts(1);
+        check(cs_index_search_similar_scoped(h_, scope.handle(), &id, 1, (uint32_t)limit,
+                                             other_files ? CS_SIMILAR_EXCLUDE_GROUP : CS_SIMILAR_EXCLUDE_SELF,
+                                             -std::numeric_limits<float>::infinity(), cos.data(), ids.data(), counts.data()));
+        return results(cos, ids, counts[0]);
+    }
     std::vector<SearchResult> search_variants_per_file(const std::vector<std::vector<float>>& variants, size_t limit,
                                                        uint32_t per_file, const Scope* scope = nullptr,
                                                        bool* high_confidence = nullptr) const {

@@ -774,12 +774,15 @@ class VectorStore:
     _SIMILAR_MODES = {"none": _lib.CS_SIMILAR_EXCLUDE_NONE, "self": _lib.CS_SIMILAR_EXCLUDE_SELF,
                       "file": _lib.CS_SIMILAR_EXCLUDE_GROUP}
 
-    def similar_raw(self, chunk_ids, limit: int, exclude: str = "self", min_cos: Optional[float] = None):
+    def similar_raw(self, chunk_ids, limit: int, exclude: str = "self", min_cos: Optional[float] = None,
+                    scope: Optional[Scope] = None):
         """cs_index_search_similar: per source chunk id, the `limit` stored chunks nearest to that chunk's stored row —
         the rows are gathered on the device, no vector crosses the bus — without what `exclude` names: "none" nothing
         (the source comes back first), "self" the source chunk, "file" the source chunk and every chunk of its group
         (its file; set_groups for rows without metadata).  The exclusion is part of the selection, not a filter on a ranked
         list.  min_cos: only chunks whose cosine is strictly greater are returned (None: no bound).
+        scope: only the scope's chunks are returned (cs_index_search_similar_scoped: the exact best `limit` among them); the
+        sources themselves need not be in it.
         -> (cos [n, limit] f32, ids [n, limit] u32, counts [n] u32); more than CS_MAX_QUERIES sources go in several calls."""
         if self.sharded:
             raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no similar-chunk search: no cs_shards_ form yet")
@@ -791,21 +794,28 @@ class VectorStore:
         cos = np.zeros((n, max(limit, 1)), np.float32)
         ids = np.zeros((n, max(limit, 1)), np.uint32)
         counts = np.zeros(n, np.uint32)
+        if scope is None:
+            call = lambda *a: self._lib.cs_index_search_similar(self._h, *a)
+        else:
+            sc = self._scope_handle(scope)
+            call = lambda *a: self._lib.cs_index_search_similar_scoped(self._h, sc, *a)
         for lo in range(0, max(n, 1), _lib.CS_MAX_QUERIES):  # (n == 0: one call, refused by the library like nq == 0)
             hi = min(n, lo + _lib.CS_MAX_QUERIES)
             part = src[lo:hi]
-            _lib.check(self._lib.cs_index_search_similar(self._h, part.ctypes.data_as(u32p), hi - lo, limit,
-                                                         self._SIMILAR_MODES[exclude], float(bound),
-                                                         cos[lo:hi].ctypes.data_as(f32p), ids[lo:hi].ctypes.data_as(u32p),
-                                                         counts[lo:hi].ctypes.data_as(u32p)))
+            _lib.check(call(part.ctypes.data_as(u32p), hi - lo, limit, self._SIMILAR_MODES[exclude], float(bound),
+                            cos[lo:hi].ctypes.data_as(f32p), ids[lo:hi].ctypes.data_as(u32p),
+                            counts[lo:hi].ctypes.data_as(u32p)))
         return cos, ids, counts
 
-    def similar(self, chunk_id: int, limit: int, other_files: bool = False, min_score: Optional[float] = None) -> List[SearchResult]:
+    def similar(self, chunk_id: int, limit: int, other_files: bool = False, min_score: Optional[float] = None,
+                scope: Optional[Scope] = None) -> List[SearchResult]:
         """The `limit` chunks most similar to chunk `chunk_id`, best first, never the chunk itself; other_files=True: none
         of its file either (the files assigned at insert).  min_score: only chunks whose score — the reference's scale,
-        cos_to_score — is above it.  Results whose metadata is missing are skipped, as in search()."""
+        cos_to_score — is above it.  scope: only chunks of the scope (similar_raw).  Results whose metadata is missing are
+        skipped, as in search()."""
         min_cos = None if min_score is None else score_to_cos(min_score)
-        cos, ids, counts = self.similar_raw([int(chunk_id)], limit, exclude="file" if other_files else "self", min_cos=min_cos)
+        cos, ids, counts = self.similar_raw([int(chunk_id)], limit, exclude="file" if other_files else "self", min_cos=min_cos,
+                                            scope=scope)
         return self._results(cos[0], ids[0], int(counts[0]))
 
     def chunk_ids_under(self, filter_path: str, project_root: str = "", mcp: bool = True) -> List[int]:

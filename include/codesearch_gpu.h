@@ -334,13 +334,34 @@ CS_API int32_t cs_index_search_variants_grouped_scoped(cs_index* h, cs_scope* sc
  * in 1..CS_MAX_K; there is no dim argument); a null buffer; exclude outside 0..2; a NaN min_cos; then the ids, the first
  * offending one named in the text — an id never issued is CS_ERR_BAD_ARG, and so is an id issued and deleted since, with a
  * text that says the chunk was deleted, whether its row is only tombstoned or already reclaimed.  A failing call writes
- * nothing and launches nothing.  No cs_shards_, scoped or device-pointer form yet. */
+ * nothing and launches nothing.  No cs_shards_ or device-pointer form yet. */
 #define CS_SIMILAR_EXCLUDE_NONE  0   /* nothing excluded: the source chunk comes back first */
 #define CS_SIMILAR_EXCLUDE_SELF  1   /* the source chunk itself */
 #define CS_SIMILAR_EXCLUDE_GROUP 2   /* the source chunk, and every chunk of its group when that group is not CS_NO_GROUP */
 CS_API int32_t cs_index_search_similar(cs_index* h, const uint32_t* ids, uint32_t nq, uint32_t k,
                                        int32_t exclude, float min_cos,
                                        float* out_cos, uint32_t* out_ids, uint32_t* out_counts);
+/* Similar-chunk search inside a scope — "where else under src/ is this function copied", "the clones of this chunk inside
+ * the package I am refactoring", "more like this, but only in tests".  Searching the whole store and dropping what is outside
+ * the directory loses most or all of the k hits; a scoped search of the row read back at k + 1 is exact for the chunk itself
+ * only, not for its file.
+ * THE RULE, for source ids[q]: the query is that chunk's stored row, as for cs_index_search_similar.  The source need not be
+ * in the scope: it only has to be a live chunk of the index.  Order the live rows whose id is in the scope by (cosine desc,
+ * id asc) — cosine bits those of the streaming scan; drop what `exclude` names, with cs_index_search_similar's meaning of
+ * NONE / SELF / GROUP (GROUP = SELF when no group is assigned or the source is ungrouped); drop the rows whose cosine is not
+ * strictly above min_cos; keep the first k.  Counts and unused slots as in every search.  Bit for bit (cosines, ids, counts):
+ *   - with a scope that holds every issued id it equals cs_index_search_similar;
+ *   - with CS_SIMILAR_EXCLUDE_NONE and no bound it equals cs_index_search_scoped (gathered route) of the row read back;
+ *   - with CS_SIMILAR_EXCLUDE_SELF and a source outside the scope it equals CS_SIMILAR_EXCLUDE_NONE.
+ * Errors, in this order: those of cs_index_search_similar up to and including the NaN bound, with their texts; a null scope,
+ * then a scope made for another store (a scope over a sharded store included; CS_ERR_BAD_ARG); then the ids, as there.  All
+ * of them are decided before the scope's list is refreshed and before anything is launched or written.  A scope with no live
+ * row gives the empty answer and launches nothing — after the ids were checked.  Always the gathered scan, whatever
+ * cs_scope_set_route says, counted in cs_scope_route_info's gathered_searches.  Concurrent calls through one scope or several
+ * are safe.  No cs_shards_, masked (bitmap) or device-pointer form yet. */
+CS_API int32_t cs_index_search_similar_scoped(cs_index* h, cs_scope* scope, const uint32_t* ids, uint32_t nq, uint32_t k,
+                                              int32_t exclude, float min_cos,
+                                              float* out_cos, uint32_t* out_ids, uint32_t* out_counts);
 
 /* Synchronises `stream` and reports in *overflowed whether any cs_index_search_device call of more
  * than 16 queries issued by this thread on it since the previous status call overflowed a candidate buffer
