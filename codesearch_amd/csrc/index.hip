@@ -3,6 +3,7 @@
 // searched by the exact scan of scan.hip.  Metadata (store.rs:19-85) stays with the caller.
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -16,6 +17,7 @@
 #include "grouped_plan.hpp"
 #include "index_ledger.hpp"
 #include "masked_plan.hpp"
+#include "pairs_plan.hpp"
 #include "scan.hpp"
 #include "scope.hpp"
 #include "similar_sources.hpp"
@@ -189,6 +191,33 @@ struct Workspace {
     }
 };
 
+// Scratch of a similar-pairs call (cs_index_similar_pairs, scan_pairs.hip): a stream, events and buffers of its own, pooled
+// per index — a call never touches a search's Workspace, so it runs beside searches and beside other calls.
+struct PairsWorkspace {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    uint64_t* d_cand = nullptr; size_t cand_cap = 0;      // candidate pairs (rowA | rowB << 32)
+    PairRecord* d_out = nullptr; size_t out_cap = 0;      // qualifying records
+    uint64_t* d_counters = nullptr;  // [0] candidates counted by the filter, [1] (low word) records written by the refine
+    uint64_t* h_counters = nullptr;  // pinned: where the host reads them
+
+    int32_t init() {
+        CS_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        CS_HIP(hipEventCreate(&ev[0]));
+        CS_HIP(hipEventCreate(&ev[1]));
+        CS_HIP(realloc_buf(d_counters, 2));
+        CS_HIP(realloc_buf(h_counters, 2, true));
+        return CS_OK;
+    }
+    void release_all() {
+        free_bufs(false, d_cand, d_out, d_counters);
+        free_bufs(true, h_counters);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
 }  // namespace cs
 
 using namespace cs;
@@ -264,6 +293,7 @@ struct cs_index {
 
     std::mutex mu;  // guards the pools below (search is re-entrant)
     std::vector<Workspace*> pool;
+    std::vector<PairsWorkspace*> pairs_pool;  // cs_index_similar_pairs' scratch, one set per call in flight
     // device-API scratch: one set per (stream, calling thread) — stream order makes reuse safe within a
     // thread, and two threads sharing a stream (e.g. both on the null stream) never share a set
     std::map<std::pair<hipStream_t, std::thread::id>, Workspace*> by_stream;
@@ -1147,6 +1177,157 @@ int32_t search_similar(cs_index* h, bool scope_given, cs_scope* scope, const uin
     });
 }
 
+// ---- the similar-pairs search (scan_pairs.hip, plan: pairs_plan.hpp) -------------------------------------------
+// What the calling thread's last successful call did (cs_index_similar_pairs_info).
+struct PairsInfo {
+    uint64_t candidates = 0;
+    uint32_t bands = 0;
+    double filter_ms = 0.0, refine_ms = 0.0, order_ms = 0.0;
+};
+thread_local PairsInfo last_pairs_info;
+
+PairsWorkspace* acquire_pairs(cs_index* h) {
+    {
+        std::lock_guard<std::mutex> lk(h->mu);
+        if (!h->pairs_pool.empty()) {
+            PairsWorkspace* w = h->pairs_pool.back();
+            h->pairs_pool.pop_back();
+            return w;
+        }
+    }
+    PairsWorkspace* w = new PairsWorkspace();
+    if (w->init() != CS_OK) {
+        w->release_all();
+        delete w;
+        return nullptr;
+    }
+    return w;
+}
+
+// The checks, the plan, the bands (one synchronise each: the host reads the candidate counter and stops at the first
+// overflow), the refine, the ordering on the host — std::partial_sort of the qualifying records only, by the total order
+// (cosine desc, a asc, b asc), so the answer does not depend on how the device's atomics landed.
+// The filter operand is the index's f16 copy where the index keeps one (the int8 copy does not serve it: ensure_f16, as a
+// search would).  Where the int8 copy serves, the index holds f32 + int8 and must go on doing so: the call converts the
+// rows into a buffer of its OWN (the same launch_corpus_split, the same tiles) and frees it before it returns — never
+// through the handle, where a search running beside this call could pick the copy up just before it is freed.
+int32_t similar_pairs(cs_index* h, float min_cos, int32_t mode, uint32_t max_pairs, uint32_t* out_a, uint32_t* out_b,
+                      float* out_cos, uint64_t* out_total) {
+    if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
+    CS_TRY(check_search(h, 1, h->dim, 1));
+    if (!out_a || !out_b || !out_cos || !out_total) return fail(CS_ERR_BAD_ARG, "null buffer");
+    if (mode != CS_PAIRS_ALL && mode != CS_PAIRS_OTHER_GROUP)
+        return fail(CS_ERR_BAD_ARG, "mode must be CS_PAIRS_ALL or CS_PAIRS_OTHER_GROUP (0..1), got %d", mode);
+    if (min_cos != min_cos) return fail(CS_ERR_BAD_ARG, "min_cos is NaN");
+    if (max_pairs == 0 || max_pairs > CS_MAX_PAIRS)
+        return fail(CS_ERR_BAD_ARG, "max_pairs must be in 1..%u, got %u", CS_MAX_PAIRS, max_pairs);
+    if (!split_scan_supported(h->dim))
+        return fail(CS_ERR_UNSUPPORTED, "similar pairs need dim 384, 768 or 1024 (the f16 filter's widths), got %u", h->dim);
+    if (h->ledger.live() < 2) {  // no pair: nothing is launched
+        *out_total = 0;
+        last_pairs_info = PairsInfo{};
+        return CS_OK;
+    }
+    if (!h->use_split)
+        return fail(CS_ERR_UNSUPPORTED, "similar pairs need the f16 filter copy, and CS_INDEX_SPLIT=0 turned it off");
+    DeviceGuard g(h->device);
+    const uint64_t stored = h->ledger.stored();
+    const PairsPlan plan = plan_pairs(stored, max_pairs, h->num_cus);
+    const _Float16* d_f16 = nullptr;
+    if (h->f16_eager || !q8_serves(h)) {
+        if (!ensure_f16(h)) return fail(CS_ERR_OOM, "similar pairs: no room for the f16 filter copy");
+        d_f16 = h->d_split;
+    } else {
+        std::lock_guard<std::mutex> lk(h->filter_mu);
+        if (h->d_split && h->split_rows >= stored) d_f16 = h->d_split;  // an overflowed search left one: it stays until the next build
+    }
+    struct Scratch {
+        cs_index* h;
+        PairsWorkspace* w = nullptr;
+        _Float16* d_private = nullptr;
+        ~Scratch() {
+            if (d_private) (void)hipFree(d_private);
+            if (w) {
+                std::lock_guard<std::mutex> lk(h->mu);
+                h->pairs_pool.push_back(w);
+            }
+        }
+    } sc{h};
+    sc.w = acquire_pairs(h);
+    if (!sc.w) return fail(CS_ERR_HIP, "similar pairs: could not create a HIP stream");
+    PairsWorkspace* w = sc.w;
+    if (!d_f16) {
+        if (h->normed_rows < stored) return fail(CS_ERR_HIP, "similar pairs: the index holds no row norms");
+        const size_t bytes = (size_t)plan.tiles * kPairsTileRows * h->dim * sizeof(_Float16);
+        if (cs_lab_env("CS_FAULT_F16_ALLOC") != nullptr || hipMalloc(&sc.d_private, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            sc.d_private = nullptr;
+            return fail(CS_ERR_OOM, "similar pairs: no room for the f16 filter copy (%llu bytes)", (unsigned long long)bytes);
+        }
+        CS_TRY(launch_corpus_split(h->d_corpus, h->d_norms, sc.d_private, 0, stored, h->dim, w->stream));
+        d_f16 = sc.d_private;
+    }
+    GroupView gv{nullptr, 0, h->ledger.id_base(), 0xFFFFFFFFu};
+    if (mode == CS_PAIRS_OTHER_GROUP) CS_TRY(ensure_groups(h, 0xFFFFFFFFu, &gv));
+    CS_TRY(reserve_buf(w->d_cand, w->cand_cap, (size_t)plan.cand_cap));
+    CS_TRY(reserve_buf(w->d_out, w->out_cap, (size_t)plan.cand_cap));
+    CS_HIP(hipMemsetAsync(w->d_counters, 0, 2 * sizeof(uint64_t), w->stream));
+    const uint32_t* d_dead = h->ledger.removed() ? h->d_dead : nullptr;
+    PairsInfo info;
+    for (uint64_t b = 0; b < plan.bands; ++b) {
+        const PairsBand band = plan.band(b);
+        CS_HIP(hipEventRecord(w->ev[0], w->stream));
+        CS_TRY(launch_pairs_filter(d_f16, h->dim, plan.tiles, band.first, band.count, stored, d_dead, h->row_ids(), gv,
+                                   mode == CS_PAIRS_OTHER_GROUP, min_cos, h->filter_margin, w->d_cand, w->d_counters,
+                                   (uint32_t)plan.cand_cap, w->stream));
+        CS_HIP(hipEventRecord(w->ev[1], w->stream));
+        CS_HIP(hipMemcpyAsync(w->h_counters, w->d_counters, sizeof(uint64_t), hipMemcpyDeviceToHost, w->stream));
+        CS_HIP(hipStreamSynchronize(w->stream));
+        float ms = 0.0f;
+        CS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
+        info.filter_ms += ms;
+        info.bands++;
+        if (w->h_counters[0] > plan.cand_cap)
+            return fail(CS_ERR_UNSUPPORTED,
+                        "similar pairs: %llu candidate pairs after band %llu of %llu, more than the %llu this call holds "
+                        "(2 * max_pairs + 4096): raise min_cos, exclude groups (CS_PAIRS_OTHER_GROUP) or raise max_pairs",
+                        (unsigned long long)w->h_counters[0], (unsigned long long)(b + 1), (unsigned long long)plan.bands,
+                        (unsigned long long)plan.cand_cap);
+    }
+    const uint32_t ncand = (uint32_t)w->h_counters[0];
+    info.candidates = ncand;
+    std::vector<PairRecord> rec;
+    if (ncand) {
+        CS_HIP(hipEventRecord(w->ev[0], w->stream));
+        CS_TRY(launch_pairs_rescore(h->d_corpus, h->dim, w->d_cand, ncand, h->row_ids(), min_cos, w->d_out,
+                                    reinterpret_cast<uint32_t*>(w->d_counters + 1), pairs_refine_blocks(ncand, h->num_cus),
+                                    w->stream));
+        CS_HIP(hipEventRecord(w->ev[1], w->stream));
+        CS_HIP(hipMemcpyAsync(w->h_counters + 1, w->d_counters + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, w->stream));
+        CS_HIP(hipStreamSynchronize(w->stream));
+        float ms = 0.0f;
+        CS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
+        info.refine_ms = ms;
+        rec.resize((size_t)(uint32_t)w->h_counters[1]);
+        if (!rec.empty()) {
+            CS_HIP(hipMemcpyAsync(rec.data(), w->d_out, rec.size() * sizeof(PairRecord), hipMemcpyDeviceToHost, w->stream));
+            CS_HIP(hipStreamSynchronize(w->stream));
+        }
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t keep = std::min<size_t>(rec.size(), max_pairs);
+    std::partial_sort(rec.begin(), rec.begin() + keep, rec.end(), [](const PairRecord& x, const PairRecord& y) {
+        if (x.cos != y.cos) return x.cos > y.cos;
+        if (x.a != y.a) return x.a < y.a;
+        return x.b < y.b;
+    });
+    for (size_t i = 0; i < keep; ++i) { out_a[i] = rec[i].a; out_b[i] = rec[i].b; out_cos[i] = rec[i].cos; }
+    *out_total = rec.size();
+    info.order_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    last_pairs_info = info;
+    return CS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1217,6 +1398,7 @@ void cs_index_destroy(cs_index* h) {
     (void)drain_appends(h);
     for (auto* w : h->pool) { w->release_all(); delete w; }
     for (auto& kv : h->by_stream) { kv.second->release_all(); delete kv.second; }
+    for (auto* w : h->pairs_pool) { w->release_all(); delete w; }
     for (auto& t : h->pending) {
         (void)hipEventDestroy(t.e0); (void)hipEventDestroy(t.e1); (void)hipEventDestroy(t.e2);
     }
@@ -1487,6 +1669,21 @@ int32_t cs_index_search_similar(cs_index* h, const uint32_t* ids, uint32_t nq, u
 int32_t cs_index_search_similar_scoped(cs_index* h, cs_scope* scope, const uint32_t* ids, uint32_t nq, uint32_t k,
                                        int32_t exclude, float min_cos, float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
     return search_similar(h, true, scope, ids, nq, k, exclude, min_cos, HostAnswer{out_cos, out_ids, out_counts, nullptr, false});
+}
+
+int32_t cs_index_similar_pairs(cs_index* h, float min_cos, int32_t mode, uint32_t max_pairs, uint32_t* out_a, uint32_t* out_b,
+                               float* out_cos, uint64_t* out_total) {
+    return similar_pairs(h, min_cos, mode, max_pairs, out_a, out_b, out_cos, out_total);
+}
+
+int32_t cs_index_similar_pairs_info(uint64_t* candidates, uint32_t* bands, double* filter_ms, double* refine_ms, double* order_ms) {
+    const PairsInfo& i = last_pairs_info;
+    if (candidates) *candidates = i.candidates;
+    if (bands) *bands = i.bands;
+    if (filter_ms) *filter_ms = i.filter_ms;
+    if (refine_ms) *refine_ms = i.refine_ms;
+    if (order_ms) *order_ms = i.order_ms;
+    return CS_OK;
 }
 
 int32_t cs_index_scope_create(cs_index* h, const uint32_t* ids, uint64_t n, cs_scope** out) {

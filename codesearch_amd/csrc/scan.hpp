@@ -161,6 +161,28 @@ int32_t launch_scan_similar_list(const ScanPlan& plan, const float* d_corpus, ui
                                  const uint32_t* d_list_len, const float* d_queries, uint32_t nq, uint32_t k, RowIds ids,
                                  const GroupView& gv, const SimilarView& sv, uint64_t* d_partial, hipStream_t stream);
 
+// ---- similar-pairs search (scan_pairs.hip, plan: pairs_plan.hpp) -----------------------------------------
+// A qualifying pair as the refine leaves it: the cosine's bits, the lower id, the higher id.
+struct PairRecord {
+    float cos;
+    uint32_t a, b;
+    uint32_t pad;
+};
+// The self-join's filter over the tile pairs [band_first, band_first + band_count) of the upper triangle of `tiles` x `tiles`
+// 128-row tiles of d_split (the tiled f16 unit copy): every pair of stored rows rowA < rowB, both below n_rows, neither
+// tombstoned (d_dead may be null), not of one group when other_group, whose f16 product is not <= min_cos - margin is
+// appended as (rowA | rowB << 32) to d_cand[0, cand_cap).  *d_cnt (64 bits: a band can hold more than 2^32 pairs) keeps
+// counting past cand_cap and stores stop at it; once it is past cand_cap, blocks that have not started yet score nothing.
+int32_t launch_pairs_filter(const _Float16* d_split, uint32_t dim, uint64_t tiles, uint64_t band_first, uint64_t band_count,
+                            uint64_t n_rows, const uint32_t* d_dead, RowIds ids, const GroupView& gv, bool other_group,
+                            float min_cos, float margin, uint64_t* d_cand, uint64_t* d_cnt,
+                            uint32_t cand_cap, hipStream_t stream);
+// Every candidate d_cand[0, n) re-scored from the f32 corpus with the streaming scan's arithmetic, the lower id's row as
+// the query; those with a finite cosine > min_cos become records d_out[0, *d_total) in no particular order (*d_total is
+// zeroed by the caller).
+int32_t launch_pairs_rescore(const float* d_corpus, uint32_t dim, const uint64_t* d_cand, uint32_t n, RowIds ids, float min_cos,
+                             PairRecord* d_out, uint32_t* d_total, uint32_t blocks, hipStream_t stream);
+
 // corpus[(first_out_row + r) * dim + c] = cs_synth_value(seed, (first_row + r) * dim + c)
 int32_t launch_synth_fill(float* d_rows, uint64_t n, uint32_t dim, uint64_t seed,
                           uint64_t first_row, hipStream_t stream);

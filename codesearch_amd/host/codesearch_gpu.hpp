@@ -222,6 +222,27 @@ class VectorStore {
                                       -std::numeric_limits<float>::infinity(), cos.data(), ids.data(), counts.data()));
         return results(cos, ids, counts[0]);
     }
+    // The near-duplicate report: every pair of stored chunks a < b whose cosine is strictly above min_cos, best first by
+    // (cosine desc, a asc, b asc); other_files: never two chunks of one group (file).  The corpus is joined with itself on
+    // the device, exactly (cs_index_similar_pairs).  At most max_pairs pairs come back; *total (optional) = how many there
+    // are.  Throws CS_ERR_UNSUPPORTED when the bound is so low that more than 2 * max_pairs + 4096 pairs come near it.
+    struct SimilarPair {
+        uint32_t a, b;
+        float cosine;
+    };
+    std::vector<SimilarPair> similar_pairs(float min_cos, bool other_files = true, uint32_t max_pairs = 65536,
+                                           uint64_t* total = nullptr) const {
+        if (sh_) throw Error(CS_ERR_UNSUPPORTED, "a sharded store has no similar-pairs search");
+        std::vector<uint32_t> a(max_pairs), b(max_pairs);
+        std::vector<float> cos(max_pairs);
+        uint64_t n = 0;
+        check(cs_index_similar_pairs(h_, min_cos, other_files ? CS_PAIRS_OTHER_GROUP : CS_PAIRS_ALL, max_pairs, a.data(),
+                                     b.data(), cos.data(), &n));
+        if (total) *total = n;
+        std::vector<SimilarPair> out((size_t)(n < max_pairs ? n : max_pairs));
+        for (size_t i = 0; i < out.size(); ++i) out[i] = SimilarPair{a[i], b[i], cos[i]};
+        return out;
+    }
     // all query variants in one call (src/search/mod.rs:508-511)
     std::vector<std::vector<SearchResult>> search_batch(const std::vector<std::vector<float>>& queries,
                                                         size_t limit) const {

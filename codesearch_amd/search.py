@@ -108,6 +108,37 @@ def drop_excluded(cos, ids, groups, src_id: int, src_group: int, mode: str, min_
     return kept_cos, kept_ids
 
 
+def pairs_above(full_orders, group_of, mode: str, min_cos, max_pairs: int):
+    """The contract of the similar-pairs search (cs_index_similar_pairs) on the host.  `full_orders`: {source id a: (cos,
+    ids)}, per live chunk a the live chunks with the cosines the similar-chunk search reports for source a — the full order
+    or any part of it that holds every hit that matters (hits b <= a are ignored: a pair is taken from its lower id);
+    `group_of(ids)` -> their groups.  Take every pair a < b; mode "all" drops nothing, "other_group" the pairs whose two
+    chunks carry the same group other than NO_GROUP; then pairs whose cosine is not strictly greater than min_cos go (None
+    or -inf: no bound), and so do NaN / Inf cosines; order by (cosine desc, a asc, b asc).
+    -> (cos, a, b, total): the first min(total, max_pairs) pairs as lists, and how many pairs remain in all."""
+    if mode not in ("all", "other_group"):
+        raise ValueError(f'mode must be "all" or "other_group", got {mode!r}')
+    kept = []
+    for a, (cos, ids) in full_orders.items():
+        a = int(a)
+        ids = [int(i) for i in ids]
+        ga = int(group_of([a])[0])
+        groups = group_of(ids) if mode == "other_group" else None
+        for j, (c, b) in enumerate(zip(cos, ids)):
+            if b <= a:
+                continue
+            if groups is not None and ga != NO_GROUP and int(groups[j]) == ga:
+                continue
+            if not (float("-inf") < c < float("inf")):
+                continue
+            if min_cos is not None and not (c > min_cos):
+                continue
+            kept.append((c, a, b))
+    kept.sort(key=lambda t: (-float(t[0]), t[1], t[2]))
+    top = kept[:max_pairs]
+    return [t[0] for t in top], [t[1] for t in top], [t[2] for t in top], len(kept)
+
+
 def merge_variants_capped(lists, group_of, k: int, m: int):
     """The contract of the grouped variants search (cs_index_search_variants_grouped[_scoped]) on the host.  `lists`: per
     query variant a (cos, ids) pair over the rows in play — the variant's full order, or any list that holds every row

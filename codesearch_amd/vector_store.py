@@ -818,18 +818,60 @@ class VectorStore:
                                             scope=scope)
         return self._results(cos[0], ids[0], int(counts[0]))
 
+    def similar_pairs_raw(self, min_cos: float, other_files: bool = False, max_pairs: int = 65536):
+        """cs_index_similar_pairs: every pair of stored chunks a < b whose cosine — the similar-chunk search's, bit for bit —
+        is strictly above min_cos (-inf: no bound), best first by (cosine desc, a asc, b asc); other_files=True: never two
+        chunks of one group (file; two ungrouped chunks are never one file).  The corpus is joined with itself on the
+        device, exactly.  -> (cos [m] f32, a [m] u32, b [m] u32, total) with m = min(total, max_pairs): total > max_pairs
+        says the list was cut.  The call refuses (CS_ERR_UNSUPPORTED) a bound so low that more than 2 * max_pairs + 4096
+        pairs come near it: raise min_cos, pass other_files=True or raise max_pairs."""
+        if self.sharded:
+            raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no similar-pairs search: no cs_shards_ form yet")
+        room = max(0, min(int(max_pairs), _lib.CS_MAX_PAIRS))
+        cos = np.zeros(room, np.float32)
+        a = np.zeros(room, np.uint32)
+        b = np.zeros(room, np.uint32)
+        total = C.c_uint64(0)
+        bound = np.float32(-np.inf) if min_cos is None else np.float32(min_cos)
+        _lib.check(self._lib.cs_index_similar_pairs(
+            self._h, float(bound), _lib.CS_PAIRS_OTHER_GROUP if other_files else _lib.CS_PAIRS_ALL, int(max_pairs),
+            a.ctypes.data_as(u32p), b.ctypes.data_as(u32p), cos.ctypes.data_as(f32p), C.byref(total)))
+        m = min(int(total.value), room)
+        return cos[:m], a[:m], b[:m], int(total.value)
+
+    def similar_pairs_info(self) -> dict:
+        """cs_index_similar_pairs_info: what this thread's last similar_pairs_raw did — candidate pairs, launch bands, the
+        filter's and the refine's device time and the ordering's host time (ms)."""
+        cand, bands = C.c_uint64(0), C.c_uint32(0)
+        f, r, o = C.c_double(0), C.c_double(0), C.c_double(0)
+        _lib.check(self._lib.cs_index_similar_pairs_info(C.byref(cand), C.byref(bands), C.byref(f), C.byref(r), C.byref(o)))
+        return {"candidates": int(cand.value), "bands": int(bands.value), "filter_ms": f.value, "refine_ms": r.value,
+                "order_ms": o.value}
+
+    def similar_pairs(self, min_score: float, other_files: bool = True, max_pairs: int = 65536):
+        """The near-duplicate report: every pair of stored chunks whose score — the reference's scale, cos_to_score — is
+        above min_score, best first, as (SearchResult, SearchResult, score) with the lower id first; other_files=True (the
+        default): never two chunks of one file (the files assigned at insert).  At most max_pairs pairs.  Pairs with a chunk
+        whose metadata is missing are skipped, as in search()."""
+        cos, a, b, _total = self.similar_pairs_raw(score_to_cos(min_score), other_files=other_files, max_pairs=max_pairs)
+        ra, rb = self._results(cos, a, len(a), keep_missing=True), self._results(cos, b, len(b), keep_missing=True)
+        return [(x, y, y.score) for x, y in zip(ra, rb) if x is not None and y is not None]
+
     def chunk_ids_under(self, filter_path: str, project_root: str = "", mcp: bool = True) -> List[int]:
         """Ids of the chunks whose metadata path passes the reference's filter_path rule (search.path_matches; MCP or
         CLI form), ascending: the chunk_ids of a masked search narrowed to a directory."""
         from .search import path_matches
         return sorted(i for i, m in self._meta.items() if path_matches(m.path, filter_path, project_root, mcp))
 
-    def _results(self, cos, ids, count) -> List[SearchResult]:
+    def _results(self, cos, ids, count, keep_missing: bool = False) -> List[SearchResult]:
+        """keep_missing: a None stands where an id has no metadata (the lists of a pair stay aligned)."""
         out = []
         dist = cos_to_distance(cos[:count])
         for i in range(count):
             m = self._meta.get(int(ids[i]))
             if m is None:
+                if keep_missing:
+                    out.append(None)
                 continue
             d = float(dist[i])
             out.append(SearchResult(

@@ -363,6 +363,41 @@ CS_API int32_t cs_index_search_similar_scoped(cs_index* h, cs_scope* scope, cons
                                               int32_t exclude, float min_cos,
                                               float* out_cos, uint32_t* out_ids, uint32_t* out_counts);
 
+/* Similar-pairs search — "which pairs of stored chunks are near-duplicates of each other": clones across a repository
+ * before a refactor, where a file was copied into another file.  There is no source chunk: the corpus is joined with itself
+ * on the device (one f16 MFMA pass over the upper triangle of 128-row tile pairs, an exact f32 refine of the survivors),
+ * where calling cs_index_search_similar once per chunk scans the corpus once per four sources and finds every pair twice.
+ * THE RULE: take every pair of live chunk ids a < b; its cosine is what cs_index_search_similar reports for source a and
+ * hit b (the streaming scan's bits with the lower id's stored row as the query); drop the pair when `mode` excludes it;
+ * drop it when its cosine is not strictly above min_cos (-INFINITY: no bound) or is NaN / Inf; order the rest by (cosine
+ * desc, a asc, b asc).  *out_total = the pairs that remain; the first min(total, max_pairs) are written to out_a / out_b /
+ * out_cos ([max_pairs] each) and nothing beyond them: total > max_pairs tells the caller the list was cut.
+ *   - Groups are the table of cs_index_set_groups: ids past its end are CS_NO_GROUP, and two ungrouped chunks are never
+ *     "the same file".
+ *   - BOUNDED WORK: the device holds at most cand_cap = 2 * max_pairs + 4096 candidate pairs — the live, non-excluded pairs
+ *     the f16 filter cannot rule out: every qualifying pair, plus pairs up to twice the filter's margin below the bound
+ *     (< 2.2e-3 where the f16 MFMA takes subnormal inputs exactly, checked at cs_index_create: MI355X does).  More candidates than that: CS_ERR_UNSUPPORTED, nothing written, nothing more launched (the triangle is
+ *     scored in bands and the counter is read between them); the text names the count reached and says to raise min_cos,
+ *     exclude groups or raise max_pairs.  So the call fails when more than cand_cap pairs qualify, and succeeds when at
+ *     most cand_cap live, non-excluded pairs have a cosine above min_cos - 2.2e-3.
+ *   - Fewer than two live rows: CS_OK, total 0, no launch.  Concurrent calls, also beside searches, are safe; the index is
+ *     left as it was (filter copies, routes, the bits of every search).
+ * Errors, in this order: those of cs_index_search for the handle and the built state, with their texts; a null output
+ * pointer; mode outside the two values; a NaN min_cos; max_pairs of 0 or above CS_MAX_PAIRS; a dim other than 384 / 768 /
+ * 1024 (CS_ERR_UNSUPPORTED, the text names the three); no f16 filter copy — CS_INDEX_SPLIT=0 (CS_ERR_UNSUPPORTED) or no
+ * room for it (CS_ERR_OOM), the text says which.  A failing call writes nothing.  No scoped, cs_shards_ or device-pointer
+ * form yet. */
+#define CS_MAX_PAIRS 4194304u            /* 1 << 22 */
+#define CS_PAIRS_ALL          0          /* every pair of live chunks */
+#define CS_PAIRS_OTHER_GROUP  1          /* not a pair whose two chunks carry the same group other than CS_NO_GROUP */
+CS_API int32_t cs_index_similar_pairs(cs_index* h, float min_cos, int32_t mode, uint32_t max_pairs,
+                                      uint32_t* out_a, uint32_t* out_b, float* out_cos, uint64_t* out_total);
+/* What the calling thread's last successful cs_index_similar_pairs did (each output optional): candidate pairs the filter
+ * let through, launch bands, and the device time of the filter bands and of the refine (HIP events) and the host time of
+ * the ordering, in milliseconds.  Before any such call: zeros. */
+CS_API int32_t cs_index_similar_pairs_info(uint64_t* candidates, uint32_t* bands, double* filter_ms, double* refine_ms,
+                                           double* order_ms);
+
 /* Synchronises `stream` and reports in *overflowed whether any cs_index_search_device call of more
  * than 16 queries issued by this thread on it since the previous status call overflowed a candidate buffer
  * (its results are then incomplete); clears the condition. */
