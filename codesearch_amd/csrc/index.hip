@@ -18,6 +18,7 @@
 #include "index_ledger.hpp"
 #include "masked_plan.hpp"
 #include "pairs_plan.hpp"
+#include "pairs_scoped_plan.hpp"
 #include "scan.hpp"
 #include "scope.hpp"
 #include "similar_sources.hpp"
@@ -1183,6 +1184,9 @@ struct PairsInfo {
     uint64_t candidates = 0;
     uint32_t bands = 0;
     double filter_ms = 0.0, refine_ms = 0.0, order_ms = 0.0;
+    // a scoped call only (cs_index_similar_pairs_scoped_info; zeros after an unscoped one)
+    double pack_ms = 0.0;
+    uint64_t rows_a = 0, rows_b = 0, tile_pairs = 0;
 };
 thread_local PairsInfo last_pairs_info;
 
@@ -1202,6 +1206,52 @@ PairsWorkspace* acquire_pairs(cs_index* h) {
         return nullptr;
     }
     return w;
+}
+
+// The refusal of a call whose candidates outgrew its buffer, noticed after band `band` of `bands`.
+int32_t pairs_overflow(uint64_t reached, uint64_t band, uint64_t bands, uint64_t cand_cap) {
+    return fail(CS_ERR_UNSUPPORTED,
+                "similar pairs: %llu candidate pairs after band %llu of %llu, more than the %llu this call holds "
+                "(2 * max_pairs + 4096): raise min_cos, exclude groups (CS_PAIRS_OTHER_GROUP) or raise max_pairs",
+                (unsigned long long)reached, (unsigned long long)band, (unsigned long long)bands, (unsigned long long)cand_cap);
+}
+
+// The tail of both pairs calls, behind the last filter band (w->h_counters[0] = the candidates, within the buffer): the
+// refine, the records' read-back and the ordering on the host into the caller's buffers; `info` becomes the thread's last.
+int32_t pairs_finish(cs_index* h, PairsWorkspace* w, float min_cos, uint32_t max_pairs, uint32_t* out_a, uint32_t* out_b,
+                     float* out_cos, uint64_t* out_total, PairsInfo& info) {
+    const uint32_t ncand = (uint32_t)w->h_counters[0];
+    info.candidates = ncand;
+    std::vector<PairRecord> rec;
+    if (ncand) {
+        CS_HIP(hipEventRecord(w->ev[0], w->stream));
+        CS_TRY(launch_pairs_rescore(h->d_corpus, h->dim, w->d_cand, ncand, h->row_ids(), min_cos, w->d_out,
+                                    reinterpret_cast<uint32_t*>(w->d_counters + 1), pairs_refine_blocks(ncand, h->num_cus),
+                                    w->stream));
+        CS_HIP(hipEventRecord(w->ev[1], w->stream));
+        CS_HIP(hipMemcpyAsync(w->h_counters + 1, w->d_counters + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, w->stream));
+        CS_HIP(hipStreamSynchronize(w->stream));
+        float ms = 0.0f;
+        CS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
+        info.refine_ms = ms;
+        rec.resize((size_t)(uint32_t)w->h_counters[1]);
+        if (!rec.empty()) {
+            CS_HIP(hipMemcpyAsync(rec.data(), w->d_out, rec.size() * sizeof(PairRecord), hipMemcpyDeviceToHost, w->stream));
+            CS_HIP(hipStreamSynchronize(w->stream));
+        }
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t keep = std::min<size_t>(rec.size(), max_pairs);
+    std::partial_sort(rec.begin(), rec.begin() + keep, rec.end(), [](const PairRecord& x, const PairRecord& y) {
+        if (x.cos != y.cos) return x.cos > y.cos;
+        if (x.a != y.a) return x.a < y.a;
+        return x.b < y.b;
+    });
+    for (size_t i = 0; i < keep; ++i) { out_a[i] = rec[i].a; out_b[i] = rec[i].b; out_cos[i] = rec[i].cos; }
+    *out_total = rec.size();
+    info.order_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    last_pairs_info = info;
+    return CS_OK;
 }
 
 // The checks, the plan, the bands (one synchronise each: the host reads the candidate counter and stops at the first
@@ -1287,45 +1337,119 @@ int32_t similar_pairs(cs_index* h, float min_cos, int32_t mode, uint32_t max_pai
         CS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
         info.filter_ms += ms;
         info.bands++;
-        if (w->h_counters[0] > plan.cand_cap)
-            return fail(CS_ERR_UNSUPPORTED,
-                        "similar pairs: %llu candidate pairs after band %llu of %llu, more than the %llu this call holds "
-                        "(2 * max_pairs + 4096): raise min_cos, exclude groups (CS_PAIRS_OTHER_GROUP) or raise max_pairs",
-                        (unsigned long long)w->h_counters[0], (unsigned long long)(b + 1), (unsigned long long)plan.bands,
-                        (unsigned long long)plan.cand_cap);
+        if (w->h_counters[0] > plan.cand_cap) return pairs_overflow(w->h_counters[0], b + 1, plan.bands, plan.cand_cap);
     }
-    const uint32_t ncand = (uint32_t)w->h_counters[0];
-    info.candidates = ncand;
-    std::vector<PairRecord> rec;
-    if (ncand) {
+    return pairs_finish(h, w, min_cos, max_pairs, out_a, out_b, out_cos, out_total, info);
+}
+
+// cs_index_similar_pairs_scoped: similar_pairs over the row lists of two scopes (the same handle twice: inside one).  Every
+// check comes before a list is refreshed; the lists are refreshed one after the other (no two scope mutexes are held
+// together), then each side's rows are packed into an f16 buffer of the call's own (scan_pairs_scoped.hip) — the index's
+// d_split is neither read nor made — the plan's triangle or rectangle is filtered in bands, and the tail is the unscoped
+// call's (pairs_finish).  The scopes' route counters do not move: this is no search.
+int32_t similar_pairs_scoped(cs_index* h, cs_scope* scope_a, cs_scope* scope_b, float min_cos, int32_t mode, uint32_t max_pairs,
+                             uint32_t* out_a, uint32_t* out_b, float* out_cos, uint64_t* out_total) {
+    if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
+    CS_TRY(check_search(h, 1, h->dim, 1));
+    if (!out_a || !out_b || !out_cos || !out_total) return fail(CS_ERR_BAD_ARG, "null buffer");
+    if (mode != CS_PAIRS_ALL && mode != CS_PAIRS_OTHER_GROUP)
+        return fail(CS_ERR_BAD_ARG, "mode must be CS_PAIRS_ALL or CS_PAIRS_OTHER_GROUP (0..1), got %d", mode);
+    if (min_cos != min_cos) return fail(CS_ERR_BAD_ARG, "min_cos is NaN");
+    if (max_pairs == 0 || max_pairs > CS_MAX_PAIRS)
+        return fail(CS_ERR_BAD_ARG, "max_pairs must be in 1..%u, got %u", CS_MAX_PAIRS, max_pairs);
+    if (!scope_a) return fail(CS_ERR_BAD_ARG, "null scope handle (scope_a)");
+    if (!scope_b) return fail(CS_ERR_BAD_ARG, "null scope handle (scope_b)");
+    CS_TRY(check_scope_handle(h, scope_a));
+    CS_TRY(check_scope_handle(h, scope_b));
+    if (!split_scan_supported(h->dim))
+        return fail(CS_ERR_UNSUPPORTED, "similar pairs need dim 384, 768 or 1024 (the f16 filter's widths), got %u", h->dim);
+    if (!h->use_split)
+        return fail(CS_ERR_UNSUPPORTED, "similar pairs need the f16 filter copy, and CS_INDEX_SPLIT=0 turned it off");
+    DeviceGuard g(h->device);
+    const bool same = scope_a == scope_b;
+    uint64_t live_a = 0, live_b = 0;
+    CS_TRY(scope_ready(h, scope_a, &live_a));
+    if (same) live_b = live_a;
+    else CS_TRY(scope_ready(h, scope_b, &live_b));
+    PairsScopedPlan plan = plan_pairs_scoped(same, live_a, live_b, max_pairs);
+    cs_scope* const sa = plan.swapped ? scope_b : scope_a;
+    cs_scope* const sb = plan.swapped ? scope_a : scope_b;
+    PairsInfo info;
+    info.rows_a = plan.rows_a;
+    info.rows_b = plan.rows_b;
+    struct Scratch {
+        cs_index* h;
+        PairsWorkspace* w = nullptr;
+        _Float16* d_packed[2] = {nullptr, nullptr};
+        ~Scratch() {
+            for (_Float16* p : d_packed)
+                if (p) (void)hipFree(p);
+            if (w) {
+                std::lock_guard<std::mutex> lk(h->mu);
+                h->pairs_pool.push_back(w);
+            }
+        }
+    } sc{h};
+    if (plan.tile_pairs) {
+        sc.w = acquire_pairs(h);
+        if (!sc.w) return fail(CS_ERR_HIP, "similar pairs: could not create a HIP stream");
+    }
+    PairsWorkspace* w = sc.w;
+    if (plan.tile_pairs && !same && plan.rows_a == 1 && plan.rows_b == 1) {  // two handles, one row each: the same row is no pair
+        uint32_t* rows = reinterpret_cast<uint32_t*>(w->h_counters);
+        CS_HIP(hipMemcpyAsync(rows, sa->d_list, sizeof(uint32_t), hipMemcpyDeviceToHost, w->stream));
+        CS_HIP(hipMemcpyAsync(rows + 1, sb->d_list, sizeof(uint32_t), hipMemcpyDeviceToHost, w->stream));
+        CS_HIP(hipStreamSynchronize(w->stream));
+        if (rows[0] == rows[1]) { plan.tile_pairs = 0; plan.bands = 0; }
+    }
+    if (plan.tile_pairs == 0) {  // no pair: no filter is launched
+        *out_total = 0;
+        last_pairs_info = info;
+        return CS_OK;
+    }
+    info.tile_pairs = plan.tile_pairs;
+    if (h->normed_rows < h->ledger.stored()) return fail(CS_ERR_HIP, "similar pairs: the index holds no row norms");
+    const uint64_t side_tiles[2] = {plan.tiles_a, plan.tiles_b};
+    for (int s = 0; s < (same ? 1 : 2); ++s) {
+        const size_t bytes = packed_bytes_of(side_tiles[s], h->dim);
+        if (cs_lab_env("CS_FAULT_F16_ALLOC") != nullptr || hipMalloc(&sc.d_packed[s], bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            sc.d_packed[s] = nullptr;
+            return fail(CS_ERR_OOM, "similar pairs: no room for the f16 filter copy (%llu bytes)", (unsigned long long)bytes);
+        }
+    }
+    GroupView gv{nullptr, 0, h->ledger.id_base(), 0xFFFFFFFFu};
+    if (mode == CS_PAIRS_OTHER_GROUP) CS_TRY(ensure_groups(h, 0xFFFFFFFFu, &gv));
+    CS_TRY(reserve_buf(w->d_cand, w->cand_cap, (size_t)plan.cand_cap));
+    CS_TRY(reserve_buf(w->d_out, w->out_cap, (size_t)plan.cand_cap));
+    CS_HIP(hipMemsetAsync(w->d_counters, 0, 2 * sizeof(uint64_t), w->stream));
+    CS_HIP(hipEventRecord(w->ev[0], w->stream));
+    CS_TRY(launch_pairs_pack(h->d_corpus, h->d_norms, sa->d_list, plan.rows_a, h->dim, sc.d_packed[0], w->stream));
+    if (!same) CS_TRY(launch_pairs_pack(h->d_corpus, h->d_norms, sb->d_list, plan.rows_b, h->dim, sc.d_packed[1], w->stream));
+    CS_HIP(hipEventRecord(w->ev[1], w->stream));
+    CS_HIP(hipStreamSynchronize(w->stream));
+    {
+        float ms = 0.0f;
+        CS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
+        info.pack_ms = ms;
+    }
+    const _Float16* d_b = same ? sc.d_packed[0] : sc.d_packed[1];
+    for (uint64_t b = 0; b < plan.bands; ++b) {
+        const PairsBand band = plan.band(b);
         CS_HIP(hipEventRecord(w->ev[0], w->stream));
-        CS_TRY(launch_pairs_rescore(h->d_corpus, h->dim, w->d_cand, ncand, h->row_ids(), min_cos, w->d_out,
-                                    reinterpret_cast<uint32_t*>(w->d_counters + 1), pairs_refine_blocks(ncand, h->num_cus),
-                                    w->stream));
+        CS_TRY(launch_pairs_scoped_filter(plan, sc.d_packed[0], d_b, sa->d_list, sb->d_list, h->dim, band.first, band.count,
+                                          h->row_ids(), gv, mode == CS_PAIRS_OTHER_GROUP, min_cos, h->filter_margin, w->d_cand,
+                                          w->d_counters, w->stream));
         CS_HIP(hipEventRecord(w->ev[1], w->stream));
-        CS_HIP(hipMemcpyAsync(w->h_counters + 1, w->d_counters + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, w->stream));
+        CS_HIP(hipMemcpyAsync(w->h_counters, w->d_counters, sizeof(uint64_t), hipMemcpyDeviceToHost, w->stream));
         CS_HIP(hipStreamSynchronize(w->stream));
         float ms = 0.0f;
         CS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
-        info.refine_ms = ms;
-        rec.resize((size_t)(uint32_t)w->h_counters[1]);
-        if (!rec.empty()) {
-            CS_HIP(hipMemcpyAsync(rec.data(), w->d_out, rec.size() * sizeof(PairRecord), hipMemcpyDeviceToHost, w->stream));
-            CS_HIP(hipStreamSynchronize(w->stream));
-        }
+        info.filter_ms += ms;
+        info.bands++;
+        if (w->h_counters[0] > plan.cand_cap) return pairs_overflow(w->h_counters[0], b + 1, plan.bands, plan.cand_cap);
     }
-    const auto t0 = std::chrono::steady_clock::now();
-    const size_t keep = std::min<size_t>(rec.size(), max_pairs);
-    std::partial_sort(rec.begin(), rec.begin() + keep, rec.end(), [](const PairRecord& x, const PairRecord& y) {
-        if (x.cos != y.cos) return x.cos > y.cos;
-        if (x.a != y.a) return x.a < y.a;
-        return x.b < y.b;
-    });
-    for (size_t i = 0; i < keep; ++i) { out_a[i] = rec[i].a; out_b[i] = rec[i].b; out_cos[i] = rec[i].cos; }
-    *out_total = rec.size();
-    info.order_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    last_pairs_info = info;
-    return CS_OK;
+    return pairs_finish(h, w, min_cos, max_pairs, out_a, out_b, out_cos, out_total, info);
 }
 
 }  // namespace
@@ -1674,6 +1798,20 @@ int32_t cs_index_search_similar_scoped(cs_index* h, cs_scope* scope, const uint3
 int32_t cs_index_similar_pairs(cs_index* h, float min_cos, int32_t mode, uint32_t max_pairs, uint32_t* out_a, uint32_t* out_b,
                                float* out_cos, uint64_t* out_total) {
     return similar_pairs(h, min_cos, mode, max_pairs, out_a, out_b, out_cos, out_total);
+}
+
+int32_t cs_index_similar_pairs_scoped(cs_index* h, cs_scope* scope_a, cs_scope* scope_b, float min_cos, int32_t mode,
+                                      uint32_t max_pairs, uint32_t* out_a, uint32_t* out_b, float* out_cos, uint64_t* out_total) {
+    return similar_pairs_scoped(h, scope_a, scope_b, min_cos, mode, max_pairs, out_a, out_b, out_cos, out_total);
+}
+
+int32_t cs_index_similar_pairs_scoped_info(double* pack_ms, uint64_t* rows_a, uint64_t* rows_b, uint64_t* tile_pairs) {
+    const PairsInfo& i = last_pairs_info;
+    if (pack_ms) *pack_ms = i.pack_ms;
+    if (rows_a) *rows_a = i.rows_a;
+    if (rows_b) *rows_b = i.rows_b;
+    if (tile_pairs) *tile_pairs = i.tile_pairs;
+    return CS_OK;
 }
 
 int32_t cs_index_similar_pairs_info(uint64_t* candidates, uint32_t* bands, double* filter_ms, double* refine_ms, double* order_ms) {

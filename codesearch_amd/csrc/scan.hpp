@@ -183,6 +183,22 @@ int32_t launch_pairs_filter(const _Float16* d_split, uint32_t dim, uint64_t tile
 int32_t launch_pairs_rescore(const float* d_corpus, uint32_t dim, const uint64_t* d_cand, uint32_t n, RowIds ids, float min_cos,
                              PairRecord* d_out, uint32_t* d_total, uint32_t blocks, hipStream_t stream);
 
+// ---- scoped similar-pairs search (scan_pairs_scoped.hip, plan: pairs_scoped_plan.hpp) ----------------------
+// Packed row i of d_packed (ceil(n_list / 128) whole tiles of the filter copy's tiled layout) = the unit row of stored row
+// d_list[i] rounded to f16, from the f32 row and d_norms with launch_corpus_split's arithmetic; packed rows past n_list
+// are zeros.
+int32_t launch_pairs_pack(const float* d_corpus, const float* d_norms, const uint32_t* d_list, uint64_t n_list, uint32_t dim,
+                          _Float16* d_packed, hipStream_t stream);
+struct PairsScopedPlan;
+// launch_pairs_filter over the tile pairs [band_first, band_first + band_count) of the plan's triangle (one packed buffer
+// and list, passed twice) or rectangle (two): candidates are appended as stored rows (lower | higher << 32) through the
+// lists (ascending live rows; plan.rows_a / rows_b of them), each unordered pair once however the lists overlap.  The
+// counter and the cap (plan.cand_cap) as there.
+int32_t launch_pairs_scoped_filter(const PairsScopedPlan& plan, const _Float16* d_packed_a, const _Float16* d_packed_b,
+                                   const uint32_t* d_list_a, const uint32_t* d_list_b, uint32_t dim, uint64_t band_first,
+                                   uint64_t band_count, RowIds ids, const GroupView& gv, bool other_group, float min_cos,
+                                   float margin, uint64_t* d_cand, uint64_t* d_cnt, hipStream_t stream);
+
 // corpus[(first_out_row + r) * dim + c] = cs_synth_value(seed, (first_row + r) * dim + c)
 int32_t launch_synth_fill(float* d_rows, uint64_t n, uint32_t dim, uint64_t seed,
                           uint64_t first_row, hipStream_t stream);

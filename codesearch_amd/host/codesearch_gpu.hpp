@@ -395,6 +395,23 @@ class VectorStore {
                                              -std::numeric_limits<float>::infinity(), cos.data(), ids.data(), counts.data()));
         return results(cos, ids, counts[0]);
     }
+    // similar_pairs() inside `scope` (other == nullptr) or between `scope` and `*other`: every pair with one chunk in each
+    // scope, once however the two overlap, with the bytes the unscoped call gives (cs_index_similar_pairs_scoped).  The
+    // candidate bound counts those pairs only.  One index only.
+    std::vector<SimilarPair> similar_pairs(const Scope& scope, const Scope* other, float min_cos, bool other_files = true,
+                                           uint32_t max_pairs = 65536, uint64_t* total = nullptr) const {
+        if (sh_) throw Error(CS_ERR_UNSUPPORTED, "a sharded store has no similar-pairs search");
+        std::vector<uint32_t> a(max_pairs), b(max_pairs);
+        std::vector<float> cos(max_pairs);
+        uint64_t n = 0;
+        check(cs_index_similar_pairs_scoped(h_, scope.handle(), other ? other->handle() : scope.handle(), min_cos,
+                                            other_files ? CS_PAIRS_OTHER_GROUP : CS_PAIRS_ALL, max_pairs, a.data(), b.data(),
+                                            cos.data(), &n));
+        if (total) *total = n;
+        std::vector<SimilarPair> out((size_t)(n < max_pairs ? n : max_pairs));
+        for (size_t i = 0; i < out.size(); ++i) out[i] = SimilarPair{a[i], b[i], cos[i]};
+        return out;
+    }
     std::vector<SearchResult> search_variants_per_file(const std::vector<std::vector<float>>& variants, size_t limit,
                                                        uint32_t per_file, const Scope* scope = nullptr,
                                                        bool* high_confidence = nullptr) const {

@@ -139,6 +139,23 @@ def pairs_above(full_orders, group_of, mode: str, min_cos, max_pairs: int):
     return [t[0] for t in top], [t[1] for t in top], [t[2] for t in top], len(kept)
 
 
+def pairs_between(cos, a, b, in_a, in_b):
+    """The rule of the scoped similar-pairs search (cs_index_similar_pairs_scoped) on the host, as a filter over an
+    unscoped answer: `cos` / `a` / `b` are the pairs of cs_index_similar_pairs (a < b, ordered by cosine desc, a asc, b asc,
+    neither refused nor cut); `in_a` / `in_b` the ids of the two scopes (the same collection twice: the pairs inside one).
+    A pair stays when one of its ids is in A and the other in B, either way round — once, however A and B overlap: the
+    input holds every unordered pair once.  The order is kept.  -> (cos, a, b, total) with cos float32, a and b uint32."""
+    import numpy as np
+
+    cos = np.asarray(cos, np.float32).ravel()
+    a = np.asarray(a, np.uint32).ravel()
+    b = np.asarray(b, np.uint32).ravel()
+    sa = np.unique(np.asarray(list(in_a) if not isinstance(in_a, np.ndarray) else in_a, np.uint32))
+    sb = np.unique(np.asarray(list(in_b) if not isinstance(in_b, np.ndarray) else in_b, np.uint32))
+    keep = (np.isin(a, sa) & np.isin(b, sb)) | (np.isin(a, sb) & np.isin(b, sa))
+    return cos[keep], a[keep], b[keep], int(keep.sum())
+
+
 def merge_variants_capped(lists, group_of, k: int, m: int):
     """The contract of the grouped variants search (cs_index_search_variants_grouped[_scoped]) on the host.  `lists`: per
     query variant a (cos, ids) pair over the rows in play — the variant's full order, or any list that holds every row

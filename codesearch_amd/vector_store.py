@@ -818,13 +818,19 @@ class VectorStore:
                                             scope=scope)
         return self._results(cos[0], ids[0], int(counts[0]))
 
-    def similar_pairs_raw(self, min_cos: float, other_files: bool = False, max_pairs: int = 65536):
+    def similar_pairs_raw(self, min_cos: float, other_files: bool = False, max_pairs: int = 65536,
+                          scope: Optional[Scope] = None, other: Optional[Scope] = None):
         """cs_index_similar_pairs: every pair of stored chunks a < b whose cosine — the similar-chunk search's, bit for bit —
         is strictly above min_cos (-inf: no bound), best first by (cosine desc, a asc, b asc); other_files=True: never two
         chunks of one group (file; two ungrouped chunks are never one file).  The corpus is joined with itself on the
         device, exactly.  -> (cos [m] f32, a [m] u32, b [m] u32, total) with m = min(total, max_pairs): total > max_pairs
         says the list was cut.  The call refuses (CS_ERR_UNSUPPORTED) a bound so low that more than 2 * max_pairs + 4096
-        pairs come near it: raise min_cos, pass other_files=True or raise max_pairs."""
+        pairs come near it: raise min_cos, pass other_files=True or raise max_pairs.
+        scope alone: only the pairs inside the scope; scope with other: only the pairs with one chunk in each, every pair
+        once however the two overlap (cs_index_similar_pairs_scoped).  The candidate bound then counts those pairs only, so
+        near-duplicates elsewhere in the store do not make the call refuse.  other without scope is a ValueError."""
+        if other is not None and scope is None:
+            raise ValueError("other= needs scope=: the pairs between two scopes")
         if self.sharded:
             raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no similar-pairs search: no cs_shards_ form yet")
         room = max(0, min(int(max_pairs), _lib.CS_MAX_PAIRS))
@@ -833,27 +839,40 @@ class VectorStore:
         b = np.zeros(room, np.uint32)
         total = C.c_uint64(0)
         bound = np.float32(-np.inf) if min_cos is None else np.float32(min_cos)
-        _lib.check(self._lib.cs_index_similar_pairs(
-            self._h, float(bound), _lib.CS_PAIRS_OTHER_GROUP if other_files else _lib.CS_PAIRS_ALL, int(max_pairs),
-            a.ctypes.data_as(u32p), b.ctypes.data_as(u32p), cos.ctypes.data_as(f32p), C.byref(total)))
+        args = (float(bound), _lib.CS_PAIRS_OTHER_GROUP if other_files else _lib.CS_PAIRS_ALL, int(max_pairs),
+                a.ctypes.data_as(u32p), b.ctypes.data_as(u32p), cos.ctypes.data_as(f32p), C.byref(total))
+        if scope is None:
+            _lib.check(self._lib.cs_index_similar_pairs(self._h, *args))
+        else:
+            sa = self._scope_handle(scope)
+            sb = sa if other is None else self._scope_handle(other)
+            _lib.check(self._lib.cs_index_similar_pairs_scoped(self._h, sa, sb, *args))
         m = min(int(total.value), room)
         return cos[:m], a[:m], b[:m], int(total.value)
 
     def similar_pairs_info(self) -> dict:
         """cs_index_similar_pairs_info: what this thread's last similar_pairs_raw did — candidate pairs, launch bands, the
-        filter's and the refine's device time and the ordering's host time (ms)."""
+        filter's and the refine's device time and the ordering's host time (ms); after a scoped call also the packing's
+        device time, the two sides' live rows and the tile pairs scored (cs_index_similar_pairs_scoped_info; else zeros)."""
         cand, bands = C.c_uint64(0), C.c_uint32(0)
         f, r, o = C.c_double(0), C.c_double(0), C.c_double(0)
         _lib.check(self._lib.cs_index_similar_pairs_info(C.byref(cand), C.byref(bands), C.byref(f), C.byref(r), C.byref(o)))
+        pack, ra, rb, tp = C.c_double(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _lib.check(self._lib.cs_index_similar_pairs_scoped_info(C.byref(pack), C.byref(ra), C.byref(rb), C.byref(tp)))
         return {"candidates": int(cand.value), "bands": int(bands.value), "filter_ms": f.value, "refine_ms": r.value,
-                "order_ms": o.value}
+                "order_ms": o.value, "pack_ms": pack.value, "rows_a": int(ra.value), "rows_b": int(rb.value),
+                "tile_pairs": int(tp.value)}
 
-    def similar_pairs(self, min_score: float, other_files: bool = True, max_pairs: int = 65536):
+    def similar_pairs(self, min_score: float, other_files: bool = True, max_pairs: int = 65536,
+                      scope: Optional[Scope] = None, other: Optional[Scope] = None):
         """The near-duplicate report: every pair of stored chunks whose score — the reference's scale, cos_to_score — is
         above min_score, best first, as (SearchResult, SearchResult, score) with the lower id first; other_files=True (the
         default): never two chunks of one file (the files assigned at insert).  At most max_pairs pairs.  Pairs with a chunk
-        whose metadata is missing are skipped, as in search()."""
-        cos, a, b, _total = self.similar_pairs_raw(score_to_cos(min_score), other_files=other_files, max_pairs=max_pairs)
+        whose metadata is missing are skipped, as in search().  scope / other: only the pairs inside the scope, or between
+        the two scopes (similar_pairs_raw) — "src/ against vendor/" is scope(chunk_ids_under("src/")) and the same of
+        "vendor/"."""
+        cos, a, b, _total = self.similar_pairs_raw(score_to_cos(min_score), other_files=other_files, max_pairs=max_pairs,
+                                                   scope=scope, other=other)
         ra, rb = self._results(cos, a, len(a), keep_missing=True), self._results(cos, b, len(b), keep_missing=True)
         return [(x, y, y.score) for x, y in zip(ra, rb) if x is not None and y is not None]
 

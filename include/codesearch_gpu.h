@@ -385,8 +385,8 @@ CS_API int32_t cs_index_search_similar_scoped(cs_index* h, cs_scope* scope, cons
  * Errors, in this order: those of cs_index_search for the handle and the built state, with their texts; a null output
  * pointer; mode outside the two values; a NaN min_cos; max_pairs of 0 or above CS_MAX_PAIRS; a dim other than 384 / 768 /
  * 1024 (CS_ERR_UNSUPPORTED, the text names the three); no f16 filter copy — CS_INDEX_SPLIT=0 (CS_ERR_UNSUPPORTED) or no
- * room for it (CS_ERR_OOM), the text says which.  A failing call writes nothing.  No scoped, cs_shards_ or device-pointer
- * form yet. */
+ * room for it (CS_ERR_OOM), the text says which.  A failing call writes nothing.  The scoped form is
+ * cs_index_similar_pairs_scoped below; no cs_shards_ or device-pointer form yet. */
 #define CS_MAX_PAIRS 4194304u            /* 1 << 22 */
 #define CS_PAIRS_ALL          0          /* every pair of live chunks */
 #define CS_PAIRS_OTHER_GROUP  1          /* not a pair whose two chunks carry the same group other than CS_NO_GROUP */
@@ -397,6 +397,44 @@ CS_API int32_t cs_index_similar_pairs(cs_index* h, float min_cos, int32_t mode, 
  * the ordering, in milliseconds.  Before any such call: zeros. */
 CS_API int32_t cs_index_similar_pairs_info(uint64_t* candidates, uint32_t* bands, double* filter_ms, double* refine_ms,
                                            double* order_ms);
+
+/* Similar-pairs search inside a scope and between two scopes — "which chunks under src/ are clones of each other", "what in
+ * vendor/ was copied from src/".  THE RULE: let A and B be the live chunk ids in scope_a and scope_b at the moment of the
+ * call (the lists are refreshed first if a build has passed, as every scoped search does; cs_scope_info's `refreshes`
+ * moves then).  Take every pair of live ids a < b with (a in A and b in B) or (a in B and b in A), each unordered pair once
+ * however A and B overlap; its cosine is cs_index_similar_pairs's (the streaming scan's bits with the lower id's stored
+ * row as the query); drop the pair when `mode` excludes it (CS_PAIRS_OTHER_GROUP: the unscoped call's meaning, the same
+ * group table); drop it when its cosine is not strictly above min_cos or is NaN / Inf; order the rest by (cosine desc, a
+ * asc, b asc).  *out_total = the pairs that remain; the first min(total, max_pairs) are written and nothing beyond them.
+ * Bit for bit:
+ *   - scope_a == scope_b (the same handle) gives the pairs inside one scope; two different handles holding the same ids
+ *     give the same bytes as one handle passed twice; swapping the two arguments changes nothing;
+ *   - with a scope holding every issued id passed twice the answer equals cs_index_similar_pairs;
+ *   - in every case the answer equals the unscoped call's full list restricted on the host to the pairs the rule names,
+ *     whenever the unscoped call is neither refused nor cut.  "Scope x everything" is a scope of all ids on one side.
+ *   - BOUNDED WORK as in the unscoped call, counted over the pairs the rule names only (a pair inside both scopes counts
+ *     once): more than cand_cap = 2 * max_pairs + 4096 candidates is CS_ERR_UNSUPPORTED with the unscoped call's text; the
+ *     join is launched in bands and the counter is read between them.  So near-duplicates elsewhere in the store — which
+ *     make the unscoped call refuse — do not matter to a scoped one.
+ *   - Each side's rows are converted into an f16 buffer of the call's own (2 * dim bytes per live row of the scope) that
+ *     is freed before the call returns; no room: CS_ERR_OOM, the text names the byte count.  The index's copies are
+ *     neither used nor made, filter state and the bits of every search stay what they were.
+ *   - An empty result — either scope without a live row, or both holding the same single row — launches no filter: CS_OK,
+ *     total 0, and cs_index_similar_pairs_info reports zero bands.
+ * Errors, in this order, each decided before a list is refreshed or anything is launched or written: those of
+ * cs_index_similar_pairs up to and including max_pairs, with its texts; a null scope_a, then a null scope_b (CS_ERR_BAD_ARG,
+ * the text says which: NULL does not mean "the whole store"); a scope made for another store, a scope over a sharded store
+ * included (CS_ERR_BAD_ARG); the dim and the CS_INDEX_SPLIT=0 refusals of the unscoped call, with its texts.
+ * cs_index_similar_pairs_info reports the calling thread's last pairs call of either kind; cs_scope_route_info's counters do
+ * not move (this is not a search).  Concurrent calls are safe, also beside searches and through the same scopes. */
+CS_API int32_t cs_index_similar_pairs_scoped(cs_index* h, cs_scope* scope_a, cs_scope* scope_b,
+                                             float min_cos, int32_t mode, uint32_t max_pairs,
+                                             uint32_t* out_a, uint32_t* out_b, float* out_cos, uint64_t* out_total);
+/* DIAGNOSTIC, for benchmarks — not part of the search contract, an embedder needs no binding for it (INTEGRATION.md has
+ * none, as for cs_index_similar_pairs_info).  What the calling thread's last successful cs_index_similar_pairs_scoped did
+ * beside what cs_index_similar_pairs_info reports (each output optional): the device time of the packing in milliseconds, the live rows of the join's two sides
+ * (the smaller scope first; one scope: equal) and the tile pairs scored.  After an unscoped call or none: zeros. */
+CS_API int32_t cs_index_similar_pairs_scoped_info(double* pack_ms, uint64_t* rows_a, uint64_t* rows_b, uint64_t* tile_pairs);
 
 /* Synchronises `stream` and reports in *overflowed whether any cs_index_search_device call of more
  * than 16 queries issued by this thread on it since the previous status call overflowed a candidate buffer
