@@ -234,6 +234,15 @@ DIAG_SIGNATURES = {
                                            C.c_uint32, u32p, C.c_uint32, f32p, i32p]),
     "cs_debug_gemm": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, f32p, f32p, f32p, f32p, f32p,
                                   C.c_uint32, C.c_uint32, C.c_uint32, u32p]),
+    "cs_debug_rows": (C.c_int32, [C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_int32,
+                                  i32p, f32p, f32p, f32p, i32p, C.c_uint32, C.c_uint32, f32p, i32p, f32p, C.c_uint32, f32p, f32p, f32p,
+                                  C.c_int32, f32p, f32p, f32p, f32p, u32p]),
+    "cs_debug_elementwise": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                         C.c_int32, C.c_float, f32p, f32p, f32p, f32p, u32p]),
+    "cs_debug_attention_cls": (C.c_int32, [C.c_int32, f32p, i32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, f32p,
+                                           f32p, C.POINTER(C.c_uint16)]),
+    "cs_debug_attention_f32": (C.c_int32, [C.c_int32, f32p, i32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32p, C.c_uint32,
+                                           f32p]),
     "cs_debug_attention": (C.c_int32, [C.c_int32, f32p, i32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32p, C.c_uint32,
                                        u32p, u32p, C.c_uint32, f32p, f32p, f32p, f32p, f32p, C.c_uint32, u32p, u32p]),
 }

@@ -102,10 +102,14 @@ attention_cls_kernel(const _Float16* __restrict__ q_cls, const _Float16* __restr
             vv[u] = *reinterpret_cast<const f16x8*>(base + ((size_t)jj * nch + (nh + head) * NC + line) * 64 + slot * 8);
             pu[u] = j < L ? p_s[jj] : 0.0f;
         }
+        // a key of probability 0 (masked, or past L) adds nothing — skipped, not multiplied: 0 x inf is NaN, and a value
+        // outside the f16 range at a masked position would reach every output of the sequence
 #pragma unroll
         for (int u = 0; u < U; ++u)
+            if (pu[u] != 0.0f) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = fmaf(pu[u], (float)vv[u][e], o[e]);
+                for (int e = 0; e < 8; ++e) o[e] = fmaf(pu[u], (float)vv[u][e], o[e]);
+            }
     }
     // sum over the key slots (lanes with the same chunk), then hi + lo / 2048 (lanes slot and slot + 4)
 #pragma unroll

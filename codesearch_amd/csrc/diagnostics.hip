@@ -452,6 +452,293 @@ int32_t cs_debug_attention(int32_t device, const float* qkv, const int32_t* mask
     return st;
 }
 
+}  // extern "C"
+
+namespace {
+
+// The device buffers of one diagnostic call: freed together when the call returns, after the device has gone idle.
+struct DiagBufs {
+    std::vector<void*> owned;
+    ~DiagBufs() {
+        (void)hipDeviceSynchronize();
+        for (void* q : owned) (void)hipFree(q);
+    }
+    template <class T>
+    int32_t get(T** out, size_t bytes, const void* host = nullptr) {
+        void* q = nullptr;
+        CS_HIP(hipMalloc(&q, bytes ? bytes : 4));
+        owned.push_back(q);
+        if (host && bytes) CS_HIP(hipMemcpy(q, host, bytes, hipMemcpyHostToDevice));
+        *out = static_cast<T*>(q);
+        return CS_OK;
+    }
+};
+
+int32_t diag_device(int32_t device) {
+    int ndev = 0;
+    CS_HIP(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(CS_ERR_HIP, "HIP device %d not available (%d visible)", device, ndev);
+    return CS_OK;
+}
+
+// a split tensor [rows][N/32][64] on the device -> f32 [rows][N] on the host, hi + lo / 2048
+int32_t diag_read_split(const _Float16* d_split, size_t rows, size_t N, float* out) {
+    std::vector<_Float16> hs(rows * N * 2);
+    CS_HIP(hipMemcpy(hs.data(), d_split, rows * N * 4, hipMemcpyDeviceToHost));
+    const size_t nch = N / 32;
+    for (size_t m = 0; m < rows; ++m)
+        for (size_t n = 0; n < N; ++n) {
+            const _Float16* line = hs.data() + (m * nch + n / 32) * 64;
+            out[m * N + n] = (float)line[n % 32] + (float)line[32 + n % 32] * (1.0f / 2048.0f);
+        }
+    return CS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Diagnostics: the row kernels of encoder.hip alone on host buffers — launch_row_kernel as the embedder calls it.  Contract
+// in include/codesearch_gpu_diag.h.
+int32_t cs_debug_rows(int32_t device, int32_t which, uint32_t H, uint32_t T, uint32_t L, uint32_t B, float eps, int32_t pooling,
+                      const int32_t* ids, const float* word, const float* pos, const float* type_table, const int32_t* types,
+                      uint32_t ntypes, uint32_t vocab, const float* x, const int32_t* mask, const float* parts, uint32_t nparts,
+                      const float* bias, const float* gamma, const float* beta, int32_t range_mode, float* out, float* out_split,
+                      float* src_after, float* range_out, uint32_t* range_flag) {
+    if (which < 0 || which > 4) return fail(CS_ERR_BAD_ARG, "cs_debug_rows: which = %d (0 embeddings, 1 LayerNorm, 2 pooling, 3 slab sum, 4 LayerNorm of a source)", which);
+    if (!out || H == 0) return fail(CS_ERR_BAD_ARG, "cs_debug_rows: null output or H = 0");
+    if (which == 2) {
+        if (!x || !mask || B == 0 || L == 0) return fail(CS_ERR_BAD_ARG, "cs_debug_rows: pooling needs x, mask, B > 0 and L > 0");
+        if (pooling != CS_POOL_CLS && pooling != CS_POOL_MEAN) return fail(CS_ERR_BAD_ARG, "cs_debug_rows: unknown pooling %d", pooling);
+        if (out_split || src_after || range_mode) return fail(CS_ERR_BAD_ARG, "cs_debug_rows: pooling writes f32 rows only");
+        T = B * L;
+    } else {
+        if (T == 0 || !gamma || !beta) return fail(CS_ERR_BAD_ARG, "cs_debug_rows: needs T > 0, gamma and beta");
+        if (which == 0 && (!ids || !word || !type_table || vocab == 0 || ntypes == 0 || L == 0))
+            return fail(CS_ERR_BAD_ARG, "cs_debug_rows: the embedding kernel needs ids, the word and type tables, vocab, ntypes and L > 0");
+        if (which != 0 && !x) return fail(CS_ERR_BAD_ARG, "cs_debug_rows: null input rows");
+        if (which == 3 && (!parts || !bias || nparts == 0)) return fail(CS_ERR_BAD_ARG, "cs_debug_rows: the slab sum needs parts, bias and nparts > 0");
+        if (range_mode < 0 || range_mode > 2 || (range_mode != 0) != (range_out != nullptr))
+            return fail(CS_ERR_BAD_ARG, "cs_debug_rows: range_mode (1 per block, 2 per row) and range_out go together");
+        if (range_mode && which != 0 && which != 1) return fail(CS_ERR_BAD_ARG, "cs_debug_rows: only kernels 0 and 1 report ranges");
+        if (src_after && which != 4) return fail(CS_ERR_BAD_ARG, "cs_debug_rows: src_after belongs to kernel 4");
+    }
+    if ((uint64_t)T * H > (1ull << 28)) return fail(CS_ERR_UNSUPPORTED, "cs_debug_rows: T * H <= 2^28");
+    CS_TRY(diag_device(device));
+    DeviceGuard g(device);
+    DiagBufs bufs;
+    const size_t row_n = (size_t)T * H;
+    EncoderLaunch a;
+    float *dX = nullptr, *dSrc = nullptr, *dOut = nullptr, *dRange = nullptr;
+    _Float16* dXs = nullptr;
+    uint32_t* dF = nullptr;
+    CS_TRY(bufs.get(&dF, 4));
+    CS_HIP(hipMemset(dF, 0, 4));
+    a.flag = dF;
+    a.eps = eps;
+    a.T = T; a.L = L; a.B = B;
+    if (which == 2) {
+        int32_t* dM = nullptr;
+        CS_TRY(bufs.get(&dX, row_n * 4, x));
+        CS_TRY(bufs.get(&dM, (size_t)T * 4, mask));
+        CS_TRY(bufs.get(&dOut, (size_t)B * H * 4));
+        CS_HIP(hipMemset(dOut, 0xff, (size_t)B * H * 4));
+        a.x = dX; a.mask = dM; a.out = dOut; a.pooling = pooling;
+        CS_TRY(launch_row_kernel(2, a, H, nullptr));
+        CS_HIP(hipDeviceSynchronize());
+        CS_HIP(hipMemcpy(out, dOut, (size_t)B * H * 4, hipMemcpyDeviceToHost));
+        if (range_flag) CS_HIP(hipMemcpy(range_flag, dF, 4, hipMemcpyDeviceToHost));
+        return CS_OK;
+    }
+    float *dG = nullptr, *dB = nullptr;
+    CS_TRY(bufs.get(&dG, (size_t)H * 4, gamma));
+    CS_TRY(bufs.get(&dB, (size_t)H * 4, beta));
+    a.g = dG; a.b = dB;
+    if (which == 0) {
+        int32_t *dIds = nullptr, *dTypes = nullptr;
+        float *dWord = nullptr, *dPos = nullptr, *dType = nullptr;
+        CS_TRY(bufs.get(&dIds, (size_t)T * 4, ids));
+        CS_TRY(bufs.get(&dWord, (size_t)vocab * H * 4, word));
+        CS_TRY(bufs.get(&dType, (size_t)ntypes * H * 4, type_table));
+        if (pos) CS_TRY(bufs.get(&dPos, (size_t)L * H * 4, pos));
+        if (types) CS_TRY(bufs.get(&dTypes, (size_t)T * 4, types));
+        CS_TRY(bufs.get(&dX, row_n * 4));
+        CS_HIP(hipMemset(dX, 0xff, row_n * 4));
+        a.ids = dIds; a.word = dWord; a.pos = dPos; a.type0 = dType; a.types = dTypes; a.ntypes = ntypes; a.vocab = vocab;
+    } else if (which == 4) {
+        CS_TRY(bufs.get(&dSrc, row_n * 4, x));
+        CS_TRY(bufs.get(&dX, row_n * 4));
+        CS_HIP(hipMemset(dX, 0xff, row_n * 4));
+        a.src = dSrc;
+    } else {
+        CS_TRY(bufs.get(&dX, row_n * 4, x));
+        if (which == 3) {
+            float *dParts = nullptr, *dBias = nullptr;
+            CS_TRY(bufs.get(&dParts, (size_t)nparts * row_n * 4, parts));
+            CS_TRY(bufs.get(&dBias, (size_t)H * 4, bias));
+            a.parts = dParts; a.nparts = nparts; a.bias = dBias;
+        }
+    }
+    a.x = dX;
+    if (out_split) {
+        if (H % 32) return fail(CS_ERR_UNSUPPORTED, "cs_debug_rows: the split form needs H %% 32 == 0");
+        CS_TRY(bufs.get(&dXs, row_n * 4));
+        CS_HIP(hipMemset(dXs, 0xff, row_n * 4));
+        a.xs = dXs;
+    }
+    const size_t range_pairs = range_mode == 2 ? T : (T + 3) / 4;
+    if (range_mode) {  // unwritten pairs come back as NaN
+        CS_TRY(bufs.get(&dRange, range_pairs * 8));
+        CS_HIP(hipMemset(dRange, 0xff, range_pairs * 8));
+        a.range_out = dRange;
+        a.range_rows = range_mode == 2;
+    }
+    CS_TRY(launch_row_kernel(which, a, H, nullptr));
+    CS_HIP(hipDeviceSynchronize());
+    CS_HIP(hipMemcpy(out, dX, row_n * 4, hipMemcpyDeviceToHost));
+    if (out_split) CS_TRY(diag_read_split(dXs, T, H, out_split));
+    if (src_after) CS_HIP(hipMemcpy(src_after, dSrc, row_n * 4, hipMemcpyDeviceToHost));
+    if (range_mode) CS_HIP(hipMemcpy(range_out, dRange, range_pairs * 8, hipMemcpyDeviceToHost));
+    if (range_flag) CS_HIP(hipMemcpy(range_flag, dF, 4, hipMemcpyDeviceToHost));
+    return CS_OK;
+}
+
+// Diagnostics: the element-wise kernels of nomic.hip alone on host buffers — the rotary map (op 0), the feed-forward gate
+// (op 1) and the query / key LayerNorm (op 2), each in its split and its f32 form.  Contract in include/codesearch_gpu_diag.h.
+int32_t cs_debug_elementwise(int32_t device, int32_t op, int32_t split, uint32_t T, uint32_t L, uint32_t H, uint32_t heads,
+                             uint32_t I, int32_t gelu_gate, float eps, const float* a, const float* b, const float* table,
+                             float* out, uint32_t* flags) {
+    if (op < 0 || op > 2) return fail(CS_ERR_BAD_ARG, "cs_debug_elementwise: op = %d (0 rotary map, 1 gate, 2 query / key LayerNorm)", op);
+    if (!a || !out || T == 0) return fail(CS_ERR_BAD_ARG, "cs_debug_elementwise: null buffer or T = 0");
+    if (op == 1 ? I == 0 : H == 0) return fail(CS_ERR_BAD_ARG, "cs_debug_elementwise: zero width");
+    if (op != 1 && !table) return fail(CS_ERR_BAD_ARG, "cs_debug_elementwise: the rotary map needs its (cos, sin) table, the LayerNorm its four vectors");
+    if (op == 0 && (L == 0 || heads == 0 || H % heads)) return fail(CS_ERR_BAD_ARG, "cs_debug_elementwise: the rotary map needs L > 0 and heads dividing H");
+    if (op == 1 && !split && (!b || I % 4)) return fail(CS_ERR_BAD_ARG, "cs_debug_elementwise: the f32 gate needs the gate matrix and I %% 4 == 0");
+    const size_t width = op == 1 ? (split ? 2 * (size_t)I : (size_t)I) : 3 * (size_t)H;  // of the input rows
+    const size_t out_w = op == 1 ? (size_t)I : width;
+    if ((uint64_t)T * width > (1ull << 28)) return fail(CS_ERR_UNSUPPORTED, "cs_debug_elementwise: T * row width <= 2^28");
+    CS_TRY(diag_device(device));
+    DeviceGuard g(device);
+    DiagBufs bufs;
+    float *dA = nullptr, *dB = nullptr, *dT = nullptr;
+    _Float16 *sA = nullptr, *sO = nullptr;
+    uint32_t* dF = nullptr;  // [0] the kernel's flag, [1] the input split's
+    CS_TRY(bufs.get(&dF, 8));
+    CS_HIP(hipMemset(dF, 0, 8));
+    CS_TRY(bufs.get(&dA, (size_t)T * width * 4, a));
+    if (op == 0) CS_TRY(bufs.get(&dT, (size_t)L * (H / heads / 2) * 8, table));
+    if (op == 2) CS_TRY(bufs.get(&dT, (size_t)4 * H * 4, table));
+    if (split) {
+        CS_TRY(bufs.get(&sA, (size_t)T * width * 4));
+        CS_HIP(hipMemset(sA, 0, (size_t)T * width * 4));
+        // (a width the split form cannot hold goes to the launcher unsplit: its refusal is the answer)
+        if (width % 32 == 0) CS_TRY(launch_split_rows(dA, sA, T, (uint32_t)width, dF + 1, nullptr));
+    }
+    if (op == 0) {
+        if (split) CS_TRY(launch_rope_split(sA, reinterpret_cast<const float2*>(dT), T, L, H, heads, dF, nullptr));
+        else CS_TRY(launch_rope_f32(dA, reinterpret_cast<const float2*>(dT), T, L, H, heads, nullptr));
+    } else if (op == 1) {
+        if (split) {
+            CS_TRY(bufs.get(&sO, (size_t)T * I * 4));
+            CS_HIP(hipMemset(sO, 0xff, (size_t)T * I * 4));
+            CS_TRY(launch_swiglu_split(sA, sO, T, I, dF, nullptr, gelu_gate != 0));
+        } else {
+            CS_TRY(bufs.get(&dB, (size_t)T * I * 4, b));
+            CS_TRY(launch_swiglu_f32(dA, dB, T, I, nullptr, gelu_gate != 0));
+        }
+    } else {
+        if (split) CS_TRY(launch_qk_layernorm_split(sA, dT, eps, T, H, dF, nullptr));
+        else CS_TRY(launch_qk_layernorm_f32(dA, dT, eps, T, H, nullptr));
+    }
+    CS_HIP(hipDeviceSynchronize());
+    if (split) CS_TRY(diag_read_split(sO ? sO : sA, T, out_w, out));
+    else CS_HIP(hipMemcpy(out, dA, (size_t)T * out_w * 4, hipMemcpyDeviceToHost));
+    if (flags) CS_HIP(hipMemcpy(flags, dF, 8, hipMemcpyDeviceToHost));
+    return CS_OK;
+}
+
+// Diagnostics: the CLS tail's own kernels (cls_tail.hip) alone on host buffers: the one-query attention and the gather of
+// the CLS rows.  Contract in include/codesearch_gpu_diag.h.
+int32_t cs_debug_attention_cls(int32_t device, const float* qkv, const int32_t* mask, uint32_t B, uint32_t L, uint32_t H,
+                               uint32_t heads, float* out, uint32_t* flags, const float* gather_src, float* x_cls,
+                               uint16_t* xs_cls) {
+    if ((qkv != nullptr) != (mask != nullptr) || (qkv != nullptr) != (out != nullptr))
+        return fail(CS_ERR_BAD_ARG, "cs_debug_attention_cls: qkv, mask and out go together");
+    if ((gather_src != nullptr) != (x_cls != nullptr) || (gather_src != nullptr) != (xs_cls != nullptr))
+        return fail(CS_ERR_BAD_ARG, "cs_debug_attention_cls: gather_src, x_cls and xs_cls go together");
+    if (!qkv && !gather_src) return fail(CS_ERR_BAD_ARG, "cs_debug_attention_cls: nothing to run");
+    if (B == 0 || L == 0 || H == 0 || H % 32) return fail(CS_ERR_BAD_ARG, "cs_debug_attention_cls needs B, L > 0 and H a multiple of 32");
+    if ((uint64_t)B * L > (1u << 20)) return fail(CS_ERR_UNSUPPORTED, "cs_debug_attention_cls: B * L <= 2^20");
+    CS_TRY(diag_device(device));
+    DeviceGuard g(device);
+    DiagBufs bufs;
+    const size_t T = (size_t)B * L;
+    uint32_t* dF = nullptr;  // [0] the kernel's flag, [1] the input split's
+    CS_TRY(bufs.get(&dF, 8));
+    CS_HIP(hipMemset(dF, 0, 8));
+    if (qkv) {
+        float* dQ = nullptr;
+        _Float16 *sQ = nullptr, *kvs = nullptr, *q_cls = nullptr, *ctxs = nullptr;
+        int32_t* dM = nullptr;
+        const size_t rowb = (size_t)3 * H * 4;  // bytes of a qkv row, f32 or split
+        CS_TRY(bufs.get(&dQ, T * rowb, qkv));
+        CS_TRY(bufs.get(&dM, T * 4, mask));
+        CS_TRY(bufs.get(&sQ, T * rowb));
+        CS_TRY(bufs.get(&kvs, T * (size_t)2 * H * 4));
+        CS_TRY(bufs.get(&q_cls, (size_t)B * H * 4));
+        CS_TRY(bufs.get(&ctxs, (size_t)B * H * 4));
+        CS_HIP(hipMemset(ctxs, 0xff, (size_t)B * H * 4));
+        CS_TRY(launch_split_rows(dQ, sQ, T, 3 * H, dF + 1, nullptr));
+        // kvs [T][2H/32][64]: per token the K lines, then the V lines; q_cls [B][H/32][64]: the Q lines of the rows b * L
+        CS_HIP(hipMemcpy2D(kvs, (size_t)2 * H * 4, reinterpret_cast<const char*>(sQ) + (size_t)H * 4, rowb, (size_t)2 * H * 4, T, hipMemcpyDeviceToDevice));
+        CS_HIP(hipMemcpy2D(q_cls, (size_t)H * 4, sQ, (size_t)L * rowb, (size_t)H * 4, B, hipMemcpyDeviceToDevice));
+        CS_TRY(launch_attention_cls(q_cls, kvs, dM, ctxs, dF, B, L, H, heads, nullptr));
+        CS_HIP(hipDeviceSynchronize());
+        CS_TRY(diag_read_split(ctxs, B, H, out));
+    }
+    if (gather_src) {
+        float *dX = nullptr, *dXc = nullptr;
+        _Float16 *sX = nullptr, *sXc = nullptr;
+        CS_TRY(bufs.get(&dX, T * H * 4, gather_src));
+        CS_TRY(bufs.get(&sX, T * H * 4));
+        CS_TRY(bufs.get(&dXc, (size_t)B * H * 4));
+        CS_TRY(bufs.get(&sXc, (size_t)B * H * 4));
+        CS_HIP(hipMemset(dXc, 0xff, (size_t)B * H * 4));
+        CS_HIP(hipMemset(sXc, 0xff, (size_t)B * H * 4));
+        CS_TRY(launch_split_rows(dX, sX, T, H, dF + 1, nullptr));
+        CS_TRY(launch_gather_cls(sX, dXc, sXc, B, L, H, nullptr));
+        CS_HIP(hipDeviceSynchronize());
+        CS_HIP(hipMemcpy(x_cls, dXc, (size_t)B * H * 4, hipMemcpyDeviceToHost));
+        CS_HIP(hipMemcpy(xs_cls, sXc, (size_t)B * H * 4, hipMemcpyDeviceToHost));
+    }
+    if (flags) CS_HIP(hipMemcpy(flags, dF, 8, hipMemcpyDeviceToHost));
+    return CS_OK;
+}
+
+// Diagnostics: the exact-f32 attention kernels of encoder.hip (attention_kernel<false>, attention64_kernel) alone on host
+// buffers — launch_attention as the f32 forward and every re-run after a raised range flag call it.
+int32_t cs_debug_attention_f32(int32_t device, const float* qkv, const int32_t* mask, uint32_t B, uint32_t L, uint32_t H,
+                               uint32_t heads, const float* alibi_slopes, uint32_t window, float* out) {
+    if (!qkv || !mask || !out) return fail(CS_ERR_BAD_ARG, "null buffer");
+    if (B == 0 || L == 0 || H == 0 || heads == 0) return fail(CS_ERR_BAD_ARG, "cs_debug_attention_f32 needs B, L, H, heads > 0");
+    if (L > 512 || (uint64_t)B * L > (1u << 20)) return fail(CS_ERR_UNSUPPORTED, "cs_debug_attention_f32: L <= 512, B * L <= 2^20");
+    CS_TRY(diag_device(device));
+    DeviceGuard g(device);
+    DiagBufs bufs;
+    const size_t T = (size_t)B * L;
+    float *dQ = nullptr, *dC = nullptr, *dAl = nullptr;
+    int32_t* dM = nullptr;
+    CS_TRY(bufs.get(&dQ, T * 3 * H * 4, qkv));
+    CS_TRY(bufs.get(&dM, T * 4, mask));
+    CS_TRY(bufs.get(&dC, T * H * 4));
+    CS_HIP(hipMemset(dC, 0xff, T * H * 4));
+    if (alibi_slopes) CS_TRY(bufs.get(&dAl, (size_t)heads * 4, alibi_slopes));
+    CS_TRY(launch_attention(dQ, dM, dC, B, L, H, heads, nullptr, dAl, window));
+    CS_HIP(hipDeviceSynchronize());
+    CS_HIP(hipMemcpy(out, dC, T * H * 4, hipMemcpyDeviceToHost));
+    return CS_OK;
+}
+
 // Diagnostics: device time of one dense layer on synthetic operands already in HBM (no PCIe, no allocation inside the
 // timed region).  mode as cs_debug_gemm (0 f32 MFMA, 1 split-f16 128 x 128 / skinny kernels, 2 split-f16 wide kernel);
 // epilogue 0 f32 store, 1 GELU -> split store, 2 + residual, 3 LayerNorm-fused (mode 2, N = 384), 4 bias -> split store

@@ -2,7 +2,7 @@
  * codesearch_gpu_diag.h — operator-level diagnostics of libcsgpu, exported ONLY by codesearch_amd/libcsgpu_diag.so (the
  * product library built once more with -DCS_DIAGNOSTICS: it additionally holds csrc/diagnostics.hip, the ablation
  * instantiations of the wide GEMM kernel and its in-kernel clock stamps).  Used by tests/test_gpu_gemm_split.py,
- * tests/test_gpu_quantized.py, tests/test_gpu_attention.py (operator parity) and benchmarks/ (A/B timing); nothing in INTEGRATION.md binds it and a
+ * tests/test_gpu_quantized.py, tests/test_gpu_attention.py, tests/test_gpu_rows.py, tests/test_gpu_attention_cls.py (operator parity) and benchmarks/ (A/B timing); nothing in INTEGRATION.md binds it and a
  * deployment does not ship it.  The diagnostic library exports every symbol of include/codesearch_gpu.h as well, so a
  * process may use it in place of libcsgpu.so.
  */
@@ -80,6 +80,56 @@ CS_API int32_t cs_debug_attention(int32_t device, const float* qkv, const int32_
                            const uint32_t* unit_len, uint32_t units, const float* proj_w, const float* proj_bias,
                            const float* proj_resid, float* out, float* range_pairs_out, uint32_t range_pairs_cap,
                            uint32_t* range_pairs, uint32_t* range_flag);
+
+/* Diagnostics: the row kernels of csrc/encoder.hip alone on host buffers, for unit parity against float64
+ * (tests/test_gpu_rows.py): launch_row_kernel(which, ...) exactly as the embedder calls it.  H = 384 | 768 | 1024.
+ *   which 0  embed_ln_kernel: ids [T], word [vocab, H], pos [L, H] (optional: no position table), type_table [ntypes, H], types
+ *            [T] (optional: every token has type 0); row t = LayerNorm((word[id] + type) + pos[t % L])
+ *   which 1  layernorm_kernel: x [T, H], in place
+ *   which 2  pool_normalize_kernel / mean_pool_normalize_kernel (the launcher chooses): x [B * L, H], mask [B, L], pooling =
+ *            CS_POOL_CLS | CS_POOL_MEAN -> out [B, H]; T is not read
+ *   which 3  layernorm_sum_kernel: x [T, H] the residual, parts [nparts, T, H] the slabs of a split-K product, bias [H]
+ *   which 4  layernorm_to_kernel: x [T, H] the source, left as it is (src_after, optional, receives it back)
+ * gamma / beta [H] and eps for which != 2.  out [T, H] receives the f32 rows; out_split (optional, which != 2) makes the
+ * launch write the split form too and receives it read back as hi + lo / 2048.  range_mode 1 (which 0 | 1): range_out
+ * [ceil(T / 4)][2] receives each block's (lo, hi); 2: [T][2], one pair per row; pairs the kernel does not write come back
+ * as NaN.  *range_flag (optional): set when a split-form value left the f16 range. */
+CS_API int32_t cs_debug_rows(int32_t device, int32_t which, uint32_t H, uint32_t T, uint32_t L, uint32_t B, float eps, int32_t pooling,
+                      const int32_t* ids, const float* word, const float* pos, const float* type_table, const int32_t* types,
+                      uint32_t ntypes, uint32_t vocab, const float* x, const int32_t* mask, const float* parts, uint32_t nparts,
+                      const float* bias, const float* gamma, const float* beta, int32_t range_mode, float* out, float* out_split,
+                      float* src_after, float* range_out, uint32_t* range_flag);
+
+/* Diagnostics: the element-wise kernels of csrc/nomic.hip alone on host buffers (tests/test_gpu_rows.py), split != 0: the
+ * split-f16 form (the f32 input goes through launch_split_rows first, the result is read back as hi + lo / 2048), else f32.
+ *   op 0  launch_rope_split / launch_rope_f32: a = qkv [T, 3H], table = [L][dh / 2] (cos, sin) pairs, dh = H / heads; token
+ *         t takes table row t % L.  out [T, 3H]: the whole tensor, V columns included.
+ *   op 1  launch_swiglu_split: a = [T, 2I], every 32 columns = 16 values | their 16 gates (the interleaved order of the up
+ *         projection's weight rows); launch_swiglu_f32: a = value [T, I], b = gate [T, I].  out [T, I] = value * act(gate),
+ *         act = silu, or the erf-GELU with gelu_gate != 0.
+ *   op 2  launch_qk_layernorm_split / _f32: a = qkv [T, 3H], table = gamma_q | beta_q | gamma_k | beta_k [4][H], eps.
+ *         out [T, 3H]: the whole tensor.
+ * flags [2] (optional): [0] the kernel's range flag, [1] that of the input's split. */
+CS_API int32_t cs_debug_elementwise(int32_t device, int32_t op, int32_t split, uint32_t T, uint32_t L, uint32_t H, uint32_t heads,
+                             uint32_t I, int32_t gelu_gate, float eps, const float* a, const float* b, const float* table,
+                             float* out, uint32_t* flags);
+
+/* Diagnostics: the kernels of the CLS tail (csrc/cls_tail.hip) alone on host buffers (tests/test_gpu_attention_cls.py).
+ * qkv [B*L, 3H] f32 as cs_debug_attention takes it, mask [B, L] -> out [B, H]: the rows are split, the K and V lines of every
+ * token become kvs [T][2H/32][64], the Q lines of the rows b * L become q_cls, and launch_attention_cls runs as the
+ * embedder's last layer calls it; out receives the split context read back as hi + lo / 2048.
+ * gather_src [B*L, H] f32 (optional, with x_cls [B, H] and xs_cls [B][H/32][64] f16 words): launch_gather_cls on its split
+ * form.  Either part may be left out (all its pointers null).  flags [2] (optional): [0] the attention kernel's range flag,
+ * [1] that of the inputs' split. */
+CS_API int32_t cs_debug_attention_cls(int32_t device, const float* qkv, const int32_t* mask, uint32_t B, uint32_t L, uint32_t H,
+                               uint32_t heads, float* out, uint32_t* flags, const float* gather_src, float* x_cls,
+                               uint16_t* xs_cls);
+
+/* Diagnostics: the exact-f32 attention kernels of csrc/encoder.hip alone on host buffers: launch_attention, as the f32
+ * forward and every mini-batch that raised the range flag run it.  Arguments as cs_debug_attention's of the same names
+ * (alibi_slopes [heads], optional); out [B*L, H] f32, padded query rows included.  L <= 512. */
+CS_API int32_t cs_debug_attention_f32(int32_t device, const float* qkv, const int32_t* mask, uint32_t B, uint32_t L, uint32_t H,
+                               uint32_t heads, const float* alibi_slopes, uint32_t window, float* out);
 
 /* Diagnostics: device milliseconds per launch of one dense layer on synthetic operands resident in HBM.
  * mode 0 exact-f32 MFMA, 1 split-f16 (128 x 128 / skinny kernels), 2 split-f16 wide kernel (N % 384 == 0);
