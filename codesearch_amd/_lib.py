@@ -243,6 +243,9 @@ DIAG_SIGNATURES = {
                                            f32p, C.POINTER(C.c_uint16)]),
     "cs_debug_attention_f32": (C.c_int32, [C.c_int32, f32p, i32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32p, C.c_uint32,
                                            f32p]),
+    "cs_debug_small_path": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                        C.c_float, f32p, f32p, f32p, f32p, f32p, f32p, i32p, f32p, f32p, f32p, i32p, C.c_uint32,
+                                        C.c_uint32, f32p, f32p, f32p, f32p, f32p, f32p, u32p, u32p]),
     "cs_debug_attention": (C.c_int32, [C.c_int32, f32p, i32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32p, C.c_uint32,
                                        u32p, u32p, C.c_uint32, f32p, f32p, f32p, f32p, f32p, C.c_uint32, u32p, u32p]),
 }

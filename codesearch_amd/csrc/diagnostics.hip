@@ -739,6 +739,118 @@ int32_t cs_debug_attention_f32(int32_t device, const float* qkv, const int32_t* 
     return CS_OK;
 }
 
+// Diagnostics: the dense kernels of the small path (small_path.hip) alone on host buffers — launch_sp_ln_gemm (op 0) and
+// launch_sp_partial (op 1) as Slice::run_small calls them, the route (narrow or wide form) chosen by the launcher.  Every
+// input holds exactly T rows (the kernels clamp their reads to row T - 1); every output is followed by kSpGuardRows rows of a
+// bit pattern that must come back unchanged.  Contract in include/codesearch_gpu_diag.h.
+constexpr uint32_t kSpGuardRows = 16, kSpGuardWord = 0xA5A5A5A5u;
+
+int32_t cs_debug_small_path(int32_t device, int32_t op, int32_t epi, int32_t pro, uint32_t H, uint32_t T, uint32_t N, uint32_t L,
+                            float eps, const float* gamma, const float* beta, const float* rows, const float* parts,
+                            const float* parts_bias, const float* x, const int32_t* ids, const float* word, const float* pos,
+                            const float* type_table, const int32_t* types, uint32_t ntypes, uint32_t vocab, const float* W,
+                            const float* bias, float* xout, float* cs_out, float* x_after, float* parts_out, uint32_t* flags,
+                            uint32_t* guard_changed) {
+    if (op != 0 && op != 1) return fail(CS_ERR_BAD_ARG, "cs_debug_small_path: op = %d (0 LayerNorm + product, 1 FFN-down K slices)", op);
+    if (H != 384 && H != 768 && H != 1024) return fail(CS_ERR_UNSUPPORTED, "hidden size %u not supported (384/768/1024)", H);
+    if (T == 0 || T > SP_MAX_ROWS || N == 0 || N % 32) return fail(CS_ERR_BAD_ARG, "cs_debug_small_path needs 1 <= T <= %u and N a positive multiple of 32", SP_MAX_ROWS);
+    if (!W || !guard_changed) return fail(CS_ERR_BAD_ARG, "cs_debug_small_path: null weights or guard counter");
+    if (op == 0) {
+        if (epi != 0 && epi != 1) return fail(CS_ERR_BAD_ARG, "cs_debug_small_path: epi = %d (0 split, 1 GELU -> split)", epi);
+        if (pro < 0 || pro > 2) return fail(CS_ERR_BAD_ARG, "cs_debug_small_path: pro = %d (0 rows, 1 slab sum, 2 embedding gather)", pro);
+        if (!gamma || !beta || !bias || !xout || !cs_out) return fail(CS_ERR_BAD_ARG, "cs_debug_small_path: op 0 needs gamma, beta, bias, xout and cs_out");
+        if (pro == 0 && !rows) return fail(CS_ERR_BAD_ARG, "cs_debug_small_path: prologue 0 needs its rows");
+        if (pro == 1 && (!parts || !parts_bias || !x)) return fail(CS_ERR_BAD_ARG, "cs_debug_small_path: prologue 1 needs parts, parts_bias and x");
+        if (pro == 2 && (!ids || !word || !pos || !type_table || vocab == 0 || ntypes == 0 || L == 0))
+            return fail(CS_ERR_BAD_ARG, "cs_debug_small_path: prologue 2 needs ids, the word, position and type tables, vocab, ntypes and L > 0");
+        if (x_after && pro != 1) return fail(CS_ERR_BAD_ARG, "cs_debug_small_path: x_after belongs to prologue 1");
+    } else if (!rows || !parts_out) {
+        return fail(CS_ERR_BAD_ARG, "cs_debug_small_path: op 1 needs its rows and parts_out");
+    }
+    CS_TRY(diag_device(device));
+    DeviceGuard g(device);
+    DiagBufs bufs;
+    const uint32_t K = op == 0 ? H : 4 * H;
+    const size_t row_n = (size_t)T * H, w_n = (size_t)N * K;
+    uint32_t* dF = nullptr;  // [0] the kernel's flag, [1] that of the operands' split
+    float* dW = nullptr;
+    _Float16* sW = nullptr;
+    CS_TRY(bufs.get(&dF, 8));
+    CS_HIP(hipMemset(dF, 0, 8));
+    CS_TRY(bufs.get(&dW, w_n * 4, W));
+    CS_TRY(bufs.get(&sW, w_n * 4));
+    CS_TRY(launch_split_rows(dW, sW, N, K, dF + 1, nullptr));
+    // an output of `rows` rows of `row_bytes` each, followed by the guard rows
+    std::vector<std::pair<const char*, size_t>> guards;
+    auto guarded = [&](auto** out, size_t rows_, size_t row_bytes) -> int32_t {
+        const size_t body = rows_ * row_bytes, tail = (size_t)kSpGuardRows * row_bytes;
+        CS_TRY(bufs.get(out, body + tail));
+        CS_HIP(hipMemset(*out, 0xff, body));  // an element the launch does not write comes back as NaN
+        CS_HIP(hipMemset(reinterpret_cast<char*>(*out) + body, 0xA5, tail));
+        guards.emplace_back(reinterpret_cast<const char*>(*out) + body, tail);
+        return CS_OK;
+    };
+    auto count_guards = [&]() -> int32_t {
+        uint32_t changed = 0;
+        for (const auto& gd : guards) {
+            std::vector<uint32_t> hw(gd.second / 4);
+            CS_HIP(hipMemcpy(hw.data(), gd.first, gd.second, hipMemcpyDeviceToHost));
+            for (uint32_t w : hw) changed += w != kSpGuardWord;
+        }
+        *guard_changed = changed;
+        return CS_OK;
+    };
+    if (op == 1) {
+        float *dA = nullptr, *dParts = nullptr;
+        _Float16* sA = nullptr;
+        CS_TRY(bufs.get(&dA, (size_t)T * K * 4, rows));
+        CS_TRY(bufs.get(&sA, (size_t)T * K * 4));
+        CS_TRY(launch_split_rows(dA, sA, T, K, dF + 1, nullptr));
+        CS_TRY(guarded(&dParts, (size_t)4 * T, (size_t)N * 4));  // [4][T][N]: the guard rows follow slab 3's row T - 1
+        CS_TRY(launch_sp_partial(sA, sW, dParts, T, N, H, nullptr));
+        CS_HIP(hipDeviceSynchronize());
+        CS_HIP(hipMemcpy(parts_out, dParts, (size_t)4 * T * N * 4, hipMemcpyDeviceToHost));
+        if (flags) CS_HIP(hipMemcpy(flags, dF, 8, hipMemcpyDeviceToHost));
+        return count_guards();
+    }
+    SpLnGemmArgs a{};
+    float *dG = nullptr, *dBe = nullptr, *dBias = nullptr, *dXout = nullptr, *dX = nullptr;
+    _Float16* dCs = nullptr;
+    CS_TRY(bufs.get(&dG, (size_t)H * 4, gamma));
+    CS_TRY(bufs.get(&dBe, (size_t)H * 4, beta));
+    CS_TRY(bufs.get(&dBias, (size_t)N * 4, bias));
+    if (pro == 0) {
+        float* dY = nullptr;
+        CS_TRY(bufs.get(&dY, row_n * 4, rows));
+        a.Y = dY;
+    } else if (pro == 1) {
+        float *dParts = nullptr, *dPb = nullptr;
+        CS_TRY(bufs.get(&dParts, 4 * row_n * 4, parts));  // [4][T][H], slab stride T
+        CS_TRY(bufs.get(&dPb, (size_t)H * 4, parts_bias));
+        CS_TRY(bufs.get(&dX, row_n * 4, x));
+        a.parts = dParts; a.parts_bias = dPb; a.X = dX;
+    } else {
+        int32_t *dIds = nullptr, *dTypes = nullptr;
+        float *dWord = nullptr, *dPos = nullptr, *dType = nullptr;
+        CS_TRY(bufs.get(&dIds, (size_t)T * 4, ids));
+        CS_TRY(bufs.get(&dWord, (size_t)vocab * H * 4, word));
+        CS_TRY(bufs.get(&dPos, (size_t)L * H * 4, pos));
+        CS_TRY(bufs.get(&dType, (size_t)ntypes * H * 4, type_table));
+        if (types) CS_TRY(bufs.get(&dTypes, (size_t)T * 4, types));
+        a.ids = dIds; a.word = dWord; a.pos = dPos; a.type0 = dType; a.types = dTypes; a.ntypes = ntypes; a.vocab = vocab;
+    }
+    CS_TRY(guarded(&dXout, T, (size_t)H * 4));  // never the buffer X is read from, as in the embedder
+    CS_TRY(guarded(&dCs, T, (size_t)N * 4));
+    a.L = L; a.ln_g = dG; a.ln_b = dBe; a.eps = eps; a.Xout = dXout; a.W = sW; a.bias = dBias; a.Cs = dCs; a.T = T; a.N = N; a.flag = dF;
+    CS_TRY(launch_sp_ln_gemm(epi ? SH_OUT_SPLIT_GELU : SH_OUT_SPLIT, pro, a, H, nullptr));
+    CS_HIP(hipDeviceSynchronize());
+    CS_HIP(hipMemcpy(xout, dXout, row_n * 4, hipMemcpyDeviceToHost));
+    CS_TRY(diag_read_split(dCs, T, N, cs_out));
+    if (x_after) CS_HIP(hipMemcpy(x_after, dX, row_n * 4, hipMemcpyDeviceToHost));
+    if (flags) CS_HIP(hipMemcpy(flags, dF, 8, hipMemcpyDeviceToHost));
+    return count_guards();
+}
+
 // Diagnostics: device time of one dense layer on synthetic operands already in HBM (no PCIe, no allocation inside the
 // timed region).  mode as cs_debug_gemm (0 f32 MFMA, 1 split-f16 128 x 128 / skinny kernels, 2 split-f16 wide kernel);
 // epilogue 0 f32 store, 1 GELU -> split store, 2 + residual, 3 LayerNorm-fused (mode 2, N = 384), 4 bias -> split store

@@ -2,7 +2,7 @@
  * codesearch_gpu_diag.h — operator-level diagnostics of libcsgpu, exported ONLY by codesearch_amd/libcsgpu_diag.so (the
  * product library built once more with -DCS_DIAGNOSTICS: it additionally holds csrc/diagnostics.hip, the ablation
  * instantiations of the wide GEMM kernel and its in-kernel clock stamps).  Used by tests/test_gpu_gemm_split.py,
- * tests/test_gpu_quantized.py, tests/test_gpu_attention.py, tests/test_gpu_rows.py, tests/test_gpu_attention_cls.py (operator parity) and benchmarks/ (A/B timing); nothing in INTEGRATION.md binds it and a
+ * tests/test_gpu_quantized.py, tests/test_gpu_attention.py, tests/test_gpu_rows.py, tests/test_gpu_attention_cls.py, tests/test_gpu_small_path.py (operator parity) and benchmarks/ (A/B timing); nothing in INTEGRATION.md binds it and a
  * deployment does not ship it.  The diagnostic library exports every symbol of include/codesearch_gpu.h as well, so a
  * process may use it in place of libcsgpu.so.
  */
@@ -130,6 +130,32 @@ CS_API int32_t cs_debug_attention_cls(int32_t device, const float* qkv, const in
  * (alibi_slopes [heads], optional); out [B*L, H] f32, padded query rows included.  L <= 512. */
 CS_API int32_t cs_debug_attention_f32(int32_t device, const float* qkv, const int32_t* mask, uint32_t B, uint32_t L, uint32_t H,
                                uint32_t heads, const float* alibi_slopes, uint32_t window, float* out);
+
+/* Diagnostics: the dense kernels of the small path (csrc/small_path.hip: forwards of under 200 token rows) alone on host
+ * buffers, for unit parity against float64 (tests/test_gpu_small_path.py): the launchers exactly as Slice::run_small calls
+ * them, the narrow or the wide form chosen by the launcher.  H = 384 | 768 | 1024, 1 <= T <= 256, N % 32 == 0.
+ *   op 0  launch_sp_ln_gemm: a LayerNorm prologue, then Cs = LN rows x W^T + bias.  epi 0: split store, 1: erf-GELU, then
+ *         split store.  gamma / beta [H], eps, W [N, H] and bias [N] f32 (W is staged into split form by launch_split_rows).
+ *           pro 0  rows [T, H]: the rows to normalise
+ *           pro 1  parts [4][T][H] (slab stride T, as the kernel indexes it), parts_bias [H], x [T, H] the residual: the
+ *                  rows are ((p0 + p1 + p2 + p3) + bias) + x; x_after (optional) receives x back after the launch
+ *           pro 2  ids [T], word [vocab, H], pos [L, H], type_table [ntypes, H], types [T] (optional: row 0 of the table):
+ *                  row t = (word[id] + type) + pos[t % L], an id outside the table reads row 0, a type beyond it the last row
+ *         xout [T, H] receives the normalised f32 rows (a buffer of its own, as in the embedder), cs_out [T, N] the split
+ *         output read back as hi + lo / 2048.
+ *   op 1  launch_sp_partial: rows = A [T, 4H], W [N, 4H] f32, both staged into split form; parts_out [4][T][N] f32 receives
+ *         the four K-slice slabs, slab ks = A[:, ks H .. (ks + 1) H) W[:, the same]^T.
+ * Every input holds exactly T rows (the kernels clamp their reads to row T - 1).  Every output is allocated with 16 guard
+ * rows behind row T - 1 (parts_out: behind slab 3's; a store past row T - 1 of an earlier slab lands in the next slab's
+ * first rows), filled with a bit pattern: *guard_changed receives how many guard words came back changed.  An output element
+ * the launch does not write comes back as NaN.  flags [2] (optional): [0] the kernel's range flag, [1] that of the operands'
+ * split. */
+CS_API int32_t cs_debug_small_path(int32_t device, int32_t op, int32_t epi, int32_t pro, uint32_t H, uint32_t T, uint32_t N, uint32_t L,
+                            float eps, const float* gamma, const float* beta, const float* rows, const float* parts,
+                            const float* parts_bias, const float* x, const int32_t* ids, const float* word, const float* pos,
+                            const float* type_table, const int32_t* types, uint32_t ntypes, uint32_t vocab, const float* W,
+                            const float* bias, float* xout, float* cs_out, float* x_after, float* parts_out, uint32_t* flags,
+                            uint32_t* guard_changed);
 
 /* Diagnostics: device milliseconds per launch of one dense layer on synthetic operands resident in HBM.
  * mode 0 exact-f32 MFMA, 1 split-f16 (128 x 128 / skinny kernels), 2 split-f16 wide kernel (N % 384 == 0);
