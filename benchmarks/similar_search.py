@@ -11,7 +11,7 @@ has no streaming route for nine queries in one call.  What one call of nine rows
 once per shape and not alternated with the new call: on the library's default route (the int8 filter + exact refine: baseline_one_call_default_ms) and
 with the filter switched off (five or more queries then take the exact-f32 MFMA path: baseline_one_call_nofilter_ms).
 
-    python benchmarks/similar_search.py [--rows 10000000] [--dim 384] [--reps 20] [--out FILE] [--tree DIR] [--scoped]
+    python benchmarks/similar_search.py [--rows 10000000] [--dim 384] [--reps 20] [--out FILE] [--tree DIR] [--scoped | --routes]
 
 The store: synthetic rows in files of 8 ids, with rows [2/10, 3/10) of it replaced by one file of near-duplicates of its
 first row (0.95 s + 0.05 noise).  The "hog" source is that first row; the "ordinary" source is a row far from the file.
@@ -19,6 +19,15 @@ With 9 sources per call the other 8 are ordinary rows.
 
 --tree DIR: load the package and the library of another checkout (the parent commit's, built): the entry point it lacks is
 not timed, so the same script gives the baseline's times under the parent's library.
+
+--routes: the call's two routes against each other instead (cs_index_set_similar_route), in one process, alternated: FILTER,
+SCAN, FILTER again, --reps calls each.  The yardstick is the SCAN route — the f32 streaming scan under the exclusions, what
+the call did before it had a route — and the spread of a case is the difference between the two FILTER series' medians.
+Ordinary source, 1 and 9 sources per call, k 10 and 200, modes none / self / file, with and without the bound 0.9; then the
+fallback case, the source inside the near-duplicate file with the file excluded: the filter's candidate buffer overflows
+and the scan answers, so the call costs both (filter_fallbacks counts them).  auto_route: what CS_SIMILAR_ROUTE_AUTO picks
+for the case, read from the counters.  The single-query route stays on its default here (AUTO follows it).  Under --tree
+with a library that has no route the call itself is timed: the scan, under the parent's library.
 
 --scoped: the scoped cases instead (cs_index_search_similar_scoped) over the same store: scopes of every id, a random 10 %, a
 random 1 % and the near-duplicate file plus a random 1 %; the source is the file's first row for the last scope and the
@@ -104,6 +113,49 @@ def scoped_cases(a, st, lib, h, _lib, emit, sources, others, groups, hog_lo, hog
         sc.close()
 
 
+def route_cases(a, st, lib, h, _lib, emit, sources, others, modes, med):
+    from codesearch_amd._lib import f32p, u32p
+
+    n, dim = a.rows, a.dim
+    has_route = "cs_index_set_similar_route" in _lib.SIGNATURES
+    cases = [("ordinary", nq, k, mname, bound) for nq in (1, 9) for k in (10, 200) for mname in modes for bound in (None, 0.9)]
+    cases += [("hog", nq, k, "file", None) for nq in (1, 9) for k in (10, 200)]  # the fallback case
+    for kind, nq, k, mname, bound in cases:
+        srcs = np.ascontiguousarray(np.concatenate([[sources[kind]], others[:nq - 1]]), np.uint32)
+        cos, idb, cnt = np.zeros((nq, k), np.float32), np.zeros((nq, k), np.uint32), np.zeros(nq, np.uint32)
+
+        def similar():
+            _lib.check(lib.cs_index_search_similar(h, srcs.ctypes.data_as(u32p), nq, k, modes[mname],
+                                                   float("-inf") if bound is None else bound, cos.ctypes.data_as(f32p),
+                                                   idb.ctypes.data_as(u32p), cnt.ctypes.data_as(u32p)))
+
+        rec = {"source": kind, "rows": n, "dim": dim, "nq": nq, "k": k, "mode": mname, "min_cos": bound, "reps": a.reps,
+               "library": "new" if has_route else "parent"}
+        if not has_route:
+            rec["scan_ms"] = med(timed(similar, a.reps))
+            emit(rec)
+            continue
+        st.set_similar_route("auto")
+        i0 = st.similar_route_info()
+        similar()
+        i1 = st.similar_route_info()
+        rec["auto_route"] = "filter" if i1[0] > i0[0] else "scan"
+        st.set_similar_route("filter")
+        t1 = timed(similar, a.reps)
+        got = (cos.copy(), idb.copy(), cnt.copy())
+        st.set_similar_route("scan")
+        ts = timed(similar, a.reps)
+        rec["same_bytes"] = all(x.tobytes() == y.tobytes() for x, y in zip(got, (cos, idb, cnt)))
+        st.set_similar_route("filter")
+        t2 = timed(similar, a.reps)
+        i2 = st.similar_route_info()
+        rec.update({"filter_ms": med(t1 + t2), "filter_before_ms": med(t1), "filter_after_ms": med(t2), "scan_ms": med(ts),
+                    "spread_ms": round(abs(med(t1) - med(t2)), 4), "count": int(cnt[0]),
+                    "filter_calls": i2[0] - i1[0], "filter_fallbacks": i2[2] - i1[2]})
+        rec["ratio_vs_scan"] = round(rec["filter_ms"] / rec["scan_ms"], 4)
+        emit(rec)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=10_000_000)
@@ -112,6 +164,7 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--tree", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument("--scoped", action="store_true")
+    ap.add_argument("--routes", action="store_true")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.tree))
     from codesearch_amd import VectorStore, _lib
@@ -142,7 +195,8 @@ def main():
         st.insert_embeddings(np.float32(0.95) * s_row + np.float32(0.05) * noise)
     st.insert_synthetic(n - hog_lo - hog_n, seed, hog_lo + hog_n)
     st.build_index()
-    st.set_single_query_route(st.ROUTE_STREAM)
+    if not a.routes:
+        st.set_single_query_route(st.ROUTE_STREAM)
     assert st.next_id() == n
     lib, h = st._lib, st.handle
     has_new = "cs_index_search_similar" in _lib.SIGNATURES
@@ -154,6 +208,9 @@ def main():
     kinds = [("ordinary", np.uint32(n - n // 7)), ("hog", np.uint32(hog_lo))]
     modes = {"none": 0, "self": 1, "file": 2}
     med = lambda t: round(float(np.median(t)), 4)  # noqa: E731
+    if a.routes:
+        route_cases(a, st, lib, h, _lib, emit, dict(kinds), others, modes, med)
+        kinds = []
     if a.scoped:
         scoped_cases(a, st, lib, h, _lib, emit, dict(kinds), others, groups, hog_lo, hog_n, modes, med)
         kinds = []

@@ -20,6 +20,7 @@ CS_GEMM_F32, CS_GEMM_SPLIT_F16, CS_GEMM_Q8_DYNAMIC = 0, 1, 2
 CS_MAX_K = 1024
 CS_MAX_QUERIES = 4096
 CS_SIMILAR_EXCLUDE_NONE, CS_SIMILAR_EXCLUDE_SELF, CS_SIMILAR_EXCLUDE_GROUP = 0, 1, 2
+CS_SIMILAR_ROUTE_AUTO, CS_SIMILAR_ROUTE_SCAN, CS_SIMILAR_ROUTE_FILTER = 0, 1, 2
 CS_MAX_PAIRS = 1 << 22
 CS_PAIRS_ALL, CS_PAIRS_OTHER_GROUP = 0, 1
 
@@ -101,6 +102,8 @@ SIGNATURES = {
     "cs_index_search_variants_grouped_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32p,
                                                             u32p, u32p, i32p]),
     "cs_index_search_similar": (C.c_int32, [vp, u32p, C.c_uint32, C.c_uint32, C.c_int32, C.c_float, f32p, u32p, u32p]),
+    "cs_index_set_similar_route": (C.c_int32, [vp, C.c_int32]),
+    "cs_index_similar_route_info": (C.c_int32, [vp, u64p, u64p, u64p]),
     "cs_index_search_similar_scoped": (C.c_int32, [vp, vp, u32p, C.c_uint32, C.c_uint32, C.c_int32, C.c_float, f32p, u32p,
                                                    u32p]),
     "cs_index_similar_pairs": (C.c_int32, [vp, C.c_float, C.c_int32, C.c_uint32, u32p, u32p, f32p, u64p]),

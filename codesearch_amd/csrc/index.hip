@@ -21,6 +21,7 @@
 #include "pairs_scoped_plan.hpp"
 #include "scan.hpp"
 #include "scope.hpp"
+#include "similar_route.hpp"
 #include "similar_sources.hpp"
 
 namespace cs {
@@ -277,6 +278,12 @@ struct cs_index {
     float filter_margin = 0.0f;  // scan_filter.hip: bound of the f16 filter's error for this dim
     RouteKnobs route;  // search_route.hpp: the thresholds of plan_route (route_knobs_from_env)
     uint64_t batched_searches = 0, batched_fallbacks = 0, q8_reruns = 0;
+    // The similar-chunk search's route (similar_route.hpp; cs_index_set_similar_route, CS_SIMILAR_ROUTE) and its own counters
+    // (cs_index_similar_route_info): unscoped calls the filter answered — those whose candidate buffer overflowed and that
+    // the similar scan then answered among them, counted again in the fallbacks — and unscoped calls the scan answered.
+    // The counters above and the int8 copy's strikes do not move for similar calls.
+    std::atomic<int32_t> similar_route{CS_SIMILAR_ROUTE_AUTO};
+    std::atomic<uint64_t> similar_filter_searches{0}, similar_scan_searches{0}, similar_filter_fallbacks{0};
     bool built = false;
     // Build generation: cs_index_build and cs_index_clear advance it.  Every other mutation un-builds the index and a
     // search needs a build, so whatever a scope derived from the stored rows (its row list, scope.hpp) is current
@@ -1124,10 +1131,73 @@ int32_t search_grouped(cs_index* h, bool scope_given, cs_scope* scope, const flo
     });
 }
 
+// The similar scan and its merge over every stored row: the SCAN route, and the exact answer of a FILTER-route call whose
+// candidate buffer overflowed (never list_scan, which knows no exclusions).
+int32_t similar_scan(cs_index* h, Workspace* w, const ScanPlan& plan, uint32_t nq, uint32_t k, const GroupView& gv,
+                     const SimilarView& sv, uint64_t* keys) {
+    CS_TRY(launch_scan_similar(plan, h->d_corpus, h->ledger.stored(), h->dim, w->d_queries, nq, k,
+                               h->ledger.removed() ? h->d_dead : nullptr, h->row_ids(), gv, sv, w->d_partial, w->stream));
+    return launch_merge(w->d_partial, plan.blocks, nq, k, false, w->d_tmp_a, w->d_tmp_b, keys, nullptr, nullptr, nullptr, w->stream);
+}
+
+// An unscoped similar-chunk search whose source rows are gathered in w->d_queries: plans its route (similar_route.hpp) and
+// enqueues it.  FILTER: the ordinary search's filter on the copy run_search would choose — the int8 copy when it serves and
+// its query planes fit, else the f16 copy (ensure_f16) — with the similar refine and fold (scan_similar_filter.hip); when a
+// copy or the filter's buffers cannot be had ("no room") the call scans and counts as a scan.  The overflow word is read
+// here, on the host; an overflowed candidate buffer — usually the excluded file's doing, not the copy's: its rows all beat
+// the k-th best of the others — is settled by the similar scan into the same outputs, with no f16 rerun.
+// A similar search never strikes the int8 copy and never moves the ordinary searches' counters: it does not call q8_strike,
+// it is no reading of the int8 copy in the workspace's bookkeeping (last_via_q8), and its overflow word is cleared in stream
+// order behind the read (as run_scoped clears a scope's), so the next search's prep kernel on this pooled workspace folds
+// nothing into the device's count of overflowed searches and mirrors nothing new: fold_overflows has nothing to charge to
+// whichever ordinary search runs here later.  What EARLIER ordinary searches left in the mirror is folded first, against them.
+int32_t run_similar(cs_index* h, Workspace* w, const ScanPlan& plan, uint32_t nq, uint32_t k, const GroupView& gv,
+                    const SimilarView& sv, uint64_t* keys) {
+    const int32_t forced = h->similar_route.load();
+    const uint64_t stored = h->ledger.stored();
+    const SearchShape shape{nq, k, h->dim, stored, h->num_cus, stored > 0 && h->normed_rows >= stored, h->use_split,
+                            batched_supported(h->dim), scan_prime_supported(h->dim), false, (uint64_t)plan.blocks * plan.passes};
+    const bool serves = q8_serves(h);
+    bool via_q8 = false, have_copy = false;
+    if (similar_wants_filter(h->route, shape, serves, false, forced)) {
+        fold_overflows(h, w);
+        via_q8 = q8_serves(h);
+        bool planes = false;
+        int32_t room = w->reserve_split_queries(nq, h->dim, via_q8, &planes);
+        via_q8 = via_q8 && planes;  // no room for the int8 query planes: the f16 copy
+        if (room == CS_OK && (via_q8 || ensure_f16(h))) {
+            room = w->reserve_batched(nq, k);
+            have_copy = room == CS_OK;
+        }
+        if (room != CS_OK && room != CS_ERR_OOM) return room;
+        if (room == CS_ERR_OOM) (void)hipGetLastError();  // no room: the scan answers
+    }
+    if (plan_similar_route(h->route, shape, serves, have_copy, false, forced) != SimilarRoute::Filter) {
+        h->similar_scan_searches.fetch_add(1);
+        return similar_scan(h, w, plan, nq, k, gv, sv, keys);
+    }
+    w->qw.q_pinned = nullptr;  // the gathered rows are device memory (QuerySource::Device)
+    w->last_via_q8 = false;
+    Q8View q8;
+    if (via_q8) { q8.d_q8 = h->d_q8; q8.d_tmeta = h->d_tmeta; q8.d_mu = h->d_mu; q8.rows = h->q8_rows; }
+    const SimilarRefine refine{sv, gv};
+    CS_TRY(launch_scan_split(w->bs, w->qw, h->d_corpus, h->d_split, stored, h->dim, w->d_queries, nq, k,
+                             h->ledger.removed() ? h->d_dead : nullptr, h->row_ids(), keys, nullptr, nullptr, nullptr, w->stream,
+                             h->filter_margin, &q8, nullptr, nullptr, &refine));
+    h->similar_filter_searches.fetch_add(1);
+    if (stored <= batched_cap(k)) return CS_OK;  // a phase appends at most one candidate per row
+    bool overflow = false;
+    CS_TRY(w->read_overflow(w->stream, &overflow));
+    if (!overflow) return CS_OK;
+    h->similar_filter_fallbacks.fetch_add(1);
+    CS_HIP(hipMemsetAsync(w->bs.d_overflow, 0, 2 * sizeof(uint32_t), w->stream));
+    return similar_scan(h, w, plan, nq, k, gv, sv, keys);
+}
+
 // The similar-chunk searches (scan_similar.hip): the sources resolved on the host (similar_sources.hpp), their rows gathered
 // into w->d_queries on the device, the scan's arithmetic under the per-query exclusions, the ordinary merge.  Over the whole
-// store (scope_given false: the streaming scan over every stored row) or over a scope's row list (the gathered scan, always,
-// as for the grouped search).  Every check, the scope's handle-level ones before the ids, comes before the scope's list is
+// store (scope_given false: run_similar — the streaming scan over every stored row, or the filter with the similar refine) or
+// over a scope's row list (the gathered scan, always, as for the grouped search).  Every check, the scope's handle-level ones before the ids, comes before the scope's list is
 // refreshed; groups_mu is released before the scope's mutex is taken.
 int32_t search_similar(cs_index* h, bool scope_given, cs_scope* scope, const uint32_t* ids, uint32_t nq, uint32_t k,
                        int32_t exclude, float min_cos, const HostAnswer& out) {
@@ -1170,8 +1240,7 @@ int32_t search_similar(cs_index* h, bool scope_given, cs_scope* scope, const uin
             CS_TRY(launch_scan_similar_list(plan, h->d_corpus, h->dim, scope->d_list, scope->d_blocks + scope_list_blocks(scope->n_ids),
                                             w->d_queries, nq, k, h->row_ids(), gv, sv, w->d_partial, w->stream));
         } else {
-            CS_TRY(launch_scan_similar(plan, h->d_corpus, h->ledger.stored(), h->dim, w->d_queries, nq, k,
-                                       h->ledger.removed() ? h->d_dead : nullptr, h->row_ids(), gv, sv, w->d_partial, w->stream));
+            return run_similar(h, w, plan, nq, k, gv, sv, keys);
         }
         return launch_merge(w->d_partial, plan.blocks, nq, k, false, w->d_tmp_a, w->d_tmp_b, keys, nullptr, nullptr, nullptr,
                             w->stream);
@@ -1494,6 +1563,8 @@ int32_t cs_index_create(uint32_t dim, uint64_t capacity_rows, int32_t device, ui
         if (const char* e = std::getenv("CS_INDEX_COMPACT_DEAD_PCT")) h->compact_dead_pct = (uint32_t)std::max(0, std::min(100, std::atoi(e)));
     }
     h->route = route_knobs_from_env();
+    if (const char* e = std::getenv("CS_SIMILAR_ROUTE"))  // auto | scan | filter (anything else: auto)
+        h->similar_route.store(!strcmp(e, "scan") ? CS_SIMILAR_ROUTE_SCAN : !strcmp(e, "filter") ? CS_SIMILAR_ROUTE_FILTER : CS_SIMILAR_ROUTE_AUTO);
     if (h->use_split) {
         // does the f16 MFMA take subnormal inputs exactly?  One one-wave launch per device per process.
         static std::mutex mu;
@@ -2164,6 +2235,22 @@ int32_t cs_index_set_single_query_route(cs_index* h, int32_t route) {
     if (route != CS_ROUTE_COST && route != CS_ROUTE_STREAM && route != CS_ROUTE_FILTER)
         return fail(CS_ERR_BAD_ARG, "route must be CS_ROUTE_COST, CS_ROUTE_STREAM or CS_ROUTE_FILTER, got %d", route);
     h->route.single_route = route;
+    return CS_OK;
+}
+
+int32_t cs_index_set_similar_route(cs_index* h, int32_t route) {
+    if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
+    if (route != CS_SIMILAR_ROUTE_AUTO && route != CS_SIMILAR_ROUTE_SCAN && route != CS_SIMILAR_ROUTE_FILTER)
+        return fail(CS_ERR_BAD_ARG, "route must be CS_SIMILAR_ROUTE_AUTO, _SCAN or _FILTER (0..2), got %d", route);
+    h->similar_route.store(route);
+    return CS_OK;
+}
+
+int32_t cs_index_similar_route_info(cs_index* h, uint64_t* filter_searches, uint64_t* scan_searches, uint64_t* filter_fallbacks) {
+    if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
+    if (filter_searches) *filter_searches = h->similar_filter_searches.load();
+    if (scan_searches) *scan_searches = h->similar_scan_searches.load();
+    if (filter_fallbacks) *filter_fallbacks = h->similar_filter_fallbacks.load();
     return CS_OK;
 }
 

@@ -161,6 +161,25 @@ int32_t launch_scan_similar_list(const ScanPlan& plan, const float* d_corpus, ui
                                  const uint32_t* d_list_len, const float* d_queries, uint32_t nq, uint32_t k, RowIds ids,
                                  const GroupView& gv, const SimilarView& sv, uint64_t* d_partial, hipStream_t stream);
 
+// The similar-chunk search through the filter (scan_similar_filter.hip): what launch_scan_split needs to hand every phase's
+// candidates to the similar refine and fold instead of the ordinary ones.
+struct SimilarRefine {
+    SimilarView sv;
+    GroupView gv;  // per_group is not read
+};
+struct BatchedState;
+struct SplitQueryWs;
+// rescore_keys_kernel's work and grid (rk_blocks blocks per query; first_rows != 0: phase 0, candidate i is row i) with the
+// similar search's final store: the key is empty unless the cosine is > sv.min_cos and the query keeps the row.
+int32_t launch_similar_rescore(const BatchedState& st, const SplitQueryWs& qw, const float* d_corpus, uint32_t dim,
+                               const float* d_queries, uint32_t nq, uint32_t cap, uint32_t rk_blocks, uint32_t first_rows,
+                               const uint32_t* d_dead, RowIds ids, const GroupView& gv, const SimilarView& sv,
+                               hipStream_t stream);
+// launch_select_candidates whose threshold never falls below sv.min_cos.
+int32_t launch_similar_select(const BatchedState& st, uint32_t nq, uint32_t cap, uint32_t k, bool last, const SimilarView& sv,
+                              uint64_t* d_out_keys, float* d_out_cos, uint32_t* d_out_ids, uint32_t* d_out_counts,
+                              hipStream_t stream);
+
 // ---- similar-pairs search (scan_pairs.hip, plan: pairs_plan.hpp) -----------------------------------------
 // A qualifying pair as the refine leaves it: the cosine's bits, the lower id, the higher id.
 struct PairRecord {
@@ -211,6 +230,9 @@ constexpr uint32_t kCntStride = 32;
 // Device-API searches of up to this many queries carry a gated exact rerun behind the filter path (index.hip
 // run_search); above it an overflowed candidate buffer is reported through the sticky word of BatchedState.
 constexpr uint32_t kGatedMaxQ = 16;
+// The fold's block and the keys it sorts per chunk (scan_mfma.hip MB_SEL_THREADS / MB_SEL_CAP; scan_similar_filter.hip
+// restates the kernel)
+constexpr uint32_t kSelThreads = 1024, kSelCap = 4096;
 struct BatchedState {
     uint64_t* d_cand = nullptr;   // [nq][cap] candidate keys
     uint32_t* d_cnt = nullptr;    // [nq][kCntStride], word 0 of each line used
@@ -279,10 +301,13 @@ int32_t launch_scan_split(const BatchedState& st, const SplitQueryWs& qw, const 
                           const _Float16* d_split, uint64_t n_rows, uint32_t dim, const float* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_dead,
                           RowIds id_base, uint64_t* d_out_keys, float* d_out_cos, uint32_t* d_out_ids,
                           uint32_t* d_out_counts, hipStream_t stream, float margin, const Q8View* q8 = nullptr,
-                          const FilterPlan* prepared = nullptr, const uint32_t* d_phase0_list = nullptr);
+                          const FilterPlan* prepared = nullptr, const uint32_t* d_phase0_list = nullptr,
+                          const SimilarRefine* similar = nullptr);
 const FilterKnobs& filter_knobs();  // the plan's laboratory knobs as the launcher reads them (the product: the defaults)
 // prepared (a scoped search, scoped_filter_plan.hpp): launch that plan instead of plan_filter's — its phase 0 re-scores
 // the first prepared->phase0_rows entries of d_phase0_list, and d_dead is the scope's blocked-rows bitmap.
+// similar (a similar-chunk search, scan_similar_filter.hip): every phase's refine and fold are the similar ones; not with a
+// prepared plan.
 // Proven bound of |filter cosine - exact cosine| for unit vectors of this width (scan_filter.hip header);
 // `subnormals_exact` = the f16 MFMA consumes subnormal inputs exactly (sh_denorm_selftest).
 float filter_margin(uint32_t dim, bool subnormals_exact);

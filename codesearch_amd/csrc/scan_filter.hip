@@ -1551,7 +1551,8 @@ static int32_t scan_split_impl(const BatchedState& st, const SplitQueryWs& qw, c
                                const _Float16* d_split, uint64_t n_rows, const float* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_dead,
                                RowIds id_base, uint64_t* d_out_keys, float* d_out_cos,
                                uint32_t* d_out_ids, uint32_t* d_out_counts, hipStream_t stream, float margin,
-                               const Q8View* q8, const FilterPlan* prepared, const uint32_t* d_phase0_list) {
+                               const Q8View* q8, const FilterPlan* prepared, const uint32_t* d_phase0_list,
+                               const SimilarRefine* similar) {
     constexpr uint32_t dim = 128 * J;
     const uint32_t cap = batched_cap(k);
     static PerDeviceOnce attr_set;  // function attributes are per device
@@ -1571,6 +1572,7 @@ static int32_t scan_split_impl(const BatchedState& st, const SplitQueryWs& qw, c
     // phase0_rows entries of d_phase0_list, and d_dead is the scope's blocked-rows bitmap
     if (prepared && !(q8_ready && d_phase0_list && d_dead && prepared->use_q8 && (!prepared->two_planes || (qw.d_q8q_hi && qw.d_q8q_lo))))
         return fail(CS_ERR_BAD_ARG, "a prepared filter plan needs the int8 copy, its query planes, a bitmap and a phase-0 list");
+    if (prepared && similar) return fail(CS_ERR_BAD_ARG, "a similar-chunk search takes no prepared filter plan");
     const FilterPlan plan = prepared ? *prepared
                                      : plan_filter(dim, n_rows, nq, k, q8_ready ? q8->rows : 0, qw.d_q8q_hi && qw.d_q8q_lo, cu_count(), kn);
     hipLaunchKernelGGL(prep_queries_kernel<J>, dim3((nq + 7) / 8), dim3(256), 0, stream,
@@ -1615,6 +1617,12 @@ static int32_t scan_split_impl(const BatchedState& st, const SplitQueryWs& qw, c
                                st.d_cnt, cap);
         const bool first = ph.lo == 0, last = p + 1 == plan.nphases;  // (plan_filter: the phase that reaches n_rows)
         if (ph.hi > ph.lo && !first) CS_HIP(hipGetLastError());
+        if (similar) {  // a similar-chunk search: its own refine and fold (scan_similar_filter.hip), same grids
+            CS_TRY(launch_similar_rescore(st, qw, d_corpus, dim, d_queries, nq, cap, ph.rk_blocks, first ? (uint32_t)ph.hi : 0u,
+                                          d_dead, id_base, similar->gv, similar->sv, stream));
+            CS_TRY(launch_similar_select(st, nq, cap, k, last, similar->sv, d_out_keys, d_out_cos, d_out_ids, d_out_counts, stream));
+            continue;
+        }
         if (first && prepared)
             hipLaunchKernelGGL((rescore_keys_kernel<J, true>), dim3(ph.rk_blocks, nq), dim3(RK_THREADS), 0, stream, d_corpus,
                                d_queries, qw.d_qmag, st.d_cand, st.d_cnt, cap, id_base, plan.phase0_rows, d_phase0_list);
@@ -1631,11 +1639,11 @@ int32_t launch_scan_split(const BatchedState& st, const SplitQueryWs& qw, const 
                           const _Float16* d_split, uint64_t n_rows, uint32_t dim, const float* d_queries, uint32_t nq, uint32_t k, const uint32_t* d_dead,
                           RowIds id_base, uint64_t* d_out_keys, float* d_out_cos, uint32_t* d_out_ids,
                           uint32_t* d_out_counts, hipStream_t stream, float margin, const Q8View* q8,
-                          const FilterPlan* prepared, const uint32_t* d_phase0_list) {
+                          const FilterPlan* prepared, const uint32_t* d_phase0_list, const SimilarRefine* similar) {
     const auto impl = dim == 384 ? scan_split_impl<3> : dim == 768 ? scan_split_impl<6> : dim == 1024 ? scan_split_impl<8> : nullptr;
     if (!impl) return fail(CS_ERR_UNSUPPORTED, "split scan supports dim 384/768/1024, got %u", dim);
     return impl(st, qw, d_corpus, d_split, n_rows, d_queries, nq, k, d_dead, id_base, d_out_keys, d_out_cos, d_out_ids,
-                d_out_counts, stream, margin, q8, prepared, d_phase0_list);
+                d_out_counts, stream, margin, q8, prepared, d_phase0_list, similar);
 }
 
 }  // namespace cs

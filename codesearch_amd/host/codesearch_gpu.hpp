@@ -222,6 +222,21 @@ class VectorStore {
                                       -std::numeric_limits<float>::infinity(), cos.data(), ids.data(), counts.data()));
         return results(cos, ids, counts[0]);
     }
+    // CS_SIMILAR_ROUTE_AUTO / _SCAN / _FILTER for similar() without a scope (cs_index_set_similar_route): same bits on every
+    // route.  similar_route_info: calls the filter answered, calls the scan answered, filter calls the scan had to finish.
+    void set_similar_route(int32_t route) {
+        if (sh_) throw Error(CS_ERR_UNSUPPORTED, "a sharded store has no similar-chunk search");
+        check(cs_index_set_similar_route(h_, route));
+    }
+    struct SimilarRouteInfo {
+        uint64_t filter_searches, scan_searches, filter_fallbacks;
+    };
+    SimilarRouteInfo similar_route_info() const {
+        if (sh_) throw Error(CS_ERR_UNSUPPORTED, "a sharded store has no similar-chunk search");
+        SimilarRouteInfo i{0, 0, 0};
+        check(cs_index_similar_route_info(h_, &i.filter_searches, &i.scan_searches, &i.filter_fallbacks));
+        return i;
+    }
     // The near-duplicate report: every pair of stored chunks a < b whose cosine is strictly above min_cos, best first by
     // (cosine desc, a asc, b asc); other_files: never two chunks of one group (file).  The corpus is joined with itself on
     // the device, exactly (cs_index_similar_pairs).  At most max_pairs pairs come back; *total (optional) = how many there

@@ -807,6 +807,27 @@ class VectorStore:
                             counts[lo:hi].ctypes.data_as(u32p)))
         return cos, ids, counts
 
+    SIMILAR_ROUTES = {"auto": _lib.CS_SIMILAR_ROUTE_AUTO, "scan": _lib.CS_SIMILAR_ROUTE_SCAN,
+                      "filter": _lib.CS_SIMILAR_ROUTE_FILTER}
+
+    def set_similar_route(self, route) -> None:
+        """The route of similar_raw / similar without a scope (cs_index_set_similar_route): "auto" (default: the int8 / f16
+        filter with an exact refine where an ordinary search of as many queries would take it, else the scan), "scan" (always
+        the f32 streaming scan) or "filter" (the filter whenever a copy can serve).  Same bits on every route."""
+        if self.sharded:
+            raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no similar-chunk search: no cs_shards_ form yet")
+        _lib.check(self._lib.cs_index_set_similar_route(self._h, self.SIMILAR_ROUTES.get(route, route)))
+
+    def similar_route_info(self):
+        """-> (filter_searches, scan_searches, filter_fallbacks) of the unscoped similar searches so far
+        (cs_index_similar_route_info): a call whose candidate buffer overflowed and that the scan then answered counts in
+        filter_searches and in filter_fallbacks."""
+        if self.sharded:
+            raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no similar-chunk search: no cs_shards_ form yet")
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _lib.check(self._lib.cs_index_similar_route_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
     def similar(self, chunk_id: int, limit: int, other_files: bool = False, min_score: Optional[float] = None,
                 scope: Optional[Scope] = None) -> List[SearchResult]:
         """The `limit` chunks most similar to chunk `chunk_id`, best first, never the chunk itself; other_files=True: none

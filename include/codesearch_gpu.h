@@ -334,13 +334,33 @@ CS_API int32_t cs_index_search_variants_grouped_scoped(cs_index* h, cs_scope* sc
  * in 1..CS_MAX_K; there is no dim argument); a null buffer; exclude outside 0..2; a NaN min_cos; then the ids, the first
  * offending one named in the text — an id never issued is CS_ERR_BAD_ARG, and so is an id issued and deleted since, with a
  * text that says the chunk was deleted, whether its row is only tombstoned or already reclaimed.  A failing call writes
- * nothing and launches nothing.  No cs_shards_ or device-pointer form yet. */
+ * nothing and launches nothing.  No cs_shards_ or device-pointer form yet.
+ * ROUTE (cs_index_set_similar_route; the answer is the same bits on every route): CS_SIMILAR_ROUTE_SCAN is the f32 streaming
+ * scan under the exclusions.  CS_SIMILAR_ROUTE_AUTO (default) takes the int8 / f16 filter with an exact refine exactly when
+ * cs_index_search would take it for nq queries at this k — the refine drops the excluded rows and the rows under the
+ * bound, so the filter's threshold is the k-th best of the rows the query may return — and scans otherwise.
+ * CS_SIMILAR_ROUTE_FILTER takes the filter whenever a copy can serve (dim 384 / 768 / 1024, filter copies kept, room for its
+ * buffers) and scans, counted as a scan, when none can.  A call whose candidate buffer overflows — an excluded file of
+ * thousands of near-duplicates of the source does that — is answered by the scan after the filter: exact, at the cost of
+ * both.  Similar calls never strike the int8 copy and do not move cs_index_debug_counters or cs_index_filter_state; their
+ * own counters are cs_index_similar_route_info's. */
 #define CS_SIMILAR_EXCLUDE_NONE  0   /* nothing excluded: the source chunk comes back first */
 #define CS_SIMILAR_EXCLUDE_SELF  1   /* the source chunk itself */
 #define CS_SIMILAR_EXCLUDE_GROUP 2   /* the source chunk, and every chunk of its group when that group is not CS_NO_GROUP */
 CS_API int32_t cs_index_search_similar(cs_index* h, const uint32_t* ids, uint32_t nq, uint32_t k,
                                        int32_t exclude, float min_cos,
                                        float* out_cos, uint32_t* out_ids, uint32_t* out_counts);
+/* The route of cs_index_search_similar on this index (cs_index_search_similar_scoped always takes its gathered scan).  The
+ * initial route is CS_SIMILAR_ROUTE=auto|scan|filter in the environment of cs_index_create.  A null handle or a route outside
+ * 0..2 is CS_ERR_BAD_ARG.  cs_index_similar_route_info: unscoped calls the filter route answered (filter_searches), those of
+ * them whose candidate buffer overflowed and that the scan then answered (filter_fallbacks: counted in both), and calls the
+ * scan answered from the start (scan_searches); any pointer may be null. */
+#define CS_SIMILAR_ROUTE_AUTO   0   /* default */
+#define CS_SIMILAR_ROUTE_SCAN   1   /* always the f32 streaming scan: what the call did before */
+#define CS_SIMILAR_ROUTE_FILTER 2   /* the filter whenever a copy can serve; else the scan */
+CS_API int32_t cs_index_set_similar_route(cs_index* h, int32_t route);
+CS_API int32_t cs_index_similar_route_info(cs_index* h, uint64_t* filter_searches, uint64_t* scan_searches,
+                                           uint64_t* filter_fallbacks);
 /* Similar-chunk search inside a scope — "where else under src/ is this function copied", "the clones of this chunk inside
  * the package I am refactoring", "more like this, but only in tests".  Searching the whole store and dropping what is outside
  * the directory loses most or all of the k hits; a scoped search of the row read back at k + 1 is exact for the chunk itself
