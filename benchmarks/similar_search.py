@@ -11,7 +11,7 @@ has no streaming route for nine queries in one call.  What one call of nine rows
 once per shape and not alternated with the new call: on the library's default route (the int8 filter + exact refine: baseline_one_call_default_ms) and
 with the filter switched off (five or more queries then take the exact-f32 MFMA path: baseline_one_call_nofilter_ms).
 
-    python benchmarks/similar_search.py [--rows 10000000] [--dim 384] [--reps 20] [--out FILE] [--tree DIR] [--scoped | --routes]
+    python benchmarks/similar_search.py [--rows 10000000] [--dim 384] [--reps 20] [--out FILE] [--tree DIR] [--scoped] [--routes]
 
 The store: synthetic rows in files of 8 ids, with rows [2/10, 3/10) of it replaced by one file of near-duplicates of its
 first row (0.95 s + 0.05 noise).  The "hog" source is that first row; the "ordinary" source is a row far from the file.
@@ -34,7 +34,17 @@ random 1 % and the near-duplicate file plus a random 1 %; the source is the file
 ordinary row for the others, which does not lie in the random scopes' ids unless drawn.  The baseline is what a caller can
 do without the call: one read per source (cs_index_read_rows), then ONE cs_index_search_scoped of those rows with the
 scope on CS_SCOPE_ROUTE_GATHER at k + 1, the excluded rows dropped on the host — exact for "self" only.  The same
-alternation, and baseline_exact_found as above."""
+alternation, and baseline_exact_found as above.
+
+--scoped --routes: the scoped call's two routes against each other (cs_scope_set_route), as --routes does for the unscoped
+call: FILTER, GATHER, FILTER again in one process, --reps calls each, the bytes of the two routes compared before anything
+is timed.  The scopes of --scoped and a contiguous 10 % in the store's far half.  planned_span: the rows the filter phases
+stream for the case (scoped_filter_plan.hpp: from the end of the granule that holds list entry 3,071 to the end of the
+granule that holds the last one) and span_over_live its ratio to the scope's rows; auto_route: what CS_SCOPE_ROUTE_AUTO
+picks, read from the scope's counters; filter_calls / overflow_reruns: whether the FILTER series were answered by the filter
+and how many of them fell back to the gathered similar scan after an overflowed candidate buffer (the call then costs
+both).  Under --tree with a library whose scoped call has no filter route, filter_calls is 0 and both series time the
+gathered scan."""
 import argparse
 import json
 import os
@@ -110,6 +120,61 @@ def scoped_cases(a, st, lib, h, _lib, emit, sources, others, groups, hog_lo, hog
                         else:
                             rec["baseline_ms"] = med(timed(baseline, a.reps))
                         emit(rec)
+        sc.close()
+
+
+def scoped_route_cases(a, st, lib, h, _lib, emit, sources, others, hog_lo, hog_n, modes, med):
+    from codesearch_amd._lib import f32p, u32p
+
+    n, dim = a.rows, a.dim
+    rng = np.random.default_rng(3)
+    tenth, hundredth = np.sort(rng.choice(n, n // 10, replace=False)), np.sort(rng.choice(n, n // 100, replace=False))
+    hog = np.union1d(np.arange(hog_lo, hog_lo + hog_n), np.sort(rng.choice(n, n // 100, replace=False)))
+    far = np.arange(n - n // 10 - n // 20, n - n // 20)  # contiguous 10 % in the far half
+    up = lambda v: (int(v) + 1023) // 1024 * 1024  # noqa: E731
+    for sname, ids, kind in (("all", np.arange(n), "ordinary"), ("10%", tenth, "ordinary"), ("1%", hundredth, "ordinary"),
+                             ("hog+1%", hog, "hog"), ("far 10%", far, "ordinary")):
+        sc = st.scope(ids)
+        span = (min(up(ids[-1] + 1), n) - up(ids[3071] + 1)) if ids.size > 3072 else 0
+        for nq, k, mname, bound in ((nq, k, m, b) for nq in (1, 9) for k in (10, 200) for m in modes for b in (None, 0.9)):
+            srcs = np.ascontiguousarray(np.concatenate([[sources[kind]], others[:nq - 1]]), np.uint32)
+            cos, idb, cnt = np.zeros((nq, k), np.float32), np.zeros((nq, k), np.uint32), np.zeros(nq, np.uint32)
+
+            def similar():
+                _lib.check(lib.cs_index_search_similar_scoped(h, sc.handle, srcs.ctypes.data_as(u32p), nq, k, modes[mname],
+                                                              float("-inf") if bound is None else bound,
+                                                              cos.ctypes.data_as(f32p), idb.ctypes.data_as(u32p),
+                                                              cnt.ctypes.data_as(u32p)))
+
+            rec = {"scope": sname, "scope_ids": int(ids.size), "source": kind, "rows": n, "dim": dim, "nq": nq, "k": k,
+                   "mode": mname, "min_cos": bound, "reps": a.reps, "planned_span": int(span),
+                   "span_over_live": round(span / ids.size, 3)}
+            sc.set_route("auto")
+            i0 = sc.route_info()
+            similar()
+            i1 = sc.route_info()
+            rec["auto_route"] = "filter" if i1[0] > i0[0] else "gather"
+            sc.set_route("filter")
+            similar()
+            got = (cos.copy(), idb.copy(), cnt.copy())
+            sc.set_route("gather")
+            similar()
+            rec["same_bytes"] = all(x.tobytes() == y.tobytes() for x, y in zip(got, (cos, idb, cnt)))
+            i1 = sc.route_info()
+            sc.set_route("filter")
+            t1 = timed(similar, a.reps)
+            sc.set_route("gather")
+            tg = timed(similar, a.reps)
+            sc.set_route("filter")
+            t2 = timed(similar, a.reps)
+            i2 = sc.route_info()
+            calls = 2 * (a.reps + 1)
+            rec.update({"filter_ms": med(t1 + t2), "filter_before_ms": med(t1), "filter_after_ms": med(t2), "gather_ms": med(tg),
+                        "spread_ms": round(abs(med(t1) - med(t2)), 4), "count": int(cnt[0]), "filter_series_calls": calls,
+                        "filter_calls": i2[0] - i1[0], "overflow_reruns": i2[2] - i1[2]})
+            rec["fell_back"] = rec["filter_calls"] < calls or rec["overflow_reruns"] > 0
+            rec["ratio_vs_gather"] = round(rec["filter_ms"] / rec["gather_ms"], 4)
+            emit(rec)
         sc.close()
 
 
@@ -208,10 +273,13 @@ def main():
     kinds = [("ordinary", np.uint32(n - n // 7)), ("hog", np.uint32(hog_lo))]
     modes = {"none": 0, "self": 1, "file": 2}
     med = lambda t: round(float(np.median(t)), 4)  # noqa: E731
-    if a.routes:
+    if a.routes and a.scoped:
+        scoped_route_cases(a, st, lib, h, _lib, emit, dict(kinds), others, hog_lo, hog_n, modes, med)
+        kinds = []
+    elif a.routes:
         route_cases(a, st, lib, h, _lib, emit, dict(kinds), others, modes, med)
         kinds = []
-    if a.scoped:
+    elif a.scoped:
         scoped_cases(a, st, lib, h, _lib, emit, dict(kinds), others, groups, hog_lo, hog_n, modes, med)
         kinds = []
     for kind, src in kinds:

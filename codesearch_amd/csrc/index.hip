@@ -1194,10 +1194,61 @@ int32_t run_similar(cs_index* h, Workspace* w, const ScanPlan& plan, uint32_t nq
     return similar_scan(h, w, plan, nq, k, gv, sv, keys);
 }
 
+// The scope's gathered similar scan and its merge: the GATHER route of a scoped similar-chunk search, and the exact answer
+// of a FILTER-route call whose candidate buffer overflowed (never run_row_list, which knows no exclusions).
+int32_t similar_list_scan(cs_index* h, cs_scope* sc, Workspace* w, const ScanPlan& plan, uint32_t nq, uint32_t k,
+                          const GroupView& gv, const SimilarView& sv, uint64_t* keys) {
+    CS_TRY(launch_scan_similar_list(plan, h->d_corpus, h->dim, sc->d_list, sc->d_blocks + scope_list_blocks(sc->n_ids), w->d_queries,
+                                    nq, k, h->row_ids(), gv, sv, w->d_partial, w->stream));
+    return launch_merge(w->d_partial, plan.blocks, nq, k, false, w->d_tmp_a, w->d_tmp_b, keys, nullptr, nullptr, nullptr, w->stream);
+}
+
+// A scoped similar-chunk search whose source rows are gathered in w->d_queries: run_scoped's sequence with run_similar's
+// query handling.  With a filter plan (scope_ready: the scope's route, scoped_wants_filter as for the ordinary scoped search)
+// whose int8 query planes and buffers fit, the index's filter runs over the plan's row ranges with the scope's bitmap where
+// the tombstones go and the similar refine and fold (scan_similar_filter.hip; phase 0 in its list form); "no room" anywhere
+// quietly takes the gathered scan and counts as gathered.  An overflowed candidate buffer — the excluded file's doing, as in
+// run_similar — is settled here by the gathered similar scan into the same keys, counted per scope.  No strike against the
+// int8 copy, no f16 stage, none of the index's counters: last_via_q8 is false and words [0] and [1] of the overflow state are
+// cleared in stream order behind the read, as run_scoped clears them.
+int32_t run_similar_scoped(cs_index* h, cs_scope* sc, Workspace* w, const ScanPlan& plan, uint64_t live, const ScopedFilterPlan& fp,
+                           uint32_t nq, uint32_t k, const GroupView& gv, const SimilarView& sv, uint64_t* keys) {
+    bool room = false;
+    if (fp.ok) {
+        bool planes = false;
+        int32_t rc = w->reserve_split_queries(nq, h->dim, true, &planes);
+        if (rc == CS_OK && planes) rc = w->reserve_batched(nq, k);
+        if (rc != CS_OK && rc != CS_ERR_OOM) return rc;
+        if (rc == CS_ERR_OOM) (void)hipGetLastError();  // no room: the gathered scan answers
+        room = rc == CS_OK && planes;
+    }
+    if (!room) {
+        sc->gathered_searches.fetch_add(1);
+        return similar_list_scan(h, sc, w, plan, nq, k, gv, sv, keys);
+    }
+    sc->filter_searches.fetch_add(1);
+    w->qw.q_pinned = nullptr;  // the gathered rows are device memory (QuerySource::Device)
+    w->last_via_q8 = false;    // (this search is no reading of the int8 copy in the strike bookkeeping)
+    Q8View q8;
+    q8.d_q8 = h->d_q8; q8.d_tmeta = h->d_tmeta; q8.d_mu = h->d_mu; q8.rows = h->q8_rows;
+    const SimilarRefine refine{sv, gv};
+    CS_TRY(launch_scan_split(w->bs, w->qw, h->d_corpus, nullptr, h->ledger.stored(), h->dim, w->d_queries, nq, k, sc->d_blocked,
+                             h->row_ids(), keys, nullptr, nullptr, nullptr, w->stream, h->filter_margin, &q8, &fp.plan, sc->d_list,
+                             &refine));
+    if (live <= batched_cap(k)) return CS_OK;  // a phase appends at most one candidate per allowed row
+    bool overflow = false;
+    CS_TRY(w->read_overflow(w->stream, &overflow));
+    if (!overflow) return CS_OK;
+    sc->overflow_reruns.fetch_add(1);
+    CS_HIP(hipMemsetAsync(w->bs.d_overflow, 0, 2 * sizeof(uint32_t), w->stream));  // (run_scoped: the overflow is the scope's alone)
+    return similar_list_scan(h, sc, w, plan, nq, k, gv, sv, keys);
+}
+
 // The similar-chunk searches (scan_similar.hip): the sources resolved on the host (similar_sources.hpp), their rows gathered
 // into w->d_queries on the device, the scan's arithmetic under the per-query exclusions, the ordinary merge.  Over the whole
 // store (scope_given false: run_similar — the streaming scan over every stored row, or the filter with the similar refine) or
-// over a scope's row list (the gathered scan, always, as for the grouped search).  Every check, the scope's handle-level ones before the ids, comes before the scope's list is
+// over a scope's row list (run_similar_scoped: the gathered scan, or the int8 filter planned over the scope's rows, by the
+// scope's route).  Every check, the scope's handle-level ones before the ids, comes before the scope's list is
 // refreshed; groups_mu is released before the scope's mutex is taken.
 int32_t search_similar(cs_index* h, bool scope_given, cs_scope* scope, const uint32_t* ids, uint32_t nq, uint32_t k,
                        int32_t exclude, float min_cos, const HostAnswer& out) {
@@ -1220,8 +1271,9 @@ int32_t search_similar(cs_index* h, bool scope_given, cs_scope* scope, const uin
             return fail(CS_ERR_BAD_ARG, "ids[%u] = %u: the chunk was deleted", sc.at, ids[sc.at]);
     }
     uint64_t rows = h->ledger.stored();
+    ScopedFilterPlan fp;
     if (scope_given) {
-        CS_TRY(scope_ready(h, scope, &rows));
+        CS_TRY(scope_ready(h, scope, &rows, &fp, nq, k));
         if (rows == 0) return empty_answer(nq, k, out);  // nothing of the scope is stored
     }
     if (exclude == CS_SIMILAR_EXCLUDE_GROUP) CS_TRY(ensure_groups(h, 0xFFFFFFFFu, &gv));
@@ -1235,15 +1287,8 @@ int32_t search_similar(cs_index* h, bool scope_given, cs_scope* scope, const uin
         CS_HIP(hipMemcpyAsync(w->d_similar, w->h_similar, 3 * (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice, w->stream));
         CS_TRY(launch_gather_sources(h->d_corpus, h->dim, w->d_similar, nq, w->d_queries, w->stream));
         const SimilarView sv{w->d_similar + nq, w->d_similar + 2 * (size_t)nq, min_cos};
-        if (scope_given) {
-            scope->gathered_searches.fetch_add(1);
-            CS_TRY(launch_scan_similar_list(plan, h->d_corpus, h->dim, scope->d_list, scope->d_blocks + scope_list_blocks(scope->n_ids),
-                                            w->d_queries, nq, k, h->row_ids(), gv, sv, w->d_partial, w->stream));
-        } else {
-            return run_similar(h, w, plan, nq, k, gv, sv, keys);
-        }
-        return launch_merge(w->d_partial, plan.blocks, nq, k, false, w->d_tmp_a, w->d_tmp_b, keys, nullptr, nullptr, nullptr,
-                            w->stream);
+        if (scope_given) return run_similar_scoped(h, scope, w, plan, rows, fp, nq, k, gv, sv, keys);
+        return run_similar(h, w, plan, nq, k, gv, sv, keys);
     });
 }
 

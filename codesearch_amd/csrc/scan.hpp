@@ -171,10 +171,12 @@ struct BatchedState;
 struct SplitQueryWs;
 // rescore_keys_kernel's work and grid (rk_blocks blocks per query; first_rows != 0: phase 0, candidate i is row i) with the
 // similar search's final store: the key is empty unless the cosine is > sv.min_cos and the query keeps the row.
+// d_list != null with first_rows != 0 (phase 0 of a scoped call): candidate i is row d_list[i], i < first_rows <= cap, and
+// no bitmap is read — the list holds live, allowed rows only.
 int32_t launch_similar_rescore(const BatchedState& st, const SplitQueryWs& qw, const float* d_corpus, uint32_t dim,
                                const float* d_queries, uint32_t nq, uint32_t cap, uint32_t rk_blocks, uint32_t first_rows,
                                const uint32_t* d_dead, RowIds ids, const GroupView& gv, const SimilarView& sv,
-                               hipStream_t stream);
+                               hipStream_t stream, const uint32_t* d_list = nullptr);
 // launch_select_candidates whose threshold never falls below sv.min_cos.
 int32_t launch_similar_select(const BatchedState& st, uint32_t nq, uint32_t cap, uint32_t k, bool last, const SimilarView& sv,
                               uint64_t* d_out_keys, float* d_out_cos, uint32_t* d_out_ids, uint32_t* d_out_counts,

@@ -1572,7 +1572,6 @@ static int32_t scan_split_impl(const BatchedState& st, const SplitQueryWs& qw, c
     // phase0_rows entries of d_phase0_list, and d_dead is the scope's blocked-rows bitmap
     if (prepared && !(q8_ready && d_phase0_list && d_dead && prepared->use_q8 && (!prepared->two_planes || (qw.d_q8q_hi && qw.d_q8q_lo))))
         return fail(CS_ERR_BAD_ARG, "a prepared filter plan needs the int8 copy, its query planes, a bitmap and a phase-0 list");
-    if (prepared && similar) return fail(CS_ERR_BAD_ARG, "a similar-chunk search takes no prepared filter plan");
     const FilterPlan plan = prepared ? *prepared
                                      : plan_filter(dim, n_rows, nq, k, q8_ready ? q8->rows : 0, qw.d_q8q_hi && qw.d_q8q_lo, cu_count(), kn);
     hipLaunchKernelGGL(prep_queries_kernel<J>, dim3((nq + 7) / 8), dim3(256), 0, stream,
@@ -1618,8 +1617,10 @@ static int32_t scan_split_impl(const BatchedState& st, const SplitQueryWs& qw, c
         const bool first = ph.lo == 0, last = p + 1 == plan.nphases;  // (plan_filter: the phase that reaches n_rows)
         if (ph.hi > ph.lo && !first) CS_HIP(hipGetLastError());
         if (similar) {  // a similar-chunk search: its own refine and fold (scan_similar_filter.hip), same grids
-            CS_TRY(launch_similar_rescore(st, qw, d_corpus, dim, d_queries, nq, cap, ph.rk_blocks, first ? (uint32_t)ph.hi : 0u,
-                                          d_dead, id_base, similar->gv, similar->sv, stream));
+            // (a prepared plan's phase 0 is phase0_rows list entries; ph.hi is then a row boundary, not a count)
+            CS_TRY(launch_similar_rescore(st, qw, d_corpus, dim, d_queries, nq, cap, ph.rk_blocks,
+                                          first ? (prepared ? plan.phase0_rows : (uint32_t)ph.hi) : 0u, d_dead, id_base, similar->gv,
+                                          similar->sv, stream, prepared ? d_phase0_list : nullptr));
             CS_TRY(launch_similar_select(st, nq, cap, k, last, similar->sv, d_out_keys, d_out_cos, d_out_ids, d_out_counts, stream));
             continue;
         }

@@ -5,6 +5,8 @@
 //   refine   similar_rescore_kernel: rescore_keys_kernel (scan_filter.hip) restated — the same cosine, bit for bit — whose
 //            final store writes the empty key for a row the query may not return: one not strictly above min_cos, the row
 //            that carries the query's excluded id, a row of its excluded group (scan_similar.hip similar_keeps, restated).
+//            similar_rescore_kernel<J, true> is its list form, as rescore_keys_kernel<J, true> is that kernel's: phase 0 of
+//            a scoped call (a prepared plan, scoped_filter_plan.hpp) re-scores the scope's first c0 list entries.
 //   fold     similar_select_kernel: select_candidates_kernel (scan_mfma.hip) restated, whose threshold never falls below
 //            min_cos.
 //
@@ -15,6 +17,9 @@
 // similar scan's (scan_similar.hip) bit for bit.  What the exclusions cost is candidates: the rows of an excluded file of
 // near-duplicates all beat the k-th best of the others, and more than batched_cap(k) of them in one phase overflow the
 // buffer — then index.hip answers from the similar scan.
+// None of this asks where the row ranges or the bitmap come from: with a scope's prepared plan and its blocked-rows bitmap
+// (index.hip run_similar_scoped) "the rows scanned so far" are the scope's, and the answer equals the scope's gathered
+// similar scan (scan_similar.hip part 4) bit for bit; an overflow is then answered by that scan.
 #include "scan.hpp"
 #include "block_select.hpp"
 #include "grouped_plan.hpp"  // kNoGroup
@@ -48,7 +53,10 @@ __device__ __forceinline__ uint32_t sf_group_of(const GroupView& gv, uint32_t id
 // empty keys.  The key is 0 unless the cosine is finite and > min_cos (-inf: no bound) and the row is kept; the bound is
 // tested first, then the id, then — only for a query that excludes a group — the row's group: one 4-byte table read per
 // candidate that survived the first two.  ex_ids[q] and ex_groups[q] are block-uniform (q = blockIdx.y).
-template <int J>
+// LIST (phase 0 of a scoped call, scoped_filter_plan.hpp; first_rows != 0): candidate i is row dead[i] — the scope's ascending
+// row list is passed where the bitmap goes, as to rescore_keys_kernel<J, true>; it holds live, allowed rows only, so no bit
+// is tested.  The exclusions are: a source inside the scope, and the rows of its file, are list entries like any other.
+template <int J, bool LIST = false>
 __global__ void __launch_bounds__(SRK_THREADS)
 similar_rescore_kernel(const float* __restrict__ corpus, const float* __restrict__ queries, const float* __restrict__ qmag,
                        uint64_t* __restrict__ cand, const uint32_t* __restrict__ cnt, uint32_t cap, RowIds id_base,
@@ -78,7 +86,7 @@ similar_rescore_kernel(const float* __restrict__ corpus, const float* __restrict
 #pragma unroll
         for (int u = 0; u < RU; ++u) {
             const uint32_t i = i0 + u * (SRK_THREADS / 32) + hw;  // half-wave uniform
-            row[u] = (i < n) ? (first_rows ? i : (uint32_t)slots[i]) : 0u;
+            row[u] = (i < n) ? (first_rows ? (LIST ? dead[i] : i) : (uint32_t)slots[i]) : 0u;
         }
 #pragma unroll
         for (int u = 0; u < RU; ++u) {
@@ -105,7 +113,7 @@ similar_rescore_kernel(const float* __restrict__ corpus, const float* __restrict
                 const float d = sf_half_sum(dot);
                 const float c = (qm == 0.0f || xmag == 0.0f) ? 0.0f : d / (qm * xmag);  // batch.rs:320-323
                 // NaN/Inf scores are never returned
-                const bool live = !(first_rows && dead) || !((dead[row[u] >> 5] >> (row[u] & 31)) & 1u);
+                const bool live = LIST || !(first_rows && dead) || !((dead[row[u] >> 5] >> (row[u] & 31)) & 1u);
                 if (l32 == 0) {
                     uint64_t key = 0ull;
                     if (live && c > -__builtin_huge_valf() && c < __builtin_huge_valf() && c > min_cos) {
@@ -200,22 +208,32 @@ static int32_t check_similar_view(const SimilarView& sv) {
     return CS_OK;
 }
 
+template <int J>
+static void similar_rescore_launch(const dim3 grid, hipStream_t stream, const float* d_corpus, const float* d_queries,
+                                   const float* d_qmag, const BatchedState& st, uint32_t cap, RowIds ids, uint32_t first_rows,
+                                   const uint32_t* d_dead, const uint32_t* d_list, const GroupView& gv, const SimilarView& sv) {
+    if (first_rows && d_list)
+        hipLaunchKernelGGL((similar_rescore_kernel<J, true>), grid, dim3(SRK_THREADS), 0, stream, d_corpus, d_queries, d_qmag,
+                           st.d_cand, st.d_cnt, cap, ids, first_rows, d_list, gv, sv.d_ex_ids, sv.d_ex_groups, sv.min_cos);
+    else
+        hipLaunchKernelGGL(similar_rescore_kernel<J>, grid, dim3(SRK_THREADS), 0, stream, d_corpus, d_queries, d_qmag, st.d_cand,
+                           st.d_cnt, cap, ids, first_rows, d_dead, gv, sv.d_ex_ids, sv.d_ex_groups, sv.min_cos);
+}
+
 int32_t launch_similar_rescore(const BatchedState& st, const SplitQueryWs& qw, const float* d_corpus, uint32_t dim,
                                const float* d_queries, uint32_t nq, uint32_t cap, uint32_t rk_blocks, uint32_t first_rows,
                                const uint32_t* d_dead, RowIds ids, const GroupView& gv, const SimilarView& sv,
-                               hipStream_t stream) {
+                               hipStream_t stream, const uint32_t* d_list) {
     CS_TRY(check_similar_view(sv));
     if (rk_blocks == 0 || nq == 0) return fail(CS_ERR_BAD_ARG, "similar refine: empty grid");
-    const dim3 grid(rk_blocks, nq), block(SRK_THREADS);
+    if (d_list && first_rows > cap) return fail(CS_ERR_BAD_ARG, "similar refine: a phase-0 list of %u rows does not fit", first_rows);
+    const dim3 grid(rk_blocks, nq);
     if (dim == 384)
-        hipLaunchKernelGGL(similar_rescore_kernel<3>, grid, block, 0, stream, d_corpus, d_queries, qw.d_qmag, st.d_cand, st.d_cnt,
-                           cap, ids, first_rows, d_dead, gv, sv.d_ex_ids, sv.d_ex_groups, sv.min_cos);
+        similar_rescore_launch<3>(grid, stream, d_corpus, d_queries, qw.d_qmag, st, cap, ids, first_rows, d_dead, d_list, gv, sv);
     else if (dim == 768)
-        hipLaunchKernelGGL(similar_rescore_kernel<6>, grid, block, 0, stream, d_corpus, d_queries, qw.d_qmag, st.d_cand, st.d_cnt,
-                           cap, ids, first_rows, d_dead, gv, sv.d_ex_ids, sv.d_ex_groups, sv.min_cos);
+        similar_rescore_launch<6>(grid, stream, d_corpus, d_queries, qw.d_qmag, st, cap, ids, first_rows, d_dead, d_list, gv, sv);
     else if (dim == 1024)
-        hipLaunchKernelGGL(similar_rescore_kernel<8>, grid, block, 0, stream, d_corpus, d_queries, qw.d_qmag, st.d_cand, st.d_cnt,
-                           cap, ids, first_rows, d_dead, gv, sv.d_ex_ids, sv.d_ex_groups, sv.min_cos);
+        similar_rescore_launch<8>(grid, stream, d_corpus, d_queries, qw.d_qmag, st, cap, ids, first_rows, d_dead, d_list, gv, sv);
     else
         return fail(CS_ERR_UNSUPPORTED, "similar refine supports dim 384/768/1024, got %u", dim);
     CS_HIP(hipGetLastError());

@@ -2,6 +2,9 @@
 // exclusions (scan_similar.hip), or the int8 / f16 filter with the similar refine and fold (scan_similar_filter.hip).  Both
 // return the same bits; the route is a matter of cost only.  Plain C++17, no HIP: tests/cpp/similar_route_test.cpp pins the
 // routes on the CPU, and search_similar only launches what plan_similar_route returns.
+// This is the UNSCOPED call's route.  The scoped call (index.hip run_similar_scoped) has no logic here: its route is its
+// scope's (cs_scope_set_route), decided by scope_ready with scoped_wants_filter (scoped_filter_plan.hpp) exactly as for the
+// ordinary scoped search, and the functions below keep answering Scan for scoped == true.
 #pragma once
 
 #include <cstdint>
@@ -24,7 +27,7 @@ inline bool similar_filter_dim(uint32_t dim) { return dim == 384 || dim == 768 |
 //           counts, the single-query route); the preconditions stay: filter copies are kept (use_split), the row norms cover
 //           every row, the width, no scope.
 //   SCAN    never.
-// A scoped call always answers false: the scoped similar search keeps to its gathered scan.
+// A scoped call always answers false: cs_index_set_similar_route does not govern the scoped similar search.
 inline bool similar_wants_filter(const RouteKnobs& kn, const SearchShape& s, bool q8_serves, bool scoped, int32_t forced) {
     if (forced == CS_SIMILAR_ROUTE_SCAN || scoped || !similar_filter_dim(s.dim) || s.pinned) return false;
     if (forced == CS_SIMILAR_ROUTE_FILTER) return s.use_split && s.normed;

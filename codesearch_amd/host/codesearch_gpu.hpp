@@ -400,7 +400,8 @@ class VectorStore {
         return results(cos, ids, counts[0]);
     }
     // similar() among the chunks of a Scope only (cs_index_search_similar_scoped): "where else under src/ is this copied".
-    // Chunk `id` itself need not be in the scope.  One index only.
+    // Chunk `id` itself need not be in the scope.  One index only.  The scope's route (cs_scope_set_route) picks the gathered
+    // scan or the int8 filter planned over the scope's rows; the results are the same.
     std::vector<SearchResult> similar(uint32_t id, size_t limit, bool other_files, const Scope& scope) const {
         if (sh_) throw Error(CS_ERR_UNSUPPORTED, "a sharded store has no similar-chunk search");
         std::vector<float> cos(limit);

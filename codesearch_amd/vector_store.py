@@ -202,17 +202,18 @@ class Scope:
     ROUTES = {"auto": 0, "gather": 1, "filter": 2}  # CS_SCOPE_ROUTE_*
 
     def set_route(self, route):
-        """The route of this scope's host-buffer searches (cs_scope_set_route): "auto" (default), "gather" (always the
-        gathered f32 scan) or "filter" (the int8 filter + exact refine wherever it can serve), or the CS_SCOPE_ROUTE_*
-        value.  The answers' bytes do not depend on it."""
+        """The route of this scope's host-buffer searches — search_raw(scope=), the variants form and similar_raw(scope=)
+        (cs_scope_set_route): "auto" (default), "gather" (always the gathered f32 scan) or "filter" (the int8 filter + exact
+        refine wherever it can serve), or the CS_SCOPE_ROUTE_* value.  The answers' bytes do not depend on it.  Grouped scoped
+        searches always gather."""
         if not self._h:
             raise CsError(_lib.CS_ERR_BAD_ARG, "scope is closed")
         _lib.check(self.store._lib.cs_scope_set_route(self._h, self.ROUTES.get(route, route)))
 
     def route_info(self):
-        """-> (filter_searches, gathered_searches, overflow_reruns, extra_bytes): host-buffer searches answered through
-        the filter / by the gathered scan, exact reruns after an overflowed candidate buffer, and the bytes of HBM held
-        beyond 8 per id (cs_scope_route_info)."""
+        """-> (filter_searches, gathered_searches, overflow_reruns, extra_bytes): host-buffer searches, similar-chunk
+        searches included, answered through the filter / by the gathered scan, exact reruns after an overflowed candidate
+        buffer (counted in filter_searches too), and the bytes of HBM held beyond 8 per id (cs_scope_route_info)."""
         if not self._h:
             raise CsError(_lib.CS_ERR_BAD_ARG, "scope is closed")
         v = [C.c_uint64() for _ in range(4)]
@@ -782,7 +783,9 @@ class VectorStore:
         (its file; set_groups for rows without metadata).  The exclusion is part of the selection, not a filter on a ranked
         list.  min_cos: only chunks whose cosine is strictly greater are returned (None: no bound).
         scope: only the scope's chunks are returned (cs_index_search_similar_scoped: the exact best `limit` among them); the
-        sources themselves need not be in it.
+        sources themselves need not be in it.  The scope's route (Scope.set_route) picks between the gathered scan and the
+        int8 filter planned over the scope's rows — same bits — and Scope.route_info() counts the call; set_similar_route
+        governs the call without a scope only.
         -> (cos [n, limit] f32, ids [n, limit] u32, counts [n] u32); more than CS_MAX_QUERIES sources go in several calls."""
         if self.sharded:
             raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no similar-chunk search: no cs_shards_ form yet")
@@ -832,8 +835,8 @@ class VectorStore:
                 scope: Optional[Scope] = None) -> List[SearchResult]:
         """The `limit` chunks most similar to chunk `chunk_id`, best first, never the chunk itself; other_files=True: none
         of its file either (the files assigned at insert).  min_score: only chunks whose score — the reference's scale,
-        cos_to_score — is above it.  scope: only chunks of the scope (similar_raw).  Results whose metadata is missing are
-        skipped, as in search()."""
+        cos_to_score — is above it.  scope: only chunks of the scope (similar_raw; the scope's route picks the gathered scan or
+        the int8 filter, same results).  Results whose metadata is missing are skipped, as in search()."""
         min_cos = None if min_score is None else score_to_cos(min_score)
         cos, ids, counts = self.similar_raw([int(chunk_id)], limit, exclude="file" if other_files else "self", min_cos=min_cos,
                                             scope=scope)

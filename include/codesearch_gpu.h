@@ -226,8 +226,8 @@ CS_API void    cs_scope_destroy(cs_scope* scope);
  * on a built store (0 on one not built: the first search makes it), +1 per build generation actually searched.  Over a
  * sharded store the first two are sums over the shards.  Each output optional. */
 CS_API int32_t cs_scope_info(const cs_scope* scope, uint64_t* n_ids, uint64_t* live_rows, uint64_t* refreshes);
-/* The route of the host-buffer scoped searches (cs_index_search_scoped, cs_index_search_variants_scoped); the answer's
- * bytes do not depend on it.  A scope over a store of dim 384 / 768 / 1024 whose list outgrows 3,072 rows additionally
+/* The route of the host-buffer scoped searches (cs_index_search_scoped, cs_index_search_variants_scoped,
+ * cs_index_search_similar_scoped); the answer's bytes do not depend on it.  A scope over a store of dim 384 / 768 / 1024 whose list outgrows 3,072 rows additionally
  * keeps, remade with the list, a blocked-rows bitmap in HBM (one bit per stored row: tombstoned or not in the scope) and
  * on the host the list's first 4,096 entries and every 1,024th; with them such a search can run through the index's int8
  * filter + exact refine, its phases planned over the scope's rows, instead of the gathered f32 scan.
@@ -239,8 +239,10 @@ CS_API int32_t cs_scope_info(const cs_scope* scope, uint64_t* n_ids, uint64_t* l
  *   CS_SCOPE_ROUTE_FILTER the filter whenever it can serve: where the int8 copy does not, the dim has no filter kernels
  *                         or the whole list fits the first phase, the search quietly takes the gathered scan.
  * A candidate buffer that overflows is settled by an exact rerun over the scope's list, counted per scope; it is no
- * strike against the index's int8 copy.  The device-pointer and sharded forms always take the gathered scan; on a
- * scope over a sharded store the call is CS_ERR_BAD_ARG. */
+ * strike against the index's int8 copy.  For cs_index_search_similar_scoped the filter's refine applies the exclusions and
+ * the bound, the rerun is the gathered similar scan, and the usual cause of an overflow is an excluded file of more
+ * near-duplicates than the candidate buffer holds in one phase.  The device-pointer, grouped and sharded forms always take
+ * the gathered scan; on a scope over a sharded store the call is CS_ERR_BAD_ARG. */
 enum { CS_SCOPE_ROUTE_AUTO = 0, CS_SCOPE_ROUTE_GATHER = 1, CS_SCOPE_ROUTE_FILTER = 2 };
 CS_API int32_t cs_scope_set_route(cs_scope* scope, int32_t route);
 /* Host-buffer searches answered through the filter / by the gathered scan, exact reruns after an overflow, and the
@@ -350,7 +352,8 @@ CS_API int32_t cs_index_search_variants_grouped_scoped(cs_index* h, cs_scope* sc
 CS_API int32_t cs_index_search_similar(cs_index* h, const uint32_t* ids, uint32_t nq, uint32_t k,
                                        int32_t exclude, float min_cos,
                                        float* out_cos, uint32_t* out_ids, uint32_t* out_counts);
-/* The route of cs_index_search_similar on this index (cs_index_search_similar_scoped always takes its gathered scan).  The
+/* The route of cs_index_search_similar on this index (cs_index_search_similar_scoped follows its scope's route,
+ * cs_scope_set_route, and moves none of these counters).  The
  * initial route is CS_SIMILAR_ROUTE=auto|scan|filter in the environment of cs_index_create.  A null handle or a route outside
  * 0..2 is CS_ERR_BAD_ARG.  cs_index_similar_route_info: unscoped calls the filter route answered (filter_searches), those of
  * them whose candidate buffer overflowed and that the scan then answered (filter_fallbacks: counted in both), and calls the
@@ -376,9 +379,15 @@ CS_API int32_t cs_index_similar_route_info(cs_index* h, uint64_t* filter_searche
  * Errors, in this order: those of cs_index_search_similar up to and including the NaN bound, with their texts; a null scope,
  * then a scope made for another store (a scope over a sharded store included; CS_ERR_BAD_ARG); then the ids, as there.  All
  * of them are decided before the scope's list is refreshed and before anything is launched or written.  A scope with no live
- * row gives the empty answer and launches nothing — after the ids were checked.  Always the gathered scan, whatever
- * cs_scope_set_route says, counted in cs_scope_route_info's gathered_searches.  Concurrent calls through one scope or several
- * are safe.  No cs_shards_, masked (bitmap) or device-pointer form yet. */
+ * row gives the empty answer and launches nothing — after the ids were checked.
+ * Route: the scope's (cs_scope_set_route; cs_index_set_similar_route governs the unscoped call only), counted in
+ * cs_scope_route_info.  The gathered f32 scan under the exclusions, or — AUTO by the rule of the ordinary scoped search of
+ * as many queries, FILTER wherever it can serve — the index's int8 filter planned over the scope's rows with a refine that
+ * drops the excluded rows and the rows under the bound; the same bits either way.  A scope of 3,072 ids or fewer, a dim
+ * other than 384 / 768 / 1024, an index without a serving int8 copy and a call that finds no room for the filter's buffers
+ * take the gathered scan, quietly.  A filter call whose candidate buffer overflows is answered by the gathered scan
+ * (overflow_reruns); it is no strike against the int8 copy and moves none of the index's counters.  Concurrent calls
+ * through one scope or several are safe.  No cs_shards_, masked (bitmap) or device-pointer form yet. */
 CS_API int32_t cs_index_search_similar_scoped(cs_index* h, cs_scope* scope, const uint32_t* ids, uint32_t nq, uint32_t k,
                                               int32_t exclude, float min_cos,
                                               float* out_cos, uint32_t* out_ids, uint32_t* out_counts);
