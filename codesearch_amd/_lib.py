@@ -23,9 +23,12 @@ CS_SIMILAR_EXCLUDE_NONE, CS_SIMILAR_EXCLUDE_SELF, CS_SIMILAR_EXCLUDE_GROUP = 0, 
 CS_SIMILAR_ROUTE_AUTO, CS_SIMILAR_ROUTE_SCAN, CS_SIMILAR_ROUTE_FILTER = 0, 1, 2
 CS_MAX_PAIRS = 1 << 22
 CS_PAIRS_ALL, CS_PAIRS_OTHER_GROUP = 0, 1
+CS_NO_CLASS = 0xFFFF
+CS_MAX_CLASSES = 4096
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
+u16p = C.POINTER(C.c_uint16)
 i32p = C.POINTER(C.c_int32)
 u64p = C.POINTER(C.c_uint64)
 f64p = C.POINTER(C.c_double)
@@ -101,6 +104,12 @@ SIGNATURES = {
                                                      i32p]),
     "cs_index_search_variants_grouped_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32p,
                                                             u32p, u32p, i32p]),
+    "cs_index_set_classes": (C.c_int32, [vp, u32p, u16p, C.c_uint64]),
+    "cs_index_classes_info": (C.c_int32, [vp, u64p, u64p]),
+    "cs_index_search_boosted": (C.c_int32, [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, C.c_uint32, f32p, f32p, u32p,
+                                            u32p]),
+    "cs_index_search_boosted_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, C.c_uint32, f32p,
+                                                   f32p, u32p, u32p]),
     "cs_index_search_similar": (C.c_int32, [vp, u32p, C.c_uint32, C.c_uint32, C.c_int32, C.c_float, f32p, u32p, u32p]),
     "cs_index_set_similar_route": (C.c_int32, [vp, C.c_int32]),
     "cs_index_similar_route_info": (C.c_int32, [vp, u64p, u64p, u64p]),

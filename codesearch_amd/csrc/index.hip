@@ -91,6 +91,10 @@ struct Workspace {
     // [3][nq] — resolved on the host into the pinned copy, one copy to the device
     uint32_t* h_similar = nullptr; uint32_t* d_similar = nullptr;
     size_t h_similar_cap = 0, d_similar_cap = 0;
+    // boosted searches (search_boosted): the call's weight table — pinned, then one copy to the device — and the pinned
+    // [nq][k] cosines of the winners, which the cosine pass writes beside the keys
+    float* h_weights = nullptr; float* d_weights = nullptr; float* h_winner_cos = nullptr;
+    size_t h_weights_cap = 0, d_weights_cap = 0, h_winner_cos_cap = 0;
     std::vector<EventTriple> free_events;
     BatchedState bs;
     size_t cnt_cap = 0, tau_cap = 0, cand_cap = 0, carry_cap = 0;
@@ -141,6 +145,12 @@ struct Workspace {
         return reserve_buf(d_similar, d_similar_cap, 3 * (size_t)nq);
     }
 
+    int32_t reserve_boosted(uint32_t nq, uint32_t k, uint32_t n_classes) {
+        CS_TRY(reserve_buf(h_weights, h_weights_cap, n_classes, true));
+        CS_TRY(reserve_buf(d_weights, d_weights_cap, n_classes));
+        return reserve_buf(h_winner_cos, h_winner_cos_cap, (size_t)nq * k, true);
+    }
+
     int32_t reserve_batched(uint32_t nq, uint32_t k) {
         if (!h_overflow) {
             CS_HIP(realloc_buf(h_overflow, 4, true));
@@ -184,8 +194,8 @@ struct Workspace {
     void release_all() {
         free_bufs(false, d_partial, d_tmp_a, d_tmp_b, d_queries, d_keys, d_cos, d_ids, d_counts, prime.d_wave_max, prime.d_done,
                   prime.d_floor, bs.d_cand, bs.d_cnt, bs.d_tau, bs.d_carry, bs.d_overflow, qw.d_qsplit, qw.d_qmag, qw.d_q8q,
-                  qw.d_q8q_hi, qw.d_qmeta, d_allow, d_list, d_mblocks, d_similar);
-        free_bufs(true, h_keys, h_queries, h_overflow, h_variant_meta, h_similar);
+                  qw.d_q8q_hi, qw.d_qmeta, d_allow, d_list, d_mblocks, d_similar, d_weights);
+        free_bufs(true, h_keys, h_queries, h_overflow, h_variant_meta, h_similar, h_weights, h_winner_cos);
         for (auto& t : free_events) {
             (void)hipEventDestroy(t.e0); (void)hipEventDestroy(t.e1); (void)hipEventDestroy(t.e2);
         }
@@ -244,6 +254,12 @@ struct cs_index {
     uint32_t* d_groups = nullptr;
     uint64_t groups_cap = 0;  // elements allocated on the device
     std::mutex groups_mu;
+    // Classes of the boosted search (scan_boosted.hip): the group table's sibling, 2 B per id, brought up to date under
+    // classes_mu by the first boosted search that finds it dirty (ensure_classes); searches read it only.
+    ClassTable classes;
+    uint16_t* d_classes = nullptr;
+    uint64_t classes_cap = 0;  // elements allocated on the device
+    std::mutex classes_mu;
     float* d_corpus = nullptr;
     uint32_t* d_dead = nullptr;  // bitmap over rows, sized for `capacity`
     float* d_norms = nullptr;    // |row| for rows [0, normed_rows) (batched-query path)
@@ -943,6 +959,31 @@ int32_t ensure_groups(cs_index* h, uint32_t per_group, GroupView* gv) {
     return CS_OK;
 }
 
+// ensure_groups for the class table: the index's side of a boosted search's BoostView (the call adds its weights).  No
+// class assigned: a null table, every id CS_NO_CLASS.
+int32_t ensure_classes(cs_index* h, BoostView* bv) {
+    std::lock_guard<std::mutex> lk(h->classes_mu);
+    *bv = BoostView{};
+    bv->id_base = h->ledger.id_base();
+    if (h->classes.assigned() == 0) return CS_OK;
+    const uint64_t n = h->classes.size();
+    if (n > h->classes_cap) {
+        CS_HIP(hipDeviceSynchronize());  // a search that was only enqueued may still read the old table
+        const uint64_t cap = std::max<uint64_t>(n, std::min<uint64_t>(2 * h->classes_cap, 0xffffffffull));
+        h->classes_cap = 0;
+        h->classes.uploaded(0);  // the new table holds nothing yet
+        CS_HIP(realloc_buf(h->d_classes, (size_t)cap));
+        h->classes_cap = cap;
+    }
+    uint64_t lo = 0, hi = 0;
+    if (h->classes.pending(&lo, &hi))
+        CS_HIP(hipMemcpy(h->d_classes + lo, h->classes.data() + lo, (size_t)(hi - lo) * sizeof(uint16_t), hipMemcpyHostToDevice));
+    h->classes.uploaded(n);
+    bv->classes = h->d_classes;
+    bv->len = (uint32_t)n;
+    return CS_OK;
+}
+
 // A grouped search (scan_grouped.hip) on `stream`: the capped scan over every stored row, then the capped merge -> the
 // best k keys per query in d_keys [nq][k].
 int32_t run_grouped(cs_index* h, Workspace* w, const GroupedPlan& plan, const GroupView& gv, const float* d_queries,
@@ -962,6 +1003,49 @@ int32_t run_grouped_list(cs_index* h, Workspace* w, const GroupedPlan& plan, con
                                     stream));
     return launch_merge_grouped(plan, w->d_partial, nq, k, gv, w->d_tmp_a, w->d_tmp_b, d_keys, nullptr, nullptr, nullptr,
                                 stream);
+}
+
+// The prime pass of a boosted search over `rows` rows (every stored row, or a scope's list): by the streaming route's rule
+// (masked_prime_rows), a boosted pass over the first rows that leaves w->prime.d_floor[q] below query q's k-th best b.
+// -> w->prime, or null when the rule asks for none.
+int32_t boosted_prime(cs_index* h, Workspace* w, uint64_t rows, const BoostView& bv, const uint32_t* d_list, const uint32_t* d_len,
+                      const float* d_queries, uint32_t nq, uint32_t k, hipStream_t stream, const ScanPrime** prime) {
+    *prime = nullptr;
+    const uint64_t prime_rows = masked_prime_rows(h->route, rows, nq, k, h->dim, h->num_cus, scan_prime_supported(h->dim));
+    if (!prime_rows) return CS_OK;
+    const ScanPlan pp = plan_prime(prime_rows, h->dim, nq, k, h->num_cus);
+    CS_TRY(w->reserve_prime(pp, nq));
+    if (d_list)
+        CS_TRY(launch_scan_boosted_list(pp, h->d_corpus, h->dim, d_list, d_len, d_queries, nq, k, h->row_ids(), bv, nullptr, stream,
+                                        &w->prime, true, prime_rows));
+    else
+        CS_TRY(launch_scan_boosted(pp, h->d_corpus, prime_rows, h->dim, d_queries, nq, k, h->ledger.removed() ? h->d_dead : nullptr,
+                                   h->row_ids(), bv, nullptr, stream, &w->prime, true));
+    *prime = &w->prime;
+    return CS_OK;
+}
+
+// A boosted search (scan_boosted.hip) on `stream`: the optional prime pass and the boosted scan over every stored row,
+// then the ordinary merge -> the best k keys of (b, id) per query in d_keys [nq][k].
+int32_t run_boosted(cs_index* h, Workspace* w, const ScanPlan& plan, const BoostView& bv, const float* d_queries, uint32_t nq,
+                    uint32_t k, uint64_t* d_keys, hipStream_t stream) {
+    const ScanPrime* prime = nullptr;
+    CS_TRY(boosted_prime(h, w, h->ledger.stored(), bv, nullptr, nullptr, d_queries, nq, k, stream, &prime));
+    CS_TRY(launch_scan_boosted(plan, h->d_corpus, h->ledger.stored(), h->dim, d_queries, nq, k, h->ledger.removed() ? h->d_dead : nullptr,
+                               h->row_ids(), bv, w->d_partial, stream, prime));
+    return launch_merge(w->d_partial, plan.blocks, nq, k, false, w->d_tmp_a, w->d_tmp_b, d_keys, nullptr, nullptr, nullptr, stream);
+}
+
+// run_boosted over a scope's row list d_list[0, *d_len) (live rows only; `rows` = the list's length, which sized the plan):
+// the gathered boosted scan, then the same merge.
+int32_t run_boosted_list(cs_index* h, Workspace* w, const ScanPlan& plan, uint64_t rows, const BoostView& bv, const uint32_t* d_list,
+                         const uint32_t* d_len, const float* d_queries, uint32_t nq, uint32_t k, uint64_t* d_keys,
+                         hipStream_t stream) {
+    const ScanPrime* prime = nullptr;
+    CS_TRY(boosted_prime(h, w, rows, bv, d_list, d_len, d_queries, nq, k, stream, &prime));
+    CS_TRY(launch_scan_boosted_list(plan, h->d_corpus, h->dim, d_list, d_len, d_queries, nq, k, h->row_ids(), bv, w->d_partial,
+                                    stream, prime));
+    return launch_merge(w->d_partial, plan.blocks, nq, k, false, w->d_tmp_a, w->d_tmp_b, d_keys, nullptr, nullptr, nullptr, stream);
 }
 
 // The route's thresholds of a new index: RouteKnobs' defaults, or what the environment sets.
@@ -1003,11 +1087,29 @@ int32_t check_search(const cs_index* h, uint32_t nq, uint32_t dim, uint32_t k) {
 // one list [k] with counts[0] = its length and the optional high-confidence flag (cs_index_search_variants).
 // `capped` (a grouped variants search): the group table the variants are merged under — every per-variant list is a capped
 // list and the merge caps again (launch_merge_variants_grouped); null: the plain variants merge.
+// `boosted` (a boosted search): the keys carry b, which goes to `cos`; the winners' cosines, which the kind's enqueue step
+// leaves in the pinned w->h_winner_cos, go to `winner_cos`; each of the four outputs may then be null.
 struct HostAnswer {
     float* cos; uint32_t* ids; uint32_t* counts; int32_t* high_confidence;
     bool variants;
     const GroupView* capped = nullptr;
+    bool boosted = false;
+    float* winner_cos = nullptr;
 };
+
+// unpack_keys (common.hpp) for a boosted answer: every output optional, and the second float of a slot from `cos`.
+void unpack_boosted(const uint64_t* keys, const float* cos, uint32_t nq, uint32_t k, const HostAnswer& out) {
+    for (uint32_t q = 0; q < nq; ++q) {
+        uint32_t c = 0;
+        for (size_t j = (size_t)q * k; j < (size_t)(q + 1) * k; ++j) {
+            c += keys[j] != 0;
+            if (out.cos) out.cos[j] = keys[j] ? key_cos(keys[j]) : 0.0f;
+            if (out.winner_cos) out.winner_cos[j] = keys[j] ? cos[j] : 0.0f;
+            if (out.ids) out.ids[j] = keys[j] ? key_id(keys[j]) : 0xFFFFFFFFu;
+        }
+        if (out.counts) out.counts[q] = c;
+    }
+}
 
 // The argument checks every host-buffer search starts with, in this order.
 int32_t check_host_search(const cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k, const HostAnswer& out) {
@@ -1022,8 +1124,12 @@ int32_t check_host_search(const cs_index* h, const float* queries, uint32_t nq, 
 // empty one.
 int32_t empty_answer(uint32_t nq, uint32_t k, const HostAnswer& out) {
     const size_t lists = out.variants ? 1 : nq;
-    for (size_t i = 0; i < lists * k; ++i) { out.cos[i] = 0.0f; out.ids[i] = 0xFFFFFFFFu; }
-    memset(out.counts, 0, lists * sizeof(uint32_t));
+    for (size_t i = 0; i < lists * k; ++i) {
+        if (out.cos) out.cos[i] = 0.0f;
+        if (out.winner_cos) out.winner_cos[i] = 0.0f;
+        if (out.ids) out.ids[i] = 0xFFFFFFFFu;
+    }
+    if (out.counts) memset(out.counts, 0, lists * sizeof(uint32_t));
     if (out.variants && out.high_confidence) *out.high_confidence = 0;
     return CS_OK;
 }
@@ -1053,7 +1159,8 @@ int32_t host_search(cs_index* h, const float* queries, uint32_t nq, uint32_t k, 
             CS_TRY(launch_merge_variants(w->d_keys, nq, k, k, w->h_keys, nullptr, nullptr, w->h_variant_meta,
                                          w->h_variant_meta + 1, w->stream));
         CS_HIP(hipStreamSynchronize(w->stream));
-        unpack_keys(w->h_keys, out.variants ? 1 : nq, k, out.cos, out.ids, out.variants ? nullptr : out.counts);
+        if (out.boosted) unpack_boosted(w->h_keys, w->h_winner_cos, nq, k, out);
+        else unpack_keys(w->h_keys, out.variants ? 1 : nq, k, out.cos, out.ids, out.variants ? nullptr : out.counts);
         if (out.variants) {
             *out.counts = w->h_variant_meta[0];
             if (out.high_confidence) *out.high_confidence = (int32_t)w->h_variant_meta[1];
@@ -1128,6 +1235,67 @@ int32_t search_grouped(cs_index* h, bool scope_given, cs_scope* scope, const flo
         scope->gathered_searches.fetch_add(1);
         return run_grouped_list(h, w, plan, gv, scope->d_list, scope->d_blocks + scope_list_blocks(scope->n_ids), w->d_queries, nq,
                                 k, keys, w->stream);
+    });
+}
+
+// The call's weight table checked: n_classes entries, each finite and in [0, 65536] (so b stays finite and no key of a
+// live row is a NaN's).  *wmin / *wmax: the table's extremes widened to hold 1, the weight of a row without a class.
+int32_t check_weights(const float* weights, uint32_t n_classes, float* wmin, float* wmax) {
+    *wmin = *wmax = 1.0f;
+    if (n_classes > CS_MAX_CLASSES) return fail(CS_ERR_BAD_ARG, "n_classes must be at most %u, got %u", CS_MAX_CLASSES, n_classes);
+    for (uint32_t i = 0; weights && i < n_classes; ++i) {
+        const float x = weights[i];
+        if (!(x >= 0.0f && x <= 65536.0f))  // NaN fails both
+            return fail(CS_ERR_BAD_ARG, "weights[%u] = %g: a weight must be finite and in [0, 65536]", i, (double)x);
+        *wmin = std::min(*wmin, x);
+        *wmax = std::max(*wmax, x);
+    }
+    return CS_OK;
+}
+
+// The boosted searches (scan_boosted.hip): over the whole store (scope_given false: the boosted scan over every stored
+// row) or over a scope's row list (the gathered boosted scan, always: the int8 filter's threshold is a cosine's, not a
+// weighted score's).  The call's weights travel in its workspace, never in the index: concurrent calls with different
+// tables do not meet.  Behind the merge the cosine pass recovers the winners' cosines and hands keys and cosines to pinned
+// memory: one stream sync, no further round trip.
+int32_t search_boosted(cs_index* h, bool scope_given, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                       const float* weights, uint32_t n_classes, float* out_score, float* out_cos, uint32_t* out_ids,
+                       uint32_t* out_counts) {
+    CS_TRY(check_search(h, nq, dim, k));
+    if (!queries) return fail(CS_ERR_BAD_ARG, "null buffer");
+    if (!out_score && !out_cos && !out_ids && !out_counts) return fail(CS_ERR_BAD_ARG, "no output buffer given");
+    if (!weights) n_classes = 0;
+    float wmin = 1.0f, wmax = 1.0f;
+    CS_TRY(check_weights(weights, n_classes, &wmin, &wmax));
+    HostAnswer out{out_score, out_ids, out_counts, nullptr, false};
+    out.boosted = true;
+    out.winner_cos = out_cos;
+    DeviceGuard g(h->device);
+    uint64_t rows = h->ledger.stored();
+    if (scope_given) CS_TRY(scope_ready(h, scope, &rows));
+    if (rows == 0) return empty_answer(nq, k, out);  // nothing the call may return is stored
+    BoostView bv;
+    CS_TRY(ensure_classes(h, &bv));
+    bv.wmin = wmin;
+    bv.wmax = wmax;
+    const ScanPlan plan = plan_scan(rows, h->dim, nq, k, h->num_cus);  // a scope: the grid follows the list's length
+    return host_search(h, queries, nq, k, plan.partial_keys, plan.merge_keys, out, [&](Workspace* w, uint64_t* keys) {
+        CS_TRY(w->reserve_boosted(nq, k, n_classes));
+        CS_TRY(upload_queries(h, w, nq));
+        if (n_classes) {
+            memcpy(w->h_weights, weights, n_classes * sizeof(float));
+            CS_HIP(hipMemcpyAsync(w->d_weights, w->h_weights, n_classes * sizeof(float), hipMemcpyHostToDevice, w->stream));
+            bv.weights = w->d_weights;
+            bv.n_classes = n_classes;
+        }
+        if (!scope_given) CS_TRY(run_boosted(h, w, plan, bv, w->d_queries, nq, k, w->d_keys, w->stream));
+        else {
+            scope->gathered_searches.fetch_add(1);
+            CS_TRY(run_boosted_list(h, w, plan, rows, bv, scope->d_list, scope->d_blocks + scope_list_blocks(scope->n_ids), w->d_queries,
+                                    nq, k, w->d_keys, w->stream));
+        }
+        return launch_boosted_cos(h->d_corpus, h->ledger.stored(), h->dim, w->d_queries, nq, k, h->row_ids(), w->d_keys, keys,
+                                  w->h_winner_cos, w->stream);
     });
 }
 
@@ -1651,6 +1819,7 @@ void cs_index_destroy(cs_index* h) {
     if (h->d_mu) (void)hipFree(h->d_mu);
     if (h->d_ids) (void)hipFree(h->d_ids);
     if (h->d_groups) (void)hipFree(h->d_groups);
+    if (h->d_classes) (void)hipFree(h->d_classes);
     delete h;
 }
 
@@ -1820,6 +1989,12 @@ int32_t cs_index_clear(cs_index* h) {
         std::lock_guard<std::mutex> lk(h->groups_mu);
         h->groups.clear();
     }
+    {  // and so do the classes, with their device table (the device is idle: drain_appends synchronised it)
+        std::lock_guard<std::mutex> lk(h->classes_mu);
+        h->classes.clear();
+        h->classes_cap = 0;
+        CS_HIP(realloc_buf(h->d_classes, 0));
+    }
     h->build_gen.fetch_add(1);
     h->built = false;  // store.rs:702
     return CS_OK;
@@ -1887,6 +2062,31 @@ int32_t cs_index_groups_info(cs_index* h, uint64_t* assigned_ids, uint64_t* tabl
     if (assigned_ids) *assigned_ids = h->groups.assigned();
     if (table_bytes) *table_bytes = h->groups_cap * sizeof(uint32_t);
     return CS_OK;
+}
+
+int32_t cs_index_set_classes(cs_index* h, const uint32_t* ids, const uint16_t* classes, uint64_t n) {
+    if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
+    if (n == 0) return CS_OK;
+    if (!ids || !classes) return fail(CS_ERR_BAD_ARG, "ids or classes is null");
+    std::lock_guard<std::mutex> lk(h->classes_mu);
+    const int64_t bad = h->classes.set(ids, classes, n, h->ledger);
+    if (bad >= 0)
+        return fail(CS_ERR_BAD_ARG, "ids[%llu] = %u was never issued (the index has issued ids %u to %llu)",
+                    (unsigned long long)bad, ids[bad], h->ledger.id_base(), (unsigned long long)h->ledger.next_id());
+    return CS_OK;
+}
+
+int32_t cs_index_classes_info(cs_index* h, uint64_t* assigned_ids, uint64_t* table_bytes) {
+    if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
+    std::lock_guard<std::mutex> lk(h->classes_mu);
+    if (assigned_ids) *assigned_ids = h->classes.assigned();
+    if (table_bytes) *table_bytes = h->classes_cap * sizeof(uint16_t);
+    return CS_OK;
+}
+
+int32_t cs_index_search_boosted(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k, const float* weights,
+                                uint32_t n_classes, float* out_score, float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
+    return search_boosted(h, false, nullptr, queries, nq, dim, k, weights, n_classes, out_score, out_cos, out_ids, out_counts);
 }
 
 int32_t cs_index_search_grouped(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k, uint32_t per_group,
@@ -2038,6 +2238,12 @@ int32_t cs_index_search_variants_scoped(cs_index* h, cs_scope* scope, const floa
 int32_t cs_index_search_grouped_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
                                        uint32_t per_group, float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
     return search_grouped(h, true, scope, queries, nq, dim, k, per_group, HostAnswer{out_cos, out_ids, out_counts, nullptr, false});
+}
+
+int32_t cs_index_search_boosted_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                                       const float* weights, uint32_t n_classes, float* out_score, float* out_cos,
+                                       uint32_t* out_ids, uint32_t* out_counts) {
+    return search_boosted(h, true, scope, queries, nq, dim, k, weights, n_classes, out_score, out_cos, out_ids, out_counts);
 }
 
 int32_t cs_index_search_variants_grouped_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,

@@ -1,5 +1,5 @@
 // index_ledger.hpp — the host-side ledger of an index (index.hip): which id each stored row carries, which row holds an
-// id, which rows are dead, which ids are spent — and the group of every id (scan_grouped.hip).  Plain C++17, no HIP:
+// id, which rows are dead, which ids are spent — and the group and the class of every id (scan_grouped.hip, scan_boosted.hip).  Plain C++17, no HIP:
 // tests/cpp/index_ledger_test.cpp walks it against a model on the CPU, and index.hip only allocates, copies and launches
 // what it answers.
 //
@@ -21,7 +21,7 @@
 #include <cstdint>
 #include <vector>
 
-#include "../../include/codesearch_gpu.h"  // CS_NO_GROUP
+#include "../../include/codesearch_gpu.h"  // CS_NO_GROUP, CS_NO_CLASS
 
 namespace cs {
 
@@ -148,44 +148,46 @@ private:
     std::vector<uint32_t> dead_;  // tombstone bitmap over the stored rows
 };
 
-// The group of every id (the grouped search, scan_grouped.hip): entry id - id_base for the ids assigned so far (shorter
-// than the issued ids when ids were appended since: those are CS_NO_GROUP), empty = none assigned — and what a device
-// copy of device_len entries has not seen of it.  The groups are a property of ids and go when the ids go (clear()).
-class GroupTable {
+// A value of every id — its group (the grouped search, scan_grouped.hip: GroupTable) or its class (the boosted search,
+// scan_boosted.hip: ClassTable): entry id - id_base for the ids assigned so far (shorter than the issued ids when ids
+// were appended since: those are NONE), empty = none assigned — and what a device copy of device_len entries has not seen
+// of it.  The values are a property of ids and go when the ids go (clear()).
+template <class T, T NONE>
+class IdTable {
 public:
-    // groups[i] becomes the group of ids[i] (CS_NO_GROUP un-assigns it).  An id the ledger never issued: nothing is changed
+    // values[i] becomes the value of ids[i] (NONE un-assigns it).  An id the ledger never issued: nothing is changed
     // and its position in ids is returned; -1 otherwise.
-    int64_t set(const uint32_t* ids, const uint32_t* groups, uint64_t n, const IndexLedger& ledger) {
+    int64_t set(const uint32_t* ids, const T* values, uint64_t n, const IndexLedger& ledger) {
         uint32_t top = 0;  // the highest entry touched
         for (uint64_t i = 0; i < n; ++i) {
             if (!ledger.issued(ids[i])) return (int64_t)i;
             top = std::max(top, ids[i] - ledger.id_base());
         }
-        if (n && groups_.size() <= top) groups_.resize((size_t)top + 1, CS_NO_GROUP);
+        if (n && values_.size() <= top) values_.resize((size_t)top + 1, NONE);
         for (uint64_t i = 0; i < n; ++i) {
             const uint32_t e = ids[i] - ledger.id_base();
-            uint32_t& g = groups_[e];
-            if (g == groups[i]) continue;
-            assigned_ += (uint64_t)(groups[i] != CS_NO_GROUP) - (uint64_t)(g != CS_NO_GROUP);
-            g = groups[i];
+            T& g = values_[e];
+            if (g == values[i]) continue;
+            assigned_ += (uint64_t)(values[i] != NONE) - (uint64_t)(g != NONE);
+            g = values[i];
             dirty_lo_ = dirty_hi_ > dirty_lo_ ? std::min<uint64_t>(dirty_lo_, e) : e;
             dirty_hi_ = std::max<uint64_t>(dirty_hi_, (uint64_t)e + 1);
         }
         return -1;
     }
 
-    uint64_t assigned() const { return assigned_; }  // entries != CS_NO_GROUP
-    uint64_t size() const { return groups_.size(); }
-    const uint32_t* data() const { return groups_.data(); }
+    uint64_t assigned() const { return assigned_; }  // entries != NONE
+    uint64_t size() const { return values_.size(); }
+    const T* data() const { return values_.data(); }
 
     // Entries [*lo, *hi) the device copy has not seen: the ones changed since uploaded(), and the ones past its end.
     // false: it is up to date.
     bool pending(uint64_t* lo, uint64_t* hi) const {
         *lo = dirty_lo_;
         *hi = dirty_hi_;
-        if (groups_.size() > device_len_) {
+        if (values_.size() > device_len_) {
             *lo = dirty_hi_ > dirty_lo_ ? std::min(dirty_lo_, device_len_) : device_len_;
-            *hi = groups_.size();
+            *hi = values_.size();
         }
         return *hi > *lo;
     }
@@ -195,13 +197,15 @@ public:
         dirty_lo_ = dirty_hi_ = 0;
     }
 
-    void clear() { *this = GroupTable(); }
+    void clear() { *this = IdTable(); }
 
 private:
-    std::vector<uint32_t> groups_;
+    std::vector<T> values_;
     uint64_t assigned_ = 0;
     uint64_t dirty_lo_ = 0, dirty_hi_ = 0;  // entries [lo, hi) changed since uploaded()
     uint64_t device_len_ = 0;
 };
+using GroupTable = IdTable<uint32_t, CS_NO_GROUP>;            // 4 B per id issued
+using ClassTable = IdTable<uint16_t, (uint16_t)CS_NO_CLASS>;  // 2 B per id issued
 
 }  // namespace cs

@@ -182,6 +182,38 @@ int32_t launch_similar_select(const BatchedState& st, uint32_t nq, uint32_t cap,
                               uint64_t* d_out_keys, float* d_out_cos, uint32_t* d_out_ids, uint32_t* d_out_counts,
                               hipStream_t stream);
 
+// ---- boosted search (scan_boosted.hip; plan: plan_scan) ---------------------------------------------------
+// What a boosted search weighs rows by: the class table of the index as the kernels read it — classes[id - id_base] for
+// ids below id_base + len, no class for every other id (and for all of them when classes is null) — and the call's own
+// weight table on the device.  A row weighs weights[class] when its class is below n_classes, else 1.  wmin / wmax: the
+// smallest and the largest weight a row can take (the table's extremes, widened to hold 1).
+struct BoostView {
+    const uint16_t* classes = nullptr;
+    uint32_t len = 0;
+    uint32_t id_base = 0;
+    const float* weights = nullptr;  // [n_classes]
+    uint32_t n_classes = 0;
+    float wmin = 1.0f, wmax = 1.0f;
+};
+// The streaming scan's arithmetic selecting by b = fl(score(cosine) * weight): the same per-block partial lists as
+// launch_scan, holding packed keys of (b, id), for launch_merge.
+// prime + prime_pass: the prime pass over these rows instead (plan from plan_prime, tuned dims only, no partial lists
+// written): d_floor[q] = a lower bound of query q's k-th best b;  prime alone: the lists start from prime->d_floor.
+int32_t launch_scan_boosted(const ScanPlan& plan, const float* d_corpus, uint64_t n_rows, uint32_t dim, const float* d_queries,
+                            uint32_t nq, uint32_t k, const uint32_t* d_dead, RowIds ids, const BoostView& bv,
+                            uint64_t* d_partial, hipStream_t stream, const ScanPrime* prime = nullptr, bool prime_pass = false);
+// launch_scan_boosted over the live rows d_list[0, *d_list_len) (a scope's row list, ascending; plan: plan_scan of the
+// length).  The list holds live rows only: no tombstone test.  A prime pass takes the first min(prime_rows, *d_list_len)
+// entries.
+int32_t launch_scan_boosted_list(const ScanPlan& plan, const float* d_corpus, uint32_t dim, const uint32_t* d_list,
+                                 const uint32_t* d_list_len, const float* d_queries, uint32_t nq, uint32_t k, RowIds ids,
+                                 const BoostView& bv, uint64_t* d_partial, hipStream_t stream, const ScanPrime* prime = nullptr,
+                                 bool prime_pass = false, uint64_t prime_rows = 0);
+// The merged winners d_keys [nq][k] (every non-empty key names a stored row of [0, n_rows), n_rows > 0) -> out_cos[nq][k] =
+// the streaming scan's cosine of each winner's row, 0 for an empty slot; out_keys (optional) receives the keys as they are.
+int32_t launch_boosted_cos(const float* d_corpus, uint64_t n_rows, uint32_t dim, const float* d_queries, uint32_t nq, uint32_t k,
+                           RowIds ids, const uint64_t* d_keys, uint64_t* out_keys, float* out_cos, hipStream_t stream);
+
 // ---- similar-pairs search (scan_pairs.hip, plan: pairs_plan.hpp) -----------------------------------------
 // A qualifying pair as the refine leaves it: the cosine's bits, the lower id, the higher id.
 struct PairRecord {

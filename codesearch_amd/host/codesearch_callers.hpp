@@ -4,6 +4,7 @@
 //
 //   prepare_text / clean_docstring / BatchEmbedder / EmbeddingStats   /root/reference/src/embed/batch.rs:12-231
 //   retrieval_limit / merge_variant_results / should_use_vector_only   src/search/mod.rs:494-611
+//   kChunkKinds / kind_boost_weights                                   src/chunker/mod.rs:140-159, src/search/mod.rs:238-252
 //   rrf_fusion / vector_only / rrf_fusion_with_exact                   src/rerank/mod.rs:14-241
 //
 // Same names, argument meaning and known answers as the reference's own unit tests
@@ -258,6 +259,22 @@ inline bool should_use_vector_only(const std::vector<SearchResult>& results, boo
 }
 
 // ---- result fusion: src/rerank/mod.rs:14-241 -------------------------------------------------------------
+// ChunkKind's Debug names in the enum's order (src/chunker/mod.rs:140-159): a chunk's class for the boosted search is its
+// kind's position here (VectorStore::set_classes).
+constexpr const char* kChunkKinds[18] = {"Function", "Class", "Method", "Struct", "Enum", "Trait", "Interface", "Impl", "Mod",
+                                         "TypeAlias", "Const", "Static", "Block", "Anchor", "Comment", "Imports", "ModuleDocs",
+                                         "Other"};
+constexpr float kStructuralBoost = 0.15f;  // mod.rs:243: score *= 1.0 + boost_factor for hits of the intended kind
+
+// The weight table of the structural-intent boost (mod.rs:238-252) for VectorStore::search_boosted: ones, 1 + boost at
+// `kind`; all ones for a name that is no kind.
+inline std::vector<float> kind_boost_weights(const std::string& kind, float boost = kStructuralBoost) {
+    std::vector<float> w(18, 1.0f);
+    for (size_t i = 0; i < 18; ++i)
+        if (kind == kChunkKinds[i]) w[i] = 1.0f + boost;
+    return w;
+}
+
 constexpr float kDefaultRrfK = 20.0f;    // rerank/mod.rs:15
 constexpr float kExactMatchRrfK = 5.0f;  // rerank/mod.rs:18
 

@@ -159,7 +159,9 @@ class VectorStore {
         *bits = mask.empty() ? 0 : next;
         return mask;
     }
-    std::vector<SearchResult> results(const std::vector<float>& cos, const std::vector<uint32_t>& ids, uint32_t count) const {
+    // score != null: the results' scores when they are not 1 - distance (a boosted search's)
+    std::vector<SearchResult> results(const std::vector<float>& cos, const std::vector<uint32_t>& ids, uint32_t count,
+                                      const std::vector<float>* score = nullptr) const {
         std::vector<SearchResult> out;
         for (uint32_t j = 0; j < count; ++j) {
             auto it = meta_.find(ids[j]);
@@ -168,7 +170,7 @@ class VectorStore {
             r.id = ids[j];
             r.meta = it->second;
             r.distance = cs_cos_to_distance(cos[j]);
-            r.score = 1.0f - r.distance;
+            r.score = score ? (*score)[j] : 1.0f - r.distance;
             out.push_back(std::move(r));
         }
         return out;
@@ -211,6 +213,17 @@ class VectorStore {
                                       per_file, cos.data(), ids.data(), counts.data()));
         return results(cos, ids, counts[0]);
     }
+    // The kind and language boosts done exactly (src/search/mod.rs:238-252, :789-806 multiply the scores of hits already
+    // ranked): every chunk id may carry a 16-bit class (set_classes; CS_NO_CLASS un-assigns), a call brings one weight per
+    // class, and the best `limit` chunks by f32(score * weight), then id, are selected on the device
+    // (cs_index_search_boosted; with a Scope, cs_index_search_boosted_scoped).  A chunk without a class, or with a class
+    // past the table, weighs 1.  SearchResult::score is the boosted score, ::distance the chunk's own.  One index only.
+    void set_classes(const std::vector<uint32_t>& ids, const std::vector<uint16_t>& classes) {
+        if (sh_) throw Error(CS_ERR_UNSUPPORTED, "a sharded store has no boosted search");
+        if (ids.size() != classes.size()) throw Error(CS_ERR_BAD_ARG, "ids and classes of unequal length");
+        check(cs_index_set_classes(h_, ids.data(), classes.data(), ids.size()));
+    }
+    // (search_boosted itself follows Scope, below)
     // "More like this": the `limit` stored chunks nearest to chunk `id`'s stored row, never the chunk itself; other_files:
     // none of its group (its file, set_groups) either.  The row is gathered and the exclusion applied on the device
     // (cs_index_search_similar), not on a ranked list.  One index only: no sharded form yet.
@@ -398,6 +411,20 @@ class VectorStore {
         check(cs_index_search_grouped_scoped(h_, scope.handle(), query_embedding.data(), 1, (uint32_t)query_embedding.size(),
                                              (uint32_t)limit, per_file, cos.data(), ids.data(), counts.data()));
         return results(cos, ids, counts[0]);
+    }
+    // The boosted search (set_classes, above) over the whole store or, with `scope`, over its chunks.
+    std::vector<SearchResult> search_boosted(const std::vector<float>& query_embedding, size_t limit,
+                                             const std::vector<float>& class_weights, const Scope* scope = nullptr) const {
+        if (sh_) throw Error(CS_ERR_UNSUPPORTED, "a sharded store has no boosted search");
+        std::vector<float> score(limit), cos(limit);
+        std::vector<uint32_t> ids(limit), counts(1);
+        const uint32_t dim = (uint32_t)query_embedding.size(), nc = (uint32_t)class_weights.size();
+        check(scope ? cs_index_search_boosted_scoped(h_, scope->handle(), query_embedding.data(), 1, dim, (uint32_t)limit,
+                                                     class_weights.data(), nc, score.data(), cos.data(), ids.data(), counts.data())
+                    : cs_index_search_boosted(h_, query_embedding.data(), 1, dim, (uint32_t)limit, class_weights.data(), nc,
+                                              score.data(), cos.data(), ids.data(), counts.data()));
+        std::vector<SearchResult> out = results(cos, ids, counts[0], &score);
+        return out;
     }
     // similar() among the chunks of a Scope only (cs_index_search_similar_scoped): "where else under src/ is this copied".
     // Chunk `id` itself need not be in the scope.  One index only.  The scope's route (cs_scope_set_route) picks the gathered

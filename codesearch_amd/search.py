@@ -84,6 +84,29 @@ def cap_per_group(cos, ids, groups, k: int, m: int):
     return kept_cos, kept_ids
 
 
+def boost_order(cos, ids, classes, weights, k: int):
+    """The contract of the boosted search (cs_index_search_boosted) on the host, in numpy float32: `cos` / `ids` are the
+    live rows in (cosine desc, id asc) order — the full order, not a top-k: that is the point — and `classes` their classes
+    (NO_CLASS: none).  s = 1 - (1 - c) * 0.5 (cos_to_score), b = s * w with one rounding, w = weights[class] for a class
+    below len(weights) and 1 otherwise (weights None: every row weighs 1); the answer is the k rows with the largest
+    key_pack(b, id): b descending, then id ascending.  -> (score, cos, ids) of those rows as arrays, best first."""
+    import numpy as np
+
+    from .sharded import key_pack
+    from .vector_store import NO_CLASS, cos_to_score
+
+    cos = np.asarray(cos, np.float32).ravel()
+    ids = np.asarray(ids, np.uint32).ravel()
+    cls = np.asarray(classes, np.int64).ravel()
+    wt = np.zeros(0, np.float32) if weights is None else np.asarray(weights, np.float32).ravel()
+    covered = (cls != NO_CLASS) & (cls >= 0) & (cls < wt.size)
+    w = np.ones(cos.size, np.float32)
+    w[covered] = wt[cls[covered]]
+    b = (cos_to_score(cos) * w).astype(np.float32)
+    order = np.argsort(key_pack(b, ids), kind="stable")[::-1][:max(int(k), 0)]
+    return b[order], cos[order], ids[order]
+
+
 def drop_excluded(cos, ids, groups, src_id: int, src_group: int, mode: str, min_cos, k: int):
     """The contract of the similar-chunk search (cs_index_search_similar) on the host: `cos` / `ids` are the live rows in
     (cosine desc, id asc) order for the source's stored row as the query, `groups` their groups.  mode "none" drops

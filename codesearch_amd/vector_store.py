@@ -155,6 +155,11 @@ def scope_ids(chunk_ids) -> np.ndarray:
 
 
 NO_GROUP = 0xFFFFFFFF  # CS_NO_GROUP: an id that carries no group is never capped
+NO_CLASS = 0xFFFF  # CS_NO_CLASS: an id that carries no class weighs 1 in a boosted search
+# The reference's ChunkKind (src/chunker/mod.rs:140-159) by its Debug names, in the enum's order: the class a chunk inserted
+# with metadata carries is its kind's position here.
+CHUNK_KINDS = ["Function", "Class", "Method", "Struct", "Enum", "Trait", "Interface", "Impl", "Mod", "TypeAlias", "Const",
+               "Static", "Block", "Anchor", "Comment", "Imports", "ModuleDocs", "Other"]
 
 
 def _one_of(chunk_ids, scope, per_file=None):
@@ -164,9 +169,15 @@ def _one_of(chunk_ids, scope, per_file=None):
         raise ValueError("chunk_ids= and scope= are exclusive: a scope already is a set of chunk ids")
 
 
-def _filters_ok(chunk_ids, scope, per_file):
-    """The argument check of the searches: per_file= may come with scope= (the grouped scoped search); every other pair is
-    _one_of's to refuse — per_file= with chunk_ids= (no masked grouped form), chunk_ids= with scope=."""
+def _filters_ok(chunk_ids, scope, per_file, class_weights=None):
+    """The argument check of the searches: per_file= may come with scope= (the grouped scoped search), and so may
+    class_weights= (the boosted scoped search); every other pair is refused — class_weights= with chunk_ids= (no masked
+    boosted form) or with per_file= (no boosted form under the per-file cap), and _one_of's: per_file= with chunk_ids= (no
+    masked grouped form), chunk_ids= with scope=."""
+    if class_weights is not None and chunk_ids is not None:
+        raise ValueError("class_weights= is exclusive with chunk_ids=: the boosted search has no masked form (use scope=)")
+    if class_weights is not None and per_file is not None:
+        raise ValueError("class_weights= is exclusive with per_file=: the boosted search has no form under the per-file cap")
     _one_of(chunk_ids, None if (per_file is not None and chunk_ids is None) else scope, per_file)
 
 
@@ -356,6 +367,7 @@ class VectorStore:
             self._persisted_meta_ids = set(self._meta)
             if not self.sharded:  # the groups are not stored: they follow from the sidecar's paths
                 self._assign_file_groups([i for i in sorted(self._meta) if i >= self.id_base])  # (< next_id: above)
+                self._assign_kind_classes([i for i in sorted(self._meta) if i >= self.id_base])  # (nor are the classes)
         for cid in self._removed:  # deletes committed after the last build (delete_chunks) win over older lines
             if self._meta.pop(cid, None) is not None:
                 self._chunks_rewrite = True
@@ -518,6 +530,7 @@ class VectorStore:
             self._meta[i] = ChunkMetadata.from_embedded_chunk(ch)
         if not self.sharded:
             self._assign_file_groups(ids.tolist())
+            self._assign_kind_classes(ids.tolist())
         return ids.tolist()
 
     def insert_chunks(self, chunks: Sequence[EmbeddedChunk]) -> int:
@@ -649,6 +662,37 @@ class VectorStore:
         groups = np.ascontiguousarray(groups, np.uint32)
         _lib.check(self._lib.cs_index_set_groups(self._h, ids.ctypes.data_as(u32p), groups.ctypes.data_as(u32p), ids.size))
 
+    def set_classes(self, ids, classes) -> None:
+        """cs_index_set_classes: classes[i] (16 bits) becomes the class of chunk id ids[i] (NO_CLASS un-assigns it); takes
+        effect at the next search(class_weights=...), no rebuild.  An id never issued is an error and nothing is assigned;
+        a deleted one is accepted.  Chunks inserted with metadata carry CHUNK_KINDS.index(kind) (insert_chunks_with_ids);
+        a caller who boosts by something else re-assigns them, e.g. class = language * len(CHUNK_KINDS) + kind."""
+        self._writable()
+        if self.sharded:
+            raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no boosted search (class_weights): no cs_shards_ form yet")
+        ids = np.ascontiguousarray(ids, np.uint32).ravel()
+        classes = np.ascontiguousarray(classes, np.uint16).ravel()
+        if ids.size != classes.size:
+            raise ValueError("ids and classes must have one entry per id")
+        _lib.check(self._lib.cs_index_set_classes(self._h, ids.ctypes.data_as(u32p), classes.ctypes.data_as(_lib.u16p), ids.size))
+
+    def classes_info(self):
+        """-> (ids that carry a class, bytes of HBM the class table holds) (cs_index_classes_info)."""
+        if self.sharded:
+            raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no boosted search (class_weights): no cs_shards_ form yet")
+        a, b = C.c_uint64(), C.c_uint64()
+        _lib.check(self._lib.cs_index_classes_info(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def _assign_kind_classes(self, ids) -> None:
+        """The chunks' kinds as classes: the kind's position in CHUNK_KINDS, NO_CLASS for a kind that is not there."""
+        if not len(ids):
+            return
+        classes = [CHUNK_KINDS.index(self._meta[i].kind) if self._meta[i].kind in CHUNK_KINDS else NO_CLASS for i in ids]
+        ids = np.ascontiguousarray(ids, np.uint32)
+        classes = np.ascontiguousarray(classes, np.uint16)
+        _lib.check(self._lib.cs_index_set_classes(self._h, ids.ctypes.data_as(u32p), classes.ctypes.data_as(_lib.u16p), ids.size))
+
     def _mask_args(self, chunk_ids):
         """(allow pointer, allow_bits, keep-alive) of a masked search over `chunk_ids`."""
         nxt = self.next_id()
@@ -667,14 +711,22 @@ class VectorStore:
             raise CsError(_lib.CS_ERR_BAD_ARG, "scope is closed")
         return scope._h
 
-    def search_raw(self, queries, limit: int, chunk_ids=None, scope: Optional[Scope] = None, per_file: Optional[int] = None):
+    def search_raw(self, queries, limit: int, chunk_ids=None, scope: Optional[Scope] = None, per_file: Optional[int] = None,
+                   class_weights=None):
         """-> (cos [nq, limit] f32, ids [nq, limit] u32, counts [nq] u32); rows best-first.
+        class_weights: -> (score, cos, ids, counts) instead — the boosted search (cs_index_search_boosted): one f32 weight
+        per class (set_classes; at most 4096, each finite and in [0, 65536]; a row without a class, or with a class past the
+        table, weighs 1), the exact top `limit` by b = f32(cos_to_score(cos) * weight), then id; score = b, cos = the row's
+        cosine.  May come with scope= (cs_index_search_boosted_scoped); exclusive with chunk_ids= and per_file=.
+        A language boost is the caller's through set_classes, e.g. class = language * len(CHUNK_KINDS) + kind and a table
+        of 1.2 for the language's classes, 1.15 for the kind's and f32(1.2 * 1.15) where both hold — which is one rounding
+        of the product and so not bit-equal to the reference's two successive multiplies (f32(f32(s * 1.15) * 1.2)).
         chunk_ids: only these chunks are searched (cs_index_search_masked: the exact top `limit` among them).
         scope: the same through a prepared Scope (cs_index_search_scoped); exclusive with chunk_ids.
         per_file: at most this many rows of one group (a chunk's file; set_groups for rows without metadata) among the
         `limit` best, decided on the device (cs_index_search_grouped); with scope=, among the scope's rows
         (cs_index_search_grouped_scoped); exclusive with chunk_ids."""
-        _filters_ok(chunk_ids, scope, per_file)
+        _filters_ok(chunk_ids, scope, per_file, class_weights)
         q = np.ascontiguousarray(queries, np.float32)
         if q.ndim == 1:
             q = q[None, :]
@@ -682,6 +734,19 @@ class VectorStore:
         cos = np.zeros((nq, max(limit, 1)), np.float32)
         ids = np.zeros((nq, max(limit, 1)), np.uint32)
         counts = np.zeros(nq, np.uint32)
+        if class_weights is not None:
+            if self.sharded:
+                raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no boosted search (class_weights): no cs_shards_ form yet")
+            w = np.ascontiguousarray(class_weights, np.float32).ravel()
+            score = np.zeros_like(cos)
+            tail = (w.ctypes.data_as(f32p) if w.size else None, w.size, score.ctypes.data_as(f32p), cos.ctypes.data_as(f32p),
+                    ids.ctypes.data_as(u32p), counts.ctypes.data_as(u32p))
+            if scope is not None:
+                _lib.check(self._lib.cs_index_search_boosted_scoped(self._h, self._scope_handle(scope), q.ctypes.data_as(f32p),
+                                                                    nq, dim, limit, *tail))
+            else:
+                _lib.check(self._lib.cs_index_search_boosted(self._h, q.ctypes.data_as(f32p), nq, dim, limit, *tail))
+            return score, cos, ids, counts
         if per_file is not None:
             if self.sharded:
                 raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no grouped search (per_file): no cs_shards_ form yet")
@@ -709,9 +774,20 @@ class VectorStore:
         return cos, ids, counts
 
     def search(self, query_embedding, limit: int, chunk_ids=None, scope: Optional[Scope] = None,
-               per_file: Optional[int] = None) -> List[SearchResult]:
+               per_file: Optional[int] = None, boost_kind: Optional[str] = None, boost: float = 0.15) -> List[SearchResult]:
         """store.rs:431-486.  Results whose metadata is missing are skipped (store.rs:465).  chunk_ids / scope / per_file:
-        search_raw."""
+        search_raw.
+        boost_kind (a CHUNK_KINDS name, e.g. "Struct"): the reference's structural-intent boost (src/search/mod.rs:238-252)
+        inside the selection — every chunk of that kind weighs 1 + boost, the others 1 (search_raw class_weights=, with its
+        exclusions); `score` is then the boosted score and `distance` still the chunk's own."""
+        if boost_kind is not None:
+            if boost_kind not in CHUNK_KINDS:
+                raise ValueError(f"boost_kind must be one of CHUNK_KINDS, got {boost_kind!r}")
+            w = np.ones(len(CHUNK_KINDS), np.float32)
+            w[CHUNK_KINDS.index(boost_kind)] = np.float32(1.0) + np.float32(boost)
+            score, cos, ids, counts = self.search_raw(query_embedding, limit, chunk_ids=chunk_ids, scope=scope, per_file=per_file,
+                                                      class_weights=w)
+            return self._results(cos[0], ids[0], int(counts[0]), score=score[0])
         cos, ids, counts = self.search_raw(query_embedding, limit, chunk_ids=chunk_ids, scope=scope, per_file=per_file)
         return self._results(cos[0], ids[0], int(counts[0]))
 
@@ -906,8 +982,9 @@ class VectorStore:
         from .search import path_matches
         return sorted(i for i, m in self._meta.items() if path_matches(m.path, filter_path, project_root, mcp))
 
-    def _results(self, cos, ids, count, keep_missing: bool = False) -> List[SearchResult]:
-        """keep_missing: a None stands where an id has no metadata (the lists of a pair stay aligned)."""
+    def _results(self, cos, ids, count, keep_missing: bool = False, score=None) -> List[SearchResult]:
+        """keep_missing: a None stands where an id has no metadata (the lists of a pair stay aligned).
+        score: the results' scores when they are not 1 - distance (a boosted search's)."""
         out = []
         dist = cos_to_distance(cos[:count])
         for i in range(count):
@@ -920,7 +997,8 @@ class VectorStore:
             out.append(SearchResult(
                 id=int(ids[i]), content=m.content, path=m.path, start_line=m.start_line,
                 end_line=m.end_line, kind=m.kind, signature=m.signature, docstring=m.docstring,
-                context=m.context, hash=m.hash, distance=d, score=float(np.float32(1.0) - np.float32(d)),
+                context=m.context, hash=m.hash, distance=d,
+                score=float(np.float32(1.0) - np.float32(d)) if score is None else float(score[i]),
                 context_prev=m.context_prev, context_next=m.context_next))
         return out
 

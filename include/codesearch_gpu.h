@@ -315,6 +315,44 @@ CS_API int32_t cs_index_search_variants_grouped_scoped(cs_index* h, cs_scope* sc
                                                        uint32_t dim, uint32_t k, uint32_t per_group, float* out_cos,
                                                        uint32_t* out_ids, uint32_t* out_count, int32_t* out_high_confidence);
 
+/* Boosted search — the exact form of the reference's kind and language boosts, which multiply the score of the hits of a
+ * ChunkKind by 1.15 (src/search/mod.rs:238-252) and of a language by 1.20 (:789-806) only after `retrieval_limit` hits
+ * have been ranked, and re-sort those: a chunk of the wanted kind just outside the fetched list never rises into it.  It
+ * is also the general soft filter: prefer `src/` over `tests/` without excluding anything, push generated code down.
+ * Every chunk id may carry a 16-bit class; ids never assigned one are CS_NO_CLASS.  One weight table serves a call.
+ * THE RULE, per query, for a live row with c = its cosine (the bits cs_index_search returns on the streaming route):
+ *   s = 1.0f - (1.0f - c) * 0.5f   in f32: the reference's score (store.rs:478); the multiply by 0.5 is exact
+ *   b = s * w                      in f32, one rounding; w = weights[class] when the id has a class < n_classes, else 1
+ * and the answer is the k live rows with the largest cs_key_pack(b, id), best first: b descending, then id ascending.
+ * s is not injective in c, so with every weight 1 the call returns the set of cs_index_search EXCEPT among rows whose
+ * scores tie: those ties go by id here, whatever their cosines.
+ * Classes belong to chunk ids, as groups do: they survive cs_index_build (the reclaim of deleted rows included), apply to
+ * the next search without a build, and cs_index_clear drops them.  The index keeps a table of 2 B per id issued on the
+ * host and, from the first boosted search after an assignment, in HBM. */
+#define CS_NO_CLASS 0xFFFFu
+#define CS_MAX_CLASSES 4096u
+/* classes[i] becomes the class of ids[i] (CS_NO_CLASS un-assigns it).  An id never issued fails with CS_ERR_BAD_ARG and
+ * nothing is assigned; an id issued and deleted since is accepted.  Not to be called while the index is searched. */
+CS_API int32_t cs_index_set_classes(cs_index* h, const uint32_t* ids, const uint16_t* classes, uint64_t n);
+/* *assigned_ids: ids that carry a class other than CS_NO_CLASS; *table_bytes: HBM the table holds.  Each output optional. */
+CS_API int32_t cs_index_classes_info(cs_index* h, uint64_t* assigned_ids, uint64_t* table_bytes);
+/* weights[0, n_classes): n_classes <= CS_MAX_CLASSES, every weight finite and in [0, 65536] — anything else, NaN included,
+ * is CS_ERR_BAD_ARG and the message names the entry.  n_classes == 0 or weights == NULL: every row weighs 1.
+ * Outputs, each optional but at least one given: out_score[q][j] = b, out_cos[q][j] = c (bit for bit the streaming scan's
+ * cosine of that row), out_ids[q][j], out_counts[q] = slots filled; unfilled slots hold 0, 0 and 0xFFFFFFFF.
+ * Errors and limits are those of cs_index_search, with the same texts, then the weight table's.  An empty store gives
+ * empty lists.  Concurrent calls with different tables are safe: a call's table travels with the call.
+ * The scoped form has the same contract over the scope's live rows and always takes the gathered scan (counted in
+ * cs_scope_route_info's gathered_searches); a null scope or one made for another store is CS_ERR_BAD_ARG, a scope with no
+ * live row gives empty lists and launches nothing.  No cs_shards_, masked, variants or device-pointer form, no int8 filter
+ * route and no combination with the per-file cap yet. */
+CS_API int32_t cs_index_search_boosted(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                                       const float* weights, uint32_t n_classes, float* out_score, float* out_cos,
+                                       uint32_t* out_ids, uint32_t* out_counts);
+CS_API int32_t cs_index_search_boosted_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,
+                                              uint32_t k, const float* weights, uint32_t n_classes, float* out_score,
+                                              float* out_cos, uint32_t* out_ids, uint32_t* out_counts);
+
 /* Similar-chunk search — "which stored chunks are nearest to this stored chunk": more like this, clone and near-duplicate
  * detection, "where else is this function copied".  The queries are chunk ids, not vectors: the source rows are gathered
  * on the device and never leave HBM.  A caller who reads the row back, searches with it and filters the ranked list on
