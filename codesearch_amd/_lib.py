@@ -110,6 +110,14 @@ SIGNATURES = {
                                             u32p]),
     "cs_index_search_boosted_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, C.c_uint32, f32p,
                                                    f32p, u32p, u32p]),
+    "cs_index_search_variants_boosted": (C.c_int32, [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, C.c_uint32, f32p, f32p,
+                                                     u32p, u32p, i32p]),
+    "cs_index_search_variants_boosted_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, C.c_uint32,
+                                                            f32p, f32p, u32p, u32p, i32p]),
+    "cs_index_search_variants_boosted_grouped": (C.c_int32, [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32p,
+                                                             C.c_uint32, f32p, f32p, u32p, u32p, i32p]),
+    "cs_index_search_variants_boosted_grouped_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                                    f32p, C.c_uint32, f32p, f32p, u32p, u32p, i32p]),
     "cs_index_search_similar": (C.c_int32, [vp, u32p, C.c_uint32, C.c_uint32, C.c_int32, C.c_float, f32p, u32p, u32p]),
     "cs_index_set_similar_route": (C.c_int32, [vp, C.c_int32]),
     "cs_index_similar_route_info": (C.c_int32, [vp, u64p, u64p, u64p]),

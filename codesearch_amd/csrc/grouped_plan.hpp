@@ -33,6 +33,14 @@
 // capped: the plain top-k of a variant can consist of one group's rows, and the row the cap promotes is then in no
 // list (tests/cpp/grouped_variants_test.cpp shows one).  capped_variants_merge_block below is one block of
 // merge_variants_grouped_kernel on the host.
+//
+// Boosted keys (cs_index_search_variants_boosted_grouped, scan_boosted_grouped.hip): neither argument above reads what a
+// key's float is.  They need two things only — every variant orders the rows by a key that is unique per row, and a row's
+// merged key is the maximum of its per-variant keys.  Both hold for key_pack(b, id) with b = fl(score(c) * w): w belongs
+// to the row, not to the variant, and score and the rounding are monotone in c, so the largest of a row's per-variant b
+// is the b of its largest cosine.  Per-variant lists that are capped lists of b (the per-wave lists of the boosted capped
+// scan, merged by launch_merge_grouped), merged with de-duplication and the cap at every level, are therefore the capped
+// top-k under the best b.  The uncapped boosted variants search is the same merge under a GroupView that caps nothing.
 #pragma once
 
 #include <algorithm>

@@ -95,6 +95,9 @@ struct Workspace {
     // [nq][k] cosines of the winners, which the cosine pass writes beside the keys
     float* h_weights = nullptr; float* d_weights = nullptr; float* h_winner_cos = nullptr;
     size_t h_weights_cap = 0, d_weights_cap = 0, h_winner_cos_cap = 0;
+    // boosted searches over query variants (search_variants_boosted): the [k] merged keys, between the variants merge and
+    // the cosine pass
+    uint64_t* d_merged = nullptr; size_t merged_cap = 0;
     std::vector<EventTriple> free_events;
     BatchedState bs;
     size_t cnt_cap = 0, tau_cap = 0, cand_cap = 0, carry_cap = 0;
@@ -151,6 +154,11 @@ struct Workspace {
         return reserve_buf(h_winner_cos, h_winner_cos_cap, (size_t)nq * k, true);
     }
 
+    int32_t reserve_boosted_variants(uint32_t k, uint32_t n_classes) {
+        CS_TRY(reserve_boosted(1, k, n_classes));
+        return reserve_buf(d_merged, merged_cap, k);
+    }
+
     int32_t reserve_batched(uint32_t nq, uint32_t k) {
         if (!h_overflow) {
             CS_HIP(realloc_buf(h_overflow, 4, true));
@@ -194,7 +202,7 @@ struct Workspace {
     void release_all() {
         free_bufs(false, d_partial, d_tmp_a, d_tmp_b, d_queries, d_keys, d_cos, d_ids, d_counts, prime.d_wave_max, prime.d_done,
                   prime.d_floor, bs.d_cand, bs.d_cnt, bs.d_tau, bs.d_carry, bs.d_overflow, qw.d_qsplit, qw.d_qmag, qw.d_q8q,
-                  qw.d_q8q_hi, qw.d_qmeta, d_allow, d_list, d_mblocks, d_similar, d_weights);
+                  qw.d_q8q_hi, qw.d_qmeta, d_allow, d_list, d_mblocks, d_similar, d_weights, d_merged);
         free_bufs(true, h_keys, h_queries, h_overflow, h_variant_meta, h_similar, h_weights, h_winner_cos);
         for (auto& t : free_events) {
             (void)hipEventDestroy(t.e0); (void)hipEventDestroy(t.e1); (void)hipEventDestroy(t.e2);
@@ -1089,6 +1097,10 @@ int32_t check_search(const cs_index* h, uint32_t nq, uint32_t dim, uint32_t k) {
 // list and the merge caps again (launch_merge_variants_grouped); null: the plain variants merge.
 // `boosted` (a boosted search): the keys carry b, which goes to `cos`; the winners' cosines, which the kind's enqueue step
 // leaves in the pinned w->h_winner_cos, go to `winner_cos`; each of the four outputs may then be null.
+// `boosted` with `variants` (a boosted search over query variants): score, cos, count and flag together.  The kind's
+// enqueue step merges the variants itself (keys of b, so the merge's own cosine predicate would read b) and leaves the ONE
+// list's keys in the pinned `keys` it is handed and the winners' cosines in w->h_winner_cos; count and flag are taken
+// from those after the synchronisation (confident_list), and high_confidence may be null like the rest.
 struct HostAnswer {
     float* cos; uint32_t* ids; uint32_t* counts; int32_t* high_confidence;
     bool variants;
@@ -1109,6 +1121,15 @@ void unpack_boosted(const uint64_t* keys, const float* cos, uint32_t nq, uint32_
         }
         if (out.counts) out.counts[q] = c;
     }
+}
+
+// The high-confidence predicate of cs_index_search_variants (mod.rs:601-611) on a list of `count` cosines, best first: the
+// list is not empty and the distance (1 - cos) / 2 of each of its first five entries is below 0.15, in f32.
+bool confident_list(const float* cos, uint32_t count) {
+    const uint32_t want = std::min<uint32_t>(count, 5);
+    for (uint32_t j = 0; j < want; ++j)
+        if (!((1.0f - cos[j]) * 0.5f < 0.15f)) return false;
+    return count > 0;
 }
 
 // The argument checks every host-buffer search starts with, in this order.
@@ -1149,21 +1170,26 @@ int32_t host_search(cs_index* h, const float* queries, uint32_t nq, uint32_t k, 
     if (!w) return fail(CS_ERR_HIP, "could not create a HIP stream");
     const int32_t s = [&]() -> int32_t {
         CS_TRY(w->reserve(partial_keys, merge_keys, nq, h->dim, k, true));
-        if (out.variants && !w->h_variant_meta) CS_HIP(hipHostMalloc(&w->h_variant_meta, 2 * sizeof(uint32_t)));
+        const bool merge_here = out.variants && !out.boosted;  // a boosted kind merges its variants itself
+        if (merge_here && !w->h_variant_meta) CS_HIP(hipHostMalloc(&w->h_variant_meta, 2 * sizeof(uint32_t)));
         if (queries) memcpy(w->h_queries, queries, (size_t)nq * h->dim * sizeof(float));
-        CS_TRY(enqueue(w, out.variants ? w->d_keys : w->h_keys));
-        if (out.variants && out.capped)
+        CS_TRY(enqueue(w, merge_here ? w->d_keys : w->h_keys));
+        if (merge_here && out.capped)
             CS_TRY(launch_merge_variants_grouped(w->d_keys, nq, k, *out.capped, w->d_tmp_a, w->d_tmp_b, w->h_keys, nullptr,
                                                  nullptr, w->h_variant_meta, w->h_variant_meta + 1, w->stream));
-        else if (out.variants)
+        else if (merge_here)
             CS_TRY(launch_merge_variants(w->d_keys, nq, k, k, w->h_keys, nullptr, nullptr, w->h_variant_meta,
                                          w->h_variant_meta + 1, w->stream));
         CS_HIP(hipStreamSynchronize(w->stream));
-        if (out.boosted) unpack_boosted(w->h_keys, w->h_winner_cos, nq, k, out);
+        if (out.boosted) unpack_boosted(w->h_keys, w->h_winner_cos, out.variants ? 1 : nq, k, out);
         else unpack_keys(w->h_keys, out.variants ? 1 : nq, k, out.cos, out.ids, out.variants ? nullptr : out.counts);
-        if (out.variants) {
+        if (merge_here) {
             *out.counts = w->h_variant_meta[0];
             if (out.high_confidence) *out.high_confidence = (int32_t)w->h_variant_meta[1];
+        } else if (out.variants && out.high_confidence) {  // boosted: the list is best first, its empty slots last
+            uint32_t count = 0;
+            while (count < k && w->h_keys[count]) ++count;
+            *out.high_confidence = confident_list(w->h_winner_cos, count) ? 1 : 0;
         }
         return CS_OK;
     }();
@@ -1296,6 +1322,70 @@ int32_t search_boosted(cs_index* h, bool scope_given, cs_scope* scope, const flo
         }
         return launch_boosted_cos(h->d_corpus, h->ledger.stored(), h->dim, w->d_queries, nq, k, h->row_ids(), w->d_keys, keys,
                                   w->h_winner_cos, w->stream);
+    });
+}
+
+// The boosted searches over query variants (cs_index_search_variants_boosted and its scoped / grouped forms): one list of
+// the rows' best b over the nq variants, uncapped (per_group null) or under the per-file cap.  Per variant a list of b —
+// run_boosted / run_boosted_list with their prime pass, or under the cap the boosted capped scan and the capped merge
+// (scan_boosted_grouped.hip) — then the de-duplicating variants merge over those keys, which caps at every level (under a
+// GroupView that caps nothing it is a plain de-duplicating merge), then the winners' cosines over all variants.  The
+// scoped forms take the gathered scans, always.  Count and flag: host_search, from the keys and the cosines.
+int32_t search_variants_boosted(cs_index* h, bool scope_given, cs_scope* scope, const uint32_t* per_group, const float* queries,
+                                uint32_t nq, uint32_t dim, uint32_t k, const float* weights, uint32_t n_classes, float* out_score,
+                                float* out_cos, uint32_t* out_ids, uint32_t* out_count, int32_t* out_high_confidence) {
+    CS_TRY(check_search(h, nq, dim, k));
+    if (nq > CS_MAX_VARIANTS) return fail(CS_ERR_BAD_ARG, "at most %u query variants per call, got %u", CS_MAX_VARIANTS, nq);
+    if (!queries) return fail(CS_ERR_BAD_ARG, "null buffer");
+    if (!out_score && !out_cos && !out_ids && !out_count && !out_high_confidence)
+        return fail(CS_ERR_BAD_ARG, "no output buffer given");
+    if (per_group && *per_group == 0) return fail(CS_ERR_BAD_ARG, "per_group must be at least 1");
+    if (!weights) n_classes = 0;
+    float wmin = 1.0f, wmax = 1.0f;
+    CS_TRY(check_weights(weights, n_classes, &wmin, &wmax));
+    HostAnswer out{out_score, out_ids, out_count, out_high_confidence, true};
+    out.boosted = true;
+    out.winner_cos = out_cos;
+    DeviceGuard g(h->device);
+    uint64_t rows = h->ledger.stored();
+    if (scope_given) CS_TRY(scope_ready(h, scope, &rows));
+    if (rows == 0) return empty_answer(nq, k, out);  // nothing the call may return is stored
+    BoostView bv;
+    CS_TRY(ensure_classes(h, &bv));
+    bv.wmin = wmin;
+    bv.wmax = wmax;
+    GroupView gv;  // as it stands it caps nothing
+    if (per_group) CS_TRY(ensure_groups(h, *per_group, &gv));
+    // a scope: the grids follow the list's length
+    const ScanPlan plan = plan_scan(rows, h->dim, nq, k, h->num_cus);
+    const GroupedPlan gplan = plan_grouped(rows, h->dim, nq, k, h->num_cus);
+    const size_t partial_keys = per_group ? gplan.partial_keys : plan.partial_keys;
+    const size_t merge_keys = std::max(per_group ? gplan.merge_keys : plan.merge_keys, grouped_variants_tmp_keys(nq, k));
+    return host_search(h, queries, nq, k, partial_keys, merge_keys, out, [&](Workspace* w, uint64_t* keys) {
+        CS_TRY(w->reserve_boosted_variants(k, n_classes));
+        CS_TRY(upload_queries(h, w, nq));
+        if (n_classes) {
+            memcpy(w->h_weights, weights, n_classes * sizeof(float));
+            CS_HIP(hipMemcpyAsync(w->d_weights, w->h_weights, n_classes * sizeof(float), hipMemcpyHostToDevice, w->stream));
+            bv.weights = w->d_weights;
+            bv.n_classes = n_classes;
+        }
+        const uint32_t* d_list = scope_given ? scope->d_list : nullptr;
+        const uint32_t* d_len = scope_given ? scope->d_blocks + scope_list_blocks(scope->n_ids) : nullptr;
+        if (scope_given) scope->gathered_searches.fetch_add(1);
+        if (per_group) {
+            CS_TRY(launch_scan_boosted_grouped(gplan, h->d_corpus, h->ledger.stored(), h->dim, d_list, d_len, w->d_queries, nq, k,
+                                               h->ledger.removed() ? h->d_dead : nullptr, h->row_ids(), bv, gv, w->d_partial,
+                                               w->stream));
+            CS_TRY(launch_merge_grouped(gplan, w->d_partial, nq, k, gv, w->d_tmp_a, w->d_tmp_b, w->d_keys, nullptr, nullptr, nullptr,
+                                        w->stream));
+        } else if (!scope_given) CS_TRY(run_boosted(h, w, plan, bv, w->d_queries, nq, k, w->d_keys, w->stream));
+        else CS_TRY(run_boosted_list(h, w, plan, rows, bv, d_list, d_len, w->d_queries, nq, k, w->d_keys, w->stream));
+        // the merge's decode of "cos" would yield b and its flag would read b: neither is asked for here
+        CS_TRY(launch_merge_variants_grouped(w->d_keys, nq, k, gv, w->d_tmp_a, w->d_tmp_b, w->d_merged, nullptr, nullptr, nullptr,
+                                             nullptr, w->stream));
+        return launch_boosted_variants_cos(h->d_corpus, h->ledger.stored(), h->dim, w->d_queries, nq, k, h->row_ids(), w->d_merged,
+                                           keys, w->h_winner_cos, w->stream);
     });
 }
 
@@ -2244,6 +2334,37 @@ int32_t cs_index_search_boosted_scoped(cs_index* h, cs_scope* scope, const float
                                        const float* weights, uint32_t n_classes, float* out_score, float* out_cos,
                                        uint32_t* out_ids, uint32_t* out_counts) {
     return search_boosted(h, true, scope, queries, nq, dim, k, weights, n_classes, out_score, out_cos, out_ids, out_counts);
+}
+
+int32_t cs_index_search_variants_boosted(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                                         const float* weights, uint32_t n_classes, float* out_score, float* out_cos,
+                                         uint32_t* out_ids, uint32_t* out_count, int32_t* out_high_confidence) {
+    return search_variants_boosted(h, false, nullptr, nullptr, queries, nq, dim, k, weights, n_classes, out_score, out_cos, out_ids,
+                                   out_count, out_high_confidence);
+}
+
+int32_t cs_index_search_variants_boosted_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,
+                                                uint32_t k, const float* weights, uint32_t n_classes, float* out_score,
+                                                float* out_cos, uint32_t* out_ids, uint32_t* out_count,
+                                                int32_t* out_high_confidence) {
+    return search_variants_boosted(h, true, scope, nullptr, queries, nq, dim, k, weights, n_classes, out_score, out_cos, out_ids,
+                                   out_count, out_high_confidence);
+}
+
+int32_t cs_index_search_variants_boosted_grouped(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                                                 uint32_t per_group, const float* weights, uint32_t n_classes, float* out_score,
+                                                 float* out_cos, uint32_t* out_ids, uint32_t* out_count,
+                                                 int32_t* out_high_confidence) {
+    return search_variants_boosted(h, false, nullptr, &per_group, queries, nq, dim, k, weights, n_classes, out_score, out_cos,
+                                   out_ids, out_count, out_high_confidence);
+}
+
+int32_t cs_index_search_variants_boosted_grouped_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq,
+                                                        uint32_t dim, uint32_t k, uint32_t per_group, const float* weights,
+                                                        uint32_t n_classes, float* out_score, float* out_cos, uint32_t* out_ids,
+                                                        uint32_t* out_count, int32_t* out_high_confidence) {
+    return search_variants_boosted(h, true, scope, &per_group, queries, nq, dim, k, weights, n_classes, out_score, out_cos,
+                                   out_ids, out_count, out_high_confidence);
 }
 
 int32_t cs_index_search_variants_grouped_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,

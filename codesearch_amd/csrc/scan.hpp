@@ -214,6 +214,21 @@ int32_t launch_scan_boosted_list(const ScanPlan& plan, const float* d_corpus, ui
 int32_t launch_boosted_cos(const float* d_corpus, uint64_t n_rows, uint32_t dim, const float* d_queries, uint32_t nq, uint32_t k,
                            RowIds ids, const uint64_t* d_keys, uint64_t* out_keys, float* out_cos, hipStream_t stream);
 
+// ---- boosted search under the per-file cap, and across query variants (scan_boosted_grouped.hip; plan: plan_grouped) ----
+// launch_scan_boosted's selection by b with launch_scan_grouped's capped per-wave lists: d_partial[q][plan.lists][k], one
+// unsorted capped list of packed (b, id) keys per wave, for launch_merge_grouped.  No prime pass.  d_list / d_list_len null:
+// every stored row [0, n_rows) with the tombstone test; else the live rows d_list[0, *d_list_len) (a scope's row list,
+// ascending; the plan made for its length), and n_rows / d_dead are not read.
+int32_t launch_scan_boosted_grouped(const GroupedPlan& plan, const float* d_corpus, uint64_t n_rows, uint32_t dim,
+                                    const uint32_t* d_list, const uint32_t* d_list_len, const float* d_queries, uint32_t nq,
+                                    uint32_t k, const uint32_t* d_dead, RowIds ids, const BoostView& bv, const GroupView& gv,
+                                    uint64_t* d_partial, hipStream_t stream);
+// launch_boosted_cos for the ONE merged list d_keys[k] of nv query variants: out_cos[j] = the largest of winner j's
+// cosines over the variants (each the streaming scan's, bit for bit), 0 for an empty slot; out_keys as there.
+int32_t launch_boosted_variants_cos(const float* d_corpus, uint64_t n_rows, uint32_t dim, const float* d_queries, uint32_t nv,
+                                    uint32_t k, RowIds ids, const uint64_t* d_keys, uint64_t* out_keys, float* out_cos,
+                                    hipStream_t stream);
+
 // ---- similar-pairs search (scan_pairs.hip, plan: pairs_plan.hpp) -----------------------------------------
 // A qualifying pair as the refine leaves it: the cosine's bits, the lower id, the higher id.
 struct PairRecord {

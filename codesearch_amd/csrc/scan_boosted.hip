@@ -31,24 +31,14 @@
 //      so the host-buffer call makes no extra round trip.
 #include "scan.hpp"
 #include "scan_wave.hpp"
+#include "scan_rules.hpp"
 
 namespace cs {
 
 static_assert(CS_MAX_CLASSES <= CS_NO_CLASS, "a class past every table must exist");
 
-// s of c: the reference's score
-__device__ __forceinline__ float boosted_score(float c) { return 1.0f - (1.0f - c) * 0.5f; }
-// An upper bound of fl(s * w) over every weight a row can take, wmin <= w <= wmax: the pre-gate's value
-__device__ __forceinline__ float boosted_bound(float s, float wmin, float wmax) { return s * (s < 0.0f ? wmin : wmax); }
-
-// The weight of the row that carries `id`: 1 without a class (ids past the table were appended after the last
-// assignment; CS_NO_CLASS is past every table) or with a class the call's table does not cover.
-__device__ __forceinline__ float boosted_weight(const BoostView& bv, uint32_t id) {
-    const uint32_t i = id - bv.id_base;
-    if (!bv.classes || i >= bv.len) return 1.0f;
-    const uint32_t cls = bv.classes[i];
-    return cls < bv.n_classes ? bv.weights[cls] : 1.0f;
-}
+// boosted_score (s of c), boosted_bound (the pre-gate's value), boosted_weight (w of an id) and boosted_row_of (the stored
+// row of a winner's id): scan_rules.hpp.
 
 // ---- 1. boosted scan --------------------------------------------------------------------------------------
 // scan_topk_kernel (scan.hip) without the gate word: see there for J, U, QT and PRIME.  LIST: half-wave h of tile t
@@ -207,19 +197,6 @@ scan_boosted_generic_kernel(const float* __restrict__ corpus, uint64_t n_rows, c
 }
 
 // ---- 3. cosine of the winners ---------------------------------------------------------------------------------
-// The stored row that carries `id`, which some stored row does: id - base under the identity numbering, else the
-// position of id in the ascending table ids[0, n_rows).
-__device__ __forceinline__ uint64_t boosted_row_of(const RowIds& row_ids, uint64_t n_rows, uint32_t id) {
-    if (!row_ids.ids) return (uint64_t)(id - row_ids.base);
-    uint64_t lo = 0, hi = n_rows;  // the first entry >= id
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (row_ids.ids[mid] < id) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < n_rows ? lo : n_rows - 1;  // (a key always names a stored row; never read past the table)
-}
-
 // Wave (blockIdx.x * kWaves + wave) of query blockIdx.y takes winner j of keys[q][k]: out_cos[q][j] = the streaming
 // scan's cosine of the row (0 for an empty slot), out_keys[q][j] = the key (optional).  J = dim / 128 for the tuned dims
 // — both half-waves score the row, as either would in the scan — and 0 for any other dim.

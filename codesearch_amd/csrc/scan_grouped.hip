@@ -18,87 +18,13 @@
 #include "scan.hpp"
 #include "grouped_plan.hpp"
 #include "scan_wave.hpp"
+#include "scan_rules.hpp"
 
 namespace cs {
 
 static_assert(kNoGroup == CS_NO_GROUP, "grouped_plan.hpp restates the public constant");
 
-__device__ __forceinline__ uint32_t group_of(const GroupView& gv, uint32_t id) {
-    const uint32_t i = id - gv.id_base;  // ids past the table (appended after the last assignment) are ungrouped
-    return (gv.groups && i < gv.len) ? gv.groups[i] : kNoGroup;
-}
-
-typedef volatile uint32_t __attribute__((address_space(3))) lds_vu32;
-
-// wave_list_insert (scan_wave.hpp) under the cap.  `list` holds the capped top-k of the rows this wave has met, `glist`
-// their groups; thr / wpos as there (wpos < 2^31 counts the filled slots of a list that is not full yet, thr = -inf then).
-// The caller has established c > thr.  Rows arrive in ascending id, so a row that ties a key already there loses to it:
-// packed keys compare that way by themselves (equal cosine, larger id -> smaller key).
-//   group CS_NO_GROUP, or fewer than m slots hold g  -> the ordinary insert: next empty slot, or over the worst key;
-//   m slots hold g                                   -> over the worst key OF GROUP g, and only if the row beats it.
-// The slot search is skipped while fewer than m slots are filled at all: no group can be saturated yet.
-__device__ __forceinline__ void wave_list_insert_grouped(volatile uint64_t* list_generic, volatile uint32_t* glist_generic,
-                                                         uint32_t k, uint32_t m, int lane, float c, uint32_t id, uint32_t g,
-                                                         float& thr, uint32_t& wpos) {
-    constexpr uint32_t kListFull = 0x80000000u;
-    lds_vu64* const list = (lds_vu64*)list_generic;
-    lds_vu32* const glist = (lds_vu32*)glist_generic;
-    const bool full = (wpos & kListFull) != 0;
-    const uint32_t filled = full ? k : wpos;
-    const uint64_t key = key_pack(c, id);
-    if (g != kNoGroup && filled >= m) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        uint32_t cnt = 0;
-        uint64_t wk = ~0ull;
-        uint32_t wp = 0xffffffffu;
-        for (uint32_t i0 = 0; i0 < filled; i0 += 64) {
-            const uint32_t i = i0 + lane;
-            const bool hit = i < filled && glist[i] == g;
-            cnt += (uint32_t)__popcll(__ballot(hit));
-            if (hit) {
-                const uint64_t v = list[i];
-                if (v < wk) { wk = v; wp = i; }
-            }
-        }
-        if (cnt >= m) {  // wave-uniform
-#pragma unroll
-            for (int s = 32; s >= 1; s >>= 1) {
-                const uint64_t ok = shfl_xor_u64(wk, s);
-                const uint32_t op = __shfl_xor(wp, s, 64);
-                if (ok < wk || (ok == wk && op < wp)) { wk = ok; wp = op; }
-            }
-            if (key > wk) {
-                if (lane == 0) list[wp] = key;  // the slot keeps its group
-                if (full) {
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    wave_list_worst<true>(list, k, lane, thr, wpos);  // a full list has no empty slot
-                }
-            }
-            return;
-        }
-    }
-    const uint32_t slot = wpos & ~kListFull;
-    if (lane == 0) {
-        list[slot] = key;
-        glist[slot] = g;
-    }
-    if (!full && slot + 1 < k) {
-        wpos = slot + 1;
-        return;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    wave_list_worst<true>(list, k, lane, thr, wpos);  // a full list has no empty slot
-}
-
-// A wave's list -> HBM, unsorted, empty slots as 0: list `blockIdx.x * kWaves + wave` of query q.
-__device__ __forceinline__ void wave_list_store(const uint64_t* list, uint32_t k, int lane, uint64_t* __restrict__ partial,
-                                                uint32_t q, int wave) {
-    uint64_t* out = partial + ((size_t)q * (gridDim.x * kWaves) + (size_t)blockIdx.x * kWaves + wave) * k;
-    for (uint32_t i = lane; i < k; i += 64) out[i] = list[i];
-}
+// group_of, wave_list_insert_grouped (the capped insert of a wave's list) and wave_list_store: scan_rules.hpp.
 
 // ---- 1. capped scan ---------------------------------------------------------------------------------
 // scan_topk_kernel (scan.hip) without PRIME, the floor and the gate: see there for J, U and QT.

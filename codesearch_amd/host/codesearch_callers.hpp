@@ -266,7 +266,8 @@ constexpr const char* kChunkKinds[18] = {"Function", "Class", "Method", "Struct"
                                          "Other"};
 constexpr float kStructuralBoost = 0.15f;  // mod.rs:243: score *= 1.0 + boost_factor for hits of the intended kind
 
-// The weight table of the structural-intent boost (mod.rs:238-252) for VectorStore::search_boosted: ones, 1 + boost at
+// The weight table of the structural-intent boost (mod.rs:238-252) for VectorStore::search_boosted and, over the merged
+// query variants, in a Scope and under `--per-file`, VectorStore::search_variants_boosted: ones, 1 + boost at
 // `kind`; all ones for a name that is no kind.
 inline std::vector<float> kind_boost_weights(const std::string& kind, float boost = kStructuralBoost) {
     std::vector<float> w(18, 1.0f);

@@ -426,6 +426,41 @@ class VectorStore {
         std::vector<SearchResult> out = results(cos, ids, counts[0], &score);
         return out;
     }
+    // The boosted search over the merged query variants — a chunk keeps its best cosine, and so its best boosted score —
+    // with or without a Scope, and with per_file != 0 under the per-file cap, all decided on the device
+    // (cs_index_search_variants_boosted and its _scoped / _grouped / _grouped_scoped forms): what one reference search
+    // computes.  The flag is the predicate on the returned list's cosines.  One index only.
+    std::vector<SearchResult> search_variants_boosted(const std::vector<std::vector<float>>& variants, size_t limit,
+                                                      const std::vector<float>& class_weights, uint32_t per_file = 0,
+                                                      const Scope* scope = nullptr, bool* high_confidence = nullptr) const {
+        if (sh_) throw Error(CS_ERR_UNSUPPORTED, "a sharded store has no boosted search");
+        const size_t nq = variants.size();
+        if (nq == 0) return {};
+        const size_t qdim = variants[0].size();
+        std::vector<float> q;
+        for (const auto& v : variants) {
+            if (v.size() != qdim) throw Error(CS_ERR_BAD_ARG, "queries of unequal length");
+            q.insert(q.end(), v.begin(), v.end());
+        }
+        std::vector<float> score(limit), cos(limit);
+        std::vector<uint32_t> ids(limit);
+        uint32_t count = 0;
+        int32_t flag = 0;
+        const uint32_t n = (uint32_t)nq, dim = (uint32_t)qdim, k = (uint32_t)limit, nc = (uint32_t)class_weights.size();
+        const float* w = class_weights.data();
+        if (per_file)
+            check(scope ? cs_index_search_variants_boosted_grouped_scoped(h_, scope->handle(), q.data(), n, dim, k, per_file, w, nc,
+                                                                          score.data(), cos.data(), ids.data(), &count, &flag)
+                        : cs_index_search_variants_boosted_grouped(h_, q.data(), n, dim, k, per_file, w, nc, score.data(),
+                                                                   cos.data(), ids.data(), &count, &flag));
+        else
+            check(scope ? cs_index_search_variants_boosted_scoped(h_, scope->handle(), q.data(), n, dim, k, w, nc, score.data(),
+                                                                  cos.data(), ids.data(), &count, &flag)
+                        : cs_index_search_variants_boosted(h_, q.data(), n, dim, k, w, nc, score.data(), cos.data(), ids.data(),
+                                                           &count, &flag));
+        if (high_confidence) *high_confidence = flag != 0;
+        return results(cos, ids, count, &score);
+    }
     // similar() among the chunks of a Scope only (cs_index_search_similar_scoped): "where else under src/ is this copied".
     // Chunk `id` itself need not be in the scope.  One index only.  The scope's route (cs_scope_set_route) picks the gathered
     // scan or the int8 filter planned over the scope's rows; the results are the same.

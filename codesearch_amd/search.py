@@ -195,6 +195,32 @@ def merge_variants_capped(lists, group_of, k: int, m: int):
     return cap_per_group([best[i] for i in order], order, group_of(order) if order else [], k, m)
 
 
+def merge_variants_boosted(lists, class_of, weights, k: int, group_of=None, m: Optional[int] = None):
+    """The contract of the boosted variants searches (cs_index_search_variants_boosted and its _scoped / _grouped forms) on
+    the host, in numpy float32.  `lists`: per query variant a (cos, ids) pair over the rows in play — the variant's FULL
+    order (a boosted row just outside a top-k is the point), every row once per variant; `class_of(ids)` -> their classes,
+    `group_of(ids)` -> their groups.  A chunk keeps c = its best cosine over the variants; b = f32(cos_to_score(c) * w) by
+    boost_order's arithmetic, which is also the best of its per-variant boosted scores; the chunks are ordered by
+    key_pack(b, id) — b descending, then id ascending — and, when group_of and m are given, capped by cap_per_group's walk
+    over that order.  -> (score, cos, ids) of the first k kept rows as arrays, best first."""
+    import numpy as np
+
+    cos = np.concatenate([np.asarray(c, np.float32).ravel() for c, _ in lists]) if len(lists) else np.zeros(0, np.float32)
+    ids = np.concatenate([np.asarray(i, np.uint32).ravel() for _, i in lists]) if len(lists) else np.zeros(0, np.uint32)
+    order = np.lexsort((-cos, ids))  # by id, a chunk's best cosine first
+    cos, ids = cos[order], ids[order]
+    first = np.ones(ids.size, bool)
+    first[1:] = ids[1:] != ids[:-1]
+    cos, ids = cos[first], ids[first]
+    capped = group_of is not None and m is not None
+    b, c, i = boost_order(cos, ids, class_of(ids) if ids.size else [], weights, ids.size if capped else k)
+    if capped and i.size:
+        pos, _ = cap_per_group(range(i.size), i, group_of(i), k, m)
+        pos = np.asarray(pos, np.int64)
+        b, c, i = b[pos], c[pos], i[pos]
+    return b[:max(int(k), 0)], c[:max(int(k), 0)], i[:max(int(k), 0)]
+
+
 def high_confidence(cos, top_n: int = 5, max_distance: float = 0.15) -> bool:
     """The early-termination predicate of the variants searches on a returned list's cosines (src/search/mod.rs:595-611):
     the list is not empty and its first top_n entries all have distance (1 - cos) / 2 < max_distance, in float32."""

@@ -169,14 +169,15 @@ def _one_of(chunk_ids, scope, per_file=None):
         raise ValueError("chunk_ids= and scope= are exclusive: a scope already is a set of chunk ids")
 
 
-def _filters_ok(chunk_ids, scope, per_file, class_weights=None):
+def _filters_ok(chunk_ids, scope, per_file, class_weights=None, variants=False):
     """The argument check of the searches: per_file= may come with scope= (the grouped scoped search), and so may
     class_weights= (the boosted scoped search); every other pair is refused — class_weights= with chunk_ids= (no masked
-    boosted form) or with per_file= (no boosted form under the per-file cap), and _one_of's: per_file= with chunk_ids= (no
+    boosted form) or with per_file= (independent queries have no boosted form under the per-file cap; `variants`, the
+    variants searches, have: cs_index_search_variants_boosted_grouped), and _one_of's: per_file= with chunk_ids= (no
     masked grouped form), chunk_ids= with scope=."""
     if class_weights is not None and chunk_ids is not None:
         raise ValueError("class_weights= is exclusive with chunk_ids=: the boosted search has no masked form (use scope=)")
-    if class_weights is not None and per_file is not None:
+    if class_weights is not None and per_file is not None and not variants:
         raise ValueError("class_weights= is exclusive with per_file=: the boosted search has no form under the per-file cap")
     _one_of(chunk_ids, None if (per_file is not None and chunk_ids is None) else scope, per_file)
 
@@ -717,7 +718,8 @@ class VectorStore:
         class_weights: -> (score, cos, ids, counts) instead — the boosted search (cs_index_search_boosted): one f32 weight
         per class (set_classes; at most 4096, each finite and in [0, 65536]; a row without a class, or with a class past the
         table, weighs 1), the exact top `limit` by b = f32(cos_to_score(cos) * weight), then id; score = b, cos = the row's
-        cosine.  May come with scope= (cs_index_search_boosted_scoped); exclusive with chunk_ids= and per_file=.
+        cosine.  May come with scope= (cs_index_search_boosted_scoped); exclusive with chunk_ids= and per_file= (the capped
+        boosted search of one query is search_variants_raw(class_weights=, per_file=) with one variant).
         A language boost is the caller's through set_classes, e.g. class = language * len(CHUNK_KINDS) + kind and a table
         of 1.2 for the language's classes, 1.15 for the kind's and f32(1.2 * 1.15) where both hold — which is one rounding
         of the product and so not bit-equal to the reference's two successive multiplies (f32(f32(s * 1.15) * 1.2)).
@@ -799,22 +801,38 @@ class VectorStore:
         return [self._results(cos[i], ids[i], int(counts[i])) for i in range(len(counts))]
 
     def search_variants(self, query_embeddings, limit: int, chunk_ids=None, scope: Optional[Scope] = None,
-                        per_file: Optional[int] = None):
+                        per_file: Optional[int] = None, boost_kind: Optional[str] = None, boost: float = 0.15):
         """search::search's vector leg (src/search/mod.rs:508-611) in one call: every variant searched for `limit`
         rows, union with a chunk keeping its best score, best `limit` distinct chunks best-first, merged on
         the device.  -> (results, high_confidence) where high_confidence is the early-termination predicate
         (top five all distance < 0.15).  chunk_ids / scope: only these chunks are searched (search_raw).
         per_file: at most this many chunks of one file among the `limit` returned, the cap applied to the merged order
         on the device (cs_index_search_variants_grouped, with scope= cs_index_search_variants_grouped_scoped); the flag
-        is then the predicate on the capped list.  Exclusive with chunk_ids."""
+        is then the predicate on the capped list.  Exclusive with chunk_ids.
+        boost_kind / boost: as in search() — the weight is part of the selection and `score` is the boosted score; here it
+        combines with scope= and per_file= (search_variants_raw class_weights=)."""
+        if boost_kind is not None:
+            if boost_kind not in CHUNK_KINDS:
+                raise ValueError(f"boost_kind must be one of CHUNK_KINDS, got {boost_kind!r}")
+            w = np.ones(len(CHUNK_KINDS), np.float32)
+            w[CHUNK_KINDS.index(boost_kind)] = np.float32(1.0) + np.float32(boost)
+            score, cos, ids, count, flag = self.search_variants_raw(query_embeddings, limit, chunk_ids=chunk_ids, scope=scope,
+                                                                    per_file=per_file, class_weights=w)
+            return self._results(cos, ids, count, score=score), flag
         cos, ids, count, flag = self.search_variants_raw(query_embeddings, limit, chunk_ids=chunk_ids, scope=scope,
                                                          per_file=per_file)
         return self._results(cos, ids, count), flag
 
     def search_variants_raw(self, query_embeddings, limit: int, chunk_ids=None, scope: Optional[Scope] = None,
-                            per_file: Optional[int] = None):
-        """search_variants without the metadata join -> (cos [limit] f32, ids [limit] u32, count, high_confidence)."""
-        _filters_ok(chunk_ids, scope, per_file)
+                            per_file: Optional[int] = None, class_weights=None):
+        """search_variants without the metadata join -> (cos [limit] f32, ids [limit] u32, count, high_confidence).
+        class_weights (search_raw's table): -> (score, cos, ids, count, high_confidence) instead — the boosted search over
+        the variants (cs_index_search_variants_boosted): a chunk's cos is its best cosine over the variants, score = b =
+        f32(cos_to_score(cos) * weight), the exact top `limit` by (b, id); the flag is the predicate on the returned
+        list's cosines.  Alone, with scope=, with per_file= (the capped walk over b, decided on the device) or with both;
+        exclusive with chunk_ids=.  The capped boosted search of ONE query, which search_raw refuses, is this call with
+        one variant."""
+        _filters_ok(chunk_ids, scope, per_file, class_weights, variants=True)
         q = np.ascontiguousarray(query_embeddings, np.float32)
         if q.ndim == 1:
             q = q[None, :]
@@ -822,6 +840,19 @@ class VectorStore:
         cos = np.zeros(max(limit, 1), np.float32)
         ids = np.zeros(max(limit, 1), np.uint32)
         count, flag = C.c_uint32(), C.c_int32()
+        if class_weights is not None:
+            if self.sharded:
+                raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no boosted search (class_weights): no cs_shards_ form yet")
+            w = np.ascontiguousarray(class_weights, np.float32).ravel()
+            score = np.zeros_like(cos)
+            head = (self._h,) + ((self._scope_handle(scope),) if scope is not None else ()) + (q.ctypes.data_as(f32p), nq, dim, limit)
+            tail = (w.ctypes.data_as(f32p) if w.size else None, w.size, score.ctypes.data_as(f32p), cos.ctypes.data_as(f32p),
+                    ids.ctypes.data_as(u32p), C.byref(count), C.byref(flag))
+            name = "cs_index_search_variants_boosted" + ("_grouped" if per_file is not None else "") + \
+                ("_scoped" if scope is not None else "")
+            cap = (int(per_file),) if per_file is not None else ()
+            _lib.check(getattr(self._lib, name)(*head, *cap, *tail))
+            return score, cos, ids, int(count.value), bool(flag.value)
         if per_file is not None:
             if self.sharded:
                 raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no grouped search (per_file): no cs_shards_ form yet")

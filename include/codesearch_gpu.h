@@ -344,14 +344,51 @@ CS_API int32_t cs_index_classes_info(cs_index* h, uint64_t* assigned_ids, uint64
  * empty lists.  Concurrent calls with different tables are safe: a call's table travels with the call.
  * The scoped form has the same contract over the scope's live rows and always takes the gathered scan (counted in
  * cs_scope_route_info's gathered_searches); a null scope or one made for another store is CS_ERR_BAD_ARG, a scope with no
- * live row gives empty lists and launches nothing.  No cs_shards_, masked, variants or device-pointer form, no int8 filter
- * route and no combination with the per-file cap yet. */
+ * live row gives empty lists and launches nothing.  Across query variants and under the per-file cap:
+ * cs_index_search_variants_boosted below.  No cs_shards_, masked or device-pointer form, no int8 filter route, no
+ * independent-query form under the cap and one weight table per call. */
 CS_API int32_t cs_index_search_boosted(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
                                        const float* weights, uint32_t n_classes, float* out_score, float* out_cos,
                                        uint32_t* out_ids, uint32_t* out_counts);
 CS_API int32_t cs_index_search_boosted_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,
                                               uint32_t k, const float* weights, uint32_t n_classes, float* out_score,
                                               float* out_cos, uint32_t* out_ids, uint32_t* out_counts);
+/* Boosted search across query variants, in a scope, under the per-file cap — what one reference search computes (up to nine
+ * variants merged, an optional filter_path, the kind and language boosts, `--per-file`), each step part of the selection
+ * instead of a pass over the list the step before left.
+ * THE RULE, for a live row (in the scope, for the scoped forms): c_v = the streaming scan's cosine of the row under variant
+ * v, bit for bit; c = the largest c_v; s = 1.0f - (1.0f - c) * 0.5f; b = s * w, one rounding, w as in
+ * cs_index_search_boosted.  s and the rounding are monotone, so b is also the largest of the row's per-variant boosted
+ * scores, and the row's key cs_key_pack(b, id) the best of its keys over the variants.
+ * Uncapped forms: the k rows with the largest key, best first.  Grouped forms: walk the rows in key order, keep a row when
+ * its group is CS_NO_GROUP or fewer than per_group rows of its group have been kept, stop at k.
+ * Outputs, each optional but at least one given: out_score[j] = b, out_cos[j] = c, out_ids[j], *out_count = rows kept;
+ * unfilled slots hold 0, 0 and 0xFFFFFFFF.  *out_high_confidence = the predicate of cs_index_search_variants on the list
+ * returned: not empty, and (1 - out_cos) / 2 < 0.15 in f32 for each of its first five entries; computed from c.
+ * With nq == 1 the uncapped forms equal cs_index_search_boosted / _boosted_scoped bit for bit; with per_group >= k or no
+ * group assigned a grouped form equals its uncapped sibling; a scope holding every id equals the unscoped form.
+ * Errors, texts and their order: those of cs_index_search_variants (nq <= CS_MAX_VARIANTS), then per_group == 0 for the
+ * grouped forms, then the weight table's, then the scope's.  A scope with no live row, or an empty store, gives the empty
+ * answer and launches nothing.  The scoped forms always take the gathered scan (cs_scope_route_info's gathered_searches);
+ * none takes the int8 filter.  Concurrent calls with different tables and caps are safe.  On the device every variant's
+ * list is a list of b — capped, for the grouped forms — and the merge de-duplicates, and caps, at every level
+ * (scan_boosted_grouped.hip); boosting or capping a merged list on the host is not the same thing and can lose rows. */
+CS_API int32_t cs_index_search_variants_boosted(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                                                const float* weights, uint32_t n_classes, float* out_score, float* out_cos,
+                                                uint32_t* out_ids, uint32_t* out_count, int32_t* out_high_confidence);
+CS_API int32_t cs_index_search_variants_boosted_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq,
+                                                       uint32_t dim, uint32_t k, const float* weights, uint32_t n_classes,
+                                                       float* out_score, float* out_cos, uint32_t* out_ids,
+                                                       uint32_t* out_count, int32_t* out_high_confidence);
+CS_API int32_t cs_index_search_variants_boosted_grouped(cs_index* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                                                        uint32_t per_group, const float* weights, uint32_t n_classes,
+                                                        float* out_score, float* out_cos, uint32_t* out_ids,
+                                                        uint32_t* out_count, int32_t* out_high_confidence);
+CS_API int32_t cs_index_search_variants_boosted_grouped_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq,
+                                                               uint32_t dim, uint32_t k, uint32_t per_group,
+                                                               const float* weights, uint32_t n_classes, float* out_score,
+                                                               float* out_cos, uint32_t* out_ids, uint32_t* out_count,
+                                                               int32_t* out_high_confidence);
 
 /* Similar-chunk search — "which stored chunks are nearest to this stored chunk": more like this, clone and near-duplicate
  * detection, "where else is this function copied".  The queries are chunk ids, not vectors: the source rows are gathered
