@@ -23,6 +23,7 @@ CS_SIMILAR_EXCLUDE_NONE, CS_SIMILAR_EXCLUDE_SELF, CS_SIMILAR_EXCLUDE_GROUP = 0, 
 CS_SIMILAR_ROUTE_AUTO, CS_SIMILAR_ROUTE_SCAN, CS_SIMILAR_ROUTE_FILTER = 0, 1, 2
 CS_MAX_PAIRS = 1 << 22
 CS_PAIRS_ALL, CS_PAIRS_OTHER_GROUP = 0, 1
+CS_NO_ID = 0xFFFFFFFF
 CS_NO_CLASS = 0xFFFF
 CS_MAX_CLASSES = 4096
 
@@ -125,6 +126,8 @@ SIGNATURES = {
                                                    u32p]),
     "cs_index_similar_pairs": (C.c_int32, [vp, C.c_float, C.c_int32, C.c_uint32, u32p, u32p, f32p, u64p]),
     "cs_index_similar_pairs_info": (C.c_int32, [u64p, u32p, f64p, f64p, f64p]),
+    "cs_index_similar_clusters": (C.c_int32, [vp, C.c_float, C.c_int32, u32p, C.c_uint64, u64p, u64p]),
+    "cs_index_similar_clusters_info": (C.c_int32, [u64p, u64p, u64p, u32p, f64p, f64p]),
     "cs_index_similar_pairs_scoped": (C.c_int32, [vp, vp, vp, C.c_float, C.c_int32, C.c_uint32, u32p, u32p, f32p, u64p]),
     "cs_index_similar_pairs_scoped_info": (C.c_int32, [f64p, u64p, u64p, u64p]),
     "cs_index_search_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p]),

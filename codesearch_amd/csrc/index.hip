@@ -17,6 +17,7 @@
 #include "grouped_plan.hpp"
 #include "index_ledger.hpp"
 #include "masked_plan.hpp"
+#include "clusters_plan.hpp"
 #include "pairs_plan.hpp"
 #include "pairs_scoped_plan.hpp"
 #include "scan.hpp"
@@ -238,6 +239,36 @@ struct PairsWorkspace {
     }
 };
 
+// Scratch of a similar-clusters call (cs_index_similar_clusters, scan_clusters.hip), pooled per index beside PairsWorkspace:
+// O(stored rows) for the union-find and the labels, one word per tile, and the ambiguous buffer, whose size is fixed.
+struct ClustersWorkspace {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    uint32_t* d_parent = nullptr; size_t parent_cap = 0;        // [stored rows]
+    uint32_t* d_mark = nullptr; size_t mark_cap = 0;            // [stored rows]: the label kernel's "this root was counted"
+    uint32_t* d_tile_root = nullptr; size_t tile_root_cap = 0;  // [tiles]
+    uint32_t* d_label = nullptr; size_t label_cap = 0;          // [ids issued]
+    uint64_t* d_amb = nullptr; size_t amb_cap = 0;              // ambiguous pairs (rowA | rowB << 32)
+    uint64_t* d_counters = nullptr;  // [0] ambiguous pairs of the launch, [1] its skipped tile pairs, [2] classes, [3] members
+    uint64_t* h_counters = nullptr;  // pinned: where the host reads them
+
+    int32_t init() {
+        CS_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        CS_HIP(hipEventCreate(&ev[0]));
+        CS_HIP(hipEventCreate(&ev[1]));
+        CS_HIP(realloc_buf(d_counters, 4));
+        CS_HIP(realloc_buf(h_counters, 4, true));
+        return CS_OK;
+    }
+    void release_all() {
+        free_bufs(false, d_parent, d_mark, d_tile_root, d_label, d_amb, d_counters);
+        free_bufs(true, h_counters);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
 }  // namespace cs
 
 using namespace cs;
@@ -326,6 +357,7 @@ struct cs_index {
     std::mutex mu;  // guards the pools below (search is re-entrant)
     std::vector<Workspace*> pool;
     std::vector<PairsWorkspace*> pairs_pool;  // cs_index_similar_pairs' scratch, one set per call in flight
+    std::vector<ClustersWorkspace*> clusters_pool;  // cs_index_similar_clusters', likewise
     // device-API scratch: one set per (stream, calling thread) — stream order makes reuse safe within a
     // thread, and two threads sharing a stream (e.g. both on the null stream) never share a set
     std::map<std::pair<hipStream_t, std::thread::id>, Workspace*> by_stream;
@@ -1714,6 +1746,199 @@ int32_t similar_pairs(cs_index* h, float min_cos, int32_t mode, uint32_t max_pai
     return pairs_finish(h, w, min_cos, max_pairs, out_a, out_b, out_cos, out_total, info);
 }
 
+// ---- the similar-clusters search (scan_clusters.hip, plan: clusters_plan.hpp) -----------------------------------
+// What the calling thread's last successful call did (cs_index_similar_clusters_info).
+struct ClustersInfo {
+    uint64_t scored = 0, skipped = 0, rescored = 0;
+    uint32_t launches = 0;
+    double join_ms = 0.0, label_ms = 0.0;
+};
+thread_local ClustersInfo last_clusters_info;
+
+ClustersWorkspace* acquire_clusters(cs_index* h) {
+    {
+        std::lock_guard<std::mutex> lk(h->mu);
+        if (!h->clusters_pool.empty()) {
+            ClustersWorkspace* w = h->clusters_pool.back();
+            h->clusters_pool.pop_back();
+            return w;
+        }
+    }
+    ClustersWorkspace* w = new ClustersWorkspace();
+    if (w->init() != CS_OK) {
+        w->release_all();
+        delete w;
+        return nullptr;
+    }
+    return w;
+}
+
+uint64_t clusters_knob(const char* name) {
+    const char* e = cs_lab_env(name);  // (read per call: tests set it mid-process)
+    return e ? std::strtoull(e, nullptr, 10) : 0;
+}
+
+// The checks; the f16 operand as similar_pairs finds or makes it; then the plan's walk: per launch the tile roots, the join
+// and one synchronise to read the ambiguous counter — within the buffer: the rescore unites what qualifies; past it: the
+// launch is void and its two halves are walked instead (lo first, so the walk stays in the triangle's order) — and at the
+// end the label kernel.  Labels are staged on the host and copied out last: a HIP failure half-way writes nothing either.
+int32_t similar_clusters(cs_index* h, float min_cos, int32_t mode, uint32_t* out_label, uint64_t n_labels,
+                         uint64_t* out_clusters, uint64_t* out_members) {
+    if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
+    CS_TRY(check_search(h, 1, h->dim, 1));
+    if (!out_label) return fail(CS_ERR_BAD_ARG, "null buffer");
+    if (mode != CS_PAIRS_ALL && mode != CS_PAIRS_OTHER_GROUP)
+        return fail(CS_ERR_BAD_ARG, "mode must be CS_PAIRS_ALL or CS_PAIRS_OTHER_GROUP (0..1), got %d", mode);
+    if (min_cos != min_cos) return fail(CS_ERR_BAD_ARG, "min_cos is NaN");
+    const uint64_t issued = h->ledger.issued_ids();
+    if (n_labels != issued)
+        return fail(CS_ERR_BAD_ARG, "n_labels must be cs_index_next_id - id_base = %llu (one label per id issued), got %llu",
+                    (unsigned long long)issued, (unsigned long long)n_labels);
+    if (!split_scan_supported(h->dim))
+        return fail(CS_ERR_UNSUPPORTED, "similar clusters need dim 384, 768 or 1024 (the f16 filter's widths), got %u", h->dim);
+    const uint64_t stored = h->ledger.stored();
+    if (h->ledger.live() < 2) {  // no pair: every live id is its own label, nothing is launched
+        std::vector<uint32_t> rows;
+        h->ledger.survivors(0, stored, rows);
+        std::fill(out_label, out_label + n_labels, (uint32_t)CS_NO_ID);
+        for (uint32_t r : rows) {
+            const uint32_t id = h->ledger.compacted() ? h->ledger.ids_data()[r] : h->ledger.id_base() + r;
+            out_label[id - h->ledger.id_base()] = id;
+        }
+        if (out_clusters) *out_clusters = 0;
+        if (out_members) *out_members = 0;
+        last_clusters_info = ClustersInfo{};
+        return CS_OK;
+    }
+    if (!h->use_split)
+        return fail(CS_ERR_UNSUPPORTED, "similar clusters need the f16 filter copy, and CS_INDEX_SPLIT=0 turned it off");
+    DeviceGuard g(h->device);
+    const ClustersPlan plan = plan_clusters(stored, clusters_knob("CS_CLUSTERS_LAUNCH_TILE_PAIRS"),
+                                            clusters_knob("CS_CLUSTERS_AMBIGUOUS_CAP"));
+    const _Float16* d_f16 = nullptr;
+    if (h->f16_eager || !q8_serves(h)) {
+        if (!ensure_f16(h)) return fail(CS_ERR_OOM, "similar clusters: no room for the f16 filter copy");
+        d_f16 = h->d_split;
+    } else {
+        std::lock_guard<std::mutex> lk(h->filter_mu);
+        if (h->d_split && h->split_rows >= stored) d_f16 = h->d_split;  // an overflowed search left one: it stays until the next build
+    }
+    struct Scratch {
+        cs_index* h;
+        ClustersWorkspace* w = nullptr;
+        _Float16* d_private = nullptr;
+        hipEvent_t ev[2] = {nullptr, nullptr};  // the rescore's, read one synchronise later than the join's
+        ~Scratch() {
+            for (hipEvent_t e : ev)
+                if (e) (void)hipEventDestroy(e);
+            if (d_private) (void)hipFree(d_private);
+            if (w) {
+                std::lock_guard<std::mutex> lk(h->mu);
+                h->clusters_pool.push_back(w);
+            }
+        }
+    } sc{h};
+    sc.w = acquire_clusters(h);
+    if (!sc.w) return fail(CS_ERR_HIP, "similar clusters: could not create a HIP stream");
+    ClustersWorkspace* w = sc.w;
+    if (!d_f16) {  // the int8 copy serves the index: the call brings its own f16 rows and frees them (similar_pairs)
+        if (h->normed_rows < stored) return fail(CS_ERR_HIP, "similar clusters: the index holds no row norms");
+        const size_t bytes = (size_t)plan.tiles * kPairsTileRows * h->dim * sizeof(_Float16);
+        if (cs_lab_env("CS_FAULT_F16_ALLOC") != nullptr || hipMalloc(&sc.d_private, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            sc.d_private = nullptr;
+            return fail(CS_ERR_OOM, "similar clusters: no room for the f16 filter copy (%llu bytes)", (unsigned long long)bytes);
+        }
+        CS_TRY(launch_corpus_split(h->d_corpus, h->d_norms, sc.d_private, 0, stored, h->dim, w->stream));
+        d_f16 = sc.d_private;
+    }
+    GroupView gv{nullptr, 0, h->ledger.id_base(), 0xFFFFFFFFu};
+    if (mode == CS_PAIRS_OTHER_GROUP) CS_TRY(ensure_groups(h, 0xFFFFFFFFu, &gv));
+    CS_TRY(reserve_buf(w->d_parent, w->parent_cap, (size_t)stored));
+    CS_TRY(reserve_buf(w->d_mark, w->mark_cap, (size_t)stored));
+    CS_TRY(reserve_buf(w->d_tile_root, w->tile_root_cap, (size_t)plan.tiles));
+    CS_TRY(reserve_buf(w->d_label, w->label_cap, (size_t)n_labels));
+    CS_TRY(reserve_buf(w->d_amb, w->amb_cap, (size_t)plan.ambiguous_cap));
+    CS_HIP(hipEventCreate(&sc.ev[0]));
+    CS_HIP(hipEventCreate(&sc.ev[1]));
+    CS_HIP(hipMemsetAsync(w->d_counters, 0, 4 * sizeof(uint64_t), w->stream));
+    CS_HIP(hipMemsetAsync(w->d_label, 0xFF, (size_t)n_labels * sizeof(uint32_t), w->stream));  // CS_NO_ID
+    CS_TRY(launch_clusters_init(w->d_parent, w->d_mark, stored, w->stream));
+    const uint32_t* d_dead = h->ledger.removed() ? h->d_dead : nullptr;
+    const float* d_norms = h->normed_rows >= stored ? h->d_norms : nullptr;  // none: no pair is united without a rescore
+    const RowIds ids = h->row_ids();
+    ClustersInfo info;
+    std::vector<PairsBand> halves;  // of launches whose ambiguous pairs did not fit; the next to walk is at the back
+    uint64_t next = 0;
+    bool rescore_timed = false;
+    float ms = 0.0f;
+    while (next < plan.tile_pairs || !halves.empty()) {
+        PairsBand r;
+        if (!halves.empty()) {
+            r = halves.back();
+            halves.pop_back();
+        } else {
+            r = plan.launch_at(next);
+            next += r.count;
+        }
+        CS_HIP(hipMemsetAsync(w->d_counters, 0, 2 * sizeof(uint64_t), w->stream));
+        CS_HIP(hipEventRecord(w->ev[0], w->stream));
+        CS_TRY(launch_clusters_tile_roots(w->d_parent, plan.tiles, stored, d_dead, w->d_tile_root, w->stream));
+        CS_TRY(launch_clusters_join(d_f16, h->dim, plan.tiles, r.first, r.count, stored, d_dead, ids, gv,
+                                    mode == CS_PAIRS_OTHER_GROUP, min_cos, h->filter_margin, d_norms, w->d_parent,
+                                    w->d_tile_root, w->d_amb, w->d_counters, (uint32_t)plan.ambiguous_cap, w->stream));
+        CS_HIP(hipEventRecord(w->ev[1], w->stream));
+        CS_HIP(hipMemcpyAsync(w->h_counters, w->d_counters, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, w->stream));
+        CS_HIP(hipStreamSynchronize(w->stream));
+        CS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
+        info.join_ms += ms;
+        if (rescore_timed) {  // the previous launch's rescore has finished with this synchronise
+            CS_HIP(hipEventElapsedTime(&ms, sc.ev[0], sc.ev[1]));
+            info.join_ms += ms;
+            rescore_timed = false;
+        }
+        info.launches++;
+        const uint64_t ambiguous = w->h_counters[0];
+        if (ambiguous > plan.ambiguous_cap) {
+            PairsBand lo, hi;
+            if (!clusters_split(r, lo, hi))
+                return fail(CS_ERR_HIP, "similar clusters: one tile pair reported %llu ambiguous pairs, more than 128 * 128",
+                            (unsigned long long)ambiguous);
+            halves.push_back(hi);
+            halves.push_back(lo);
+            continue;
+        }
+        info.skipped += w->h_counters[1];
+        info.scored += r.count - w->h_counters[1];
+        info.rescored += ambiguous;
+        if (ambiguous) {
+            CS_HIP(hipEventRecord(sc.ev[0], w->stream));
+            CS_TRY(launch_clusters_rescore(h->d_corpus, h->dim, w->d_amb, (uint32_t)ambiguous, ids, min_cos, w->d_parent,
+                                           pairs_refine_blocks(ambiguous, h->num_cus), w->stream));
+            CS_HIP(hipEventRecord(sc.ev[1], w->stream));
+            rescore_timed = true;
+        }
+    }
+    CS_HIP(hipEventRecord(w->ev[0], w->stream));
+    CS_TRY(launch_clusters_label(w->d_parent, w->d_mark, stored, d_dead, ids, w->d_label, n_labels, w->d_counters + 2, w->stream));
+    CS_HIP(hipEventRecord(w->ev[1], w->stream));
+    CS_HIP(hipMemcpyAsync(w->h_counters + 2, w->d_counters + 2, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, w->stream));
+    std::vector<uint32_t> staged((size_t)n_labels);
+    CS_HIP(hipMemcpyAsync(staged.data(), w->d_label, staged.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, w->stream));
+    CS_HIP(hipStreamSynchronize(w->stream));
+    CS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
+    info.label_ms = ms;
+    if (rescore_timed) {
+        CS_HIP(hipEventElapsedTime(&ms, sc.ev[0], sc.ev[1]));
+        info.join_ms += ms;
+    }
+    std::copy(staged.begin(), staged.end(), out_label);
+    if (out_clusters) *out_clusters = w->h_counters[2];
+    if (out_members) *out_members = w->h_counters[3];
+    last_clusters_info = info;
+    return CS_OK;
+}
+
 // cs_index_similar_pairs_scoped: similar_pairs over the row lists of two scopes (the same handle twice: inside one).  Every
 // check comes before a list is refreshed; the lists are refreshed one after the other (no two scope mutexes are held
 // together), then each side's rows are packed into an f16 buffer of the call's own (scan_pairs_scoped.hip) — the index's
@@ -1897,6 +2122,7 @@ void cs_index_destroy(cs_index* h) {
     for (auto* w : h->pool) { w->release_all(); delete w; }
     for (auto& kv : h->by_stream) { kv.second->release_all(); delete kv.second; }
     for (auto* w : h->pairs_pool) { w->release_all(); delete w; }
+    for (auto* w : h->clusters_pool) { w->release_all(); delete w; }
     for (auto& t : h->pending) {
         (void)hipEventDestroy(t.e0); (void)hipEventDestroy(t.e1); (void)hipEventDestroy(t.e2);
     }
@@ -2209,6 +2435,23 @@ int32_t cs_index_similar_pairs(cs_index* h, float min_cos, int32_t mode, uint32_
 int32_t cs_index_similar_pairs_scoped(cs_index* h, cs_scope* scope_a, cs_scope* scope_b, float min_cos, int32_t mode,
                                       uint32_t max_pairs, uint32_t* out_a, uint32_t* out_b, float* out_cos, uint64_t* out_total) {
     return similar_pairs_scoped(h, scope_a, scope_b, min_cos, mode, max_pairs, out_a, out_b, out_cos, out_total);
+}
+
+int32_t cs_index_similar_clusters(cs_index* h, float min_cos, int32_t mode, uint32_t* out_label, uint64_t n_labels,
+                                  uint64_t* out_clusters, uint64_t* out_members) {
+    return similar_clusters(h, min_cos, mode, out_label, n_labels, out_clusters, out_members);
+}
+
+int32_t cs_index_similar_clusters_info(uint64_t* tile_pairs_scored, uint64_t* tile_pairs_skipped, uint64_t* rescored_pairs,
+                                       uint32_t* launches, double* join_ms, double* label_ms) {
+    const ClustersInfo& i = last_clusters_info;
+    if (tile_pairs_scored) *tile_pairs_scored = i.scored;
+    if (tile_pairs_skipped) *tile_pairs_skipped = i.skipped;
+    if (rescored_pairs) *rescored_pairs = i.rescored;
+    if (launches) *launches = i.launches;
+    if (join_ms) *join_ms = i.join_ms;
+    if (label_ms) *label_ms = i.label_ms;
+    return CS_OK;
 }
 
 int32_t cs_index_similar_pairs_scoped_info(double* pack_ms, uint64_t* rows_a, uint64_t* rows_b, uint64_t* tile_pairs) {

@@ -267,6 +267,31 @@ int32_t launch_pairs_scoped_filter(const PairsScopedPlan& plan, const _Float16* 
                                    uint64_t band_count, RowIds ids, const GroupView& gv, bool other_group, float min_cos,
                                    float margin, uint64_t* d_cand, uint64_t* d_cnt, hipStream_t stream);
 
+// ---- similar-clusters search (scan_clusters.hip, plan: clusters_plan.hpp) ----------------------------------
+// d_parent[r] = r and d_mark[r] = 0 for the stored rows: every row its own component.
+int32_t launch_clusters_init(uint32_t* d_parent, uint32_t* d_mark, uint64_t n_rows, hipStream_t stream);
+// d_tile_root[t] = the common root of the live rows of tile t (128 rows), kClustersNoRoot when they have none,
+// kClustersEmptyTile when no row of the tile is live.
+int32_t launch_clusters_tile_roots(uint32_t* d_parent, uint64_t tiles, uint64_t n_rows, const uint32_t* d_dead,
+                                   uint32_t* d_tile_root, hipStream_t stream);
+// launch_pairs_filter's join over the tile pairs [first, first + count), into the union-find d_parent: a tile pair whose
+// tiles share a root in d_tile_root (or with an empty tile) is skipped and counted in d_counters[1]; a pair of stored, live,
+// non-excluded rows with a product above min_cos + margin (finite, both norms of ordinary size; d_norms null: never) is
+// united at once; one not <= min_cos - margin otherwise is appended to d_amb[0, amb_cap) and counted in d_counters[0], which
+// keeps counting past amb_cap (the launch is then void: blocks that have not started score nothing).
+int32_t launch_clusters_join(const _Float16* d_split, uint32_t dim, uint64_t tiles, uint64_t first, uint64_t count,
+                             uint64_t n_rows, const uint32_t* d_dead, RowIds ids, const GroupView& gv, bool other_group,
+                             float min_cos, float margin, const float* d_norms, uint32_t* d_parent,
+                             const uint32_t* d_tile_root, uint64_t* d_amb, uint64_t* d_counters, uint32_t amb_cap,
+                             hipStream_t stream);
+// Every pair d_amb[0, n) re-scored as launch_pairs_rescore does and united when its cosine is finite and > min_cos.
+int32_t launch_clusters_rescore(const float* d_corpus, uint32_t dim, const uint64_t* d_amb, uint32_t n, RowIds ids, float min_cos,
+                                uint32_t* d_parent, uint32_t blocks, hipStream_t stream);
+// d_label[id - ids.base] = the id of the root of the id's row, for every live row (other slots are left alone: the caller
+// fills them); d_parent is flattened; d_totals[0] += components of two or more rows, d_totals[1] += rows in them.
+int32_t launch_clusters_label(uint32_t* d_parent, uint32_t* d_mark, uint64_t n_rows, const uint32_t* d_dead, RowIds ids,
+                              uint32_t* d_label, uint64_t n_labels, uint64_t* d_totals, hipStream_t stream);
+
 // corpus[(first_out_row + r) * dim + c] = cs_synth_value(seed, (first_row + r) * dim + c)
 int32_t launch_synth_fill(float* d_rows, uint64_t n, uint32_t dim, uint64_t seed,
                           uint64_t first_row, hipStream_t stream);

@@ -91,7 +91,7 @@ class VectorStore {
     // VectorStore::new(db_path, dimensions) — store.rs:110-176 (db_path unused: nothing persists)
     VectorStore(const std::string& /*db_path*/, size_t dimensions, int device = 0, uint64_t capacity = 0,
                 uint32_t id_base = 0)
-        : dimensions_(dimensions) {
+        : dimensions_(dimensions), id_base_(id_base) {
         check(cs_index_create((uint32_t)dimensions, capacity, device, id_base, &h_));
     }
     // The same store row-sharded over several GPUs of the node inside this process (cs_shards_*):
@@ -269,6 +269,31 @@ class VectorStore {
         if (total) *total = n;
         std::vector<SimilarPair> out((size_t)(n < max_pairs ? n : max_pairs));
         for (size_t i = 0; i < out.size(); ++i) out[i] = SimilarPair{a[i], b[i], cos[i]};
+        return out;
+    }
+    // The duplicate-code report by clone class (cs_index_similar_clusters): the connected components of the graph whose
+    // edges are the pairs similar_pairs(min_cos, other_files) would return — however many those are: there is no max_pairs
+    // and no refusal.  Classes of at least min_size chunks, the largest first, then by label (the smallest id of the
+    // class); members by id.  A member's distance and score are a chunk's against itself: a class carries no cosine.
+    // Chunks without metadata are skipped; a class is sized by what remains.  *clusters / *members (optional): the classes
+    // of two or more ids and the ids in them, as the device counted them.
+    std::vector<std::vector<SearchResult>> similar_clusters(float min_cos, bool other_files = true, size_t min_size = 2,
+                                                            uint64_t* clusters = nullptr, uint64_t* members = nullptr) const {
+        if (sh_) throw Error(CS_ERR_UNSUPPORTED, "a sharded store has no similar-clusters search: no cs_shards_ form yet");
+        std::vector<uint32_t> label((size_t)(cs_index_next_id(h_) - id_base_), (uint32_t)CS_NO_ID);
+        check(cs_index_similar_clusters(h_, min_cos, other_files ? CS_PAIRS_OTHER_GROUP : CS_PAIRS_ALL, label.data(),
+                                        label.size(), clusters, members));
+        std::map<uint32_t, std::vector<uint32_t>> by_label;  // ascending labels, members ascending
+        for (size_t i = 0; i < label.size(); ++i)
+            if (label[i] != CS_NO_ID) by_label[label[i]].push_back(id_base_ + (uint32_t)i);
+        std::vector<std::vector<SearchResult>> out;
+        for (const auto& kv : by_label) {
+            std::vector<SearchResult> rs = results(std::vector<float>(kv.second.size(), 1.0f), kv.second, (uint32_t)kv.second.size());
+            if (rs.size() >= (min_size ? min_size : 1)) out.push_back(std::move(rs));
+        }
+        std::stable_sort(out.begin(), out.end(), [](const std::vector<SearchResult>& x, const std::vector<SearchResult>& y) {
+            return x.size() > y.size();
+        });
         return out;
     }
     // all query variants in one call (src/search/mod.rs:508-511)
@@ -573,6 +598,7 @@ class VectorStore {
     cs_index* h_ = nullptr;
     cs_shards* sh_ = nullptr;
     size_t dimensions_;
+    uint32_t id_base_ = 0;
     std::map<uint32_t, ChunkMetadata> meta_;
 };
 

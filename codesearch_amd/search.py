@@ -179,6 +179,36 @@ def pairs_between(cos, a, b, in_a, in_b):
     return cos[keep], a[keep], b[keep], int(keep.sum())
 
 
+def clusters_of_pairs(live_ids, a, b):
+    """The contract of the similar-clusters search (cs_index_similar_clusters) on the host, as a reduction of a pair list:
+    `live_ids` are the vertices, (a[i], b[i]) the edges — the pairs of cs_index_similar_pairs with the same bound and mode,
+    neither refused nor cut.  Union by smallest id: the label of an id is the smallest id of its connected component, an id
+    without an edge is its own label.  An edge that names an id not in live_ids is a ValueError (the pairs call never
+    returns one); a repeated edge, or (a, b) given as (b, a), changes nothing.
+    -> (labels, clusters, members): {id: label} over live_ids, the components of two or more ids, the ids in them."""
+    parent = {int(i): int(i) for i in live_ids}
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    for x, y in zip(a, b):
+        x, y = int(x), int(y)
+        if x not in parent or y not in parent:
+            raise ValueError(f"pair ({x}, {y}) names an id that is not live")
+        rx, ry = find(x), find(y)
+        if rx != ry:
+            parent[max(rx, ry)] = min(rx, ry)  # the smaller root stays a root: a root is its component's smallest id
+    labels = {i: find(i) for i in parent}
+    sizes = {}
+    for root in labels.values():
+        sizes[root] = sizes.get(root, 0) + 1
+    big = [n for n in sizes.values() if n >= 2]
+    return labels, len(big), sum(big)
+
+
 def merge_variants_capped(lists, group_of, k: int, m: int):
     """The contract of the grouped variants search (cs_index_search_variants_grouped[_scoped]) on the host.  `lists`: per
     query variant a (cos, ids) pair over the rows in play — the variant's full order, or any list that holds every row

@@ -1007,6 +1007,54 @@ class VectorStore:
         ra, rb = self._results(cos, a, len(a), keep_missing=True), self._results(cos, b, len(b), keep_missing=True)
         return [(x, y, y.score) for x, y in zip(ra, rb) if x is not None and y is not None]
 
+    def similar_clusters_raw(self, min_cos: float, other_files: bool = False):
+        """cs_index_similar_clusters: the clone classes of the store — the connected components of the graph whose edges are
+        the pairs similar_pairs_raw(min_cos, other_files) would count (-inf / None: no bound).
+        -> (labels [next_id - id_base] u32, clusters, members): labels[i] = the smallest id of the class of id id_base + i
+        (its own id when it has no clone), CS_NO_ID (0xFFFFFFFF) for an id that is not live; the classes of two or more
+        ids; the ids in them.  There is no max_pairs: a store full of duplicates is answered, not refused."""
+        if self.sharded:
+            raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no similar-clusters search: no cs_shards_ form yet")
+        n = self.next_id() - self.id_base
+        labels = np.full(max(n, 0), _lib.CS_NO_ID, np.uint32)
+        clusters, members = C.c_uint64(0), C.c_uint64(0)
+        bound = np.float32(-np.inf) if min_cos is None else np.float32(min_cos)
+        _lib.check(self._lib.cs_index_similar_clusters(
+            self._h, float(bound), _lib.CS_PAIRS_OTHER_GROUP if other_files else _lib.CS_PAIRS_ALL,
+            labels.ctypes.data_as(u32p), n, C.byref(clusters), C.byref(members)))
+        return labels, int(clusters.value), int(members.value)
+
+    def similar_clusters_info(self) -> dict:
+        """cs_index_similar_clusters_info: what this thread's last similar_clusters_raw did — the join's tile pairs scored
+        and skipped (both tiles already one class), the pairs re-scored exactly, the join's launches, and the device time
+        (ms) of the launches and of the labelling."""
+        scored, skipped, rescored, launches = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        j, lab = C.c_double(0), C.c_double(0)
+        _lib.check(self._lib.cs_index_similar_clusters_info(C.byref(scored), C.byref(skipped), C.byref(rescored),
+                                                            C.byref(launches), C.byref(j), C.byref(lab)))
+        return {"tile_pairs_scored": int(scored.value), "tile_pairs_skipped": int(skipped.value),
+                "rescored_pairs": int(rescored.value), "launches": int(launches.value), "join_ms": j.value,
+                "label_ms": lab.value}
+
+    def similar_clusters(self, min_score: float, other_files: bool = True, min_size: int = 2) -> List[List[SearchResult]]:
+        """The duplicate-code report by clone class: the classes of chunks connected by pairs whose score — the reference's
+        scale, cos_to_score — is above min_score; other_files=True (the default): a pair of chunks of one file connects
+        nothing (the files assigned at insert).  Classes of at least min_size chunks, the largest first, then by label (the
+        smallest id); members by id.  A result's distance and score are those of a chunk against itself: a class carries
+        no cosine.  Chunks whose metadata is missing are skipped, as in search(); a class is sized by what remains."""
+        labels, _clusters, _members = self.similar_clusters_raw(score_to_cos(min_score), other_files=other_files)
+        live = np.flatnonzero(labels != _lib.CS_NO_ID)
+        classes = {}
+        for i in live.tolist():
+            classes.setdefault(int(labels[i]), []).append(int(self.id_base) + i)
+        out = []
+        for label, ids in classes.items():
+            res = self._results(np.ones(len(ids), np.float32), ids, len(ids))
+            if len(res) >= max(int(min_size), 1):
+                out.append((label, res))
+        out.sort(key=lambda t: (-len(t[1]), t[0]))
+        return [res for _, res in out]
+
     def chunk_ids_under(self, filter_path: str, project_root: str = "", mcp: bool = True) -> List[int]:
         """Ids of the chunks whose metadata path passes the reference's filter_path rule (search.path_matches; MCP or
         CLI form), ascending: the chunk_ids of a masked search narrowed to a directory."""

@@ -540,6 +540,45 @@ CS_API int32_t cs_index_similar_pairs_scoped(cs_index* h, cs_scope* scope_a, cs_
  * (the smaller scope first; one scope: equal) and the tile pairs scored.  After an unscoped call or none: zeros. */
 CS_API int32_t cs_index_similar_pairs_scoped_info(double* pack_ms, uint64_t* rows_a, uint64_t* rows_b, uint64_t* tile_pairs);
 
+/* Similar-clusters search — "which chunks are clones of each other", as CLONE CLASSES: the connected components of the
+ * graph whose edges are the pairs cs_index_similar_pairs would count.  The answer is one label per chunk id: its size is
+ * known before the call and does not grow with the number of pairs, so a store full of duplicates — where the pair list
+ * is refused — is answered like any other.
+ * THE RULE: the vertices are the live chunk ids.  {a, b} with a < b is an edge exactly when cs_index_similar_pairs with the
+ * same min_cos and mode would count the pair: its cosine — the similar search's bits with the lower id's stored row as the
+ * query — is strictly above min_cos and finite, and in CS_PAIRS_OTHER_GROUP the two chunks do not share a group other than
+ * CS_NO_GROUP.  out_label[i] belongs to id id_base + i: for a live id, the SMALLEST chunk id of its connected component (a
+ * chunk with no edge is its own label); for an id that is not live (deleted, or reclaimed by a build), CS_NO_ID.
+ * n_labels must equal cs_index_next_id(h) - id_base.  *out_clusters = the components with at least two members,
+ * *out_members = the ids in them (each optional).
+ *   - The answer is a function of the store alone: it does not depend on how the device's atomics landed, and repeated
+ *     calls return identical bytes.
+ *   - NEVER REFUSED FOR ABUNDANCE: there is no max_pairs and no candidate bound.  Device memory is O(stored rows) (a
+ *     union-find over the rows, the labels) plus one buffer of fixed size (8 MiB) for the pairs within the f16 filter's
+ *     margin of the bound, which are re-scored exactly; whatever the number of pairs.
+ *   - Fewer than two live rows: CS_OK, every live id its own label, no launch.
+ *   - The index is left as it was (filter copies, routes, the bits of every search); where the int8 copy serves, the
+ *     call converts the rows into an f16 buffer of its own and frees it, as cs_index_similar_pairs does.  Concurrent calls
+ *     are safe, also beside searches.
+ * Errors, in this order, each decided before anything is launched or written: those of cs_index_search for the handle and
+ * the built state, with their texts; a null out_label; mode outside the two values; a NaN min_cos; n_labels other than
+ * cs_index_next_id(h) - id_base (CS_ERR_BAD_ARG, the text names the number wanted); a dim other than 384 / 768 / 1024
+ * (CS_ERR_UNSUPPORTED, the text names the three); no f16 filter copy — CS_INDEX_SPLIT=0 (CS_ERR_UNSUPPORTED) or no room for
+ * it (CS_ERR_OOM), the text says which.  A failing call writes nothing.  No scoped, cs_shards_ or device-pointer form yet. */
+#define CS_NO_ID 0xFFFFFFFFu             /* the label of an id that is not live */
+CS_API int32_t cs_index_similar_clusters(cs_index* h, float min_cos, int32_t mode,
+                                         uint32_t* out_label, uint64_t n_labels,
+                                         uint64_t* out_clusters, uint64_t* out_members);
+/* DIAGNOSTIC, for benchmarks — not part of the search contract, an embedder needs no binding for it (INTEGRATION.md has
+ * none, as for cs_index_similar_pairs_info).  What the calling thread's last successful cs_index_similar_clusters did (each
+ * output optional): the tile pairs of the join it scored and those it skipped because both tiles were already one
+ * component (or one held no live row), the pairs it re-scored exactly, the join's launches (those repeated in halves
+ * because their near-bound pairs outgrew the buffer included), and the device time (HIP events, milliseconds) of the
+ * launches — tile roots, join, re-score — and of the labelling.  Before any such call: zeros. */
+CS_API int32_t cs_index_similar_clusters_info(uint64_t* tile_pairs_scored, uint64_t* tile_pairs_skipped,
+                                              uint64_t* rescored_pairs, uint32_t* launches,
+                                              double* join_ms, double* label_ms);
+
 /* Synchronises `stream` and reports in *overflowed whether any cs_index_search_device call of more
  * than 16 queries issued by this thread on it since the previous status call overflowed a candidate buffer
  * (its results are then incomplete); clears the condition. */
