@@ -20,6 +20,14 @@ The second half is the walk generator: `make_walk(seed, dim, sharded)` returns a
 operations that drives a store through every state the index keeps books for, `resolve` turns an operation into concrete
 arguments for the state the model is in, `apply` performs it on the model, and `walk_coverage` reports — from the model
 alone — which states a walk reaches, so a test can refuse a walk that quietly stopped exercising one.
+
+The kinds that start from stored rows (similar chunks, similar pairs, similar clusters) and the boosted search have judges
+of their own on the same float64 cosines and the same band: `check_similar` (which hands the eligible rows to `check`),
+`check_pairs`, `check_clusters` and `check_boosted`, whose second tolerance — the cosine's band carried through the score
+plus the three f32 roundings of the score — is derived too.  A bound that float64 cannot place (a cosine within tol of it) is
+refused, not judged: the inputs keep that from happening, never the judge.  `make_walk(..., extended=True)` is the same
+walk with a class table beside every group table and near-copies planted around BOUND (`clone_layout`), `Planted` follows
+their ids, `extended_coverage` reports what the checked states of such a walk hold.
 """
 from __future__ import annotations
 
@@ -29,6 +37,8 @@ from codesearch_amd.synth import synth_rows
 
 NO_GROUP = 0xFFFFFFFF  # CS_NO_GROUP
 NO_ID = 0xFFFFFFFF     # the id of an empty result slot
+NO_CLASS = 0xFFFF      # CS_NO_CLASS
+BOUND = np.float32(0.9)  # the cosine bound of the walks' pairs and clusters calls: the planted clones straddle it
 EDGES = (128, 1024, 1025, 1152, 2048)  # stored-row counts at which the index changes what it does
 NOT_BUILT = "Index not built"
 # the walks the GPU test runs and the CPU test vouches for: (seed, dim, sharded)
@@ -53,6 +63,7 @@ class StoreModel:
         self.removed = set()     # ids deleted since the last clear()
         self.reclaimed = set()   # ... whose rows a build has dropped
         self.groups = {}         # id -> group, for ids that carry one (every other id: NO_GROUP)
+        self.classes = {}        # id -> class, for ids that carry one (every other id: NO_CLASS)
         self.built = False
         self.stored = [[] for _ in range(self.shards)]  # ids in storage order, per shard
         self.compacted = [False] * self.shards
@@ -141,10 +152,25 @@ class StoreModel:
     def groups_assigned(self) -> int:
         return len(self.groups)
 
+    def set_classes(self, ids, classes):
+        ids, classes = [int(i) for i in ids], [int(c) for c in classes]
+        for i in ids:
+            if not self.id_base <= i < self.next_id:
+                raise ValueError(f"id {i} was never issued")
+        for i, c in zip(ids, classes):
+            if c == NO_CLASS:
+                self.classes.pop(i, None)
+            else:
+                self.classes[i] = c
+        self._touch()
+
+    def classes_assigned(self) -> int:
+        return len(self.classes)
+
     def reopen(self):
         """Close and open again from disk: the state of the last build, minus what was deleted since (a delete is
-        committed at once); rows appended since are lost; groups are not stored (they follow from chunk metadata, which
-        the walks do not use).  The loader re-adds every persisted row, removes the removed ids and builds."""
+        committed at once); rows appended since are lost; groups and classes are not stored (they follow from chunk
+        metadata, which the walks do not use).  The loader re-adds every persisted row, removes the removed ids and builds."""
         keep_next, removed, rows = self.persisted_next, self.removed, self.rows
         self._reset()
         if keep_next is None:
@@ -224,7 +250,9 @@ class StoreModel:
 
     def _eligible(self, allowed) -> np.ndarray:
         ids = self.live_ids()
-        return np.ones(len(ids), bool) if allowed is None else np.isin(ids, np.asarray(list(allowed), np.int64))
+        if allowed is None:
+            return np.ones(len(ids), bool)
+        return np.isin(ids, allowed if isinstance(allowed, np.ndarray) else np.asarray(list(allowed), np.int64))
 
     # ---- the model's own answer --------------------------------------------------------------------------
     def topk(self, q, k, allowed=None, per_file=None):
@@ -333,6 +361,341 @@ class StoreModel:
                     need(full, f"duplicate id {x} is returned while the identical row of lower id {y} is left out")
         return float(err.max())
 
+    # ---- the kinds that start from stored rows: similar, pairs, clusters; and the boosted search ----------
+    def _why_not_live(self, i: int) -> str:
+        return "was deleted and reclaimed" if i in self.reclaimed else "is deleted" if i in self.removed else "was never issued"
+
+    def _gram(self) -> np.ndarray:
+        """float64 cosine of every live row with every live row (order of live_ids()); 0.0 where a row has no magnitude."""
+        if "gram" not in self._cache:
+            m, norms = self._matrix()
+            unit = m / np.where(norms > 0, norms, 1.0)[:, None]
+            self._cache["gram"] = unit @ unit.T
+        return self._cache["gram"]
+
+    def ambiguous_pairs(self, bound) -> int:
+        """How many live pairs a < b have their float64 cosine within tol of `bound`: a judge of pairs or clusters refuses
+        to judge a state where there is one (bound None: no pair is near -inf)."""
+        if bound is None or len(self.live_ids()) < 2:
+            return 0
+        key = ("near", float(np.float32(bound)))
+        if key not in self._cache:
+            self._cache[key] = int(np.triu(np.abs(self._gram() - key[1]) <= self.tol, 1).sum())
+        return self._cache[key]
+
+    def _pair_list(self, bound, other_files, inside=None, other=None):
+        """The model's pairs -> (a, b, c64): a < b both live, float64 cosine above bound (None: every pair), not in one
+        assigned group when other_files; inside: both ends in it; inside and other: one end in each, every pair once."""
+        ids = self.live_ids()
+        if len(ids) < 2:
+            return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0)
+        g = self._gram()
+        key = ("above", None if bound is None else float(np.float32(bound)))
+        if key not in self._cache:  # positions (in live_ids()) of the pairs above the bound, before the group and scope rules
+            above = np.ones(g.shape, bool) if bound is None else g > key[1]
+            self._cache[key] = np.nonzero(np.triu(above, 1))
+        ia, ib = self._cache[key]
+        keep = np.ones(len(ia), bool)
+        if other_files:
+            grp = self._live_groups()
+            keep &= ~((grp[ia] == grp[ib]) & (grp[ia] != NO_GROUP))
+        if inside is not None:
+            in_a = self._eligible(inside)
+            in_b = in_a if other is None else self._eligible(other)
+            keep &= (in_a[ia] & in_b[ib]) | (in_b[ia] & in_a[ib])
+        elif other is not None:
+            raise ValueError("other needs inside")
+        ia, ib = ia[keep], ib[keep]
+        return ids[ia], ids[ib], g[ia, ib]
+
+    def _need_decidable(self, bound, what):
+        n = self.ambiguous_pairs(bound)
+        if n:
+            raise AssertionError(f"{what}: refused, {n} live pair(s) lie within tol {self.tol:.2e} of the bound {bound!r}: "
+                                 f"float64 cannot decide them; change the inputs")
+
+    def pairs(self, bound, other_files, inside=None, other=None, max_pairs=65536):
+        """The model's own answer to similar_pairs_raw -> (cos f32, a u32, b u32, total)."""
+        if not self.built:
+            raise AssertionError(NOT_BUILT)
+        a, b, c = self._pair_list(bound, other_files, inside, other)
+        c32 = c.astype(np.float32)
+        order = np.lexsort((b, a, -c32))[:max_pairs]
+        return c32[order], a[order].astype(np.uint32), b[order].astype(np.uint32), len(a)
+
+    def check_pairs(self, bound, other_files, got, inside=None, other=None, max_pairs=65536) -> float:
+        """Judges got = (cos, a, b, total) of similar_pairs_raw(bound, other_files, max_pairs, scope=inside, other=other)
+        against the model's pairs; -> the largest |returned cos - float64 cos|."""
+        if not self.built:
+            raise AssertionError(NOT_BUILT)
+        tol = self.tol
+        cos = np.asarray(got[0], np.float32).ravel()
+        ra, rb = np.asarray(got[1]).ravel().astype(np.int64), np.asarray(got[2]).ravel().astype(np.int64)
+        total = int(got[3])
+
+        def need(ok, msg):
+            if not ok:
+                raise AssertionError(f"{msg} (bound={bound!r}, other_files={other_files}, scoped={inside is not None}, "
+                                     f"between={other is not None}, max_pairs={max_pairs}, total={total}, returned={len(ra)})")
+
+        self._need_decidable(bound, "check_pairs")
+        ma, mb, mc = self._pair_list(bound, other_files, inside, other)
+        truth = {(int(x), int(y)): float(c) for x, y, c in zip(ma, mb, mc)}
+        need(len(ra) == len(rb) == len(cos), "cos, a and b differ in length")
+        ids = self.live_ids()
+        pos = {int(i): n for n, i in enumerate(ids)}
+        grp = self._live_groups()
+        in_a = self._eligible(inside) if inside is not None else None
+        in_b = in_a if other is None else self._eligible(other)
+        seen = set()
+        err = 0.0
+        g = self._gram()
+        for c, x, y in zip(cos.tolist(), ra.tolist(), rb.tolist()):
+            need(x < y, f"pair ({x}, {y}) is not given as a < b")
+            need((x, y) not in seen, f"pair ({x}, {y}) is returned twice")
+            seen.add((x, y))
+            for i in (x, y):
+                need(i in pos, f"pair ({x}, {y}): id {i} {self._why_not_live(i)}")
+            px, py = pos[x], pos[y]
+            if other_files:
+                need(not (grp[px] == grp[py] != NO_GROUP), f"pair ({x}, {y}) lies inside group {int(grp[px])}")
+            if in_a is not None:
+                need((in_a[px] and in_b[py]) or (in_b[px] and in_a[py]), f"pair ({x}, {y}) is outside the scope(s)")
+            c64 = float(g[px, py])
+            need(np.isfinite(c) and abs(c - c64) <= tol, f"cos of pair ({x}, {y}) is {c!r}, float64 says {c64!r} (tol {tol:.2e})")
+            err = max(err, abs(c - c64))
+            need((x, y) in truth, f"pair ({x}, {y}) is returned, but its float64 cos {c64!r} is not above the bound")
+        need(total == len(truth), f"total {total}, the model counts {len(truth)} pairs")
+        need(len(ra) == min(total, max_pairs), f"{len(ra)} pairs returned, expected min(total, max_pairs)")
+        if not len(ra):
+            return 0.0
+        bad = ~((cos[:-1] > cos[1:]) | ((cos[:-1] == cos[1:]) & ((ra[:-1] < ra[1:]) | ((ra[:-1] == ra[1:]) & (rb[:-1] < rb[1:])))))
+        need(not bad.any(), f"not sorted by (cos desc, a, b) at position {int(bad.argmax()) if bad.any() else -1}")
+        missing = [(c, p) for p, c in truth.items() if p not in seen]
+        if total <= max_pairs:
+            need(not missing, f"pair {max(missing)[1] if missing else None} (float64 cos {max(missing)[0] if missing else 0!r}) is left out")
+        elif missing:
+            c, p = max(missing)
+            need(c <= float(cos[-1]) + tol, f"the cut list leaves out pair {p} (float64 cos {c!r}); the last returned cos is {cos[-1]!r}")
+        return err
+
+    def _components(self, bound, other_files) -> dict:
+        """{live id: smallest id of its component} in the graph of the model's pairs: a plain union-find."""
+        parent = {int(i): int(i) for i in self.live_ids()}
+
+        def find(x):
+            while parent[x] != x:
+                parent[x] = parent[parent[x]]
+                x = parent[x]
+            return x
+
+        a, b, _ = self._pair_list(bound, other_files)
+        for x, y in zip(a.tolist(), b.tolist()):
+            rx, ry = find(x), find(y)
+            if rx != ry:
+                parent[max(rx, ry)] = min(rx, ry)
+        return {i: find(i) for i in parent}
+
+    def clusters(self, bound, other_files):
+        """The model's own answer to similar_clusters_raw -> (labels [next_id - id_base] u32, clusters, members)."""
+        if not self.built:
+            raise AssertionError(NOT_BUILT)
+        comp = self._components(bound, other_files)
+        labels = np.full(self.next_id - self.id_base, NO_ID, np.uint32)
+        sizes = {}
+        for i, root in comp.items():
+            labels[i - self.id_base] = root
+            sizes[root] = sizes.get(root, 0) + 1
+        big = [n for n in sizes.values() if n >= 2]
+        return labels, len(big), sum(big)
+
+    def check_clusters(self, bound, other_files, labels, clusters, members) -> float:
+        """Judges similar_clusters_raw(bound, other_files): with no ambiguous pair the answer is unique, so all three are
+        compared for equality.  -> 0.0 (a label carries no cosine)."""
+        if not self.built:
+            raise AssertionError(NOT_BUILT)
+        labels = np.asarray(labels).ravel().astype(np.int64)
+
+        def need(ok, msg):
+            if not ok:
+                raise AssertionError(f"{msg} (bound={bound!r}, other_files={other_files}, clusters={clusters}, members={members})")
+
+        self._need_decidable(bound, "check_clusters")
+        want, n_clusters, n_members = self.clusters(bound, other_files)
+        need(len(labels) == len(want), f"{len(labels)} labels, expected next_id - id_base = {len(want)}")
+        for n in np.flatnonzero(labels != want.astype(np.int64)).tolist():
+            i, got, exp = self.id_base + n, int(labels[n]), int(want[n])
+            if exp == NO_ID:
+                need(False, f"id {i} {self._why_not_live(i)} and carries label {got}, not NO_ID")
+            need(got != NO_ID, f"live id {i} carries NO_ID, the smallest id of its component is {exp}")
+            need(False, f"id {i} carries label {got}, the smallest id of its component is {exp}")
+        need(int(clusters) == n_clusters, f"clusters {clusters}, the model counts {n_clusters} components of two or more ids")
+        need(int(members) == n_members, f"members {members}, the model counts {n_members} ids in those components")
+        return 0.0
+
+    def _similar_eligible(self, src, mode, min_cos, allowed):
+        """-> (query row, eligible ids) of a similar-chunk search from `src`; refuses a bound float64 cannot place."""
+        if mode not in ("none", "self", "file"):
+            raise ValueError(mode)
+        src = int(src)
+        if not self.is_live(src):
+            raise AssertionError(f"source id {src} {self._why_not_live(src)}: the store refuses it")
+        q = self.rows[src]
+        ids, c64, elig, grp = self.live_ids(), self.cosines(q), self._eligible(allowed).copy(), self._live_groups()
+        if mode != "none":
+            elig &= ids != src
+        g = self.groups.get(src, NO_GROUP)
+        if mode == "file" and g != NO_GROUP:
+            elig &= grp != g
+        if min_cos is not None and np.isfinite(min_cos):
+            b = float(np.float32(min_cos))
+            near = elig & (np.abs(c64 - b) <= self.tol)
+            if near.any():
+                raise AssertionError(f"check_similar: refused, id {int(ids[near][0])} lies within tol {self.tol:.2e} of min_cos "
+                                     f"{b!r}: float64 cannot decide it; pick another bound (pick_min_cos)")
+            elig &= c64 > b
+        return q, ids[elig]
+
+    def similar_topk(self, src, k, mode, min_cos=None, allowed=None):
+        """The model's own answer to similar_raw([src], k, exclude=mode, min_cos, scope) -> (cos, ids, count)."""
+        if not self.built:
+            raise AssertionError(NOT_BUILT)
+        q, elig = self._similar_eligible(src, mode, min_cos, allowed)
+        return self.topk(q, k, allowed=elig)
+
+    def check_similar(self, src, k, got, mode, min_cos=None, allowed=None) -> float:
+        """Judges got = (cos, ids, count) of similar_raw([src], k, exclude=mode, min_cos=, scope=allowed): the query is the
+        stored row of src, the eligible rows are the live ones minus what mode excludes, minus those not above min_cos,
+        inside `allowed`; then `check` over that set, rules (a) to (f)."""
+        if not self.built:
+            raise AssertionError(NOT_BUILT)
+        src = int(src)
+        q, elig = self._similar_eligible(src, mode, min_cos, allowed)
+        count = int(got[2])
+        rid = np.asarray(got[1]).ravel().astype(np.int64)[:max(count, 0)]
+        ids, c64 = self.live_ids(), self.cosines(q)
+        g = self.groups.get(src, NO_GROUP)
+        try:
+            for i in rid.tolist():
+                if mode != "none" and i == src:
+                    raise AssertionError(f"the source id {i} is returned under exclude={mode!r}")
+                if mode == "file" and g != NO_GROUP and self.is_live(i) and self.groups.get(i, NO_GROUP) == g:
+                    raise AssertionError(f"id {i} of the source's group {g} is returned under exclude='file'")
+                if min_cos is not None and self.is_live(i) and not c64[np.searchsorted(ids, i)] > float(np.float32(min_cos)):
+                    raise AssertionError(f"id {i} (float64 cos {c64[np.searchsorted(ids, i)]!r}) is not above min_cos {min_cos!r}")
+            return self.check(q, k, got, allowed=elig)
+        except AssertionError as e:
+            raise AssertionError(f"similar from id {src}, exclude={mode!r}, min_cos={min_cos!r}: {e}") from None
+
+    def pick_min_cos(self, src) -> float:
+        """A bound for a similar-chunk search from `src` that float64 can place: the midpoint (rounded to f32) of the widest
+        gap between adjacent float64 cosines among the source's 30 best live rows; the gap must be wider than 4 * tol."""
+        c = np.sort(self.cosines(self.rows[int(src)]))[::-1][:30]
+        if len(c) < 2:
+            raise AssertionError(f"pick_min_cos: id {src} has fewer than two live rows to cut between")
+        gaps = c[:-1] - c[1:]
+        n = int(gaps.argmax())
+        if not gaps[n] > 4 * self.tol:
+            raise AssertionError(f"pick_min_cos: the widest gap among the 30 best of id {src} is {gaps[n]!r}, not above 4 * tol")
+        return float(np.float32((c[n] + c[n + 1]) / 2))
+
+    def _weights(self, weights) -> np.ndarray:
+        """Per live id: weights[class] as f32; 1 for NO_CLASS, a class past the table, an empty table."""
+        wt = np.zeros(0, np.float32) if weights is None else np.asarray(weights, np.float32).ravel()
+        key = ("w", wt.tobytes())
+        if key not in self._cache:
+            w = np.ones(len(self.live_ids()), np.float32)
+            for n, i in enumerate(self.live_ids().tolist()):
+                c = self.classes.get(i, NO_CLASS)
+                if c != NO_CLASS and c < len(wt):
+                    w[n] = wt[c]
+            self._cache[key] = w
+        return self._cache[key]
+
+    @staticmethod
+    def score_of(cos32, w32):
+        """b = f32(cos_to_score(cos) * w) as the boosted search states it: s = 1 - (1 - cos) * 0.5 in f32, one more rounding."""
+        cos32 = np.asarray(cos32, np.float32)
+        s = np.float32(1.0) - (np.float32(1.0) - cos32) * np.float32(0.5)
+        return (s * np.asarray(w32, np.float32)).astype(np.float32)
+
+    def boosted_topk(self, q, k, weights, allowed=None):
+        """The model's own answer to search_raw(q, k, class_weights=weights) -> (score, cos, ids, count)."""
+        if not self.built:
+            raise AssertionError(NOT_BUILT)
+        ids, c64, elig, w = self.live_ids(), self.cosines(q), self._eligible(allowed), self._weights(weights)
+        c32 = c64.astype(np.float32)
+        b = self.score_of(c32, w)
+        order = [n for n in np.lexsort((ids, -b)) if elig[n]][:k]
+        score, cos, rid = np.zeros(k, np.float32), np.zeros(k, np.float32), np.full(k, NO_ID, np.uint32)
+        score[:len(order)], cos[:len(order)], rid[:len(order)] = b[order], c32[order], ids[order]
+        return score, cos, rid, len(order)
+
+    def check_boosted(self, q, k, got, weights, allowed=None) -> float:
+        """Judges got = (score, cos, ids, count) of a boosted search for q (or variants q [nq, dim], merged) under the
+        class-weight table `weights`; -> the largest |returned cos - float64 cos|."""
+        if not self.built:
+            raise AssertionError(NOT_BUILT)
+        tol = self.tol
+        score = np.asarray(got[0], np.float32).ravel()
+        cos = np.asarray(got[1], np.float32).ravel()
+        rid_all = np.asarray(got[2]).ravel().astype(np.int64)
+        count = int(got[3])
+        ids, c64, elig, w = self.live_ids(), self.cosines(q), self._eligible(allowed), self._weights(weights)
+
+        def need(ok, msg):
+            if not ok:
+                raise AssertionError(f"{msg} (boosted, k={k}, allowed={'all' if allowed is None else len(list(allowed))}, "
+                                     f"weights={np.asarray([] if weights is None else weights).tolist()}, count={count}, "
+                                     f"ids={rid_all[:min(count, 12)].tolist()})")
+
+        need(count == min(k, int(elig.sum())), f"count {count}, expected min(k, {int(elig.sum())})")
+        need(len(cos) >= k and len(rid_all) >= k and len(score) >= k, "the answer is shorter than k")
+        need((rid_all[count:k] == NO_ID).all() and (cos[count:k] == 0.0).all() and (score[count:k] == 0.0).all(),
+             "the tail behind count is not empty slots")
+        rid, rc, rs = rid_all[:count], cos[:count], score[:count]
+        if count == 0:
+            return 0.0
+        need(len(set(rid.tolist())) == count, "an id is returned twice")
+        pos = np.minimum(np.searchsorted(ids, rid), len(ids) - 1) if len(ids) else np.zeros(count, np.int64)
+        live = (ids[pos] == rid) if len(ids) else np.zeros(count, bool)
+        for i in rid[~live].tolist():
+            need(False, f"id {i} {self._why_not_live(i)}")
+        need(elig[pos].all(), f"ids outside the allowed set: {rid[~elig[pos]].tolist()[:5]}")
+        err = np.abs(rc.astype(np.float64) - c64[pos])
+        worst = int(err.argmax())
+        need(err[worst] <= tol, f"cos of id {int(rid[worst])} is {rc[worst]!r}, float64 says {c64[pos][worst]!r} (tol {tol:.2e})")
+        want = self.score_of(rc, w[pos])
+        off = np.flatnonzero(want.view(np.uint32) != rs.view(np.uint32))
+        if len(off):
+            n = int(off[0])
+            need(False, f"score of id {int(rid[n])} is {rs[n]!r}, f32(cos_to_score({rc[n]!r}) * {w[pos][n]!r}) is {want[n]!r}")
+        bad = ~((rs[:-1] > rs[1:]) | ((rs[:-1] == rs[1:]) & (rid[:-1] < rid[1:])))
+        need(not bad.any(), f"not sorted by (score desc, id) at position {int(bad.argmax()) if bad.any() else -1}")
+        returned = np.zeros(len(ids), bool)
+        returned[pos] = True
+        omitted = elig & ~returned
+        if omitted.any():
+            w64 = w.astype(np.float64)
+            s64 = (1.0 + c64) / 2.0 * w64
+            slack = w64 * tol / 2.0 + 3.0 * 2.0 ** -24 * np.maximum(1.0, w64)
+            miss = omitted & ~((s64 <= float(rs[-1]) + slack) if count == k else np.zeros(len(ids), bool))
+            if miss.any():
+                n = int(np.flatnonzero(miss)[s64[miss].argmax()])
+                need(False, f"id {int(ids[n])} (float64 score {s64[n]!r}, weight {w[n]!r}) is left out; the last returned score is {rs[-1]!r}")
+        # byte-identical rows of one class: ascending id, never a higher one in place of an eligible lower one
+        cls, dup_members = self._dup_class(), self._dup_members()
+        for c in (set(cls[pos].tolist()) & set(dup_members) if dup_members else ()):
+            members = dup_members[c]
+            for x, kx in zip(rid.tolist(), [self.classes.get(int(i), NO_CLASS) for i in rid.tolist()]):
+                if cls[np.searchsorted(ids, x)] != c:
+                    continue
+                for n in members:
+                    y = int(ids[n])
+                    if y < x and elig[n] and not returned[n] and self.classes.get(y, NO_CLASS) == kx:
+                        need(False, f"duplicate id {x} is returned while the identical row of lower id {y} (same class) is left out")
+        return float(err.max())
+
 
 # ======================================================================================================
 # The walk
@@ -340,14 +703,82 @@ class StoreModel:
 
 def rows_of(op, dim: int) -> np.ndarray:
     """The rows of an insert operation: n synthetic rows; the last `dups` are exact copies of the first `dups`; with
-    `zero`, row 1 has no magnitude."""
+    `zero`, row 1 has no magnitude; with `clones` (extended walks), some rows are near-copies of others (clone_layout)."""
     rows = synth_rows(op["seed"], op["first"], op["n"], dim)
     d = op.get("dups", 0)
     if d:
         rows[op["n"] - d:] = rows[:d]
     if op.get("zero"):
         rows[1] = 0.0
+    for src, dst, t in clone_layout(op)[0]:
+        plant(rows, src, dst, t)
     return rows
+
+
+# the target cosines of the clones of one planted set: four inside the f16 filter's margin (1e-3) around BOUND, where only
+# the exact refine can place a pair, and outside the judge's band (4.7e-5 at dim 384), so float64 decides them
+LADDER = (0.999, 0.97, float(BOUND) + 5e-4, float(BOUND) + 2e-4, float(BOUND) - 2e-4, float(BOUND) - 5e-4, 0.85)
+CHAIN = 0.93  # b from a and c from b at 0.93: the ends come out near 0.865, so a-b and b-c are edges above BOUND, a-c is not
+
+
+def plant(rows, a: int, b: int, t: float):
+    """rows[b] becomes a near-copy of rows[a] at cosine t, in float64: direction t u + sqrt(1 - t^2) w with u the unit
+    rows[a] and w the unit part of rows[b] orthogonal to it; rows[b] keeps its norm."""
+    u = rows[a].astype(np.float64)
+    u /= np.linalg.norm(u)
+    x = rows[b].astype(np.float64)
+    w = x - (x @ u) * u
+    w /= np.linalg.norm(w)
+    rows[b] = (np.linalg.norm(x) * (t * u + np.sqrt(1.0 - t * t) * w)).astype(np.float32)
+
+
+def clone_layout(op):
+    """Where an insert operation with the key `clones` (a seed) plants near-copies, as row numbers of the insert ->
+    (plants, chains): plants = [(source row, overwritten row, target cosine)] in planting order, chains = [(a, b, c)].
+    One set per 256 rows (at least one), each in a segment of its own, clear of the exact duplicates (the first and last
+    three rows) and the zero row (row 1).  A set: the two closest clones (0.999, 0.97) right behind their sources — two
+    sources five rows apart cannot both end a group of 16 consecutive ids, so at least one pair shares a group; the chain in
+    three adjacent rows; the other five clones of LADDER 17 rows or more from their sources, so in another group."""
+    seed, n = op.get("clones"), op["n"]
+    if not seed:
+        return [], []
+    assert n >= 64
+    sets = max(1, n // 256)
+    seg = (n - 8) // sets
+    plants, chains = [], []
+    for s in range(sets):
+        rng = np.random.default_rng([int(seed), int(op["first"]), s])
+        lo = 4 + s * seg
+        p = lo + int(rng.integers(0, seg - 35 + 1))
+        far = p + 28 + np.sort(rng.choice(lo + seg - (p + 28), 5, replace=False))
+        plants += [(p, p + 1, LADDER[0]), (p + 5, p + 6, LADDER[1])]
+        plants += [(src, int(dst), t) for src, dst, t in zip((p + 2, p + 3, p + 4, p + 7, p + 11), far, LADDER[2:])]
+        plants += [(p + 8, p + 9, CHAIN), (p + 9, p + 10, CHAIN)]
+        chains.append((p + 8, p + 9, p + 10))
+    return plants, chains
+
+
+class Planted:
+    """The ids of what the walk's inserts planted, kept in step with the model: `after(op, ids, model)` follows each
+    operation.  clones = [(source id, clone id, target cosine)] (the chains' two links included), chains = [(a, b, c)]."""
+
+    def __init__(self):
+        self.clones, self.chains = [], []
+
+    def after(self, op, ids, model):
+        kind = op["op"]
+        if kind == "clear":  # the ids start over
+            self.clones, self.chains = [], []
+        elif kind == "reopen":  # ids issued after the last build are issued again, to other rows
+            self.clones = [c for c in self.clones if max(c[:2]) < model.next_id]
+            self.chains = [c for c in self.chains if max(c) < model.next_id]
+        elif kind == "insert" and op.get("clones"):
+            plants, chains = clone_layout(op)
+            self.clones += [(ids[0] + a, ids[0] + b, t) for a, b, t in plants]
+            self.chains += [(ids[0] + a, ids[0] + b, ids[0] + c) for a, b, c in chains]
+
+    def live_clones(self, model):
+        return [c for c in self.clones if model.is_live(c[0]) and model.is_live(c[1])]
 
 
 def resolve(op, model: StoreModel):
@@ -389,6 +820,11 @@ def resolve(op, model: StoreModel):
         lo = model.id_base if op["which"] == "all" else op["from"]
         ids = np.arange(lo, model.next_id)
         return ids, (ids - model.id_base) // 16
+    if kind == "classes":  # class (id - id_base) % 5, every seventh id left without one; the ids of the groups op beside it
+        lo = model.id_base if op["which"] == "all" else op["from"]
+        ids = np.arange(lo, model.next_id)
+        off = ids - model.id_base
+        return ids, np.where(off % 7 == 6, NO_CLASS, off % 5)
     return None
 
 
@@ -407,6 +843,8 @@ def apply(op, args, model: StoreModel):
         return model.reopen()
     if kind == "groups":
         return model.set_groups(*args)
+    if kind == "classes":
+        return model.set_classes(*args)
     if kind == "scope":
         return None
     raise ValueError(kind)
@@ -421,39 +859,47 @@ def new_model(walk) -> StoreModel:
 class _Plan:
     """make_walk's pen: appends operations and keeps a model in step, so sizes can be aimed at."""
 
-    def __init__(self, seed, dim, id_base, shards, stripe):
+    def __init__(self, seed, dim, id_base, shards, stripe, extended=False):
+        self.extended = extended
         self.ops = [{"op": "open", "dim": dim, "id_base": id_base, "shards": shards, "stripe": stripe}]
         self.m = StoreModel(dim, id_base, shards, stripe)
         self.seed, self.n_ops, self.first, self.grouped_to = seed, 0, 0, id_base
 
     def do(self, **op):
-        self.n_ops += 1
+        self.n_ops += op["op"] != "classes"  # (the seeds of the deletes and scopes are those of the plain walk)
         if op["op"] in ("delete", "scope"):
             op.setdefault("seed", self.seed * 1000 + self.n_ops)
         apply(op, resolve(op, self.m), self.m)
         self.ops.append(op)
 
     def insert(self, n, dups=0, zero=False):
-        self.do(op="insert", n=int(n), seed=7000 + self.seed, first=self.first, dups=dups, zero=zero)
+        more = {"clones": 8100 + self.seed} if self.extended and n >= 64 else {}
+        self.do(op="insert", n=int(n), seed=7000 + self.seed, first=self.first, dups=dups, zero=zero, **more)
         self.first += int(n)
 
     def to(self, stored, **kw):
         self.insert(stored - self.m.stored_rows(), **kw)
 
     def groups(self, which):
-        self.do(op="groups", which=which, **({"from": self.grouped_to} if which == "new" else {}))
+        span = {"from": self.grouped_to} if which == "new" else {}
+        self.do(op="groups", which=which, **span)
+        if self.extended:
+            self.do(op="classes", which=which, **span)
         self.grouped_to = self.m.next_id
 
     def build(self):
         self.do(op="build")
 
 
-def make_walk(seed: int, dim: int, sharded: bool):
-    """A deterministic list of about 40 operations (module docstring).  The first entry describes the store to open."""
+def make_walk(seed: int, dim: int, sharded: bool, extended: bool = False):
+    """A deterministic list of about 40 operations (module docstring).  The first entry describes the store to open.
+    extended: the same operations in the same order with the same sizes, and for the kinds that start from stored rows a
+    `classes` operation beside every `groups` operation and planted near-copies (`clones`) in every insert of 64 rows or
+    more."""
     rng = np.random.default_rng([seed, dim, int(sharded)])
     r = lambda lo, hi: int(rng.integers(lo, hi + 1))
     if sharded:
-        p = _Plan(seed, dim, 0, 3, 64)
+        p = _Plan(seed, dim, 0, 3, 64, extended)
         p.insert(r(90, 120))
         p.do(op="scope", name="future", pick="future")
         p.do(op="scope", name="early", pick="half")
@@ -481,7 +927,7 @@ def make_walk(seed: int, dim: int, sharded: bool):
         p.do(op="reopen")
         p.do(op="scope", name="late", pick="half")
     else:
-        p = _Plan(seed, dim, 1000 if seed % 2 else 0, 1, 1 << 32)
+        p = _Plan(seed, dim, 1000 if seed % 2 else 0, 1, 1 << 32, extended)
         p.insert(r(70, 120))
         p.do(op="scope", name="future", pick="future")
         p.do(op="scope", name="early", pick="half")
@@ -668,3 +1114,59 @@ def walk_coverage(walk) -> dict:
         if kind in ("clear",):
             last_checked, appended_only = 0, True
     return cov
+
+
+def extended_coverage(walk) -> dict:
+    """Runs an extended walk on the model alone -> what its checked states hold for the kinds that start from stored rows:
+    full_states (dim 384: states with a pair above BOUND inside one group, one across groups, a component of three whose
+    ends are not an edge, a pair within 1e-3 below BOUND and one within 1e-3 above), chain_cut (states after a chain's
+    middle was deleted while both ends live), classes_before_reclaim, appended_after_classes, checked (all checked states),
+    ambiguous (the most live pairs within tol of BOUND at any checked state; dim 384) and min_cos_failed (checked states
+    where pick_min_cos finds no gap for the first stored live id)."""
+    m = new_model(walk)
+    planted = Planted()
+    out = {"full_states": 0, "chain_cut": 0, "classes_before_reclaim": 0, "appended_after_classes": 0, "checked": 0,
+           "ambiguous": 0, "min_cos_failed": 0}
+    reclaims, classes_at, classes_to = 0, None, None
+    b = float(BOUND)
+    for op in walk[1:]:
+        kind = op["op"]
+        args = resolve(op, m)
+        res = apply(op, args, m)
+        planted.after(op, res if kind == "insert" else None, m)
+        if kind == "classes":
+            classes_at, classes_to = reclaims, m.next_id
+        if kind in ("clear", "reopen"):
+            classes_at = classes_to = None
+        if (kind == "build" and res) or (kind == "reopen" and any(m.compacted)):
+            reclaims += 1
+        if not (kind in ("build", "reopen") and m.built):
+            continue
+        out["checked"] += 1
+        if m.classes and classes_at is not None and reclaims > classes_at:
+            out["classes_before_reclaim"] += 1
+        if m.classes and classes_to is not None and len(m.live_ids()) and int(m.live_ids().max()) >= classes_to:
+            out["appended_after_classes"] += 1
+        if any(m.is_live(a) and m.is_live(c) and not m.is_live(mid) and mid < m.next_id for a, mid, c in planted.chains):
+            out["chain_cut"] += 1
+        if len(m.live_ids()) >= 2:
+            try:
+                m.pick_min_cos(m.stored_live()[0])
+            except AssertionError:
+                out["min_cos_failed"] += 1
+        if m.dim != 384:
+            continue
+        out["ambiguous"] = max(out["ambiguous"], m.ambiguous_pairs(BOUND))
+        a, bb, c = m._pair_list(BOUND, False)
+        ga = np.array([m.groups.get(int(i), NO_GROUP) for i in a], np.int64)
+        gb = np.array([m.groups.get(int(i), NO_GROUP) for i in bb], np.int64)
+        inside = bool(((ga == gb) & (ga != NO_GROUP)).any())
+        across = bool(((ga != gb) & (ga != NO_GROUP) & (gb != NO_GROUP)).any())
+        just_above = bool((c < b + 1e-3).any())
+        lo = m._pair_list(np.float32(b - 1e-3), False)[2]
+        just_below = bool((lo <= b).any())
+        edges = set(zip(a.tolist(), bb.tolist()))
+        three = any((x, y) in edges and (y, z) in edges and (x, z) not in edges and m._components(BOUND, False)[x] ==
+                    m._components(BOUND, False)[z] for x, y, z in planted.chains if all(m.is_live(i) for i in (x, y, z)))
+        out["full_states"] += inside and across and just_above and just_below and three
+    return out

@@ -1,6 +1,8 @@
 """Pins tests/store_model.py on the CPU: the model's bookkeeping, its judge against the C oracle's answers — and against
 hand-made WRONG answers, each of which it must reject: a judge that accepts everything is the failure this file guards
-against — and the coverage of every walk the GPU test runs (tests/test_gpu_store_walk.py)."""
+against — and the coverage of every walk the GPU test runs (tests/test_gpu_store_walk.py).  Below, the same for the kinds
+that start from stored rows and for the boosted search: the judges check_similar, check_pairs, check_clusters and
+check_boosted, and the extended walks of tests/test_gpu_store_walk_similar.py."""
 import json
 import os
 
@@ -8,8 +10,9 @@ import numpy as np
 import pytest
 
 from codesearch_amd.synth import synth_planted, synth_rows
-from tests.store_model import (EDGES, NO_GROUP, NO_ID, NOT_BUILT, WALKS, StoreModel, apply, make_walk, new_model,
-                               required_coverage, resolve, tolerance, walk_coverage)
+from tests.store_model import (BOUND, CHAIN, EDGES, LADDER, NO_CLASS, NO_GROUP, NO_ID, NOT_BUILT, WALKS, StoreModel,
+                               apply, clone_layout, extended_coverage, make_walk, new_model, plant, required_coverage, resolve,
+                               rows_of, tolerance, walk_coverage)
 
 GOLDEN = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "scan_golden.json")))
 
@@ -279,3 +282,397 @@ def test_every_walk_reaches_every_state(seed, dim, sharded):
 
 def test_some_walk_has_a_non_zero_id_base():
     assert any(make_walk(s, d, sh)[0]["id_base"] for s, d, sh in WALKS)
+
+
+# ======================================================================================================
+# The kinds that start from stored rows (similar, pairs, clusters) and the boosted search
+# ======================================================================================================
+
+from codesearch_amd.search import boost_order, clusters_of_pairs, drop_excluded, pairs_above  # noqa: E402
+
+SIMILAR_WALKS = [(s, 384) for s in range(4)] + [(s, 100) for s in range(2)]  # tests/test_gpu_store_walk_similar.py runs these
+TABLE = np.array([1, 1.15, 0.5, 0, 1.01], np.float32)
+B = float(BOUND)
+# rows of the fixture below (id = row + 50): (source, clone, target cosine); file = row // 16
+NEAR = {"0.999": (140, 141, 0.999), "0.97": (152, 400, 0.97), "+5e-4": (160, 420, B + 5e-4), "+2e-4": (170, 171, B + 2e-4),
+        "-2e-4": (180, 440, B - 2e-4), "-5e-4": (190, 460, B - 5e-4), "0.85": (210, 480, 0.85), "dead end": (150, 410, 0.95)}
+CHAIN_ROWS = (220, 230, 500)
+
+
+def _clone_model(cut_middle=False):
+    dim = 384
+    rows = synth_rows(41, 0, 600, dim)
+    rows[300], rows[301], rows[450] = rows[120], rows[120], rows[120]   # ids 170 = 350 = 351 = 500
+    rows[130] = 0.0
+    for a, b, t in NEAR.values():
+        plant(rows, a, b, t)
+    plant(rows, CHAIN_ROWS[0], CHAIN_ROWS[1], CHAIN)
+    plant(rows, CHAIN_ROWS[1], CHAIN_ROWS[2], CHAIN)
+    m = StoreModel(dim, id_base=50)
+    ids = m.insert(rows)
+    m.set_groups(ids, [(i - 50) // 16 for i in ids])
+    m.set_classes(ids, [NO_CLASS if (i - 50) % 7 == 6 else (i - 50) % 5 for i in ids])
+    m.build()
+    assert m.delete(range(50, 110)) == 60
+    assert m.build() and m.stored_rows() == 540
+    assert m.delete([200] + ([50 + CHAIN_ROWS[1]] if cut_middle else [])) == 1 + cut_middle
+    assert not m.build()
+    return m, rows
+
+
+@pytest.fixture(scope="module")
+def clones():
+    """`little` with planted near-copies (NEAR), a chain, classes and groups; ids 50..109 reclaimed, id 200 (the source of
+    the "dead end" clone) a tombstone."""
+    return _clone_model()
+
+
+def _pid(name):
+    a, b, _ = NEAR[name]
+    return a + 50, b + 50
+
+
+def _full_order(m, q):
+    c, i, n = m.topk(q, len(m))
+    assert n == len(m)
+    return c, i
+
+
+def test_planting_hits_its_targets(clones):
+    m, rows = clones
+    ids = m.live_ids()
+    g = m._gram()
+    at = lambda i: int(np.searchsorted(ids, i))
+    for name, (a, b, t) in NEAR.items():
+        if name != "dead end":
+            assert abs(g[at(a + 50), at(b + 50)] - t) < 1e-6, name
+    a, b, c = (r + 50 for r in CHAIN_ROWS)
+    assert g[at(a), at(b)] > B + 0.02 and g[at(b), at(c)] > B + 0.02 and 0.8 < g[at(a), at(c)] < B - 0.02
+    assert m.ambiguous_pairs(BOUND) == 0 and m.classes_assigned() == 600 - 600 // 7
+    with pytest.raises(ValueError, match="never issued"):
+        m.set_classes([650], [1])
+    assert m.classes_assigned() == 600 - 600 // 7
+
+
+def test_the_similar_judge_accepts_right_answers(clones):
+    m, rows = clones
+    grp = lambda ids: [m.groups.get(int(i), NO_GROUP) for i in ids]
+    E = list(range(50, 700, 2))
+    for src in (190, 191, 110, 649, 170, 500, 280, 180):  # a source, its clone, the ends, duplicates, the chain's middle, the zero row
+        if src == 180:
+            assert not m.rows[src].any()
+        bound = m.pick_min_cos(src) if src != 180 else None
+        fc, fi = _full_order(m, m.rows[src])
+        for mode in ("none", "self", "file"):
+            for k in (1, 10, 200, 600):
+                for min_cos in (None, bound):
+                    for allowed in (None, E):
+                        got = m.similar_topk(src, k, mode, min_cos, allowed)
+                        assert m.check_similar(src, k, got, mode, min_cos, allowed) <= 1e-7
+                        keep = np.ones(len(fi), bool) if allowed is None else np.isin(fi, E)
+                        hc, hi = drop_excluded(fc[keep], fi[keep], grp(fi[keep]), src, m.groups.get(src, NO_GROUP), mode,
+                                               None if min_cos is None else np.float32(min_cos), k)
+                        assert hi == got[1][:got[2]].tolist()   # the project's host statement agrees with the model
+                        assert m.check_similar(src, k, _padded(hc, hi, k), mode, min_cos, allowed) <= 1e-7
+    assert m.similar_topk(190, 3, "none")[1][:2].tolist() == [190, 191] and m.similar_topk(190, 3, "file")[1][0] != 191
+    assert 0.5 < m.pick_min_cos(190) < 0.95
+
+
+def test_the_similar_judge_rejects_each_wrong_answer(clones):
+    m, rows = clones
+    k = 10
+    src = 190
+    cases = []
+    c, i, n = m.similar_topk(src, k, "none")
+    cases.append(("the source under self", "self", None, (c, i, n), "source id 190 is returned under exclude='self'"))
+    c, i, n = m.similar_topk(src, k, "self")
+    assert i[0] == 191 and m.groups[191] == m.groups[190]
+    cases.append(("a group-mate under file", "file", None, (c, i, n), "id 191 of the source's group 8 is returned"))
+    bound = m.pick_min_cos(src)
+    c2, i2, n2 = m.similar_topk(src, k, "self", bound)
+    assert n2 == 1
+    cases.append(("a row at or below min_cos", "self", bound, (c, i, 2), "is not above min_cos"))
+    for bad, text in ((60, "id 60 was deleted and reclaimed"), (200, "id 200 is deleted")):
+        j = i.copy(); j[9] = bad
+        cases.append((text, "self", None, (c, j, n), text))
+    cc, j = c.copy(), i.copy(); cc[9], j[9] = 0.0, NO_ID
+    cases.append(("a short count", "self", None, (cc, j, 9), "count 9, expected"))
+    for name, mode, min_cos, got, match in cases:
+        with pytest.raises(AssertionError, match=match):
+            m.check_similar(src, k, got, mode, min_cos)
+            pytest.fail(f"the judge accepted: {name}")
+    # a bound float64 cannot place is refused, not judged
+    near = float(m.cosines(m.rows[src])[np.searchsorted(m.live_ids(), 191)])
+    with pytest.raises(AssertionError, match="refused.*float64 cannot decide"):
+        m.check_similar(src, k, (c, i, n), "self", near + 1e-5)
+    with pytest.raises(AssertionError, match="source id 200 is deleted"):
+        m.check_similar(200, k, (c, i, n), "self")
+
+
+def _host_pairs(m, bound, other_files, max_pairs=65536):
+    orders = {int(a): _full_order(m, m.rows[int(a)]) for a in m.live_ids()}
+    return pairs_above(orders, lambda ids: [m.groups.get(int(i), NO_GROUP) for i in ids], "other_group" if other_files else "all",
+                       bound, max_pairs)
+
+
+def test_the_pairs_judge_accepts_right_answers(clones):
+    m, rows = clones
+    E, O = list(range(50, 700, 2)), list(range(51, 700, 2))
+    full = m.pairs(BOUND, False)
+    got = set(zip(full[1].tolist(), full[2].tolist()))
+    want = {_pid(n) for n in ("0.999", "0.97", "+5e-4", "+2e-4")} | {(270, 280), (280, 550)} | \
+        {(170, 350), (170, 351), (170, 500), (350, 351), (350, 500), (351, 500)}
+    assert got == want and full[3] == 12
+    for other_files in (False, True):
+        for kw in ({}, {"max_pairs": 5}, {"inside": E}, {"inside": E, "other": O}, {"inside": O, "other": O}):
+            ans = m.pairs(BOUND, other_files, **kw)
+            assert m.check_pairs(BOUND, other_files, ans, **kw) <= 1e-7
+        host = _host_pairs(m, BOUND, other_files)
+        mine = m.pairs(BOUND, other_files)
+        assert host[3] == mine[3] and host[1] == mine[1].tolist() and host[2] == mine[2].tolist()
+        assert m.check_pairs(BOUND, other_files, host) <= 1e-7
+        cut = _host_pairs(m, BOUND, other_files, 5)
+        assert len(cut[0]) == 5 and m.check_pairs(BOUND, other_files, cut, max_pairs=5) <= 1e-7
+    same_file = {(190, 191), (220, 221), (350, 351)}
+    assert got - set(zip(*[x.tolist() for x in m.pairs(BOUND, True)[1:3]])) == same_file
+    between = m.pairs(BOUND, False, inside=E, other=O)
+    assert all((a % 2) != (b % 2) for a, b in zip(between[1].tolist(), between[2].tolist())) and 0 < between[3] < 12
+    # no bound: every live pair once, the zero row's pairs at 0.0, nothing that is not finite
+    small = StoreModel(384)
+    small.insert(rows[120:135])
+    small.build()
+    every = small.pairs(None, False)
+    assert every[3] == 15 * 14 // 2 and np.isfinite(every[0]).all() and (every[0][(every[1] == 10) | (every[2] == 10)] == 0).all()
+    assert small.check_pairs(None, False, every) <= 1e-7
+    assert small.check_pairs(None, False, _host_pairs(small, None, False)) <= 1e-7
+
+
+def test_the_pairs_judge_rejects_each_wrong_answer(clones):
+    m, rows = clones
+    cos, a, b, total = m.pairs(BOUND, False)
+    n = len(a)
+    cases = []
+
+    def add(name, match, c=cos, x=a, y=b, t=total, other_files=False, max_pairs=65536):
+        cases.append((name, match, (np.asarray(c, np.float32), np.asarray(x, np.uint32), np.asarray(y, np.uint32), t), other_files, max_pairs))
+
+    x, y = a.copy(), b.copy(); x[7], y[7] = b[7], a[7]
+    add("a pair as (b, a)", "is not given as a < b", x=x, y=y)
+    x, y, c = a.copy(), b.copy(), cos.copy(); x[8], y[8], c[8] = x[7], y[7], c[7]
+    add("a pair twice", "is returned twice", c=c, x=x, y=y)
+    oc, oa, ob, ot = m.pairs(BOUND, True)
+    j = a.tolist().index(190)
+    pos = int(np.searchsorted(-oc, -cos[j]))
+    add("a same-group pair under other_files", r"pair \(190, 191\) lies inside group 8", c=np.insert(oc, pos, cos[j]),
+        x=np.insert(oa, pos, 190), y=np.insert(ob, pos, 191), t=ot + 1, other_files=True)
+    add("a same-group pair under other_files, total kept", r"pair \(190, 191\) lies inside group 8", c=np.insert(oc, pos, cos[j]),
+        x=np.insert(oa, pos, 190), y=np.insert(ob, pos, 191), t=ot, other_files=True)
+    dead = (200, 460)   # the 0.95 clone of the tombstoned id 200
+    pos = int(np.searchsorted(-cos, -np.float32(0.95)))
+    add("a pair with a deleted end", r"pair \(200, 460\): id 200 is deleted", c=np.insert(cos, pos, np.float32(0.95)),
+        x=np.insert(a, pos, dead[0]), y=np.insert(b, pos, dead[1]), t=total + 1)
+    lo = _pid("-2e-4")
+    c_lo = np.float32(m._gram()[np.searchsorted(m.live_ids(), lo[0]), np.searchsorted(m.live_ids(), lo[1])])
+    add("the pair at BOUND - 2e-4 present", r"pair \(230, 490\) is returned, but its float64 cos .* is not above the bound",
+        c=np.append(cos, c_lo), x=np.append(a, lo[0]), y=np.append(b, lo[1]), t=total + 1)
+    hi = _pid("+2e-4")
+    keep = ~((a == hi[0]) & (b == hi[1]))
+    assert keep.sum() == n - 1
+    add("the pair at BOUND + 2e-4 missing", r"total 11, the model counts 12", c=cos[keep], x=a[keep], y=b[keep], t=total - 1)
+    add("the pair at BOUND + 2e-4 missing, total kept", r"pairs returned, expected", c=cos[keep], x=a[keep], y=b[keep])
+    add("a wrong total", "total 13, the model counts 12", t=total + 1)
+    cut = [0, 1, 2, 3, 4, 5, 6, 8]   # the best seven, then the ninth in place of the eighth
+    assert cos[7] > cos[8] + 2 * m.tol
+    add("a cut list that drops a better pair", r"the cut list leaves out pair \(202, 450\)", c=cos[cut], x=a[cut], y=b[cut], max_pairs=8)
+    c, x, y = cos.copy(), a.copy(), b.copy()
+    assert cos[7] > cos[9]
+    c[[7, 9]], x[[7, 9]], y[[7, 9]] = cos[[9, 7]], a[[9, 7]], b[[9, 7]]
+    add("two entries swapped", "not sorted", c=c, x=x, y=y)
+    c = cos.copy(); c[8] += np.float32(1e-3)
+    add("a cosine off by 1e-3", "cos of pair", c=c)
+    for name, match, got, other_files, max_pairs in cases:
+        with pytest.raises(AssertionError, match=match):
+            m.check_pairs(BOUND, other_files, got, max_pairs=max_pairs)
+            pytest.fail(f"the judge accepted: {name}")
+    # a pair float64 cannot place is refused, not judged
+    with pytest.raises(AssertionError, match="refused.*float64 cannot decide"):
+        m.check_pairs(np.float32(float(c_lo) + 1e-5), False, (cos, a, b, total))
+    with pytest.raises(AssertionError, match="refused"):
+        m.check_clusters(np.float32(float(c_lo) + 1e-5), False, *m.clusters(BOUND, False))
+
+
+def test_the_clusters_judge(clones):
+    m, rows = clones
+    a_, b_, c_ = (r + 50 for r in CHAIN_ROWS)
+    for other_files in (False, True):
+        labels, clusters, members = m.clusters(BOUND, other_files)
+        assert m.check_clusters(BOUND, other_files, labels, clusters, members) == 0.0
+        pc, pa, pb, _ = m.pairs(BOUND, other_files)
+        hl, hc, hm = clusters_of_pairs(m.live_ids(), pa, pb)   # the project's host statement agrees with the model
+        host = np.full(len(labels), NO_ID, np.uint32)
+        for i, root in hl.items():
+            host[i - 50] = root
+        assert host.tolist() == labels.tolist() and (hc, hm) == (clusters, members)
+        assert m.check_clusters(BOUND, other_files, host, hc, hm) == 0.0
+    labels, clusters, members = m.clusters(BOUND, False)
+    assert labels[a_ - 50] == labels[b_ - 50] == labels[c_ - 50] == a_ and labels[500 - 50] == 170 and labels[200 - 50] == NO_ID
+    assert (clusters, members) == (6, 2 * 4 + 3 + 4) and len(labels) == 600 and (labels[:60] == NO_ID).all()
+    cases = []
+    l = labels.copy(); l[[a_ - 50, b_ - 50, c_ - 50]] = b_
+    cases.append(("a label that is not the smallest id", f"id {a_} carries label {b_}, the smallest id of its component is {a_}", l, clusters, members))
+    l = labels.copy(); l[200 - 50] = 200
+    cases.append(("a deleted id with a label", "id 200 is deleted and carries label 200, not NO_ID", l, clusters, members))
+    l = labels.copy(); l[60 - 50] = 60
+    cases.append(("a reclaimed id with a label", "id 60 was deleted and reclaimed and carries label 60", l, clusters, members))
+    l = labels.copy(); l[300 - 50] = NO_ID
+    cases.append(("a live id with NO_ID", "live id 300 carries NO_ID", l, clusters, members))
+    l = labels.copy(); l[c_ - 50] = c_
+    cases.append(("the chain's ends not joined", f"id {c_} carries label {c_}, the smallest id of its component is {a_}", l, clusters - 0, members - 1))
+    cases.append(("labels shifted by one entry", "carries", np.roll(labels, 1), clusters, members))
+    cases.append(("a wrong clusters", "clusters 7, the model counts 6", labels, clusters + 1, members))
+    cases.append(("a wrong members", "members 14, the model counts 15", labels, clusters, members - 1))
+    cases.append(("too few labels", "599 labels, expected", labels[:-1], clusters, members))
+    for name, match, l, c, mm in cases:
+        with pytest.raises(AssertionError, match=match):
+            m.check_clusters(BOUND, False, l, c, mm)
+            pytest.fail(f"the judge accepted: {name}")
+    # the chain's middle deleted: the answer that still joins the ends is wrong there
+    cut, _ = _clone_model(cut_middle=True)
+    with pytest.raises(AssertionError, match=f"id {b_} is deleted and carries label|id {c_} carries label {a_}, the smallest id of its component is {c_}"):
+        cut.check_clusters(BOUND, False, labels, clusters, members)
+    l = labels.copy(); l[b_ - 50] = NO_ID
+    with pytest.raises(AssertionError, match=f"id {c_} carries label {a_}, the smallest id of its component is {c_}"):
+        cut.check_clusters(BOUND, False, l, clusters, members)
+    assert cut.check_clusters(BOUND, False, *cut.clusters(BOUND, False)) == 0.0 and cut.clusters(BOUND, False)[1:] == (5, 12)
+
+
+def _classes_of(m, ids):
+    return [m.classes.get(int(i), NO_CLASS) for i in ids]
+
+
+def test_the_boosted_judge_accepts_right_answers(clones):
+    m, rows = clones
+    q = (rows[120] + 0.3 * rows[20]).astype(np.float32)   # near the duplicates 170 = 350 = 351 = 500
+    qs = np.stack([q, rows[400], synth_rows(43, 0, 1, 384)[0]])
+    E = list(range(50, 700, 2))
+    for weights in (TABLE, TABLE[:3], np.zeros(0, np.float32), None, np.ones(5, np.float32)):
+        for k in (1, 10, 200, 600):
+            for query in (q, qs[2], qs):
+                for allowed in (None, E):
+                    got = m.boosted_topk(query, k, weights, allowed)
+                    assert m.check_boosted(query, k, got, weights, allowed) <= 1e-7
+                    fc, fi = _full_order(m, query)
+                    keep = np.ones(len(fi), bool) if allowed is None else np.isin(fi, E)
+                    hs, hc, hi = boost_order(fc[keep], fi[keep], _classes_of(m, fi[keep]), weights, k)
+                    assert hi.tolist() == got[2][:got[3]].tolist() and hs.tobytes() == got[0][:got[3]].tobytes()
+                    pad = lambda x, fill, t: np.concatenate([x, np.full(k - len(x), fill, t)]).astype(t)
+                    host = (pad(hs, 0, np.float32), pad(hc, 0, np.float32), pad(hi, NO_ID, np.uint32), len(hi))
+                    assert m.check_boosted(query, k, host, weights, allowed) <= 1e-7
+    plain = m.topk(q, 10)
+    ones = m.boosted_topk(q, 10, np.ones(5, np.float32))
+    assert ones[2].tolist() == plain[1].tolist() and ones[1].tobytes() == plain[0].tobytes()
+    assert m.boosted_topk(q, 10, TABLE)[2].tolist() != plain[1].tolist()
+
+
+def test_the_boosted_judge_rejects_each_wrong_answer(clones):
+    m, rows = clones
+    q = (rows[120] + 0.3 * rows[20]).astype(np.float32)
+    k = 10
+    score, cos, ids, cnt = m.boosted_topk(q, k, TABLE)
+    assert cnt == k
+    w = m._weights(TABLE)[np.searchsorted(m.live_ids(), ids)]
+    assert len(set(w.tolist())) >= 2
+    cases = []
+
+    def add(name, match, s=score, c=cos, i=ids, n=cnt, weights=TABLE, kk=k, query=q):
+        cases.append((name, match, (np.asarray(s, np.float32), np.asarray(c, np.float32), np.asarray(i, np.uint32), n), weights, kk, query))
+
+    j = int(np.flatnonzero(w != np.float32(1.15))[0])
+    s = score.copy(); s[j] = m.score_of(cos[j], np.float32(1.15))
+    add("the cosine's score times the wrong class's weight", f"score of id {ids[j]} is", s=s)
+    # a score rounded twice: the reference's two successive multiplies where the table holds f32(1.2 * 1.15)
+    both = np.array([np.float32(1.2) * np.float32(1.15)] * 5, np.float32)
+    s2, c2, i2, n2 = m.boosted_topk(q, 200, both)
+    classed = m._weights(both)[np.searchsorted(m.live_ids(), i2)] != 1   # (an id without a class weighs 1 either way)
+    twice = np.where(classed, (m.score_of(c2, np.float32(1.15)) * np.float32(1.2)).astype(np.float32), s2)
+    assert (twice != s2).any() and np.abs(twice - s2).max() < 2e-7
+    add("a score rounded twice", "score of id", s=twice, c=c2, i=i2, n=n2, weights=both, kk=200)
+    full = m.boosted_topk(q, k + 1, TABLE)
+    drop = int(np.flatnonzero(w > 1)[0])
+    keep = [n for n in range(k + 1) if n != drop]
+    assert full[0][drop] > full[0][k] + 1e-4
+    add("a boosted row left out", f"id {ids[drop]} .* is left out", s=full[0][keep], c=full[1][keep], i=full[2][keep])
+    by_cos = np.lexsort((ids, -cos))
+    assert by_cos.tolist() != list(range(k))
+    add("order by cosine instead of score", "not sorted by", s=score[by_cos], c=cos[by_cos], i=ids[by_cos])
+    pc, pi, pn = m.topk(q, k)
+    assert pi.tolist() != sorted(ids.tolist(), key=ids.tolist().index)
+    add("the plain top-k with scores attached", "is left out|not sorted by", c=pc, i=pi,
+        s=m.score_of(pc, m._weights(TABLE)[np.searchsorted(m.live_ids(), pi)]))
+    # weight 0: every row of class 3 scores 0.0; among them the order is the id's
+    zero = np.array([0, 0, 0, 0, 0], np.float32)
+    zs, zc, zi, zn = m.boosted_topk(q, 600, zero)
+    tied = np.flatnonzero(zs[:zn] == 0)
+    assert len(tied) > 300 and (np.diff(zi[tied].astype(np.int64)) > 0).all()
+    zi2, zc2 = zi.copy(), zc.copy()
+    zi2[tied], zc2[tied] = zi[tied][::-1], zc[tied][::-1]
+    add("a weight-0 tie in descending id", "not sorted by", s=zs, c=zc2, i=zi2, n=zn, weights=zero, kk=600)
+    i = ids.copy(); i[9] = 200
+    add("a deleted id", "id 200 is deleted", i=i)
+    add("a short count", "count 9, expected", s=np.append(score[:9], 0), c=np.append(cos[:9], 0), i=np.append(ids[:9], NO_ID), n=9)
+    # byte-identical rows of one class: 170 and 500 both carry class 0 (351 class 1, 350 none); 500 in place of 170 at the
+    # end of a list, where the scores alone cannot tell
+    assert m.classes[170] == m.classes[500] == 0 and m.classes[351] == 1 and 350 not in m.classes
+    dq = rows[120]
+    ds, dc, di, dn = m.boosted_topk(dq, 2, TABLE)
+    assert di.tolist() == [351, 170]
+    add("a higher-id duplicate of the same class in place of a lower one", "lower id 170 .* is left out", s=ds, c=dc,
+        i=np.array([351, 500]), n=2, kk=2, query=dq)
+    for name, match, got, weights, kk, query in cases:
+        with pytest.raises(AssertionError, match=match):
+            m.check_boosted(query, kk, got, weights)
+            pytest.fail(f"the judge accepted: {name}")
+
+
+def test_the_default_walks_are_unchanged():
+    import hashlib
+
+    for seed, dim, sharded in WALKS:
+        walk = make_walk(seed, dim, sharded)
+        assert walk == make_walk(seed, dim, sharded, extended=False)
+        assert not any(op["op"] == "classes" or "clones" in op for op in walk)
+        ext = make_walk(seed, dim, sharded, extended=True)
+        plain = [{k: v for k, v in op.items() if k != "clones"} for op in ext if op["op"] != "classes"]
+        assert plain == walk                                         # the same operations, order, sizes and seeds
+        assert sum(op["op"] == "classes" for op in ext) == sum(op["op"] == "groups" for op in ext)
+        assert all(("clones" in op) == (op["n"] >= 64) for op in ext if op["op"] == "insert")
+    # an insert without the key gives the rows it gave before the key existed (synth_rows, dups, zero and nothing else)
+    op = {"op": "insert", "n": 300, "seed": 7001, "first": 90, "dups": 3, "zero": True}
+    rows = synth_rows(7001, 90, 300, 384)
+    rows[297:] = rows[:3]
+    rows[1] = 0.0
+    assert rows_of(op, 384).tobytes() == rows.tobytes()
+    assert hashlib.sha256(rows_of(op, 384).tobytes()).hexdigest() == hashlib.sha256(rows.tobytes()).hexdigest()
+    cloned = rows_of(dict(op, clones=8101), 384)
+    changed = np.flatnonzero((cloned != rows).any(axis=1)).tolist()
+    plants, chains = clone_layout(dict(op, clones=8101))
+    assert changed == sorted(b for _, b, _ in plants) and len(changed) == len(LADDER) + 2
+    assert not set(changed) & {0, 1, 2, 297, 298, 299} and not set(changed) & {a for a, _, _ in plants if a not in {c[1] for c in chains}}
+    assert np.allclose(np.linalg.norm(cloned[changed], axis=1), np.linalg.norm(rows[changed], axis=1), rtol=1e-6)
+    near = [abs(a - b) for a, b, _ in plants]
+    assert sum(d <= 16 for d in near) >= 2 and sum(d > 16 for d in near) >= 2
+
+
+@pytest.mark.parametrize("seed,dim", SIMILAR_WALKS)
+def test_every_extended_walk_reaches_every_state(seed, dim):
+    walk = make_walk(seed, dim, False, extended=True)
+    cov = walk_coverage(walk)
+    missing = sorted(k for k in required_coverage(walk) if not cov[k])
+    assert not missing, missing
+    ext = extended_coverage(walk)
+    assert ext["ambiguous"] == 0 and ext["min_cos_failed"] == 0, ext     # the ambiguity cap: zero
+    assert ext["classes_before_reclaim"] >= 1 and ext["appended_after_classes"] >= 1, ext
+    if dim == 384:  # (the pairs and clusters calls have no tiles for another dim)
+        assert ext["full_states"] >= 6 and ext["chain_cut"] >= 1, ext
+    assert any(make_walk(s, d, False, True)[0]["id_base"] for s, d in SIMILAR_WALKS) and \
+        any(not make_walk(s, d, False, True)[0]["id_base"] for s, d in SIMILAR_WALKS)
