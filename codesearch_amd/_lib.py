@@ -128,6 +128,8 @@ SIGNATURES = {
     "cs_index_similar_pairs_info": (C.c_int32, [u64p, u32p, f64p, f64p, f64p]),
     "cs_index_similar_clusters": (C.c_int32, [vp, C.c_float, C.c_int32, u32p, C.c_uint64, u64p, u64p]),
     "cs_index_similar_clusters_info": (C.c_int32, [u64p, u64p, u64p, u32p, f64p, f64p]),
+    "cs_index_similar_clusters_scoped": (C.c_int32, [vp, vp, vp, C.c_float, C.c_int32, u32p, u32p, C.c_uint64, u64p, u64p, u64p]),
+    "cs_index_similar_clusters_scoped_info": (C.c_int32, [f64p, u64p, u64p, u64p]),
     "cs_index_similar_pairs_scoped": (C.c_int32, [vp, vp, vp, C.c_float, C.c_int32, C.c_uint32, u32p, u32p, f32p, u64p]),
     "cs_index_similar_pairs_scoped_info": (C.c_int32, [f64p, u64p, u64p, u64p]),
     "cs_index_search_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p]),

@@ -18,6 +18,7 @@
 #include "index_ledger.hpp"
 #include "masked_plan.hpp"
 #include "clusters_plan.hpp"
+#include "clusters_scoped_plan.hpp"
 #include "pairs_plan.hpp"
 #include "pairs_scoped_plan.hpp"
 #include "scan.hpp"
@@ -1752,6 +1753,9 @@ struct ClustersInfo {
     uint64_t scored = 0, skipped = 0, rescored = 0;
     uint32_t launches = 0;
     double join_ms = 0.0, label_ms = 0.0;
+    // a scoped call only (cs_index_similar_clusters_scoped_info; zeros after an unscoped one)
+    double pack_ms = 0.0;
+    uint64_t rows_a = 0, rows_b = 0, vertices = 0;
 };
 thread_local ClustersInfo last_clusters_info;
 
@@ -1776,6 +1780,65 @@ ClustersWorkspace* acquire_clusters(cs_index* h) {
 uint64_t clusters_knob(const char* name) {
     const char* e = cs_lab_env(name);  // (read per call: tests set it mid-process)
     return e ? std::strtoull(e, nullptr, 10) : 0;
+}
+
+// The walk of both clusters calls over `plan` (tile_pairs, launch_at, ambiguous_cap): per launch `roots_and_join(range)` —
+// the tile roots and the join, enqueued on w->stream — and one synchronise to read the ambiguous counter — within the
+// buffer: the rescore unites what qualifies; past it: the launch is void and its two halves are walked instead (lo first, so
+// the walk stays in the plan's order).  ev: the rescore's events, read one synchronise later than the join's; *rescore_timed
+// says that the last rescore's time is still to be read, behind the caller's next synchronise.
+template <typename Plan, typename RootsAndJoin>
+int32_t clusters_walk(cs_index* h, ClustersWorkspace* w, hipEvent_t* ev, const Plan& plan, RowIds ids, float min_cos,
+                      ClustersInfo& info, bool& rescore_timed, RootsAndJoin&& roots_and_join) {
+    std::vector<PairsBand> halves;  // of launches whose ambiguous pairs did not fit; the next to walk is at the back
+    uint64_t next = 0;
+    float ms = 0.0f;
+    rescore_timed = false;
+    while (next < plan.tile_pairs || !halves.empty()) {
+        PairsBand r;
+        if (!halves.empty()) {
+            r = halves.back();
+            halves.pop_back();
+        } else {
+            r = plan.launch_at(next);
+            next += r.count;
+        }
+        CS_HIP(hipMemsetAsync(w->d_counters, 0, 2 * sizeof(uint64_t), w->stream));
+        CS_HIP(hipEventRecord(w->ev[0], w->stream));
+        CS_TRY(roots_and_join(r));
+        CS_HIP(hipEventRecord(w->ev[1], w->stream));
+        CS_HIP(hipMemcpyAsync(w->h_counters, w->d_counters, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, w->stream));
+        CS_HIP(hipStreamSynchronize(w->stream));
+        CS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
+        info.join_ms += ms;
+        if (rescore_timed) {  // the previous launch's rescore has finished with this synchronise
+            CS_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+            info.join_ms += ms;
+            rescore_timed = false;
+        }
+        info.launches++;
+        const uint64_t ambiguous = w->h_counters[0];
+        if (ambiguous > plan.ambiguous_cap) {
+            PairsBand lo, hi;
+            if (!clusters_split(r, lo, hi))
+                return fail(CS_ERR_HIP, "similar clusters: one tile pair reported %llu ambiguous pairs, more than 128 * 128",
+                            (unsigned long long)ambiguous);
+            halves.push_back(hi);
+            halves.push_back(lo);
+            continue;
+        }
+        info.skipped += w->h_counters[1];
+        info.scored += r.count - w->h_counters[1];
+        info.rescored += ambiguous;
+        if (ambiguous) {
+            CS_HIP(hipEventRecord(ev[0], w->stream));
+            CS_TRY(launch_clusters_rescore(h->d_corpus, h->dim, w->d_amb, (uint32_t)ambiguous, ids, min_cos, w->d_parent,
+                                           pairs_refine_blocks(ambiguous, h->num_cus), w->stream));
+            CS_HIP(hipEventRecord(ev[1], w->stream));
+            rescore_timed = true;
+        }
+    }
+    return CS_OK;
 }
 
 // The checks; the f16 operand as similar_pairs finds or makes it; then the plan's walk: per launch the tile roots, the join
@@ -1868,57 +1931,14 @@ int32_t similar_clusters(cs_index* h, float min_cos, int32_t mode, uint32_t* out
     const float* d_norms = h->normed_rows >= stored ? h->d_norms : nullptr;  // none: no pair is united without a rescore
     const RowIds ids = h->row_ids();
     ClustersInfo info;
-    std::vector<PairsBand> halves;  // of launches whose ambiguous pairs did not fit; the next to walk is at the back
-    uint64_t next = 0;
     bool rescore_timed = false;
     float ms = 0.0f;
-    while (next < plan.tile_pairs || !halves.empty()) {
-        PairsBand r;
-        if (!halves.empty()) {
-            r = halves.back();
-            halves.pop_back();
-        } else {
-            r = plan.launch_at(next);
-            next += r.count;
-        }
-        CS_HIP(hipMemsetAsync(w->d_counters, 0, 2 * sizeof(uint64_t), w->stream));
-        CS_HIP(hipEventRecord(w->ev[0], w->stream));
+    CS_TRY(clusters_walk(h, w, sc.ev, plan, ids, min_cos, info, rescore_timed, [&](const PairsBand& r) -> int32_t {
         CS_TRY(launch_clusters_tile_roots(w->d_parent, plan.tiles, stored, d_dead, w->d_tile_root, w->stream));
-        CS_TRY(launch_clusters_join(d_f16, h->dim, plan.tiles, r.first, r.count, stored, d_dead, ids, gv,
+        return launch_clusters_join(d_f16, h->dim, plan.tiles, r.first, r.count, stored, d_dead, ids, gv,
                                     mode == CS_PAIRS_OTHER_GROUP, min_cos, h->filter_margin, d_norms, w->d_parent,
-                                    w->d_tile_root, w->d_amb, w->d_counters, (uint32_t)plan.ambiguous_cap, w->stream));
-        CS_HIP(hipEventRecord(w->ev[1], w->stream));
-        CS_HIP(hipMemcpyAsync(w->h_counters, w->d_counters, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, w->stream));
-        CS_HIP(hipStreamSynchronize(w->stream));
-        CS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
-        info.join_ms += ms;
-        if (rescore_timed) {  // the previous launch's rescore has finished with this synchronise
-            CS_HIP(hipEventElapsedTime(&ms, sc.ev[0], sc.ev[1]));
-            info.join_ms += ms;
-            rescore_timed = false;
-        }
-        info.launches++;
-        const uint64_t ambiguous = w->h_counters[0];
-        if (ambiguous > plan.ambiguous_cap) {
-            PairsBand lo, hi;
-            if (!clusters_split(r, lo, hi))
-                return fail(CS_ERR_HIP, "similar clusters: one tile pair reported %llu ambiguous pairs, more than 128 * 128",
-                            (unsigned long long)ambiguous);
-            halves.push_back(hi);
-            halves.push_back(lo);
-            continue;
-        }
-        info.skipped += w->h_counters[1];
-        info.scored += r.count - w->h_counters[1];
-        info.rescored += ambiguous;
-        if (ambiguous) {
-            CS_HIP(hipEventRecord(sc.ev[0], w->stream));
-            CS_TRY(launch_clusters_rescore(h->d_corpus, h->dim, w->d_amb, (uint32_t)ambiguous, ids, min_cos, w->d_parent,
-                                           pairs_refine_blocks(ambiguous, h->num_cus), w->stream));
-            CS_HIP(hipEventRecord(sc.ev[1], w->stream));
-            rescore_timed = true;
-        }
-    }
+                                    w->d_tile_root, w->d_amb, w->d_counters, (uint32_t)plan.ambiguous_cap, w->stream);
+    }));
     CS_HIP(hipEventRecord(w->ev[0], w->stream));
     CS_TRY(launch_clusters_label(w->d_parent, w->d_mark, stored, d_dead, ids, w->d_label, n_labels, w->d_counters + 2, w->stream));
     CS_HIP(hipEventRecord(w->ev[1], w->stream));
@@ -2047,6 +2067,168 @@ int32_t similar_pairs_scoped(cs_index* h, cs_scope* scope_a, cs_scope* scope_b, 
         if (w->h_counters[0] > plan.cand_cap) return pairs_overflow(w->h_counters[0], b + 1, plan.bands, plan.cand_cap);
     }
     return pairs_finish(h, w, min_cos, max_pairs, out_a, out_b, out_cos, out_total, info);
+}
+
+// cs_index_similar_clusters_scoped: similar_clusters over the graph of similar_pairs_scoped (scan_clusters_scoped.hip, plan:
+// clusters_scoped_plan.hpp).  Every check comes before a list is refreshed; the lists are refreshed and packed as
+// similar_pairs_scoped does — the index's d_split is neither read nor made — and the walk is similar_clusters'.  The
+// union-find is the pooled workspace's, sized by stored rows, but only the words of the scopes' rows are initialised and
+// reached: the device work of a call is O(live rows of the scopes).  The label pass writes (id, label) per list entry; the
+// host interleaves the two ascending segments, dropping the second copy of a row in both, and copies out last.  An empty
+// join (the plan's tile_pairs == 0, or two handles holding the same single row) runs the init and the label pass only.
+int32_t similar_clusters_scoped(cs_index* h, cs_scope* scope_a, cs_scope* scope_b, float min_cos, int32_t mode, uint32_t* out_ids,
+                                uint32_t* out_label, uint64_t cap, uint64_t* out_n, uint64_t* out_clusters,
+                                uint64_t* out_members) {
+    if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
+    CS_TRY(check_search(h, 1, h->dim, 1));
+    if (!out_ids || !out_label || !out_n) return fail(CS_ERR_BAD_ARG, "null buffer");
+    if (mode != CS_PAIRS_ALL && mode != CS_PAIRS_OTHER_GROUP)
+        return fail(CS_ERR_BAD_ARG, "mode must be CS_PAIRS_ALL or CS_PAIRS_OTHER_GROUP (0..1), got %d", mode);
+    if (min_cos != min_cos) return fail(CS_ERR_BAD_ARG, "min_cos is NaN");
+    if (!scope_a) return fail(CS_ERR_BAD_ARG, "null scope handle (scope_a)");
+    if (!scope_b) return fail(CS_ERR_BAD_ARG, "null scope handle (scope_b)");
+    CS_TRY(check_scope_handle(h, scope_a));
+    CS_TRY(check_scope_handle(h, scope_b));
+    const bool same = scope_a == scope_b;
+    const uint64_t want = scope_a->n_ids + (same ? 0 : scope_b->n_ids);  // (n_ids never changes after the create call)
+    if (cap < want)
+        return fail(CS_ERR_BAD_ARG, "cap must be at least n_ids(scope_a)%s = %llu (one slot per id a scope names), got %llu",
+                    same ? "" : " + n_ids(scope_b)", (unsigned long long)want, (unsigned long long)cap);
+    if (!split_scan_supported(h->dim))
+        return fail(CS_ERR_UNSUPPORTED, "similar clusters need dim 384, 768 or 1024 (the f16 filter's widths), got %u", h->dim);
+    if (!h->use_split)
+        return fail(CS_ERR_UNSUPPORTED, "similar clusters need the f16 filter copy, and CS_INDEX_SPLIT=0 turned it off");
+    DeviceGuard g(h->device);
+    uint64_t live_a = 0, live_b = 0;
+    CS_TRY(scope_ready(h, scope_a, &live_a));
+    if (same) live_b = live_a;
+    else CS_TRY(scope_ready(h, scope_b, &live_b));
+    ClustersScopedPlan plan = plan_clusters_scoped(same, live_a, live_b, clusters_knob("CS_CLUSTERS_LAUNCH_TILE_PAIRS"),
+                                                   clusters_knob("CS_CLUSTERS_AMBIGUOUS_CAP"));
+    cs_scope* const sa = plan.swapped ? scope_b : scope_a;
+    cs_scope* const sb = plan.swapped ? scope_a : scope_b;
+    const uint64_t second = same ? 0 : plan.rows_b;   // entries of the B segment of the label pass
+    const uint64_t entries = plan.rows_a + second;
+    ClustersInfo info;
+    info.rows_a = plan.rows_a;
+    info.rows_b = plan.rows_b;
+    if (entries == 0) {  // no vertex
+        *out_n = 0;
+        if (out_clusters) *out_clusters = 0;
+        if (out_members) *out_members = 0;
+        last_clusters_info = info;
+        return CS_OK;
+    }
+    struct Scratch {
+        cs_index* h;
+        ClustersWorkspace* w = nullptr;
+        _Float16* d_packed[2] = {nullptr, nullptr};
+        hipEvent_t ev[2] = {nullptr, nullptr};  // the rescore's, read one synchronise later than the join's
+        ~Scratch() {
+            for (hipEvent_t e : ev)
+                if (e) (void)hipEventDestroy(e);
+            for (_Float16* p : d_packed)
+                if (p) (void)hipFree(p);
+            if (w) {
+                std::lock_guard<std::mutex> lk(h->mu);
+                h->clusters_pool.push_back(w);
+            }
+        }
+    } sc{h};
+    sc.w = acquire_clusters(h);
+    if (!sc.w) return fail(CS_ERR_HIP, "similar clusters: could not create a HIP stream");
+    ClustersWorkspace* w = sc.w;
+    if (plan.tile_pairs && !same && plan.rows_a == 1 && plan.rows_b == 1) {  // two handles, one row each: the same row is no pair
+        uint32_t* rows = reinterpret_cast<uint32_t*>(w->h_counters);
+        CS_HIP(hipMemcpyAsync(rows, sa->d_list, sizeof(uint32_t), hipMemcpyDeviceToHost, w->stream));
+        CS_HIP(hipMemcpyAsync(rows + 1, sb->d_list, sizeof(uint32_t), hipMemcpyDeviceToHost, w->stream));
+        CS_HIP(hipStreamSynchronize(w->stream));
+        if (rows[0] == rows[1]) plan.tile_pairs = 0;
+    }
+    const uint64_t stored = h->ledger.stored();
+    if (plan.tile_pairs) {
+        if (h->normed_rows < stored) return fail(CS_ERR_HIP, "similar clusters: the index holds no row norms");
+        const uint64_t side_tiles[2] = {plan.tiles_a, plan.tiles_b};
+        for (int s = 0; s < (same ? 1 : 2); ++s) {
+            const size_t bytes = packed_bytes_of(side_tiles[s], h->dim);
+            if (cs_lab_env("CS_FAULT_F16_ALLOC") != nullptr || hipMalloc(&sc.d_packed[s], bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                sc.d_packed[s] = nullptr;
+                return fail(CS_ERR_OOM, "similar clusters: no room for the f16 filter copy (%llu bytes)", (unsigned long long)bytes);
+            }
+        }
+    }
+    GroupView gv{nullptr, 0, h->ledger.id_base(), 0xFFFFFFFFu};
+    if (plan.tile_pairs && mode == CS_PAIRS_OTHER_GROUP) CS_TRY(ensure_groups(h, 0xFFFFFFFFu, &gv));
+    CS_TRY(reserve_buf(w->d_parent, w->parent_cap, (size_t)stored));
+    CS_TRY(reserve_buf(w->d_mark, w->mark_cap, (size_t)stored));
+    CS_TRY(reserve_buf(w->d_tile_root, w->tile_root_cap, (size_t)(plan.tiles_a + plan.tiles_b)));
+    CS_TRY(reserve_buf(w->d_label, w->label_cap, (size_t)(2 * entries)));  // ids, then labels, per list entry
+    if (plan.tile_pairs) CS_TRY(reserve_buf(w->d_amb, w->amb_cap, (size_t)plan.ambiguous_cap));
+    CS_HIP(hipEventCreate(&sc.ev[0]));
+    CS_HIP(hipEventCreate(&sc.ev[1]));
+    CS_HIP(hipMemsetAsync(w->d_counters, 0, 4 * sizeof(uint64_t), w->stream));
+    CS_TRY(launch_clusters_scoped_init(w->d_parent, w->d_mark, sa->d_list, plan.rows_a, sb->d_list, second, w->stream));
+    const RowIds ids = h->row_ids();
+    bool rescore_timed = false;
+    float ms = 0.0f;
+    if (plan.tile_pairs) {
+        CS_HIP(hipEventRecord(w->ev[0], w->stream));
+        CS_TRY(launch_pairs_pack(h->d_corpus, h->d_norms, sa->d_list, plan.rows_a, h->dim, sc.d_packed[0], w->stream));
+        if (!same) CS_TRY(launch_pairs_pack(h->d_corpus, h->d_norms, sb->d_list, plan.rows_b, h->dim, sc.d_packed[1], w->stream));
+        CS_HIP(hipEventRecord(w->ev[1], w->stream));
+        CS_HIP(hipStreamSynchronize(w->stream));
+        CS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
+        info.pack_ms = ms;
+        const _Float16* d_b = same ? sc.d_packed[0] : sc.d_packed[1];
+        uint32_t* const d_root_a = w->d_tile_root;
+        uint32_t* const d_root_b = same ? d_root_a : d_root_a + plan.tiles_a;
+        CS_TRY(clusters_walk(h, w, sc.ev, plan, ids, min_cos, info, rescore_timed, [&](const PairsBand& r) -> int32_t {
+            CS_TRY(launch_clusters_scoped_tile_roots(w->d_parent, sa->d_list, plan.rows_a, d_root_a, w->stream));
+            if (!same) CS_TRY(launch_clusters_scoped_tile_roots(w->d_parent, sb->d_list, plan.rows_b, d_root_b, w->stream));
+            return launch_clusters_scoped_join(plan, sc.d_packed[0], d_b, sa->d_list, sb->d_list, h->dim, r.first, r.count, ids, gv,
+                                               mode == CS_PAIRS_OTHER_GROUP, min_cos, h->filter_margin, h->d_norms, w->d_parent,
+                                               d_root_a, d_root_b, w->d_amb, w->d_counters, w->stream);
+        }));
+    }
+    uint32_t* const d_ids = w->d_label;
+    uint32_t* const d_lab = w->d_label + entries;
+    CS_HIP(hipEventRecord(w->ev[0], w->stream));
+    CS_TRY(launch_clusters_scoped_label(w->d_parent, w->d_mark, sa->d_list, plan.rows_a, sb->d_list, second, ids, d_ids, d_lab,
+                                        w->d_counters + 2, w->stream));
+    CS_HIP(hipEventRecord(w->ev[1], w->stream));
+    CS_HIP(hipMemcpyAsync(w->h_counters + 2, w->d_counters + 2, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, w->stream));
+    std::vector<uint32_t> staged((size_t)(2 * entries));
+    CS_HIP(hipMemcpyAsync(staged.data(), w->d_label, staged.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, w->stream));
+    CS_HIP(hipStreamSynchronize(w->stream));
+    CS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
+    info.label_ms = ms;
+    if (rescore_timed) {
+        CS_HIP(hipEventElapsedTime(&ms, sc.ev[0], sc.ev[1]));
+        info.join_ms += ms;
+    }
+    // the two segments ascend by id (rows ascend with ids): one merge, a row of both lists once.  At most `entries` <= cap.
+    const uint32_t* const sid = staged.data();
+    const uint32_t* const slab = staged.data() + entries;
+    uint64_t n = 0, i = 0, j = plan.rows_a;
+    while (i < plan.rows_a || j < entries) {
+        uint64_t take;
+        if (j >= entries || (i < plan.rows_a && sid[i] <= sid[j])) {
+            if (j < entries && sid[i] == sid[j]) ++j;
+            take = i++;
+        } else {
+            take = j++;
+        }
+        out_ids[n] = sid[take];
+        out_label[n] = slab[take];
+        ++n;
+    }
+    *out_n = n;
+    if (out_clusters) *out_clusters = w->h_counters[2];
+    if (out_members) *out_members = w->h_counters[3];
+    info.vertices = n;
+    last_clusters_info = info;
+    return CS_OK;
 }
 
 }  // namespace
@@ -2451,6 +2633,21 @@ int32_t cs_index_similar_clusters_info(uint64_t* tile_pairs_scored, uint64_t* ti
     if (launches) *launches = i.launches;
     if (join_ms) *join_ms = i.join_ms;
     if (label_ms) *label_ms = i.label_ms;
+    return CS_OK;
+}
+
+int32_t cs_index_similar_clusters_scoped(cs_index* h, cs_scope* scope_a, cs_scope* scope_b, float min_cos, int32_t mode,
+                                         uint32_t* out_ids, uint32_t* out_label, uint64_t cap, uint64_t* out_n,
+                                         uint64_t* out_clusters, uint64_t* out_members) {
+    return similar_clusters_scoped(h, scope_a, scope_b, min_cos, mode, out_ids, out_label, cap, out_n, out_clusters, out_members);
+}
+
+int32_t cs_index_similar_clusters_scoped_info(double* pack_ms, uint64_t* rows_a, uint64_t* rows_b, uint64_t* vertices) {
+    const ClustersInfo& i = last_clusters_info;
+    if (pack_ms) *pack_ms = i.pack_ms;
+    if (rows_a) *rows_a = i.rows_a;
+    if (rows_b) *rows_b = i.rows_b;
+    if (vertices) *vertices = i.vertices;
     return CS_OK;
 }
 

@@ -292,6 +292,33 @@ int32_t launch_clusters_rescore(const float* d_corpus, uint32_t dim, const uint6
 int32_t launch_clusters_label(uint32_t* d_parent, uint32_t* d_mark, uint64_t n_rows, const uint32_t* d_dead, RowIds ids,
                               uint32_t* d_label, uint64_t n_labels, uint64_t* d_totals, hipStream_t stream);
 
+// ---- scoped similar-clusters search (scan_clusters_scoped.hip, plan: clusters_scoped_plan.hpp) --------------
+// The union-find stays over stored rows (d_parent, d_mark: [stored rows]), but only the words of the rows the two lists
+// name (ascending live rows; rows_b == 0: one list) are written or read by anything below.
+// d_parent[r] = r and d_mark[r] = 0 for every row of the lists.
+int32_t launch_clusters_scoped_init(uint32_t* d_parent, uint32_t* d_mark, const uint32_t* d_list_a, uint64_t rows_a,
+                                    const uint32_t* d_list_b, uint64_t rows_b, hipStream_t stream);
+// d_tile_root[t] = the common root of the rows of packed tile t of the list (entries [128 t, 128 t + 128) below `rows`),
+// kClustersNoRoot when they have none; ceil(rows / 128) words.
+int32_t launch_clusters_scoped_tile_roots(uint32_t* d_parent, const uint32_t* d_list, uint64_t rows, uint32_t* d_tile_root,
+                                          hipStream_t stream);
+struct ClustersScopedPlan;
+// launch_clusters_join over the tile pairs [first, first + count) of the plan's triangle (one packed buffer, list and root
+// array, passed twice) or rectangle (two), packed as launch_pairs_pack leaves them: pairs are united, or appended to
+// d_amb[0, plan.ambiguous_cap) as stored rows (lower | higher << 32), through the lists; a row that meets itself is no pair.
+// The counters as there.  d_norms is required.
+int32_t launch_clusters_scoped_join(const ClustersScopedPlan& plan, const _Float16* d_packed_a, const _Float16* d_packed_b,
+                                    const uint32_t* d_list_a, const uint32_t* d_list_b, uint32_t dim, uint64_t first,
+                                    uint64_t count, RowIds ids, const GroupView& gv, bool other_group, float min_cos,
+                                    float margin, const float* d_norms, uint32_t* d_parent, const uint32_t* d_root_a,
+                                    const uint32_t* d_root_b, uint64_t* d_amb, uint64_t* d_counters, hipStream_t stream);
+// Entry i of the two lists laid end to end: d_out_ids[i] = its id, d_out_label[i] = the id of its row's root (rows_a + rows_b
+// words each); d_parent is flattened; d_totals[0] += components of two or more rows, d_totals[1] += rows in them, a row in
+// both lists counted once.
+int32_t launch_clusters_scoped_label(uint32_t* d_parent, uint32_t* d_mark, const uint32_t* d_list_a, uint64_t rows_a,
+                                     const uint32_t* d_list_b, uint64_t rows_b, RowIds ids, uint32_t* d_out_ids,
+                                     uint32_t* d_out_label, uint64_t* d_totals, hipStream_t stream);
+
 // corpus[(first_out_row + r) * dim + c] = cs_synth_value(seed, (first_row + r) * dim + c)
 int32_t launch_synth_fill(float* d_rows, uint64_t n, uint32_t dim, uint64_t seed,
                           uint64_t first_row, hipStream_t stream);

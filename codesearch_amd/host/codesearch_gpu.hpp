@@ -515,6 +515,36 @@ class VectorStore {
         for (size_t i = 0; i < out.size(); ++i) out[i] = SimilarPair{a[i], b[i], cos[i]};
         return out;
     }
+    // similar_clusters() inside `scope` (other == nullptr) or of the pairs between `scope` and `*other`
+    // (cs_index_similar_clusters_scoped): the vertices are the live ids of the two scopes and an edge needs one end in
+    // each.  NOT the unscoped classes restricted to the scope: a path through a chunk outside connects nothing.  Never
+    // refused for abundance.  The report's shape is the unscoped overload's.  One index only.
+    std::vector<std::vector<SearchResult>> similar_clusters(const Scope& scope, const Scope* other, float min_cos,
+                                                            bool other_files = true, size_t min_size = 2,
+                                                            uint64_t* clusters = nullptr, uint64_t* members = nullptr) const {
+        if (sh_) throw Error(CS_ERR_UNSUPPORTED, "a sharded store has no similar-clusters search: no cs_shards_ form yet");
+        const bool same = !other || other->handle() == scope.handle();
+        uint64_t cap = 0, nb = 0;
+        check(cs_scope_info(scope.handle(), &cap, nullptr, nullptr));
+        if (!same) check(cs_scope_info(other->handle(), &nb, nullptr, nullptr));
+        cap += nb;
+        std::vector<uint32_t> ids((size_t)cap), label((size_t)cap);
+        uint64_t n = 0;
+        check(cs_index_similar_clusters_scoped(h_, scope.handle(), same ? scope.handle() : other->handle(), min_cos,
+                                               other_files ? CS_PAIRS_OTHER_GROUP : CS_PAIRS_ALL, ids.data(), label.data(), cap,
+                                               &n, clusters, members));
+        std::map<uint32_t, std::vector<uint32_t>> by_label;  // ascending labels, members ascending
+        for (size_t i = 0; i < (size_t)n; ++i) by_label[label[i]].push_back(ids[i]);
+        std::vector<std::vector<SearchResult>> out;
+        for (const auto& kv : by_label) {
+            std::vector<SearchResult> rs = results(std::vector<float>(kv.second.size(), 1.0f), kv.second, (uint32_t)kv.second.size());
+            if (rs.size() >= (min_size ? min_size : 1)) out.push_back(std::move(rs));
+        }
+        std::stable_sort(out.begin(), out.end(), [](const std::vector<SearchResult>& x, const std::vector<SearchResult>& y) {
+            return x.size() > y.size();
+        });
+        return out;
+    }
     std::vector<SearchResult> search_variants_per_file(const std::vector<std::vector<float>>& variants, size_t limit,
                                                        uint32_t per_file, const Scope* scope = nullptr,
                                                        bool* high_confidence = nullptr) const {

@@ -1007,16 +1007,27 @@ class VectorStore:
         ra, rb = self._results(cos, a, len(a), keep_missing=True), self._results(cos, b, len(b), keep_missing=True)
         return [(x, y, y.score) for x, y in zip(ra, rb) if x is not None and y is not None]
 
-    def similar_clusters_raw(self, min_cos: float, other_files: bool = False):
+    def similar_clusters_raw(self, min_cos: float, other_files: bool = False, scope: Optional[Scope] = None,
+                             other: Optional[Scope] = None):
         """cs_index_similar_clusters: the clone classes of the store — the connected components of the graph whose edges are
         the pairs similar_pairs_raw(min_cos, other_files) would count (-inf / None: no bound).
         -> (labels [next_id - id_base] u32, clusters, members): labels[i] = the smallest id of the class of id id_base + i
         (its own id when it has no clone), CS_NO_ID (0xFFFFFFFF) for an id that is not live; the classes of two or more
-        ids; the ids in them.  There is no max_pairs: a store full of duplicates is answered, not refused."""
+        ids; the ids in them.  There is no max_pairs: a store full of duplicates is answered, not refused.
+        scope alone: the classes inside the scope; scope with other: the classes of the pairs with one chunk in each
+        (similar_clusters_scoped_raw, scattered: ids outside the two scopes are CS_NO_ID too).  That is NOT the unscoped
+        answer restricted to the scope: a path through a chunk outside connects nothing.  other without scope is a
+        ValueError."""
+        if other is not None and scope is None:
+            raise ValueError("other= needs scope=: the classes between two scopes")
         if self.sharded:
             raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no similar-clusters search: no cs_shards_ form yet")
         n = self.next_id() - self.id_base
         labels = np.full(max(n, 0), _lib.CS_NO_ID, np.uint32)
+        if scope is not None:
+            ids, lab, clusters, members = self.similar_clusters_scoped_raw(min_cos, other_files, scope, other)
+            labels[ids - np.uint32(self.id_base)] = lab
+            return labels, clusters, members
         clusters, members = C.c_uint64(0), C.c_uint64(0)
         bound = np.float32(-np.inf) if min_cos is None else np.float32(min_cos)
         _lib.check(self._lib.cs_index_similar_clusters(
@@ -1024,25 +1035,53 @@ class VectorStore:
             labels.ctypes.data_as(u32p), n, C.byref(clusters), C.byref(members)))
         return labels, int(clusters.value), int(members.value)
 
-    def similar_clusters_info(self) -> dict:
-        """cs_index_similar_clusters_info: what this thread's last similar_clusters_raw did — the join's tile pairs scored
-        and skipped (both tiles already one class), the pairs re-scored exactly, the join's launches, and the device time
-        (ms) of the launches and of the labelling."""
+    def similar_clusters_scoped_raw(self, min_cos: float, other_files: bool, scope: Scope, other: Optional[Scope] = None):
+        """cs_index_similar_clusters_scoped as it answers: -> (ids [n] u32, labels [n] u32, clusters, members), the live ids
+        of the scope (of both scopes, each id once) ascending and, for each, the smallest id of its class."""
+        if self.sharded:
+            raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no similar-clusters search: no cs_shards_ form yet")
+        sa = self._scope_handle(scope)
+        sb = sa if other is None else self._scope_handle(other)
+        cap = len(scope) + (0 if other is None or other is scope else len(other))
+        ids = np.zeros(cap, np.uint32)
+        lab = np.zeros(cap, np.uint32)
+        n, clusters, members = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        bound = np.float32(-np.inf) if min_cos is None else np.float32(min_cos)
+        _lib.check(self._lib.cs_index_similar_clusters_scoped(
+            self._h, sa, sb, float(bound), _lib.CS_PAIRS_OTHER_GROUP if other_files else _lib.CS_PAIRS_ALL,
+            ids.ctypes.data_as(u32p), lab.ctypes.data_as(u32p), cap, C.byref(n), C.byref(clusters), C.byref(members)))
+        m = int(n.value)
+        return ids[:m], lab[:m], int(clusters.value), int(members.value)
+
+    def similar_clusters_info(self, scoped: bool = False) -> dict:
+        """cs_index_similar_clusters_info: what this thread's last similar_clusters_raw of either kind did — the join's tile
+        pairs scored and skipped (both tiles already one class), the pairs re-scored exactly, the join's launches, and the
+        device time (ms) of the launches and of the labelling.  scoped=True adds cs_index_similar_clusters_scoped_info's
+        fields: the packing's device time, the two sides' live rows (the smaller first) and the vertices returned — zeros
+        after an unscoped call.  (They are asked for, not always there: callers compare the plain dict as a whole.)"""
         scored, skipped, rescored, launches = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
         j, lab = C.c_double(0), C.c_double(0)
         _lib.check(self._lib.cs_index_similar_clusters_info(C.byref(scored), C.byref(skipped), C.byref(rescored),
                                                             C.byref(launches), C.byref(j), C.byref(lab)))
-        return {"tile_pairs_scored": int(scored.value), "tile_pairs_skipped": int(skipped.value),
+        info = {"tile_pairs_scored": int(scored.value), "tile_pairs_skipped": int(skipped.value),
                 "rescored_pairs": int(rescored.value), "launches": int(launches.value), "join_ms": j.value,
                 "label_ms": lab.value}
+        if scoped:
+            pack, ra, rb, nv = C.c_double(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+            _lib.check(self._lib.cs_index_similar_clusters_scoped_info(C.byref(pack), C.byref(ra), C.byref(rb), C.byref(nv)))
+            info.update({"pack_ms": pack.value, "rows_a": int(ra.value), "rows_b": int(rb.value), "vertices": int(nv.value)})
+        return info
 
-    def similar_clusters(self, min_score: float, other_files: bool = True, min_size: int = 2) -> List[List[SearchResult]]:
+    def similar_clusters(self, min_score: float, other_files: bool = True, min_size: int = 2,
+                         scope: Optional[Scope] = None, other: Optional[Scope] = None) -> List[List[SearchResult]]:
         """The duplicate-code report by clone class: the classes of chunks connected by pairs whose score — the reference's
         scale, cos_to_score — is above min_score; other_files=True (the default): a pair of chunks of one file connects
         nothing (the files assigned at insert).  Classes of at least min_size chunks, the largest first, then by label (the
         smallest id); members by id.  A result's distance and score are those of a chunk against itself: a class carries
-        no cosine.  Chunks whose metadata is missing are skipped, as in search(); a class is sized by what remains."""
-        labels, _clusters, _members = self.similar_clusters_raw(score_to_cos(min_score), other_files=other_files)
+        no cosine.  Chunks whose metadata is missing are skipped, as in search(); a class is sized by what remains.
+        scope / other: the classes inside the scope, or of the pairs between the two scopes (similar_clusters_raw)."""
+        labels, _clusters, _members = self.similar_clusters_raw(score_to_cos(min_score), other_files=other_files,
+                                                                scope=scope, other=other)
         live = np.flatnonzero(labels != _lib.CS_NO_ID)
         classes = {}
         for i in live.tolist():

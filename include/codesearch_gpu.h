@@ -564,7 +564,8 @@ CS_API int32_t cs_index_similar_pairs_scoped_info(double* pack_ms, uint64_t* row
  * the built state, with their texts; a null out_label; mode outside the two values; a NaN min_cos; n_labels other than
  * cs_index_next_id(h) - id_base (CS_ERR_BAD_ARG, the text names the number wanted); a dim other than 384 / 768 / 1024
  * (CS_ERR_UNSUPPORTED, the text names the three); no f16 filter copy — CS_INDEX_SPLIT=0 (CS_ERR_UNSUPPORTED) or no room for
- * it (CS_ERR_OOM), the text says which.  A failing call writes nothing.  No scoped, cs_shards_ or device-pointer form yet. */
+ * it (CS_ERR_OOM), the text says which.  A failing call writes nothing.  The scoped form is
+ * cs_index_similar_clusters_scoped below; no cs_shards_ or device-pointer form yet. */
 #define CS_NO_ID 0xFFFFFFFFu             /* the label of an id that is not live */
 CS_API int32_t cs_index_similar_clusters(cs_index* h, float min_cos, int32_t mode,
                                          uint32_t* out_label, uint64_t n_labels,
@@ -578,6 +579,59 @@ CS_API int32_t cs_index_similar_clusters(cs_index* h, float min_cos, int32_t mod
 CS_API int32_t cs_index_similar_clusters_info(uint64_t* tile_pairs_scored, uint64_t* tile_pairs_skipped,
                                               uint64_t* rescored_pairs, uint32_t* launches,
                                               double* join_ms, double* label_ms);
+
+/* Similar-clusters search inside a scope and between two scopes — "the clone classes under src/", "what in vendor/ hangs
+ * together with what in src/".  THE RULE: let A and B be the live chunk ids in scope_a and scope_b at the moment of the
+ * call (the lists are refreshed first if a build has passed, as every scoped search does; cs_scope_info's `refreshes`
+ * moves then).  The vertices are the ids of A u B.  {a, b} with a < b is an edge exactly when
+ * cs_index_similar_pairs_scoped(h, scope_a, scope_b, min_cos, mode, ...) would count the pair: one end is in A and the other
+ * in B, either way round; its cosine — the similar search's bits with the lower id's stored row as the query — is strictly
+ * above min_cos and finite; and in CS_PAIRS_OTHER_GROUP the two chunks do not share a group other than CS_NO_GROUP.  The
+ * same handle passed twice means the classes inside one scope.
+ * The output is compact — nothing proportional to the store is written or read back: the vertices ascending by id, each
+ * once even when A and B overlap; out_ids[i] is the id and out_label[i] the SMALLEST id of its connected component (a
+ * vertex with no edge is its own label); *out_n = their number; *out_clusters = the components with at least two vertices,
+ * *out_members = the ids in them (each of the two optional).  `cap`, the length of out_ids and out_label, must be at least
+ * n_ids(scope_a) + (scope_a == scope_b ? 0 : n_ids(scope_b)), n_ids as cs_scope_info reports it: known on the host before
+ * anything is refreshed.  Bit for bit:
+ *   - two different handles holding the same ids give the same bytes as one handle passed twice; swapping the two
+ *     arguments changes nothing; repeated calls return identical bytes (the answer does not depend on how the device's
+ *     atomics landed);
+ *   - with a scope holding every issued id passed twice the answer is exactly cs_index_similar_clusters's labels at the
+ *     live ids, and its two counts;
+ *   - in every case the answer equals cs_index_similar_pairs_scoped's full list reduced to components over the live ids
+ *     of A u B, whenever that call is neither refused nor cut.
+ *   - NOT A RESTRICTION: the answer is not cs_index_similar_clusters's answer restricted to the scope.  Two chunks of the
+ *     scope that are connected only through a chunk outside it are NOT one class here: a path through a chunk outside
+ *     connects nothing.
+ *   - NEVER REFUSED FOR ABUNDANCE: there is no max_pairs and no candidate bound; near-duplicates inside or outside the
+ *     scopes never make the call refuse.  The device work is proportional to the scopes' live rows (squared, for the join),
+ *     not to the store: a union-find over the stored rows of which only the scopes' words are touched, an f16 buffer of
+ *     the call's own per side (2 * dim bytes per live row, freed before the call returns; no room: CS_ERR_OOM, the text
+ *     names the byte count) and the fixed 8-MiB buffer of the unscoped call.
+ *   - When the join holds no pair — a side without a live row, one scope with fewer than two live rows, two handles
+ *     holding the same single row — nothing is joined: CS_OK, every vertex its own label, both counts 0, and
+ *     cs_index_similar_clusters_info reports zero launches.
+ *   - The index and the scopes are left as they were: filter copies (the index's f16 copy is neither read nor made),
+ *     filter state and the bits of every search are unchanged, and cs_scope_route_info's counters do not move (this is
+ *     not a search).  Concurrent calls are safe, also beside searches and through the same scopes.
+ * Errors, in this order, each decided before a list is refreshed or anything is launched or written: those of
+ * cs_index_similar_clusters for the handle and the built state, with its texts; a null out_ids, out_label or out_n; mode
+ * outside the two values; a NaN min_cos; a null scope_a, then a null scope_b (CS_ERR_BAD_ARG, the text says which: NULL does
+ * not mean "the whole store"); a scope made for another store, a scope over a sharded store included (CS_ERR_BAD_ARG); a
+ * `cap` below the number above (CS_ERR_BAD_ARG, the text names the number wanted); the dim and the CS_INDEX_SPLIT=0
+ * refusals of cs_index_similar_clusters, with its texts.  A failing call writes nothing.
+ * cs_index_similar_clusters_info reports the calling thread's last clusters call of either kind. */
+CS_API int32_t cs_index_similar_clusters_scoped(cs_index* h, cs_scope* scope_a, cs_scope* scope_b,
+                                                float min_cos, int32_t mode,
+                                                uint32_t* out_ids, uint32_t* out_label, uint64_t cap, uint64_t* out_n,
+                                                uint64_t* out_clusters, uint64_t* out_members);
+/* DIAGNOSTIC, for benchmarks — not part of the search contract, an embedder needs no binding for it (INTEGRATION.md has
+ * none, as for cs_index_similar_pairs_scoped_info).  What the calling thread's last successful
+ * cs_index_similar_clusters_scoped did beside what cs_index_similar_clusters_info reports (each output optional): the device
+ * time of the packing in milliseconds, the live rows of the join's two sides (the smaller scope first; one scope: equal)
+ * and the vertices returned (*out_n).  After an unscoped call or none: zeros. */
+CS_API int32_t cs_index_similar_clusters_scoped_info(double* pack_ms, uint64_t* rows_a, uint64_t* rows_b, uint64_t* vertices);
 
 /* Synchronises `stream` and reports in *overflowed whether any cs_index_search_device call of more
  * than 16 queries issued by this thread on it since the previous status call overflowed a candidate buffer
