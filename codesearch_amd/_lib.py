@@ -96,6 +96,11 @@ SIGNATURES = {
     "cs_scope_info": (C.c_int32, [vp, u64p, u64p, u64p]),
     "cs_scope_set_route": (C.c_int32, [vp, C.c_int32]),
     "cs_scope_route_info": (C.c_int32, [vp, u64p, u64p, u64p, u64p]),
+    "cs_scope_combine": (C.c_int32, [vp, vp, C.c_int32, C.POINTER(vp)]),
+    "cs_index_scope_create_range": (C.c_int32, [vp, C.c_uint32, C.c_uint64, C.POINTER(vp)]),
+    "cs_shards_scope_create_range": (C.c_int32, [vp, C.c_uint32, C.c_uint64, C.POINTER(vp)]),
+    "cs_scope_read_ids": (C.c_int32, [vp, C.c_uint64, C.c_uint64, u32p]),
+    "cs_scope_ops_tile": (C.c_uint32, []),
     "cs_index_set_groups": (C.c_int32, [vp, u32p, u32p, C.c_uint64]),
     "cs_index_groups_info": (C.c_int32, [vp, u64p, u64p]),
     "cs_index_search_grouped": (C.c_int32, [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p]),

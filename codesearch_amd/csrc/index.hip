@@ -23,6 +23,7 @@
 #include "pairs_scoped_plan.hpp"
 #include "scan.hpp"
 #include "scope.hpp"
+#include "scope_ops_plan.hpp"
 #include "similar_route.hpp"
 #include "similar_sources.hpp"
 
@@ -909,6 +910,94 @@ int32_t scope_make_list(cs_index* h, cs_scope* sc) {
 int32_t check_scope_handle(const cs_index* h, const cs_scope* sc) {
     if (!sc) return fail(CS_ERR_BAD_ARG, "null scope handle");
     if (sc->index != h) return fail(CS_ERR_BAD_ARG, "the scope was made for another store");
+    return CS_OK;
+}
+
+// ---- the making of a scope: cs_index_scope_create, _create_range and cs_scope_combine differ only in where the ids come from
+
+cs_scope* new_index_scope(cs_index* h) {
+    cs_scope* sc = new cs_scope();
+    sc->index = h;
+    sc->device = h->device;
+    return sc;
+}
+
+// The buffers of a scope of n ids over h (and its stream, unless it has one); n == 0 holds nothing.  The index's device
+// is current.
+int32_t scope_alloc(cs_index* h, cs_scope* sc, uint64_t n) {
+    sc->n_ids = n;
+    if (!n) return CS_OK;
+    if (!sc->stream) CS_HIP(hipStreamCreateWithFlags(&sc->stream, hipStreamNonBlocking));
+    CS_HIP(realloc_buf(sc->d_ids, (size_t)n));
+    CS_HIP(realloc_buf(sc->d_list, (size_t)n));
+    CS_HIP(realloc_buf(sc->d_blocks, (size_t)scope_list_blocks(n) + 1));
+    // a scope that can ever take the int8 filter keeps the stride table and reads more back per making
+    const bool tables = h->use_q8 && scope_filter_capable(h->dim, n);
+    if (tables) {
+        sc->table_words = 1 + (size_t)scope_stride_entries(n);
+        CS_HIP(realloc_buf(sc->d_table, sc->table_words));
+    }
+    CS_HIP(realloc_buf(sc->h_len, tables ? 1 + sc->table_words + (size_t)scope_head_entries(n) : 1, true));
+    return CS_OK;
+}
+
+// The list of a scope whose ids are in place.  An index that is not built has rows the device does not know yet (the
+// row -> id table is uploaded by the build): the list is then made by the first search, which needs that build.
+int32_t scope_first_list(cs_index* h, cs_scope* sc) {
+    std::lock_guard<std::mutex> lk(sc->mu);
+    return h->built ? scope_make_list(h, sc) : CS_OK;
+}
+
+// cs_scope_combine over one index: the counting pass and the scan on the result's own stream, one read-back of the total
+// that sizes the result exactly (scope_alloc, as a create call of that many ids), the ordered write, then the list as every
+// scope gets it.  The inputs' d_ids and n_ids never change after their making, so nothing of a or b is locked.
+int32_t scope_combine_one(const cs_scope* a, const cs_scope* b, int32_t op, cs_scope** out) {
+    cs_index* h = a->index;
+    DeviceGuard g(h->device);
+    cs_scope* sc = new_index_scope(h);
+    uint32_t* d_tiles = nullptr;
+    const int32_t st = [&]() -> int32_t {
+        const uint64_t na = a->n_ids, nb = b->n_ids;
+        uint64_t n = 0;
+        // short cut: an empty a, or an intersection with an empty b, is the empty scope; nothing is launched
+        const bool empty = na == 0 ? (op != CS_SCOPE_OP_UNION || nb == 0) : (nb == 0 && op == CS_SCOPE_OP_INTERSECT);
+        if (!empty) {
+            CS_HIP(hipStreamCreateWithFlags(&sc->stream, hipStreamNonBlocking));
+            const uint64_t nt = scope_ops_tiles(na, nb);
+            CS_HIP(realloc_buf(d_tiles, (size_t)nt + 1));
+            CS_TRY(launch_scope_ops_count(a->d_ids, na, b->d_ids, nb, op, d_tiles, sc->stream));
+            uint32_t total = 0;
+            CS_HIP(hipMemcpyAsync(&total, d_tiles + nt, sizeof(uint32_t), hipMemcpyDeviceToHost, sc->stream));
+            CS_HIP(hipStreamSynchronize(sc->stream));
+            // the counts are u32: only a union of every u32 id (2^32 of them) wraps, to 0, and a union of a non-empty
+            // input is never empty
+            if (op == CS_SCOPE_OP_UNION && total == 0)
+                return fail(CS_ERR_BAD_ARG, "a scope holds at most 2^32 - 1 ids (ids are u32): the union names every id");
+            n = total;
+            if (!n) {  // an empty result holds what a create call of 0 ids holds: nothing, no stream either
+                CS_HIP(hipStreamDestroy(sc->stream));
+                sc->stream = nullptr;
+            }
+        }
+        CS_TRY(scope_alloc(h, sc, n));
+        if (n) {
+            CS_TRY(launch_scope_ops_write(a->d_ids, na, b->d_ids, nb, op, d_tiles, sc->d_ids, n, sc->stream));
+            CS_HIP(hipStreamSynchronize(sc->stream));
+        }
+        return scope_first_list(h, sc);
+    }();
+    free_bufs(false, d_tiles);
+    if (st != CS_OK) {
+        scope_free(sc);
+        return st;
+    }
+    *out = sc;
+    return CS_OK;
+}
+
+int32_t scope_part_read_ids(const cs_scope* sc, uint64_t first, uint64_t n, uint32_t* out_ids) {
+    DeviceGuard g(sc->device);
+    CS_HIP(hipMemcpy(out_ids, sc->d_ids + first, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return CS_OK;
 }
 
@@ -2676,30 +2765,14 @@ int32_t cs_index_scope_create(cs_index* h, const uint32_t* ids, uint64_t n, cs_s
     if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
     CS_TRY(check_scope_ids(ids, n));
     DeviceGuard g(h->device);
-    cs_scope* sc = new cs_scope();
-    sc->index = h;
-    sc->device = h->device;
-    sc->n_ids = n;
+    cs_scope* sc = new_index_scope(h);
     const int32_t st = [&]() -> int32_t {
+        CS_TRY(scope_alloc(h, sc, n));
         if (n) {
-            CS_HIP(hipStreamCreateWithFlags(&sc->stream, hipStreamNonBlocking));
-            CS_HIP(realloc_buf(sc->d_ids, (size_t)n));
-            CS_HIP(realloc_buf(sc->d_list, (size_t)n));
-            CS_HIP(realloc_buf(sc->d_blocks, (size_t)scope_list_blocks(n) + 1));
-            // a scope that can ever take the int8 filter keeps the stride table and reads more back per making
-            const bool tables = h->use_q8 && scope_filter_capable(h->dim, n);
-            if (tables) {
-                sc->table_words = 1 + (size_t)scope_stride_entries(n);
-                CS_HIP(realloc_buf(sc->d_table, sc->table_words));
-            }
-            CS_HIP(realloc_buf(sc->h_len, tables ? 1 + sc->table_words + (size_t)scope_head_entries(n) : 1, true));
             CS_HIP(hipMemcpyAsync(sc->d_ids, ids, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, sc->stream));
             CS_HIP(hipStreamSynchronize(sc->stream));  // `ids` is the caller's again
         }
-        // an index that is not built has rows the device does not know yet (the row -> id table is uploaded by the
-        // build): the list is made by the first search, which needs that build
-        std::lock_guard<std::mutex> lk(sc->mu);
-        return h->built ? scope_make_list(h, sc) : CS_OK;
+        return scope_first_list(h, sc);
     }();
     if (st != CS_OK) {
         scope_free(sc);
@@ -2708,6 +2781,77 @@ int32_t cs_index_scope_create(cs_index* h, const uint32_t* ids, uint64_t n, cs_s
     *out = sc;
     return CS_OK;
 }
+
+int32_t cs_index_scope_create_range(cs_index* h, uint32_t first_id, uint64_t n, cs_scope** out) {
+    if (!out) return fail(CS_ERR_BAD_ARG, "out is null");
+    *out = nullptr;
+    if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
+    CS_TRY(check_scope_range(first_id, n));
+    DeviceGuard g(h->device);
+    cs_scope* sc = new_index_scope(h);
+    const int32_t st = [&]() -> int32_t {
+        CS_TRY(scope_alloc(h, sc, n));
+        if (n) {
+            CS_TRY(launch_scope_range(first_id, n, sc->d_ids, sc->stream));
+            CS_HIP(hipStreamSynchronize(sc->stream));
+        }
+        return scope_first_list(h, sc);
+    }();
+    if (st != CS_OK) {
+        scope_free(sc);
+        return st;
+    }
+    *out = sc;
+    return CS_OK;
+}
+
+int32_t cs_scope_combine(const cs_scope* a, const cs_scope* b, int32_t op, cs_scope** out) {
+    if (!out) return fail(CS_ERR_BAD_ARG, "out is null");
+    *out = nullptr;
+    if (!a) return fail(CS_ERR_BAD_ARG, "null scope handle (a)");
+    if (!b) return fail(CS_ERR_BAD_ARG, "null scope handle (b)");
+    if (op != CS_SCOPE_OP_UNION && op != CS_SCOPE_OP_INTERSECT && op != CS_SCOPE_OP_DIFFERENCE)
+        return fail(CS_ERR_BAD_ARG, "op must be CS_SCOPE_OP_UNION, _INTERSECT or _DIFFERENCE, got %d", op);
+    if ((a->index != nullptr) != (b->index != nullptr))
+        return fail(CS_ERR_BAD_ARG, "the scopes were made for different stores: one over an index, one over a sharded store");
+    if (a->index != b->index || a->shards != b->shards || a->parts.size() != b->parts.size())
+        return fail(CS_ERR_BAD_ARG, "the scopes were made for different stores");
+    if (a->index) return scope_combine_one(a, b, op, out);
+    // sharded: the stripe map sends one global id to one shard, so the per-shard operations are the global one
+    cs_scope* sc = new cs_scope();
+    sc->shards = a->shards;
+    uint64_t total = 0;
+    for (size_t s = 0; s < a->parts.size(); ++s) {
+        cs_scope* part = nullptr;
+        int32_t st = scope_combine_one(a->parts[s], b->parts[s], op, &part);
+        if (st == CS_OK) {
+            sc->parts.push_back(part);
+            total += part->n_ids;
+            if (total > 0xffffffffull) st = fail(CS_ERR_BAD_ARG, "a scope holds at most 2^32 - 1 ids (ids are u32): the union names every id");
+        }
+        if (st != CS_OK) {
+            scope_free(sc);
+            return st;
+        }
+    }
+    *out = sc;
+    return CS_OK;
+}
+
+int32_t cs_scope_read_ids(const cs_scope* scope, uint64_t first, uint64_t n, uint32_t* out_ids) {
+    if (!scope) return fail(CS_ERR_BAD_ARG, "null scope handle");
+    uint64_t have = scope->n_ids;
+    for (const cs_scope* p : scope->parts) have += p->n_ids;  // (n_ids never changes after the scope was made)
+    if (first > have || n > have - first)
+        return fail(CS_ERR_BAD_ARG, "ids [%llu, %llu) asked of a scope of %llu ids", (unsigned long long)first,
+                    (unsigned long long)(first + n), (unsigned long long)have);
+    if (n == 0) return CS_OK;
+    if (!out_ids) return fail(CS_ERR_BAD_ARG, "null buffer");
+    if (!scope->index) return shards_scope_read_ids(scope, first, n, out_ids);
+    return scope_part_read_ids(scope, first, n, out_ids);
+}
+
+uint32_t cs_scope_ops_tile(void) { return kScopeOpsTile; }
 
 void cs_scope_destroy(cs_scope* scope) {
     if (scope) scope_free(scope);

@@ -104,6 +104,22 @@ int32_t launch_scope_filter_state(const uint32_t* d_list, const uint32_t* d_len,
 // (scope_refresh_due); the index must be built.
 int32_t index_scope_live_rows(cs_index* h, cs_scope* scope, uint64_t* live_rows);
 
+// ---- scope algebra (scope_ops.hip; plan: scope_ops_plan.hpp) ---------------------------------------
+// scan_masked.hip: d_blocks[0, nb) -> their exclusive prefix sums, d_blocks[nb] = the total (mask_scan_kernel, one block).
+int32_t launch_mask_scan(uint32_t* d_blocks, uint32_t nb, hipStream_t stream);
+// The set operation `op` (CS_SCOPE_OP_*) over the strictly ascending d_a[0, na) and d_b[0, nb).  Count: d_tiles
+// [scope_ops_tiles(na, nb) + 1] receives the per-tile offsets of the result and, last, its length (mod 2^32).  Write: the
+// result, ascending, into d_out[0, out_cap) from the offsets the count pass left.
+int32_t launch_scope_ops_count(const uint32_t* d_a, uint64_t na, const uint32_t* d_b, uint64_t nb, int32_t op, uint32_t* d_tiles,
+                               hipStream_t stream);
+int32_t launch_scope_ops_write(const uint32_t* d_a, uint64_t na, const uint32_t* d_b, uint64_t nb, int32_t op, uint32_t* d_tiles,
+                               uint32_t* d_out, uint64_t out_cap, hipStream_t stream);
+// d_out[i] = first + i for i < n (first + n <= 2^32).
+int32_t launch_scope_range(uint32_t first, uint64_t n, uint32_t* d_out, hipStream_t stream);
+// shards.hip: positions [first, first + n) of a sharded scope's global ids, ascending (the parts' ids read back, restated
+// as global ids and merged on the host); the range has been checked.
+int32_t shards_scope_read_ids(const cs_scope* scope, uint64_t first, uint64_t n, uint32_t* out_ids);
+
 // ---- grouped search (scan_grouped.hip, plan: grouped_plan.hpp) -----------------------------------
 // The group table of an index as the kernels read it: groups[id - id_base] for ids below id_base + len, CS_NO_GROUP for
 // every other id (and for all of them when groups is null); at most per_group rows of a group are kept.

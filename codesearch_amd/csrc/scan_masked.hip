@@ -134,6 +134,13 @@ int32_t launch_mask_rows(const uint32_t* d_allow, uint64_t allow_lo, uint64_t al
     return CS_OK;
 }
 
+// mask_scan_kernel for another two-pass compaction (scope_ops.hip): any nb, totals modulo 2^32.
+int32_t launch_mask_scan(uint32_t* d_blocks, uint32_t nb, hipStream_t stream) {
+    hipLaunchKernelGGL(mask_scan_kernel, dim3(1), dim3(1024), 0, stream, d_blocks, nb);
+    CS_HIP(hipGetLastError());
+    return CS_OK;
+}
+
 // ---- 2. gathered scan ----------------------------------------------------------------------------
 // scan_topk_kernel (scan.hip) over the list: see there for J, U, QT and the PRIME mode.
 template <int J, int U, int QT, bool PRIME = false>
@@ -473,7 +480,11 @@ int32_t launch_scope_filter_state(const uint32_t* d_list, const uint32_t* d_len,
                                   uint32_t* d_blocked, uint32_t* d_table, hipStream_t stream) {
     CS_HIP(hipMemsetAsync(d_blocked, 0xFF, (size_t)scope_blocked_words(n_rows) * sizeof(uint32_t), stream));
     if (list_cap == 0) return CS_OK;
-    hipLaunchKernelGGL(scope_unblock_kernel, dim3((uint32_t)((list_cap + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
+    // the list holds live rows only, so *d_len <= n_rows: threads past it have nothing to do, and a scope that names
+    // more ids than the store has rows (a range of up to 2^32 - 1 ids) must not size the grid — 2^24 blocks of 256 are
+    // more threads than a launch takes
+    const uint64_t entries = list_cap < n_rows ? list_cap : n_rows;
+    hipLaunchKernelGGL(scope_unblock_kernel, dim3((uint32_t)((entries + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
                        d_list, d_len, d_blocked, d_table);
     CS_HIP(hipGetLastError());
     return CS_OK;

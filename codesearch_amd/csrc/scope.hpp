@@ -70,4 +70,15 @@ inline int32_t check_scope_ids(const uint32_t* ids, uint64_t n) {
     return CS_OK;
 }
 
+// The range of a create_range call, over one index or over shards: ids [first_id, first_id + n) inside u32, at most
+// 2^32 - 1 of them.
+inline int32_t check_scope_range(uint32_t first_id, uint64_t n) {
+    if (n > 0xffffffffull)
+        return fail(CS_ERR_BAD_ARG, "a scope holds at most 2^32 - 1 ids (ids are u32), got %llu", (unsigned long long)n);
+    if ((uint64_t)first_id + n > (1ull << 32))
+        return fail(CS_ERR_BAD_ARG, "the range [%u, %u + %llu) ends past 2^32 (ids are u32)", first_id, first_id,
+                    (unsigned long long)n);
+    return CS_OK;
+}
+
 }  // namespace cs

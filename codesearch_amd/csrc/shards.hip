@@ -34,6 +34,7 @@
 #include "masked_plan.hpp"
 #include "scan.hpp"
 #include "scope.hpp"
+#include "scope_ops_plan.hpp"
 
 using namespace cs;
 
@@ -780,6 +781,29 @@ int32_t cs_shards_scope_create(cs_shards* h, const uint32_t* ids, uint64_t n, cs
     return CS_OK;
 }
 
+int32_t cs_shards_scope_create_range(cs_shards* h, uint32_t first_id, uint64_t n, cs_scope** out) {
+    if (!out) return fail(CS_ERR_BAD_ARG, "out is null");
+    *out = nullptr;
+    if (!h) return fail(CS_ERR_BAD_ARG, "null shards handle");
+    CS_TRY(check_scope_range(first_id, n));
+    cs_scope* sc = new cs_scope();
+    sc->shards = h;
+    for (uint32_t s = 0; s < h->n; ++s) {
+        // a shard's local ids are dense, so the global range is one local range there (scope_ops_plan.hpp)
+        const uint64_t lo = shard_ids_below(first_id, h->stripe, h->n, s);
+        const uint64_t cnt = shard_ids_below((uint64_t)first_id + n, h->stripe, h->n, s) - lo;
+        cs_scope* part = nullptr;
+        const int32_t st = cs_index_scope_create_range(h->idx[s], (uint32_t)lo, cnt, &part);
+        if (st != CS_OK) {
+            cs_scope_destroy(sc);
+            return st;
+        }
+        sc->parts.push_back(part);
+    }
+    *out = sc;
+    return CS_OK;
+}
+
 int32_t cs_shards_search_scoped(cs_shards* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
                                 float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
     bool empty = true;
@@ -813,3 +837,21 @@ int32_t cs_shards_search_variants_scoped(cs_shards* h, cs_scope* scope, const fl
 }
 
 }  // extern "C"
+
+// cs_scope_read_ids over a sharded scope: every part's local ids read back and restated as global ids (ascending inside a
+// part), the parts merged on the host, positions [first, first + n) copied out.  Which local ids fall into a window of
+// global positions is not known without the ids, so every call reads all of them: O(n_ids), as the header says.
+int32_t cs::shards_scope_read_ids(const cs_scope* scope, uint64_t first, uint64_t n, uint32_t* out_ids) {
+    const cs_shards* h = scope->shards;
+    std::vector<uint32_t> all;
+    for (uint32_t s = 0; s < (uint32_t)scope->parts.size(); ++s) {
+        const cs_scope* p = scope->parts[s];
+        const size_t at = all.size();
+        all.resize(at + (size_t)p->n_ids);
+        CS_TRY(cs_scope_read_ids(p, 0, p->n_ids, all.data() + at));
+        for (size_t i = at; i < all.size(); ++i) all[i] = (uint32_t)shard_global_id(all[i], h->stripe, h->n, s);
+        std::inplace_merge(all.begin(), all.begin() + (ptrdiff_t)at, all.end());
+    }
+    memcpy(out_ids, all.data() + first, (size_t)n * sizeof(uint32_t));
+    return CS_OK;
+}

@@ -387,11 +387,36 @@ class VectorStore {
                         uint64_t* extra_bytes) const {
             check(cs_scope_route_info(h_, filter_searches, gathered_searches, overflow_reruns, extra_bytes));
         }
+        // Scope algebra on the device (cs_scope_combine): a new Scope of the same store holding the union (CS_SCOPE_OP_UNION),
+        // the intersection (_INTERSECT) or the difference (_DIFFERENCE: this minus other) of the two id sets.  It answers as
+        // a Scope made from the host-computed set would; the operands are only read.
+        Scope combine(const Scope& other, int32_t op) const {
+            Scope out;
+            check(cs_scope_combine(h_, other.h_, op, &out.h_));
+            return out;
+        }
+        // the scope's id set, ascending (global ids over a sharded store): cs_scope_read_ids
+        std::vector<uint32_t> read_ids() const {
+            uint64_t n = 0;
+            check(cs_scope_info(h_, &n, nullptr, nullptr));
+            std::vector<uint32_t> ids((size_t)n);
+            check(cs_scope_read_ids(h_, 0, n, ids.data()));
+            return ids;
+        }
 
       private:
+        friend class VectorStore;
+        Scope() = default;
         cs_scope* h_ = nullptr;
     };
     Scope scope(std::vector<uint32_t> ids) const { return Scope(*this, std::move(ids)); }
+    // The scope of ids [first_id, first_id + n), written on the device (cs_index_scope_create_range / cs_shards_): with
+    // combine(), "everything but x" is scope_range(id_base, next_id - id_base).combine(x, CS_SCOPE_OP_DIFFERENCE).
+    Scope scope_range(uint32_t first_id, uint64_t n) const {
+        Scope out;
+        check(sh_ ? cs_shards_scope_create_range(sh_, first_id, n, &out.h_) : cs_index_scope_create_range(h_, first_id, n, &out.h_));
+        return out;
+    }
     // search / search_variants over a prepared Scope (cs_index_search_scoped / cs_index_search_variants_scoped & the
     // cs_shards_ forms)
     std::vector<SearchResult> search(const std::vector<float>& query_embedding, size_t limit, const Scope& scope) const {

@@ -186,19 +186,85 @@ class Scope:
     """A prepared set of chunk ids of one VectorStore (cs_scope): ids and the row list made from them live on the device,
     and a search with `scope=` returns what the same search with `chunk_ids=` of those ids returns, without building,
     copying or compacting a mask.  The row list follows the store: the first search after a build remakes it.
-    Made by VectorStore.scope(); a context manager; keeps its store alive."""
+    Made by VectorStore.scope(); a context manager; keeps its store alive.
 
-    def __init__(self, store: "VectorStore", chunk_ids):
+    Scopes of one store combine on the device (cs_scope_combine): `a | b`, `a & b`, `a - b` (union, intersection,
+    difference) each give a new Scope that answers exactly as VectorStore.scope() of the host-computed id set would;
+    VectorStore.scope_range() / scope_all() make a range of ids without a host list, so "everything but X" is
+    `store.scope_all() - x`.  The ids of such a scope never pass through the host unless `.ids` is asked for."""
+
+    OPS = {"union": 0, "intersection": 1, "difference": 2}  # CS_SCOPE_OP_*
+
+    def __init__(self, store: "VectorStore", chunk_ids=None, _handle=None):
         self._h = None
-        self.ids = scope_ids(chunk_ids)
         self.store = store  # (a scope must be destroyed before its store)
+        if _handle is not None:  # made on the device (combine, scope_range): `ids` is read back when asked for
+            self._h = _handle
+            return
+        self.ids = scope_ids(chunk_ids)
         h = C.c_void_p()
         _lib.check(store._fn("scope_create")(store._h, self.ids.ctypes.data_as(u32p) if self.ids.size else None,
                                              self.ids.size, C.byref(h)))
         self._h = h
 
+    _ids = None  # the id set on the host: a host-made scope's from the start, a device-made one's once asked for
+    _n = None    # a device-made scope's length (cs_scope_info), asked once
+
+    @property
+    def ids(self) -> np.ndarray:
+        """The scope's id set, ascending u32.  A device-made scope reads it back at the first use (cs_scope_read_ids) and
+        keeps it — the set never changes.  Ids read before close() stay readable after it; ids never read then raise
+        "scope is closed".  Two threads that both ask first both read back, the same bytes; one array is kept."""
+        if self._ids is None:
+            if not self._h:
+                raise CsError(_lib.CS_ERR_BAD_ARG, "scope is closed")
+            ids = np.empty(len(self), np.uint32)
+            _lib.check(self.store._lib.cs_scope_read_ids(self._h, 0, ids.size, ids.ctypes.data_as(u32p) if ids.size else None))
+            self._ids = ids
+        return self._ids
+
+    @ids.setter
+    def ids(self, value) -> None:
+        self._ids = value
+
     def __len__(self) -> int:
-        return int(self.ids.size)
+        if self._ids is not None:
+            return int(self._ids.size)
+        if self._n is None:
+            self._n = self.info()[0]
+        return self._n
+
+    def _combine(self, other: "Scope", op: str) -> "Scope":
+        if not isinstance(other, Scope):
+            raise TypeError(f"a Scope combines with a Scope, not {type(other).__name__}")
+        if not self._h or not other._h:
+            raise CsError(_lib.CS_ERR_BAD_ARG, "scope is closed")
+        h = C.c_void_p()  # (a scope of another store is the library's to refuse)
+        _lib.check(self.store._lib.cs_scope_combine(self._h, other._h, self.OPS[op], C.byref(h)))
+        sc = Scope(self.store, _handle=h)
+        self.store._scopes.add(sc)
+        return sc
+
+    def union(self, other: "Scope") -> "Scope":
+        """A new Scope of this store holding the ids of either (cs_scope_combine, on the device)."""
+        return self._combine(other, "union")
+
+    def intersection(self, other: "Scope") -> "Scope":
+        """A new Scope holding the ids of both."""
+        return self._combine(other, "intersection")
+
+    def difference(self, other: "Scope") -> "Scope":
+        """A new Scope holding the ids of this scope that `other` does not hold."""
+        return self._combine(other, "difference")
+
+    def __or__(self, other):
+        return self.union(other) if isinstance(other, Scope) else NotImplemented
+
+    def __and__(self, other):
+        return self.intersection(other) if isinstance(other, Scope) else NotImplemented
+
+    def __sub__(self, other):
+        return self.difference(other) if isinstance(other, Scope) else NotImplemented
 
     def __bool__(self) -> bool:
         return True  # an empty scope is still a scope: `if scope:` must not turn its search into an unscoped one
@@ -706,6 +772,21 @@ class VectorStore:
         sc = Scope(self, chunk_ids)
         self._scopes.add(sc)
         return sc
+
+    def scope_range(self, first_id: int, n: int) -> Scope:
+        """A Scope of the ids [first_id, first_id + n), written on the device (cs_index_scope_create_range /
+        cs_shards_scope_create_range): no host list, no upload.  A snapshot of the ids named, like any scope."""
+        if first_id < 0 or first_id > 0xFFFFFFFF or n < 0:
+            raise ValueError(f"scope_range: first_id must be a u32 and n >= 0, got {first_id}, {n}")
+        h = C.c_void_p()
+        _lib.check(self._fn("scope_create_range")(self._h, int(first_id), int(n), C.byref(h)))
+        sc = Scope(self, _handle=h)
+        self._scopes.add(sc)
+        return sc
+
+    def scope_all(self) -> Scope:
+        """scope_range over every id issued so far, [id_base, next_id): `store.scope_all() - x` is "everything but x"."""
+        return self.scope_range(self.id_base, self.next_id() - self.id_base)
 
     def _scope_handle(self, scope: Scope):
         if not scope._h:  # (a scope of another store is the library's to refuse)

@@ -251,6 +251,35 @@ CS_API int32_t cs_scope_set_route(cs_scope* scope, int32_t route);
  * 3,072 rows, the bitmap; 0 for every other scope.  Each output optional.  Over a sharded store all are 0. */
 CS_API int32_t cs_scope_route_info(const cs_scope* scope, uint64_t* filter_searches, uint64_t* gathered_searches,
                                    uint64_t* overflow_reruns, uint64_t* extra_bytes);
+/* Scope algebra — union, intersection and difference of two scopes, on the device.  Real filters are compositions:
+ * "src/ without src/vendor/", "under tests/ and Rust", "everything but generated code".  The id sets are ascending and
+ * already in HBM, so combining two is one streaming merge (merge path, scope_ops.hip) instead of a host set operation and
+ * an upload.
+ * THE RULE: the scope cs_scope_combine returns answers every scoped call bit for bit, counts and flags included, as a
+ * scope made by cs_index_scope_create / cs_shards_scope_create from the host-computed union / intersection / difference
+ * (a minus b) of the two id sets — at that moment, after every later build, delete, append and clear, on every route.
+ * The operation is on id sets, not rows: it does not depend on the store's state, works on a store that is not built, and
+ * ids never issued or already deleted pass through as cs_index_scope_create lets them.  The result is a new, independent
+ * scope of the same store: its own buffers and stream, route AUTO, counters 0, its list made now if the store is built,
+ * else by the first search.  The inputs are only read and may be destroyed before the result; a == b is legal.  Over a
+ * sharded store the parts are combined one by one (a global id lives on one shard).
+ * Errors, in this order, each decided before anything is launched or allocated: a null out; a null a, then a null b; an
+ * op outside 0..2; scopes of different stores, or one over an index and one over shards (CS_ERR_BAD_ARG, the text says
+ * which).  A result of more than 2^32 - 1 ids — only the union of two scopes that together name every u32 id — is
+ * CS_ERR_BAD_ARG, the create call's limit, known after the counting pass.  A failing call leaves *out NULL and leaks
+ * nothing.
+ * cs_index_scope_create_range: the scope of ids [first_id, first_id + n), written by a kernel (no host list, no upload) —
+ * "everything but X" is difference(range(id_base, next_id - id_base), X).  A snapshot of the ids named, like any scope.
+ * first_id + n > 2^32 is CS_ERR_BAD_ARG, as is n > 2^32 - 1; n == 0 is the empty scope.
+ * cs_scope_read_ids: positions [first, first + n) of the scope's ascending id set into out_ids (first + n > n_ids:
+ * CS_ERR_BAD_ARG); over a sharded scope global ids, ascending — every part's whole id set is read back and merged on the
+ * host for each call, whatever the window, so read a large sharded scope once, not in pages.
+ * cs_scope_ops_tile: the ids of a and b together that one block of the set-operation kernels consumes. */
+enum { CS_SCOPE_OP_UNION = 0, CS_SCOPE_OP_INTERSECT = 1, CS_SCOPE_OP_DIFFERENCE = 2 /* a minus b */ };
+CS_API int32_t cs_scope_combine(const cs_scope* a, const cs_scope* b, int32_t op, cs_scope** out);
+CS_API int32_t cs_index_scope_create_range(cs_index* h, uint32_t first_id, uint64_t n, cs_scope** out);
+CS_API int32_t cs_scope_read_ids(const cs_scope* scope, uint64_t first, uint64_t n, uint32_t* out_ids);
+CS_API uint32_t cs_scope_ops_tile(void);
 /* cs_index_search_masked / cs_index_search_variants_masked with the scope in place of the mask.  Errors: those of
  * cs_index_search with the same texts, checked first; then a scope made for another store is CS_ERR_BAD_ARG. */
 CS_API int32_t cs_index_search_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,
@@ -734,6 +763,9 @@ CS_API int32_t cs_shards_search_variants_masked(cs_shards* h, const float* queri
  * scoped device search on its own stream, and the shard merge returns global ids.  Destroy with cs_scope_destroy,
  * before the store. */
 CS_API int32_t cs_shards_scope_create(cs_shards* h, const uint32_t* ids, uint64_t n, cs_scope** out);
+/* cs_index_scope_create_range over the sharded store: global ids [first_id, first_id + n); on every shard they are one
+ * range of local ids, written there by the same kernel. */
+CS_API int32_t cs_shards_scope_create_range(cs_shards* h, uint32_t first_id, uint64_t n, cs_scope** out);
 CS_API int32_t cs_shards_search_scoped(cs_shards* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,
                                 uint32_t k, float* out_cos, uint32_t* out_ids, uint32_t* out_counts);
 CS_API int32_t cs_shards_search_variants_scoped(cs_shards* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,
