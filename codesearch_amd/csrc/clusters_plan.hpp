@@ -1,5 +1,5 @@
 // clusters_plan.hpp — the host side of the similar-clusters search (cs_index_similar_clusters; kernels: scan_clusters.hip):
-// plain C++17, no HIP.  tests/cpp/clusters_plan_test.cpp walks it on the CPU; index.hip only launches what it says.
+// plain C++17, no HIP.  tests/cpp/clusters_plan_test.cpp walks it on the CPU; index_joins.hip only launches what it says.
 //
 // The join is the similar-pairs search's: the upper triangle of T x T 128-row tiles in pairs_plan.hpp's numbering (row by
 // row, the diagonal pair first; tile_pair_of).  What differs is the walk.  The answer is a union-find over the stored rows,
@@ -20,6 +20,7 @@
 #pragma once
 
 #include <cstdint>
+#include <vector>
 
 #include "pairs_plan.hpp"
 
@@ -80,5 +81,51 @@ inline bool clusters_split(const PairsBand& r, PairsBand& lo, PairsBand& hi) {
     hi = PairsBand{r.first + lo.count, r.count - lo.count};
     return true;
 }
+
+// What a launch's ambiguous count means to the walk.
+enum class ClustersStep {
+    Accepted,   // within the buffer: the launch stands, its ambiguous pairs go to the rescore
+    Split,      // past it: the launch is void, its two halves are walked instead
+    Impossible  // past it in a launch of one tile pair, which holds at most kClustersTilePairAmbiguous: the count is wrong
+};
+
+// The walk of both clusters calls over `plan` (ClustersPlan, ClustersScopedPlan: tile_pairs, launch_at, ambiguous_cap) —
+// what to launch next, and what becomes of a launch once its ambiguous pairs are counted.  It touches no device:
+// index_joins.hip's clusters_walk launches what next() says and reports the counter it read; the plans' tests report a
+// made-up one.  The plan outlives the walk.
+template <typename Plan>
+class ClustersWalk {
+public:
+    explicit ClustersWalk(const Plan& plan) : plan_(plan) {}
+
+    // r = the next launch: a half that is waiting (lo before hi, so the walk stays in the plan's order), else the plan's
+    // next launch.  false: every tile pair has been accepted, the walk has ended.
+    bool next(PairsBand& r) {
+        if (!halves_.empty()) {
+            r = halves_.back();
+            halves_.pop_back();
+            return true;
+        }
+        if (next_ >= plan_.tile_pairs) return false;
+        r = plan_.launch_at(next_);
+        next_ += r.count;
+        return true;
+    }
+
+    // The launch `r` that next() gave counted `ambiguous` pairs.
+    ClustersStep report(const PairsBand& r, uint64_t ambiguous) {
+        if (ambiguous <= plan_.ambiguous_cap) return ClustersStep::Accepted;
+        PairsBand lo, hi;
+        if (!clusters_split(r, lo, hi)) return ClustersStep::Impossible;
+        halves_.push_back(hi);
+        halves_.push_back(lo);
+        return ClustersStep::Split;
+    }
+
+private:
+    const Plan& plan_;
+    std::vector<PairsBand> halves_;  // of launches whose ambiguous pairs did not fit; the next to walk is at the back
+    uint64_t next_ = 0;              // the first tile pair no launch has named yet
+};
 
 }  // namespace cs

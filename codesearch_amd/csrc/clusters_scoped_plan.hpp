@@ -1,6 +1,6 @@
 // clusters_scoped_plan.hpp — the host side of the scoped similar-clusters search (cs_index_similar_clusters_scoped; kernels:
-// scan_clusters_scoped.hip): plain C++17, no HIP.  tests/cpp/clusters_scoped_plan_test.cpp walks it on the CPU; index.hip
-// only launches what it says.
+// scan_clusters_scoped.hip): plain C++17, no HIP.  tests/cpp/clusters_scoped_plan_test.cpp walks it on the CPU;
+// index_joins.hip only launches what it says.
 //
 // GEOMETRY: pairs_scoped_plan.hpp's.  Both sides are packed (list entry i of a scope = packed row i, T = ceil(n / 128)
 // packed tiles); the same handle twice is the TRIANGLE of pairs_plan.hpp over T tiles, two handles are the RECTANGLE

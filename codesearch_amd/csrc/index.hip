@@ -2,8 +2,6 @@
 // (/root/reference/src/vectordb/store.rs:94-750) as a device-resident row-major matrix
 // searched by the exact scan of scan.hip.  Metadata (store.rs:19-85) stays with the caller.
 #include <algorithm>
-#include <atomic>
-#include <chrono>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -15,14 +13,8 @@
 #include <cstdlib>
 
 #include "grouped_plan.hpp"
-#include "index_ledger.hpp"
+#include "index_internal.hpp"
 #include "masked_plan.hpp"
-#include "clusters_plan.hpp"
-#include "clusters_scoped_plan.hpp"
-#include "pairs_plan.hpp"
-#include "pairs_scoped_plan.hpp"
-#include "scan.hpp"
-#include "scope.hpp"
 #include "scope_ops_plan.hpp"
 #include "similar_route.hpp"
 #include "similar_sources.hpp"
@@ -42,32 +34,6 @@ int32_t fail(int32_t code, const char* fmt, ...) {
     va_end(ap);
     last_error_ref() = buf;
     return code;
-}
-
-struct EventTriple {
-    hipEvent_t e0, e1, e2;
-};
-
-// Frees p (pinned host memory when `pinned`) and, for n > 0, allocates n elements in its place: null on failure.
-template <class T>
-hipError_t realloc_buf(T*& p, size_t n, bool pinned = false) {
-    if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
-    p = nullptr;
-    if (!n) return hipSuccess;
-    return pinned ? hipHostMalloc(&p, n * sizeof(T)) : hipMalloc(&p, n * sizeof(T));
-}
-template <class... T>
-void free_bufs(bool pinned, T*&... p) {
-    ((void)realloc_buf(p, 0, pinned), ...);
-}
-// p holds at least n elements afterwards; cap = how many it holds (0 after a failed allocation)
-template <class T>
-int32_t reserve_buf(T*& p, size_t& cap, size_t n, bool pinned = false) {
-    if (n <= cap) return CS_OK;
-    cap = 0;
-    CS_HIP(realloc_buf(p, n, pinned));
-    cap = n;
-    return CS_OK;
 }
 
 // Per-call scratch.  Host-API calls borrow one from the pool (own stream); device-API
@@ -214,160 +180,93 @@ struct Workspace {
     }
 };
 
-// Scratch of a similar-pairs call (cs_index_similar_pairs, scan_pairs.hip): a stream, events and buffers of its own, pooled
-// per index — a call never touches a search's Workspace, so it runs beside searches and beside other calls.
-struct PairsWorkspace {
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    uint64_t* d_cand = nullptr; size_t cand_cap = 0;      // candidate pairs (rowA | rowB << 32)
-    PairRecord* d_out = nullptr; size_t out_cap = 0;      // qualifying records
-    uint64_t* d_counters = nullptr;  // [0] candidates counted by the filter, [1] (low word) records written by the refine
-    uint64_t* h_counters = nullptr;  // pinned: where the host reads them
+// ---- what index_joins.hip calls as well (index_internal.hpp); scope_ready is further down, beside the scopes
 
-    int32_t init() {
-        CS_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        CS_HIP(hipEventCreate(&ev[0]));
-        CS_HIP(hipEventCreate(&ev[1]));
-        CS_HIP(realloc_buf(d_counters, 2));
-        CS_HIP(realloc_buf(h_counters, 2, true));
-        return CS_OK;
-    }
-    void release_all() {
-        free_bufs(false, d_cand, d_out, d_counters);
-        free_bufs(true, h_counters);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
+// the int8 copy is the filter's operand: it exists, was not retired, and reaches past phase 0's rows
+bool q8_serves(const cs_index* h) {
+    return h->use_q8 && h->d_q8 && h->d_tmeta && h->q8_active.load() && h->q8_rows > kFilterPhase0;
+}
 
-// Scratch of a similar-clusters call (cs_index_similar_clusters, scan_clusters.hip), pooled per index beside PairsWorkspace:
-// O(stored rows) for the union-find and the labels, one word per tile, and the ambiguous buffer, whose size is fixed.
-struct ClustersWorkspace {
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    uint32_t* d_parent = nullptr; size_t parent_cap = 0;        // [stored rows]
-    uint32_t* d_mark = nullptr; size_t mark_cap = 0;            // [stored rows]: the label kernel's "this root was counted"
-    uint32_t* d_tile_root = nullptr; size_t tile_root_cap = 0;  // [tiles]
-    uint32_t* d_label = nullptr; size_t label_cap = 0;          // [ids issued]
-    uint64_t* d_amb = nullptr; size_t amb_cap = 0;              // ambiguous pairs (rowA | rowB << 32)
-    uint64_t* d_counters = nullptr;  // [0] ambiguous pairs of the launch, [1] its skipped tile pairs, [2] classes, [3] members
-    uint64_t* h_counters = nullptr;  // pinned: where the host reads them
+// The f16 copy, complete for the rows of the last build — built now if it is not there (allocation + one conversion pass
+// over the missing rows on the null stream, waited for: 7.68 GB and ~4.7 ms per 10M x 384, paid once, by the first
+// search that needs it).  false: no room (remembered until clear()).
+bool ensure_f16(cs_index* h) {
+    if (!h->use_split) return false;
+    std::lock_guard<std::mutex> lk(h->filter_mu);
+    if (h->d_split && h->split_rows >= h->ledger.stored()) return true;
+    if (h->f16_failed || h->normed_rows < h->ledger.stored()) return false;
+    const size_t cap256 = ((size_t)h->capacity + 255) / 256 * 256;
+    if (!h->d_split || h->split_cap < cap256) {
+        if (h->d_split) (void)hipFree(h->d_split);
+        h->d_split = nullptr; h->split_rows = 0; h->split_cap = 0;
+        if (cs_lab_env("CS_FAULT_F16_ALLOC") != nullptr || hipMalloc(&h->d_split, cap256 * h->dim * sizeof(_Float16)) != hipSuccess) {
+            (void)hipGetLastError();
+            h->d_split = nullptr;
+            h->f16_failed = true;
+            return false;
+        }
+        h->split_cap = cap256;
+    }
+    if (launch_corpus_split(h->d_corpus, h->d_norms, h->d_split, h->split_rows, h->ledger.stored() - h->split_rows, h->dim, nullptr) != CS_OK ||
+        hipStreamSynchronize(nullptr) != hipSuccess) {
+        (void)hipGetLastError();
+        h->f16_failed = true;
+        return false;
+    }
+    h->split_rows = h->ledger.stored();
+    return true;
+}
 
-    int32_t init() {
-        CS_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        CS_HIP(hipEventCreate(&ev[0]));
-        CS_HIP(hipEventCreate(&ev[1]));
-        CS_HIP(realloc_buf(d_counters, 4));
-        CS_HIP(realloc_buf(h_counters, 4, true));
-        return CS_OK;
+// The handle-level checks of a scoped search: they read nothing that a refresh writes and take no lock.
+int32_t check_scope_handle(const cs_index* h, const cs_scope* sc) {
+    if (!sc) return fail(CS_ERR_BAD_ARG, "null scope handle");
+    if (sc->index != h) return fail(CS_ERR_BAD_ARG, "the scope was made for another store");
+    return CS_OK;
+}
+
+// The group table as this search's kernels read it.  A dirty table is brought up to date first, under groups_mu, with
+// synchronous copies (and after the device has finished what was enqueued, when the table has to move): a concurrent
+// grouped search either waits here or finds it clean.  No group assigned: a null table, every id CS_NO_GROUP.
+int32_t ensure_groups(cs_index* h, uint32_t per_group, GroupView* gv) {
+    std::lock_guard<std::mutex> lk(h->groups_mu);
+    *gv = GroupView{nullptr, 0, h->ledger.id_base(), per_group};
+    if (h->groups.assigned() == 0) return CS_OK;
+    const uint64_t n = h->groups.size();
+    if (n > h->groups_cap) {
+        CS_HIP(hipDeviceSynchronize());  // a search that was only enqueued may still read the old table
+        const uint64_t cap = std::max<uint64_t>(n, std::min<uint64_t>(2 * h->groups_cap, 0xffffffffull));
+        h->groups_cap = 0;
+        h->groups.uploaded(0);  // the new table holds nothing yet
+        CS_HIP(realloc_buf(h->d_groups, (size_t)cap));
+        h->groups_cap = cap;
     }
-    void release_all() {
-        free_bufs(false, d_parent, d_mark, d_tile_root, d_label, d_amb, d_counters);
-        free_bufs(true, h_counters);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
+    uint64_t lo = 0, hi = 0;
+    if (h->groups.pending(&lo, &hi))
+        CS_HIP(hipMemcpy(h->d_groups + lo, h->groups.data() + lo, (size_t)(hi - lo) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    h->groups.uploaded(n);
+    gv->groups = h->d_groups;
+    gv->len = (uint32_t)n;
+    return CS_OK;
+}
+
+int32_t check_search(const cs_index* h, uint32_t nq, uint32_t dim, uint32_t k) {
+    if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
+    if (dim != h->dim)  // store.rs:432-438
+        return fail(CS_ERR_DIM_MISMATCH,
+                    "Query embedding dimension mismatch: expected %u, got %u", h->dim, dim);
+    if (!h->built)  // store.rs:440-444
+        return fail(CS_ERR_NOT_BUILT,
+                    "Index not built. Call build_index() after inserting chunks.");
+    if (nq == 0 || nq > CS_MAX_QUERIES)
+        return fail(CS_ERR_BAD_ARG, "nq must be in 1..%u, got %u", CS_MAX_QUERIES, nq);
+    if (k == 0 || k > CS_MAX_K)
+        return fail(CS_ERR_BAD_ARG, "k must be in 1..%u, got %u", CS_MAX_K, k);
+    return CS_OK;
+}
 
 }  // namespace cs
 
 using namespace cs;
-
-struct cs_index {
-    int device = 0;
-    int num_cus = 256;
-    uint32_t dim = 0;
-    uint64_t capacity = 0;   // rows allocated
-    // ids, stored rows and tombstones (index_ledger.hpp): the host's side of everything below that is numbered by them
-    IndexLedger ledger;
-    // the device copy of the ledger's row -> id table, once it is compacted: cs_index_build uploads the rows that are new
-    uint32_t* d_ids = nullptr;
-    uint64_t ids_cap = 0, ids_uploaded = 0;
-    uint32_t compact_dead_pct = 10;  // cs_index_build reclaims from this share of tombstones on (CS_INDEX_COMPACT_DEAD_PCT; 0 = never)
-    uint64_t compactions = 0;
-    // (d_ids of a compacted index is null only while it stores no row: cs_index_build uploads the table before any search)
-    RowIds row_ids() const { return RowIds(ledger.id_base(), ledger.compacted() ? d_ids : nullptr); }
-    // Groups of the grouped search (scan_grouped.hip).  The device copy is brought up to date under groups_mu by the
-    // first grouped search that finds it dirty (ensure_groups); searches read it only.
-    GroupTable groups;
-    uint32_t* d_groups = nullptr;
-    uint64_t groups_cap = 0;  // elements allocated on the device
-    std::mutex groups_mu;
-    // Classes of the boosted search (scan_boosted.hip): the group table's sibling, 2 B per id, brought up to date under
-    // classes_mu by the first boosted search that finds it dirty (ensure_classes); searches read it only.
-    ClassTable classes;
-    uint16_t* d_classes = nullptr;
-    uint64_t classes_cap = 0;  // elements allocated on the device
-    std::mutex classes_mu;
-    float* d_corpus = nullptr;
-    uint32_t* d_dead = nullptr;  // bitmap over rows, sized for `capacity`
-    float* d_norms = nullptr;    // |row| for rows [0, normed_rows) (batched-query path)
-    uint64_t normed_rows = 0;
-    // unit rows [0, split_rows) as f16 [row][dim]: the filter operand of the batched path WHEN the int8 copy does not
-    // serve (no int8 copy, retired by its spread or by strikes, <= 1024 rows).  Built on demand (ensure_f16): an index
-    // whose int8 copy serves holds 5 bytes per element (f32 + int8), not 7, and its builds skip the conversion.
-    _Float16* d_split = nullptr;
-    uint64_t split_rows = 0, split_cap = 0;
-    bool use_split = false;
-    bool f16_eager = false;    // CS_FILTER_F16_EAGER=1 (or an A/B knob that needs both copies): build it at every cs_index_build
-    bool f16_failed = false;   // no room for it: searches stay on the int8 copy / the exact paths (reset by clear())
-    std::mutex filter_mu;      // guards the on-demand build (searches are re-entrant)
-    // int8 filter copy (scan_filter.hip): complete 128-row tiles [0, q8_rows / 128), a quarter of the f32 bytes
-    int8_t* d_q8 = nullptr;
-    float4* d_tmeta = nullptr;
-    float* d_mu = nullptr;   // [dim] mean unit row of the first build: the copy holds u - mu (fixed until clear())
-    uint64_t q8_rows = 0;
-    bool use_q8 = false;
-    // The int8 copy stops being the filter operand (the f16 copy takes over, results unchanged) when the data defeat its
-    // error band: at build, when the tiles' scales say so (outlier coordinates: q8_spread), and at run time after two
-    // searches through it overflowed a candidate buffer.  clear() resets both.
-    std::atomic<bool> q8_active{true};
-    std::atomic<uint32_t> q8_strikes{0}, q8_searches{0};
-    // a strike; the copy is retired once there are two and they are more than one in sixteen of its searches
-    void q8_strike() {
-        const uint32_t s = q8_strikes.fetch_add(1) + 1;
-        if (s >= 2 && (uint64_t)s * 16 >= q8_searches.load()) q8_active.store(false);
-    }
-    float q8_spread = 0.0f;      // median over tiles of max |u - mu| * sqrt(dim) at the last build (isotropic rows: ~4.4)
-    float q8_max_spread = 7.0f;  // CS_FILTER_INT8_MAX_SPREAD
-    float filter_margin = 0.0f;  // scan_filter.hip: bound of the f16 filter's error for this dim
-    RouteKnobs route;  // search_route.hpp: the thresholds of plan_route (route_knobs_from_env)
-    uint64_t batched_searches = 0, batched_fallbacks = 0, q8_reruns = 0;
-    // The similar-chunk search's route (similar_route.hpp; cs_index_set_similar_route, CS_SIMILAR_ROUTE) and its own counters
-    // (cs_index_similar_route_info): unscoped calls the filter answered — those whose candidate buffer overflowed and that
-    // the similar scan then answered among them, counted again in the fallbacks — and unscoped calls the scan answered.
-    // The counters above and the int8 copy's strikes do not move for similar calls.
-    std::atomic<int32_t> similar_route{CS_SIMILAR_ROUTE_AUTO};
-    std::atomic<uint64_t> similar_filter_searches{0}, similar_scan_searches{0}, similar_filter_fallbacks{0};
-    bool built = false;
-    // Build generation: cs_index_build and cs_index_clear advance it.  Every other mutation un-builds the index and a
-    // search needs a build, so whatever a scope derived from the stored rows (its row list, scope.hpp) is current
-    // exactly while the generation is the one it was derived at.
-    std::atomic<uint64_t> build_gen{1};
-    // streams of OTHER devices that carry unfinished appends into this corpus (index_append_from: an encoder replica on
-    // another GPU writing its rows over xGMI); hipDeviceSynchronize on this device does not wait for them
-    // peer appends in flight: ONE event per (source device, stream), re-recorded by every append on that stream (a later
-    // record covers the stream's earlier copies), so an ingest of millions of rows in mini-batches keeps a handful of events.
-    // CONTRACT (include/codesearch_gpu.h, cs_shards_add_device / cs_embedders_index_*): a stream that carried an append must
-    // stay alive until the next build / search / read of this index has drained it — a destroyed stream whose handle value is
-    // handed out again would have its slot's event re-recorded on the NEW stream and the old copies would go untracked
-    struct ForeignAppend { int device; hipStream_t stream; hipEvent_t done; };
-    std::vector<ForeignAppend> foreign_appends;
-
-    std::mutex mu;  // guards the pools below (search is re-entrant)
-    std::vector<Workspace*> pool;
-    std::vector<PairsWorkspace*> pairs_pool;  // cs_index_similar_pairs' scratch, one set per call in flight
-    std::vector<ClustersWorkspace*> clusters_pool;  // cs_index_similar_clusters', likewise
-    // device-API scratch: one set per (stream, calling thread) — stream order makes reuse safe within a
-    // thread, and two threads sharing a stream (e.g. both on the null stream) never share a set
-    std::map<std::pair<hipStream_t, std::thread::id>, Workspace*> by_stream;
-    bool profile = false;
-    std::vector<EventTriple> pending;
-    double scan_ms = 0.0, merge_ms = 0.0;
-    uint64_t scan_launches = 0;
-};
 
 namespace {
 
@@ -499,41 +398,6 @@ int32_t grow(cs_index* h, uint64_t need_rows) {
     return CS_OK;
 }
 #undef CS_GROW_COPY
-
-// the int8 copy is the filter's operand: it exists, was not retired, and reaches past phase 0's rows
-bool q8_serves(const cs_index* h) {
-    return h->use_q8 && h->d_q8 && h->d_tmeta && h->q8_active.load() && h->q8_rows > kFilterPhase0;
-}
-
-// The f16 copy, complete for the rows of the last build — built now if it is not there (allocation + one conversion pass
-// over the missing rows on the null stream, waited for: 7.68 GB and ~4.7 ms per 10M x 384, paid once, by the first
-// search that needs it).  false: no room (remembered until clear()).
-bool ensure_f16(cs_index* h) {
-    if (!h->use_split) return false;
-    std::lock_guard<std::mutex> lk(h->filter_mu);
-    if (h->d_split && h->split_rows >= h->ledger.stored()) return true;
-    if (h->f16_failed || h->normed_rows < h->ledger.stored()) return false;
-    const size_t cap256 = ((size_t)h->capacity + 255) / 256 * 256;
-    if (!h->d_split || h->split_cap < cap256) {
-        if (h->d_split) (void)hipFree(h->d_split);
-        h->d_split = nullptr; h->split_rows = 0; h->split_cap = 0;
-        if (cs_lab_env("CS_FAULT_F16_ALLOC") != nullptr || hipMalloc(&h->d_split, cap256 * h->dim * sizeof(_Float16)) != hipSuccess) {
-            (void)hipGetLastError();
-            h->d_split = nullptr;
-            h->f16_failed = true;
-            return false;
-        }
-        h->split_cap = cap256;
-    }
-    if (launch_corpus_split(h->d_corpus, h->d_norms, h->d_split, h->split_rows, h->ledger.stored() - h->split_rows, h->dim, nullptr) != CS_OK ||
-        hipStreamSynchronize(nullptr) != hipSuccess) {
-        (void)hipGetLastError();
-        h->f16_failed = true;
-        return false;
-    }
-    h->split_rows = h->ledger.stored();
-    return true;
-}
 
 // rows idx[0 .. n) of src (relative to it) -> dst rows 0 .. n, `dim` floats each
 __global__ void __launch_bounds__(256)
@@ -906,13 +770,6 @@ int32_t scope_make_list(cs_index* h, cs_scope* sc) {
     return CS_OK;
 }
 
-// The handle-level checks of a scoped search: they read nothing that a refresh writes and take no lock.
-int32_t check_scope_handle(const cs_index* h, const cs_scope* sc) {
-    if (!sc) return fail(CS_ERR_BAD_ARG, "null scope handle");
-    if (sc->index != h) return fail(CS_ERR_BAD_ARG, "the scope was made for another store");
-    return CS_OK;
-}
-
 // ---- the making of a scope: cs_index_scope_create, _create_range and cs_scope_combine differ only in where the ids come from
 
 cs_scope* new_index_scope(cs_index* h) {
@@ -1001,11 +858,13 @@ int32_t scope_part_read_ids(const cs_scope* sc, uint64_t first, uint64_t n, uint
     return CS_OK;
 }
 
+}  // namespace
+
 // The checks of a scoped search behind check_search's, then the refresh when one is due: *live = the list's length.
 // fp != null (the host-buffer searches of nq queries, top-k): the search's route too — fp->ok says that it wants the
 // int8 filter and holds its plan (scoped_filter_plan.hpp; host arithmetic over what the scope keeps, under its mutex).
-int32_t scope_ready(cs_index* h, cs_scope* sc, uint64_t* live, ScopedFilterPlan* fp = nullptr, uint32_t nq = 0,
-                    uint32_t k = 0) {
+// (fp, nq and k default to none: index_internal.hpp.)
+int32_t cs::scope_ready(cs_index* h, cs_scope* sc, uint64_t* live, ScopedFilterPlan* fp, uint32_t nq, uint32_t k) {
     CS_TRY(check_scope_handle(h, sc));
     std::lock_guard<std::mutex> lk(sc->mu);
     if (scope_refresh_due(sc->generation, h->build_gen.load())) CS_TRY(scope_make_list(h, sc));
@@ -1026,6 +885,8 @@ int32_t scope_ready(cs_index* h, cs_scope* sc, uint64_t* live, ScopedFilterPlan*
     if (scoped_wants_filter(h->route, shape, in)) *fp = plan;
     return CS_OK;
 }
+
+namespace {
 
 // The keys of a host-buffer scoped search, enqueued on the workspace's stream: the best k per query into d_keys [nq][k]
 // (device-addressable).  The queries are in w->h_queries.  With a filter plan whose int8 query planes fit, the index's
@@ -1062,31 +923,6 @@ int32_t run_scoped(cs_index* h, cs_scope* sc, Workspace* w, const ScanPlan& plan
     // kGatedMaxQ queries, which no host-buffer search reads.  Both are cleared here, in stream order, behind the read.
     CS_HIP(hipMemsetAsync(w->bs.d_overflow, 0, 2 * sizeof(uint32_t), w->stream));
     return run_row_list(h, w, plan, live, sc->d_list, d_len, w->d_queries, nq, k, d_keys, nullptr, nullptr, nullptr, w->stream);
-}
-
-// The group table as this search's kernels read it.  A dirty table is brought up to date first, under groups_mu, with
-// synchronous copies (and after the device has finished what was enqueued, when the table has to move): a concurrent
-// grouped search either waits here or finds it clean.  No group assigned: a null table, every id CS_NO_GROUP.
-int32_t ensure_groups(cs_index* h, uint32_t per_group, GroupView* gv) {
-    std::lock_guard<std::mutex> lk(h->groups_mu);
-    *gv = GroupView{nullptr, 0, h->ledger.id_base(), per_group};
-    if (h->groups.assigned() == 0) return CS_OK;
-    const uint64_t n = h->groups.size();
-    if (n > h->groups_cap) {
-        CS_HIP(hipDeviceSynchronize());  // a search that was only enqueued may still read the old table
-        const uint64_t cap = std::max<uint64_t>(n, std::min<uint64_t>(2 * h->groups_cap, 0xffffffffull));
-        h->groups_cap = 0;
-        h->groups.uploaded(0);  // the new table holds nothing yet
-        CS_HIP(realloc_buf(h->d_groups, (size_t)cap));
-        h->groups_cap = cap;
-    }
-    uint64_t lo = 0, hi = 0;
-    if (h->groups.pending(&lo, &hi))
-        CS_HIP(hipMemcpy(h->d_groups + lo, h->groups.data() + lo, (size_t)(hi - lo) * sizeof(uint32_t), hipMemcpyHostToDevice));
-    h->groups.uploaded(n);
-    gv->groups = h->d_groups;
-    gv->len = (uint32_t)n;
-    return CS_OK;
 }
 
 // ensure_groups for the class table: the index's side of a boosted search's BoostView (the call adds its weights).  No
@@ -1195,21 +1031,6 @@ RouteKnobs route_knobs_from_env() {
     if (const char* e = std::getenv("CS_SCAN_PRIME_ROWS")) r.prime_rows = (uint64_t)std::atoll(e);
     if (const char* e = std::getenv("CS_SCOPE_FILTER_MAX_SPAN")) r.scope_span_single = r.scope_span_few = r.scope_span_many = std::atof(e);
     return r;
-}
-
-int32_t check_search(const cs_index* h, uint32_t nq, uint32_t dim, uint32_t k) {
-    if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
-    if (dim != h->dim)  // store.rs:432-438
-        return fail(CS_ERR_DIM_MISMATCH,
-                    "Query embedding dimension mismatch: expected %u, got %u", h->dim, dim);
-    if (!h->built)  // store.rs:440-444
-        return fail(CS_ERR_NOT_BUILT,
-                    "Index not built. Call build_index() after inserting chunks.");
-    if (nq == 0 || nq > CS_MAX_QUERIES)
-        return fail(CS_ERR_BAD_ARG, "nq must be in 1..%u, got %u", CS_MAX_QUERIES, nq);
-    if (k == 0 || k > CS_MAX_K)
-        return fail(CS_ERR_BAD_ARG, "k must be in 1..%u, got %u", CS_MAX_K, k);
-    return CS_OK;
 }
 
 // ---- the host-buffer searches' frame ------------------------------------------------------------------
@@ -1672,654 +1493,6 @@ int32_t search_similar(cs_index* h, bool scope_given, cs_scope* scope, const uin
     });
 }
 
-// ---- the similar-pairs search (scan_pairs.hip, plan: pairs_plan.hpp) -------------------------------------------
-// What the calling thread's last successful call did (cs_index_similar_pairs_info).
-struct PairsInfo {
-    uint64_t candidates = 0;
-    uint32_t bands = 0;
-    double filter_ms = 0.0, refine_ms = 0.0, order_ms = 0.0;
-    // a scoped call only (cs_index_similar_pairs_scoped_info; zeros after an unscoped one)
-    double pack_ms = 0.0;
-    uint64_t rows_a = 0, rows_b = 0, tile_pairs = 0;
-};
-thread_local PairsInfo last_pairs_info;
-
-PairsWorkspace* acquire_pairs(cs_index* h) {
-    {
-        std::lock_guard<std::mutex> lk(h->mu);
-        if (!h->pairs_pool.empty()) {
-            PairsWorkspace* w = h->pairs_pool.back();
-            h->pairs_pool.pop_back();
-            return w;
-        }
-    }
-    PairsWorkspace* w = new PairsWorkspace();
-    if (w->init() != CS_OK) {
-        w->release_all();
-        delete w;
-        return nullptr;
-    }
-    return w;
-}
-
-// The refusal of a call whose candidates outgrew its buffer, noticed after band `band` of `bands`.
-int32_t pairs_overflow(uint64_t reached, uint64_t band, uint64_t bands, uint64_t cand_cap) {
-    return fail(CS_ERR_UNSUPPORTED,
-                "similar pairs: %llu candidate pairs after band %llu of %llu, more than the %llu this call holds "
-                "(2 * max_pairs + 4096): raise min_cos, exclude groups (CS_PAIRS_OTHER_GROUP) or raise max_pairs",
-                (unsigned long long)reached, (unsigned long long)band, (unsigned long long)bands, (unsigned long long)cand_cap);
-}
-
-// The tail of both pairs calls, behind the last filter band (w->h_counters[0] = the candidates, within the buffer): the
-// refine, the records' read-back and the ordering on the host into the caller's buffers; `info` becomes the thread's last.
-int32_t pairs_finish(cs_index* h, PairsWorkspace* w, float min_cos, uint32_t max_pairs, uint32_t* out_a, uint32_t* out_b,
-                     float* out_cos, uint64_t* out_total, PairsInfo& info) {
-    const uint32_t ncand = (uint32_t)w->h_counters[0];
-    info.candidates = ncand;
-    std::vector<PairRecord> rec;
-    if (ncand) {
-        CS_HIP(hipEventRecord(w->ev[0], w->stream));
-        CS_TRY(launch_pairs_rescore(h->d_corpus, h->dim, w->d_cand, ncand, h->row_ids(), min_cos, w->d_out,
-                                    reinterpret_cast<uint32_t*>(w->d_counters + 1), pairs_refine_blocks(ncand, h->num_cus),
-                                    w->stream));
-        CS_HIP(hipEventRecord(w->ev[1], w->stream));
-        CS_HIP(hipMemcpyAsync(w->h_counters + 1, w->d_counters + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, w->stream));
-        CS_HIP(hipStreamSynchronize(w->stream));
-        float ms = 0.0f;
-        CS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
-        info.refine_ms = ms;
-        rec.resize((size_t)(uint32_t)w->h_counters[1]);
-        if (!rec.empty()) {
-            CS_HIP(hipMemcpyAsync(rec.data(), w->d_out, rec.size() * sizeof(PairRecord), hipMemcpyDeviceToHost, w->stream));
-            CS_HIP(hipStreamSynchronize(w->stream));
-        }
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    const size_t keep = std::min<size_t>(rec.size(), max_pairs);
-    std::partial_sort(rec.begin(), rec.begin() + keep, rec.end(), [](const PairRecord& x, const PairRecord& y) {
-        if (x.cos != y.cos) return x.cos > y.cos;
-        if (x.a != y.a) return x.a < y.a;
-        return x.b < y.b;
-    });
-    for (size_t i = 0; i < keep; ++i) { out_a[i] = rec[i].a; out_b[i] = rec[i].b; out_cos[i] = rec[i].cos; }
-    *out_total = rec.size();
-    info.order_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    last_pairs_info = info;
-    return CS_OK;
-}
-
-// The checks, the plan, the bands (one synchronise each: the host reads the candidate counter and stops at the first
-// overflow), the refine, the ordering on the host — std::partial_sort of the qualifying records only, by the total order
-// (cosine desc, a asc, b asc), so the answer does not depend on how the device's atomics landed.
-// The filter operand is the index's f16 copy where the index keeps one (the int8 copy does not serve it: ensure_f16, as a
-// search would).  Where the int8 copy serves, the index holds f32 + int8 and must go on doing so: the call converts the
-// rows into a buffer of its OWN (the same launch_corpus_split, the same tiles) and frees it before it returns — never
-// through the handle, where a search running beside this call could pick the copy up just before it is freed.
-int32_t similar_pairs(cs_index* h, float min_cos, int32_t mode, uint32_t max_pairs, uint32_t* out_a, uint32_t* out_b,
-                      float* out_cos, uint64_t* out_total) {
-    if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
-    CS_TRY(check_search(h, 1, h->dim, 1));
-    if (!out_a || !out_b || !out_cos || !out_total) return fail(CS_ERR_BAD_ARG, "null buffer");
-    if (mode != CS_PAIRS_ALL && mode != CS_PAIRS_OTHER_GROUP)
-        return fail(CS_ERR_BAD_ARG, "mode must be CS_PAIRS_ALL or CS_PAIRS_OTHER_GROUP (0..1), got %d", mode);
-    if (min_cos != min_cos) return fail(CS_ERR_BAD_ARG, "min_cos is NaN");
-    if (max_pairs == 0 || max_pairs > CS_MAX_PAIRS)
-        return fail(CS_ERR_BAD_ARG, "max_pairs must be in 1..%u, got %u", CS_MAX_PAIRS, max_pairs);
-    if (!split_scan_supported(h->dim))
-        return fail(CS_ERR_UNSUPPORTED, "similar pairs need dim 384, 768 or 1024 (the f16 filter's widths), got %u", h->dim);
-    if (h->ledger.live() < 2) {  // no pair: nothing is launched
-        *out_total = 0;
-        last_pairs_info = PairsInfo{};
-        return CS_OK;
-    }
-    if (!h->use_split)
-        return fail(CS_ERR_UNSUPPORTED, "similar pairs need the f16 filter copy, and CS_INDEX_SPLIT=0 turned it off");
-    DeviceGuard g(h->device);
-    const uint64_t stored = h->ledger.stored();
-    const PairsPlan plan = plan_pairs(stored, max_pairs, h->num_cus);
-    const _Float16* d_f16 = nullptr;
-    if (h->f16_eager || !q8_serves(h)) {
-        if (!ensure_f16(h)) return fail(CS_ERR_OOM, "similar pairs: no room for the f16 filter copy");
-        d_f16 = h->d_split;
-    } else {
-        std::lock_guard<std::mutex> lk(h->filter_mu);
-        if (h->d_split && h->split_rows >= stored) d_f16 = h->d_split;  // an overflowed search left one: it stays until the next build
-    }
-    struct Scratch {
-        cs_index* h;
-        PairsWorkspace* w = nullptr;
-        _Float16* d_private = nullptr;
-        ~Scratch() {
-            if (d_private) (void)hipFree(d_private);
-            if (w) {
-                std::lock_guard<std::mutex> lk(h->mu);
-                h->pairs_pool.push_back(w);
-            }
-        }
-    } sc{h};
-    sc.w = acquire_pairs(h);
-    if (!sc.w) return fail(CS_ERR_HIP, "similar pairs: could not create a HIP stream");
-    PairsWorkspace* w = sc.w;
-    if (!d_f16) {
-        if (h->normed_rows < stored) return fail(CS_ERR_HIP, "similar pairs: the index holds no row norms");
-        const size_t bytes = (size_t)plan.tiles * kPairsTileRows * h->dim * sizeof(_Float16);
-        if (cs_lab_env("CS_FAULT_F16_ALLOC") != nullptr || hipMalloc(&sc.d_private, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            sc.d_private = nullptr;
-            return fail(CS_ERR_OOM, "similar pairs: no room for the f16 filter copy (%llu bytes)", (unsigned long long)bytes);
-        }
-        CS_TRY(launch_corpus_split(h->d_corpus, h->d_norms, sc.d_private, 0, stored, h->dim, w->stream));
-        d_f16 = sc.d_private;
-    }
-    GroupView gv{nullptr, 0, h->ledger.id_base(), 0xFFFFFFFFu};
-    if (mode == CS_PAIRS_OTHER_GROUP) CS_TRY(ensure_groups(h, 0xFFFFFFFFu, &gv));
-    CS_TRY(reserve_buf(w->d_cand, w->cand_cap, (size_t)plan.cand_cap));
-    CS_TRY(reserve_buf(w->d_out, w->out_cap, (size_t)plan.cand_cap));
-    CS_HIP(hipMemsetAsync(w->d_counters, 0, 2 * sizeof(uint64_t), w->stream));
-    const uint32_t* d_dead = h->ledger.removed() ? h->d_dead : nullptr;
-    PairsInfo info;
-    for (uint64_t b = 0; b < plan.bands; ++b) {
-        const PairsBand band = plan.band(b);
-        CS_HIP(hipEventRecord(w->ev[0], w->stream));
-        CS_TRY(launch_pairs_filter(d_f16, h->dim, plan.tiles, band.first, band.count, stored, d_dead, h->row_ids(), gv,
-                                   mode == CS_PAIRS_OTHER_GROUP, min_cos, h->filter_margin, w->d_cand, w->d_counters,
-                                   (uint32_t)plan.cand_cap, w->stream));
-        CS_HIP(hipEventRecord(w->ev[1], w->stream));
-        CS_HIP(hipMemcpyAsync(w->h_counters, w->d_counters, sizeof(uint64_t), hipMemcpyDeviceToHost, w->stream));
-        CS_HIP(hipStreamSynchronize(w->stream));
-        float ms = 0.0f;
-        CS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
-        info.filter_ms += ms;
-        info.bands++;
-        if (w->h_counters[0] > plan.cand_cap) return pairs_overflow(w->h_counters[0], b + 1, plan.bands, plan.cand_cap);
-    }
-    return pairs_finish(h, w, min_cos, max_pairs, out_a, out_b, out_cos, out_total, info);
-}
-
-// ---- the similar-clusters search (scan_clusters.hip, plan: clusters_plan.hpp) -----------------------------------
-// What the calling thread's last successful call did (cs_index_similar_clusters_info).
-struct ClustersInfo {
-    uint64_t scored = 0, skipped = 0, rescored = 0;
-    uint32_t launches = 0;
-    double join_ms = 0.0, label_ms = 0.0;
-    // a scoped call only (cs_index_similar_clusters_scoped_info; zeros after an unscoped one)
-    double pack_ms = 0.0;
-    uint64_t rows_a = 0, rows_b = 0, vertices = 0;
-};
-thread_local ClustersInfo last_clusters_info;
-
-ClustersWorkspace* acquire_clusters(cs_index* h) {
-    {
-        std::lock_guard<std::mutex> lk(h->mu);
-        if (!h->clusters_pool.empty()) {
-            ClustersWorkspace* w = h->clusters_pool.back();
-            h->clusters_pool.pop_back();
-            return w;
-        }
-    }
-    ClustersWorkspace* w = new ClustersWorkspace();
-    if (w->init() != CS_OK) {
-        w->release_all();
-        delete w;
-        return nullptr;
-    }
-    return w;
-}
-
-uint64_t clusters_knob(const char* name) {
-    const char* e = cs_lab_env(name);  // (read per call: tests set it mid-process)
-    return e ? std::strtoull(e, nullptr, 10) : 0;
-}
-
-// The walk of both clusters calls over `plan` (tile_pairs, launch_at, ambiguous_cap): per launch `roots_and_join(range)` —
-// the tile roots and the join, enqueued on w->stream — and one synchronise to read the ambiguous counter — within the
-// buffer: the rescore unites what qualifies; past it: the launch is void and its two halves are walked instead (lo first, so
-// the walk stays in the plan's order).  ev: the rescore's events, read one synchronise later than the join's; *rescore_timed
-// says that the last rescore's time is still to be read, behind the caller's next synchronise.
-template <typename Plan, typename RootsAndJoin>
-int32_t clusters_walk(cs_index* h, ClustersWorkspace* w, hipEvent_t* ev, const Plan& plan, RowIds ids, float min_cos,
-                      ClustersInfo& info, bool& rescore_timed, RootsAndJoin&& roots_and_join) {
-    std::vector<PairsBand> halves;  // of launches whose ambiguous pairs did not fit; the next to walk is at the back
-    uint64_t next = 0;
-    float ms = 0.0f;
-    rescore_timed = false;
-    while (next < plan.tile_pairs || !halves.empty()) {
-        PairsBand r;
-        if (!halves.empty()) {
-            r = halves.back();
-            halves.pop_back();
-        } else {
-            r = plan.launch_at(next);
-            next += r.count;
-        }
-        CS_HIP(hipMemsetAsync(w->d_counters, 0, 2 * sizeof(uint64_t), w->stream));
-        CS_HIP(hipEventRecord(w->ev[0], w->stream));
-        CS_TRY(roots_and_join(r));
-        CS_HIP(hipEventRecord(w->ev[1], w->stream));
-        CS_HIP(hipMemcpyAsync(w->h_counters, w->d_counters, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, w->stream));
-        CS_HIP(hipStreamSynchronize(w->stream));
-        CS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
-        info.join_ms += ms;
-        if (rescore_timed) {  // the previous launch's rescore has finished with this synchronise
-            CS_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-            info.join_ms += ms;
-            rescore_timed = false;
-        }
-        info.launches++;
-        const uint64_t ambiguous = w->h_counters[0];
-        if (ambiguous > plan.ambiguous_cap) {
-            PairsBand lo, hi;
-            if (!clusters_split(r, lo, hi))
-                return fail(CS_ERR_HIP, "similar clusters: one tile pair reported %llu ambiguous pairs, more than 128 * 128",
-                            (unsigned long long)ambiguous);
-            halves.push_back(hi);
-            halves.push_back(lo);
-            continue;
-        }
-        info.skipped += w->h_counters[1];
-        info.scored += r.count - w->h_counters[1];
-        info.rescored += ambiguous;
-        if (ambiguous) {
-            CS_HIP(hipEventRecord(ev[0], w->stream));
-            CS_TRY(launch_clusters_rescore(h->d_corpus, h->dim, w->d_amb, (uint32_t)ambiguous, ids, min_cos, w->d_parent,
-                                           pairs_refine_blocks(ambiguous, h->num_cus), w->stream));
-            CS_HIP(hipEventRecord(ev[1], w->stream));
-            rescore_timed = true;
-        }
-    }
-    return CS_OK;
-}
-
-// The checks; the f16 operand as similar_pairs finds or makes it; then the plan's walk: per launch the tile roots, the join
-// and one synchronise to read the ambiguous counter — within the buffer: the rescore unites what qualifies; past it: the
-// launch is void and its two halves are walked instead (lo first, so the walk stays in the triangle's order) — and at the
-// end the label kernel.  Labels are staged on the host and copied out last: a HIP failure half-way writes nothing either.
-int32_t similar_clusters(cs_index* h, float min_cos, int32_t mode, uint32_t* out_label, uint64_t n_labels,
-                         uint64_t* out_clusters, uint64_t* out_members) {
-    if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
-    CS_TRY(check_search(h, 1, h->dim, 1));
-    if (!out_label) return fail(CS_ERR_BAD_ARG, "null buffer");
-    if (mode != CS_PAIRS_ALL && mode != CS_PAIRS_OTHER_GROUP)
-        return fail(CS_ERR_BAD_ARG, "mode must be CS_PAIRS_ALL or CS_PAIRS_OTHER_GROUP (0..1), got %d", mode);
-    if (min_cos != min_cos) return fail(CS_ERR_BAD_ARG, "min_cos is NaN");
-    const uint64_t issued = h->ledger.issued_ids();
-    if (n_labels != issued)
-        return fail(CS_ERR_BAD_ARG, "n_labels must be cs_index_next_id - id_base = %llu (one label per id issued), got %llu",
-                    (unsigned long long)issued, (unsigned long long)n_labels);
-    if (!split_scan_supported(h->dim))
-        return fail(CS_ERR_UNSUPPORTED, "similar clusters need dim 384, 768 or 1024 (the f16 filter's widths), got %u", h->dim);
-    const uint64_t stored = h->ledger.stored();
-    if (h->ledger.live() < 2) {  // no pair: every live id is its own label, nothing is launched
-        std::vector<uint32_t> rows;
-        h->ledger.survivors(0, stored, rows);
-        std::fill(out_label, out_label + n_labels, (uint32_t)CS_NO_ID);
-        for (uint32_t r : rows) {
-            const uint32_t id = h->ledger.compacted() ? h->ledger.ids_data()[r] : h->ledger.id_base() + r;
-            out_label[id - h->ledger.id_base()] = id;
-        }
-        if (out_clusters) *out_clusters = 0;
-        if (out_members) *out_members = 0;
-        last_clusters_info = ClustersInfo{};
-        return CS_OK;
-    }
-    if (!h->use_split)
-        return fail(CS_ERR_UNSUPPORTED, "similar clusters need the f16 filter copy, and CS_INDEX_SPLIT=0 turned it off");
-    DeviceGuard g(h->device);
-    const ClustersPlan plan = plan_clusters(stored, clusters_knob("CS_CLUSTERS_LAUNCH_TILE_PAIRS"),
-                                            clusters_knob("CS_CLUSTERS_AMBIGUOUS_CAP"));
-    const _Float16* d_f16 = nullptr;
-    if (h->f16_eager || !q8_serves(h)) {
-        if (!ensure_f16(h)) return fail(CS_ERR_OOM, "similar clusters: no room for the f16 filter copy");
-        d_f16 = h->d_split;
-    } else {
-        std::lock_guard<std::mutex> lk(h->filter_mu);
-        if (h->d_split && h->split_rows >= stored) d_f16 = h->d_split;  // an overflowed search left one: it stays until the next build
-    }
-    struct Scratch {
-        cs_index* h;
-        ClustersWorkspace* w = nullptr;
-        _Float16* d_private = nullptr;
-        hipEvent_t ev[2] = {nullptr, nullptr};  // the rescore's, read one synchronise later than the join's
-        ~Scratch() {
-            for (hipEvent_t e : ev)
-                if (e) (void)hipEventDestroy(e);
-            if (d_private) (void)hipFree(d_private);
-            if (w) {
-                std::lock_guard<std::mutex> lk(h->mu);
-                h->clusters_pool.push_back(w);
-            }
-        }
-    } sc{h};
-    sc.w = acquire_clusters(h);
-    if (!sc.w) return fail(CS_ERR_HIP, "similar clusters: could not create a HIP stream");
-    ClustersWorkspace* w = sc.w;
-    if (!d_f16) {  // the int8 copy serves the index: the call brings its own f16 rows and frees them (similar_pairs)
-        if (h->normed_rows < stored) return fail(CS_ERR_HIP, "similar clusters: the index holds no row norms");
-        const size_t bytes = (size_t)plan.tiles * kPairsTileRows * h->dim * sizeof(_Float16);
-        if (cs_lab_env("CS_FAULT_F16_ALLOC") != nullptr || hipMalloc(&sc.d_private, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            sc.d_private = nullptr;
-            return fail(CS_ERR_OOM, "similar clusters: no room for the f16 filter copy (%llu bytes)", (unsigned long long)bytes);
-        }
-        CS_TRY(launch_corpus_split(h->d_corpus, h->d_norms, sc.d_private, 0, stored, h->dim, w->stream));
-        d_f16 = sc.d_private;
-    }
-    GroupView gv{nullptr, 0, h->ledger.id_base(), 0xFFFFFFFFu};
-    if (mode == CS_PAIRS_OTHER_GROUP) CS_TRY(ensure_groups(h, 0xFFFFFFFFu, &gv));
-    CS_TRY(reserve_buf(w->d_parent, w->parent_cap, (size_t)stored));
-    CS_TRY(reserve_buf(w->d_mark, w->mark_cap, (size_t)stored));
-    CS_TRY(reserve_buf(w->d_tile_root, w->tile_root_cap, (size_t)plan.tiles));
-    CS_TRY(reserve_buf(w->d_label, w->label_cap, (size_t)n_labels));
-    CS_TRY(reserve_buf(w->d_amb, w->amb_cap, (size_t)plan.ambiguous_cap));
-    CS_HIP(hipEventCreate(&sc.ev[0]));
-    CS_HIP(hipEventCreate(&sc.ev[1]));
-    CS_HIP(hipMemsetAsync(w->d_counters, 0, 4 * sizeof(uint64_t), w->stream));
-    CS_HIP(hipMemsetAsync(w->d_label, 0xFF, (size_t)n_labels * sizeof(uint32_t), w->stream));  // CS_NO_ID
-    CS_TRY(launch_clusters_init(w->d_parent, w->d_mark, stored, w->stream));
-    const uint32_t* d_dead = h->ledger.removed() ? h->d_dead : nullptr;
-    const float* d_norms = h->normed_rows >= stored ? h->d_norms : nullptr;  // none: no pair is united without a rescore
-    const RowIds ids = h->row_ids();
-    ClustersInfo info;
-    bool rescore_timed = false;
-    float ms = 0.0f;
-    CS_TRY(clusters_walk(h, w, sc.ev, plan, ids, min_cos, info, rescore_timed, [&](const PairsBand& r) -> int32_t {
-        CS_TRY(launch_clusters_tile_roots(w->d_parent, plan.tiles, stored, d_dead, w->d_tile_root, w->stream));
-        return launch_clusters_join(d_f16, h->dim, plan.tiles, r.first, r.count, stored, d_dead, ids, gv,
-                                    mode == CS_PAIRS_OTHER_GROUP, min_cos, h->filter_margin, d_norms, w->d_parent,
-                                    w->d_tile_root, w->d_amb, w->d_counters, (uint32_t)plan.ambiguous_cap, w->stream);
-    }));
-    CS_HIP(hipEventRecord(w->ev[0], w->stream));
-    CS_TRY(launch_clusters_label(w->d_parent, w->d_mark, stored, d_dead, ids, w->d_label, n_labels, w->d_counters + 2, w->stream));
-    CS_HIP(hipEventRecord(w->ev[1], w->stream));
-    CS_HIP(hipMemcpyAsync(w->h_counters + 2, w->d_counters + 2, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, w->stream));
-    std::vector<uint32_t> staged((size_t)n_labels);
-    CS_HIP(hipMemcpyAsync(staged.data(), w->d_label, staged.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, w->stream));
-    CS_HIP(hipStreamSynchronize(w->stream));
-    CS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
-    info.label_ms = ms;
-    if (rescore_timed) {
-        CS_HIP(hipEventElapsedTime(&ms, sc.ev[0], sc.ev[1]));
-        info.join_ms += ms;
-    }
-    std::copy(staged.begin(), staged.end(), out_label);
-    if (out_clusters) *out_clusters = w->h_counters[2];
-    if (out_members) *out_members = w->h_counters[3];
-    last_clusters_info = info;
-    return CS_OK;
-}
-
-// cs_index_similar_pairs_scoped: similar_pairs over the row lists of two scopes (the same handle twice: inside one).  Every
-// check comes before a list is refreshed; the lists are refreshed one after the other (no two scope mutexes are held
-// together), then each side's rows are packed into an f16 buffer of the call's own (scan_pairs_scoped.hip) — the index's
-// d_split is neither read nor made — the plan's triangle or rectangle is filtered in bands, and the tail is the unscoped
-// call's (pairs_finish).  The scopes' route counters do not move: this is no search.
-int32_t similar_pairs_scoped(cs_index* h, cs_scope* scope_a, cs_scope* scope_b, float min_cos, int32_t mode, uint32_t max_pairs,
-                             uint32_t* out_a, uint32_t* out_b, float* out_cos, uint64_t* out_total) {
-    if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
-    CS_TRY(check_search(h, 1, h->dim, 1));
-    if (!out_a || !out_b || !out_cos || !out_total) return fail(CS_ERR_BAD_ARG, "null buffer");
-    if (mode != CS_PAIRS_ALL && mode != CS_PAIRS_OTHER_GROUP)
-        return fail(CS_ERR_BAD_ARG, "mode must be CS_PAIRS_ALL or CS_PAIRS_OTHER_GROUP (0..1), got %d", mode);
-    if (min_cos != min_cos) return fail(CS_ERR_BAD_ARG, "min_cos is NaN");
-    if (max_pairs == 0 || max_pairs > CS_MAX_PAIRS)
-        return fail(CS_ERR_BAD_ARG, "max_pairs must be in 1..%u, got %u", CS_MAX_PAIRS, max_pairs);
-    if (!scope_a) return fail(CS_ERR_BAD_ARG, "null scope handle (scope_a)");
-    if (!scope_b) return fail(CS_ERR_BAD_ARG, "null scope handle (scope_b)");
-    CS_TRY(check_scope_handle(h, scope_a));
-    CS_TRY(check_scope_handle(h, scope_b));
-    if (!split_scan_supported(h->dim))
-        return fail(CS_ERR_UNSUPPORTED, "similar pairs need dim 384, 768 or 1024 (the f16 filter's widths), got %u", h->dim);
-    if (!h->use_split)
-        return fail(CS_ERR_UNSUPPORTED, "similar pairs need the f16 filter copy, and CS_INDEX_SPLIT=0 turned it off");
-    DeviceGuard g(h->device);
-    const bool same = scope_a == scope_b;
-    uint64_t live_a = 0, live_b = 0;
-    CS_TRY(scope_ready(h, scope_a, &live_a));
-    if (same) live_b = live_a;
-    else CS_TRY(scope_ready(h, scope_b, &live_b));
-    PairsScopedPlan plan = plan_pairs_scoped(same, live_a, live_b, max_pairs);
-    cs_scope* const sa = plan.swapped ? scope_b : scope_a;
-    cs_scope* const sb = plan.swapped ? scope_a : scope_b;
-    PairsInfo info;
-    info.rows_a = plan.rows_a;
-    info.rows_b = plan.rows_b;
-    struct Scratch {
-        cs_index* h;
-        PairsWorkspace* w = nullptr;
-        _Float16* d_packed[2] = {nullptr, nullptr};
-        ~Scratch() {
-            for (_Float16* p : d_packed)
-                if (p) (void)hipFree(p);
-            if (w) {
-                std::lock_guard<std::mutex> lk(h->mu);
-                h->pairs_pool.push_back(w);
-            }
-        }
-    } sc{h};
-    if (plan.tile_pairs) {
-        sc.w = acquire_pairs(h);
-        if (!sc.w) return fail(CS_ERR_HIP, "similar pairs: could not create a HIP stream");
-    }
-    PairsWorkspace* w = sc.w;
-    if (plan.tile_pairs && !same && plan.rows_a == 1 && plan.rows_b == 1) {  // two handles, one row each: the same row is no pair
-        uint32_t* rows = reinterpret_cast<uint32_t*>(w->h_counters);
-        CS_HIP(hipMemcpyAsync(rows, sa->d_list, sizeof(uint32_t), hipMemcpyDeviceToHost, w->stream));
-        CS_HIP(hipMemcpyAsync(rows + 1, sb->d_list, sizeof(uint32_t), hipMemcpyDeviceToHost, w->stream));
-        CS_HIP(hipStreamSynchronize(w->stream));
-        if (rows[0] == rows[1]) { plan.tile_pairs = 0; plan.bands = 0; }
-    }
-    if (plan.tile_pairs == 0) {  // no pair: no filter is launched
-        *out_total = 0;
-        last_pairs_info = info;
-        return CS_OK;
-    }
-    info.tile_pairs = plan.tile_pairs;
-    if (h->normed_rows < h->ledger.stored()) return fail(CS_ERR_HIP, "similar pairs: the index holds no row norms");
-    const uint64_t side_tiles[2] = {plan.tiles_a, plan.tiles_b};
-    for (int s = 0; s < (same ? 1 : 2); ++s) {
-        const size_t bytes = packed_bytes_of(side_tiles[s], h->dim);
-        if (cs_lab_env("CS_FAULT_F16_ALLOC") != nullptr || hipMalloc(&sc.d_packed[s], bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            sc.d_packed[s] = nullptr;
-            return fail(CS_ERR_OOM, "similar pairs: no room for the f16 filter copy (%llu bytes)", (unsigned long long)bytes);
-        }
-    }
-    GroupView gv{nullptr, 0, h->ledger.id_base(), 0xFFFFFFFFu};
-    if (mode == CS_PAIRS_OTHER_GROUP) CS_TRY(ensure_groups(h, 0xFFFFFFFFu, &gv));
-    CS_TRY(reserve_buf(w->d_cand, w->cand_cap, (size_t)plan.cand_cap));
-    CS_TRY(reserve_buf(w->d_out, w->out_cap, (size_t)plan.cand_cap));
-    CS_HIP(hipMemsetAsync(w->d_counters, 0, 2 * sizeof(uint64_t), w->stream));
-    CS_HIP(hipEventRecord(w->ev[0], w->stream));
-    CS_TRY(launch_pairs_pack(h->d_corpus, h->d_norms, sa->d_list, plan.rows_a, h->dim, sc.d_packed[0], w->stream));
-    if (!same) CS_TRY(launch_pairs_pack(h->d_corpus, h->d_norms, sb->d_list, plan.rows_b, h->dim, sc.d_packed[1], w->stream));
-    CS_HIP(hipEventRecord(w->ev[1], w->stream));
-    CS_HIP(hipStreamSynchronize(w->stream));
-    {
-        float ms = 0.0f;
-        CS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
-        info.pack_ms = ms;
-    }
-    const _Float16* d_b = same ? sc.d_packed[0] : sc.d_packed[1];
-    for (uint64_t b = 0; b < plan.bands; ++b) {
-        const PairsBand band = plan.band(b);
-        CS_HIP(hipEventRecord(w->ev[0], w->stream));
-        CS_TRY(launch_pairs_scoped_filter(plan, sc.d_packed[0], d_b, sa->d_list, sb->d_list, h->dim, band.first, band.count,
-                                          h->row_ids(), gv, mode == CS_PAIRS_OTHER_GROUP, min_cos, h->filter_margin, w->d_cand,
-                                          w->d_counters, w->stream));
-        CS_HIP(hipEventRecord(w->ev[1], w->stream));
-        CS_HIP(hipMemcpyAsync(w->h_counters, w->d_counters, sizeof(uint64_t), hipMemcpyDeviceToHost, w->stream));
-        CS_HIP(hipStreamSynchronize(w->stream));
-        float ms = 0.0f;
-        CS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
-        info.filter_ms += ms;
-        info.bands++;
-        if (w->h_counters[0] > plan.cand_cap) return pairs_overflow(w->h_counters[0], b + 1, plan.bands, plan.cand_cap);
-    }
-    return pairs_finish(h, w, min_cos, max_pairs, out_a, out_b, out_cos, out_total, info);
-}
-
-// cs_index_similar_clusters_scoped: similar_clusters over the graph of similar_pairs_scoped (scan_clusters_scoped.hip, plan:
-// clusters_scoped_plan.hpp).  Every check comes before a list is refreshed; the lists are refreshed and packed as
-// similar_pairs_scoped does — the index's d_split is neither read nor made — and the walk is similar_clusters'.  The
-// union-find is the pooled workspace's, sized by stored rows, but only the words of the scopes' rows are initialised and
-// reached: the device work of a call is O(live rows of the scopes).  The label pass writes (id, label) per list entry; the
-// host interleaves the two ascending segments, dropping the second copy of a row in both, and copies out last.  An empty
-// join (the plan's tile_pairs == 0, or two handles holding the same single row) runs the init and the label pass only.
-int32_t similar_clusters_scoped(cs_index* h, cs_scope* scope_a, cs_scope* scope_b, float min_cos, int32_t mode, uint32_t* out_ids,
-                                uint32_t* out_label, uint64_t cap, uint64_t* out_n, uint64_t* out_clusters,
-                                uint64_t* out_members) {
-    if (!h) return fail(CS_ERR_BAD_ARG, "null index handle");
-    CS_TRY(check_search(h, 1, h->dim, 1));
-    if (!out_ids || !out_label || !out_n) return fail(CS_ERR_BAD_ARG, "null buffer");
-    if (mode != CS_PAIRS_ALL && mode != CS_PAIRS_OTHER_GROUP)
-        return fail(CS_ERR_BAD_ARG, "mode must be CS_PAIRS_ALL or CS_PAIRS_OTHER_GROUP (0..1), got %d", mode);
-    if (min_cos != min_cos) return fail(CS_ERR_BAD_ARG, "min_cos is NaN");
-    if (!scope_a) return fail(CS_ERR_BAD_ARG, "null scope handle (scope_a)");
-    if (!scope_b) return fail(CS_ERR_BAD_ARG, "null scope handle (scope_b)");
-    CS_TRY(check_scope_handle(h, scope_a));
-    CS_TRY(check_scope_handle(h, scope_b));
-    const bool same = scope_a == scope_b;
-    const uint64_t want = scope_a->n_ids + (same ? 0 : scope_b->n_ids);  // (n_ids never changes after the create call)
-    if (cap < want)
-        return fail(CS_ERR_BAD_ARG, "cap must be at least n_ids(scope_a)%s = %llu (one slot per id a scope names), got %llu",
-                    same ? "" : " + n_ids(scope_b)", (unsigned long long)want, (unsigned long long)cap);
-    if (!split_scan_supported(h->dim))
-        return fail(CS_ERR_UNSUPPORTED, "similar clusters need dim 384, 768 or 1024 (the f16 filter's widths), got %u", h->dim);
-    if (!h->use_split)
-        return fail(CS_ERR_UNSUPPORTED, "similar clusters need the f16 filter copy, and CS_INDEX_SPLIT=0 turned it off");
-    DeviceGuard g(h->device);
-    uint64_t live_a = 0, live_b = 0;
-    CS_TRY(scope_ready(h, scope_a, &live_a));
-    if (same) live_b = live_a;
-    else CS_TRY(scope_ready(h, scope_b, &live_b));
-    ClustersScopedPlan plan = plan_clusters_scoped(same, live_a, live_b, clusters_knob("CS_CLUSTERS_LAUNCH_TILE_PAIRS"),
-                                                   clusters_knob("CS_CLUSTERS_AMBIGUOUS_CAP"));
-    cs_scope* const sa = plan.swapped ? scope_b : scope_a;
-    cs_scope* const sb = plan.swapped ? scope_a : scope_b;
-    const uint64_t second = same ? 0 : plan.rows_b;   // entries of the B segment of the label pass
-    const uint64_t entries = plan.rows_a + second;
-    ClustersInfo info;
-    info.rows_a = plan.rows_a;
-    info.rows_b = plan.rows_b;
-    if (entries == 0) {  // no vertex
-        *out_n = 0;
-        if (out_clusters) *out_clusters = 0;
-        if (out_members) *out_members = 0;
-        last_clusters_info = info;
-        return CS_OK;
-    }
-    struct Scratch {
-        cs_index* h;
-        ClustersWorkspace* w = nullptr;
-        _Float16* d_packed[2] = {nullptr, nullptr};
-        hipEvent_t ev[2] = {nullptr, nullptr};  // the rescore's, read one synchronise later than the join's
-        ~Scratch() {
-            for (hipEvent_t e : ev)
-                if (e) (void)hipEventDestroy(e);
-            for (_Float16* p : d_packed)
-                if (p) (void)hipFree(p);
-            if (w) {
-                std::lock_guard<std::mutex> lk(h->mu);
-                h->clusters_pool.push_back(w);
-            }
-        }
-    } sc{h};
-    sc.w = acquire_clusters(h);
-    if (!sc.w) return fail(CS_ERR_HIP, "similar clusters: could not create a HIP stream");
-    ClustersWorkspace* w = sc.w;
-    if (plan.tile_pairs && !same && plan.rows_a == 1 && plan.rows_b == 1) {  // two handles, one row each: the same row is no pair
-        uint32_t* rows = reinterpret_cast<uint32_t*>(w->h_counters);
-        CS_HIP(hipMemcpyAsync(rows, sa->d_list, sizeof(uint32_t), hipMemcpyDeviceToHost, w->stream));
-        CS_HIP(hipMemcpyAsync(rows + 1, sb->d_list, sizeof(uint32_t), hipMemcpyDeviceToHost, w->stream));
-        CS_HIP(hipStreamSynchronize(w->stream));
-        if (rows[0] == rows[1]) plan.tile_pairs = 0;
-    }
-    const uint64_t stored = h->ledger.stored();
-    if (plan.tile_pairs) {
-        if (h->normed_rows < stored) return fail(CS_ERR_HIP, "similar clusters: the index holds no row norms");
-        const uint64_t side_tiles[2] = {plan.tiles_a, plan.tiles_b};
-        for (int s = 0; s < (same ? 1 : 2); ++s) {
-            const size_t bytes = packed_bytes_of(side_tiles[s], h->dim);
-            if (cs_lab_env("CS_FAULT_F16_ALLOC") != nullptr || hipMalloc(&sc.d_packed[s], bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                sc.d_packed[s] = nullptr;
-                return fail(CS_ERR_OOM, "similar clusters: no room for the f16 filter copy (%llu bytes)", (unsigned long long)bytes);
-            }
-        }
-    }
-    GroupView gv{nullptr, 0, h->ledger.id_base(), 0xFFFFFFFFu};
-    if (plan.tile_pairs && mode == CS_PAIRS_OTHER_GROUP) CS_TRY(ensure_groups(h, 0xFFFFFFFFu, &gv));
-    CS_TRY(reserve_buf(w->d_parent, w->parent_cap, (size_t)stored));
-    CS_TRY(reserve_buf(w->d_mark, w->mark_cap, (size_t)stored));
-    CS_TRY(reserve_buf(w->d_tile_root, w->tile_root_cap, (size_t)(plan.tiles_a + plan.tiles_b)));
-    CS_TRY(reserve_buf(w->d_label, w->label_cap, (size_t)(2 * entries)));  // ids, then labels, per list entry
-    if (plan.tile_pairs) CS_TRY(reserve_buf(w->d_amb, w->amb_cap, (size_t)plan.ambiguous_cap));
-    CS_HIP(hipEventCreate(&sc.ev[0]));
-    CS_HIP(hipEventCreate(&sc.ev[1]));
-    CS_HIP(hipMemsetAsync(w->d_counters, 0, 4 * sizeof(uint64_t), w->stream));
-    CS_TRY(launch_clusters_scoped_init(w->d_parent, w->d_mark, sa->d_list, plan.rows_a, sb->d_list, second, w->stream));
-    const RowIds ids = h->row_ids();
-    bool rescore_timed = false;
-    float ms = 0.0f;
-    if (plan.tile_pairs) {
-        CS_HIP(hipEventRecord(w->ev[0], w->stream));
-        CS_TRY(launch_pairs_pack(h->d_corpus, h->d_norms, sa->d_list, plan.rows_a, h->dim, sc.d_packed[0], w->stream));
-        if (!same) CS_TRY(launch_pairs_pack(h->d_corpus, h->d_norms, sb->d_list, plan.rows_b, h->dim, sc.d_packed[1], w->stream));
-        CS_HIP(hipEventRecord(w->ev[1], w->stream));
-        CS_HIP(hipStreamSynchronize(w->stream));
-        CS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
-        info.pack_ms = ms;
-        const _Float16* d_b = same ? sc.d_packed[0] : sc.d_packed[1];
-        uint32_t* const d_root_a = w->d_tile_root;
-        uint32_t* const d_root_b = same ? d_root_a : d_root_a + plan.tiles_a;
-        CS_TRY(clusters_walk(h, w, sc.ev, plan, ids, min_cos, info, rescore_timed, [&](const PairsBand& r) -> int32_t {
-            CS_TRY(launch_clusters_scoped_tile_roots(w->d_parent, sa->d_list, plan.rows_a, d_root_a, w->stream));
-            if (!same) CS_TRY(launch_clusters_scoped_tile_roots(w->d_parent, sb->d_list, plan.rows_b, d_root_b, w->stream));
-            return launch_clusters_scoped_join(plan, sc.d_packed[0], d_b, sa->d_list, sb->d_list, h->dim, r.first, r.count, ids, gv,
-                                               mode == CS_PAIRS_OTHER_GROUP, min_cos, h->filter_margin, h->d_norms, w->d_parent,
-                                               d_root_a, d_root_b, w->d_amb, w->d_counters, w->stream);
-        }));
-    }
-    uint32_t* const d_ids = w->d_label;
-    uint32_t* const d_lab = w->d_label + entries;
-    CS_HIP(hipEventRecord(w->ev[0], w->stream));
-    CS_TRY(launch_clusters_scoped_label(w->d_parent, w->d_mark, sa->d_list, plan.rows_a, sb->d_list, second, ids, d_ids, d_lab,
-                                        w->d_counters + 2, w->stream));
-    CS_HIP(hipEventRecord(w->ev[1], w->stream));
-    CS_HIP(hipMemcpyAsync(w->h_counters + 2, w->d_counters + 2, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, w->stream));
-    std::vector<uint32_t> staged((size_t)(2 * entries));
-    CS_HIP(hipMemcpyAsync(staged.data(), w->d_label, staged.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, w->stream));
-    CS_HIP(hipStreamSynchronize(w->stream));
-    CS_HIP(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
-    info.label_ms = ms;
-    if (rescore_timed) {
-        CS_HIP(hipEventElapsedTime(&ms, sc.ev[0], sc.ev[1]));
-        info.join_ms += ms;
-    }
-    // the two segments ascend by id (rows ascend with ids): one merge, a row of both lists once.  At most `entries` <= cap.
-    const uint32_t* const sid = staged.data();
-    const uint32_t* const slab = staged.data() + entries;
-    uint64_t n = 0, i = 0, j = plan.rows_a;
-    while (i < plan.rows_a || j < entries) {
-        uint64_t take;
-        if (j >= entries || (i < plan.rows_a && sid[i] <= sid[j])) {
-            if (j < entries && sid[i] == sid[j]) ++j;
-            take = i++;
-        } else {
-            take = j++;
-        }
-        out_ids[n] = sid[take];
-        out_label[n] = slab[take];
-        ++n;
-    }
-    *out_n = n;
-    if (out_clusters) *out_clusters = w->h_counters[2];
-    if (out_members) *out_members = w->h_counters[3];
-    info.vertices = n;
-    last_clusters_info = info;
-    return CS_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -2392,8 +1565,7 @@ void cs_index_destroy(cs_index* h) {
     (void)drain_appends(h);
     for (auto* w : h->pool) { w->release_all(); delete w; }
     for (auto& kv : h->by_stream) { kv.second->release_all(); delete kv.second; }
-    for (auto* w : h->pairs_pool) { w->release_all(); delete w; }
-    for (auto* w : h->clusters_pool) { w->release_all(); delete w; }
+    free_join_pools(h);
     for (auto& t : h->pending) {
         (void)hipEventDestroy(t.e0); (void)hipEventDestroy(t.e1); (void)hipEventDestroy(t.e2);
     }
@@ -2696,67 +1868,6 @@ int32_t cs_index_search_similar(cs_index* h, const uint32_t* ids, uint32_t nq, u
 int32_t cs_index_search_similar_scoped(cs_index* h, cs_scope* scope, const uint32_t* ids, uint32_t nq, uint32_t k,
                                        int32_t exclude, float min_cos, float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
     return search_similar(h, true, scope, ids, nq, k, exclude, min_cos, HostAnswer{out_cos, out_ids, out_counts, nullptr, false});
-}
-
-int32_t cs_index_similar_pairs(cs_index* h, float min_cos, int32_t mode, uint32_t max_pairs, uint32_t* out_a, uint32_t* out_b,
-                               float* out_cos, uint64_t* out_total) {
-    return similar_pairs(h, min_cos, mode, max_pairs, out_a, out_b, out_cos, out_total);
-}
-
-int32_t cs_index_similar_pairs_scoped(cs_index* h, cs_scope* scope_a, cs_scope* scope_b, float min_cos, int32_t mode,
-                                      uint32_t max_pairs, uint32_t* out_a, uint32_t* out_b, float* out_cos, uint64_t* out_total) {
-    return similar_pairs_scoped(h, scope_a, scope_b, min_cos, mode, max_pairs, out_a, out_b, out_cos, out_total);
-}
-
-int32_t cs_index_similar_clusters(cs_index* h, float min_cos, int32_t mode, uint32_t* out_label, uint64_t n_labels,
-                                  uint64_t* out_clusters, uint64_t* out_members) {
-    return similar_clusters(h, min_cos, mode, out_label, n_labels, out_clusters, out_members);
-}
-
-int32_t cs_index_similar_clusters_info(uint64_t* tile_pairs_scored, uint64_t* tile_pairs_skipped, uint64_t* rescored_pairs,
-                                       uint32_t* launches, double* join_ms, double* label_ms) {
-    const ClustersInfo& i = last_clusters_info;
-    if (tile_pairs_scored) *tile_pairs_scored = i.scored;
-    if (tile_pairs_skipped) *tile_pairs_skipped = i.skipped;
-    if (rescored_pairs) *rescored_pairs = i.rescored;
-    if (launches) *launches = i.launches;
-    if (join_ms) *join_ms = i.join_ms;
-    if (label_ms) *label_ms = i.label_ms;
-    return CS_OK;
-}
-
-int32_t cs_index_similar_clusters_scoped(cs_index* h, cs_scope* scope_a, cs_scope* scope_b, float min_cos, int32_t mode,
-                                         uint32_t* out_ids, uint32_t* out_label, uint64_t cap, uint64_t* out_n,
-                                         uint64_t* out_clusters, uint64_t* out_members) {
-    return similar_clusters_scoped(h, scope_a, scope_b, min_cos, mode, out_ids, out_label, cap, out_n, out_clusters, out_members);
-}
-
-int32_t cs_index_similar_clusters_scoped_info(double* pack_ms, uint64_t* rows_a, uint64_t* rows_b, uint64_t* vertices) {
-    const ClustersInfo& i = last_clusters_info;
-    if (pack_ms) *pack_ms = i.pack_ms;
-    if (rows_a) *rows_a = i.rows_a;
-    if (rows_b) *rows_b = i.rows_b;
-    if (vertices) *vertices = i.vertices;
-    return CS_OK;
-}
-
-int32_t cs_index_similar_pairs_scoped_info(double* pack_ms, uint64_t* rows_a, uint64_t* rows_b, uint64_t* tile_pairs) {
-    const PairsInfo& i = last_pairs_info;
-    if (pack_ms) *pack_ms = i.pack_ms;
-    if (rows_a) *rows_a = i.rows_a;
-    if (rows_b) *rows_b = i.rows_b;
-    if (tile_pairs) *tile_pairs = i.tile_pairs;
-    return CS_OK;
-}
-
-int32_t cs_index_similar_pairs_info(uint64_t* candidates, uint32_t* bands, double* filter_ms, double* refine_ms, double* order_ms) {
-    const PairsInfo& i = last_pairs_info;
-    if (candidates) *candidates = i.candidates;
-    if (bands) *bands = i.bands;
-    if (filter_ms) *filter_ms = i.filter_ms;
-    if (refine_ms) *refine_ms = i.refine_ms;
-    if (order_ms) *order_ms = i.order_ms;
-    return CS_OK;
 }
 
 int32_t cs_index_scope_create(cs_index* h, const uint32_t* ids, uint64_t n, cs_scope** out) {

@@ -1,5 +1,5 @@
 // pairs_plan.hpp — the host side of the similar-pairs search (cs_index_similar_pairs; kernels: scan_pairs.hip): the
-// geometry of the self-join as plain C++17, no HIP.  tests/cpp/pairs_plan_test.cpp walks it on the CPU; index.hip and
+// geometry of the self-join as plain C++17, no HIP.  tests/cpp/pairs_plan_test.cpp walks it on the CPU; index_joins.hip and
 // scan_pairs.hip only launch what it says.
 //
 // The corpus is T = ceil(stored_rows / 128) tiles of 128 rows (the tiles of the f16 filter copy).  The join scores every tile

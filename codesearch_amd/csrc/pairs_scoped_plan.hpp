@@ -1,6 +1,6 @@
 // pairs_scoped_plan.hpp — the host side of the scoped similar-pairs search (cs_index_similar_pairs_scoped; kernels:
 // scan_pairs_scoped.hip): the geometry of the join of two scopes' row lists as plain C++17, no HIP.
-// tests/cpp/pairs_scoped_plan_test.cpp walks it on the CPU; index.hip and scan_pairs_scoped.hip only launch what it says.
+// tests/cpp/pairs_scoped_plan_test.cpp walks it on the CPU; index_joins.hip and scan_pairs_scoped.hip only launch what it says.
 //
 // Both sides are PACKED: list entry i of a scope (its i-th live stored row, ascending) becomes packed row i of an f16 buffer
 // of the call's own, in the filter copy's tiled layout.  A side of n live rows is T = ceil(n / 128) packed tiles and

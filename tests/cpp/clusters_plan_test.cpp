@@ -5,7 +5,7 @@
 //     first tile row; the laboratory knob sets every launch's size;
 //   * the ambiguous buffer never holds fewer pairs than one tile pair can produce (128 * 128), whatever the knob;
 //   * splitting halves a range into two non-empty parts that tile it, and ends at one tile pair;
-//   * the host's walk (index.hip: launch, read the counter, split on overflow, lo half first) accepts every tile pair exactly
+//   * the host's walk (ClustersWalk: launch, read the counter, split on overflow, lo half first) accepts every tile pair exactly
 //     once and in the triangle's order, with the smallest buffer and the worst load: every tile pair full.
 #include <cstdint>
 #include <cstdio>
@@ -77,30 +77,21 @@ static void split_ends(uint64_t first, uint64_t count) {
     CHECK(singles == count);
 }
 
-// index.hip's walk against a device that reports `per_pair` ambiguous pairs for every tile pair of a launch.
+// The calls' walk (ClustersWalk, as index_joins.hip's clusters_walk drives it) against a device that reports `per_pair`
+// ambiguous pairs for every tile pair of a launch.
 static void walk(uint64_t rows, uint64_t launch_knob, uint64_t cap_knob, uint64_t per_pair) {
     const ClustersPlan p = plan_clusters(rows, launch_knob, cap_knob);
     CHECK(per_pair <= kClustersTilePairAmbiguous && p.ambiguous_cap >= kClustersTilePairAmbiguous);
-    std::vector<PairsBand> halves;
-    uint64_t next = 0, accepted = 0, launches = 0;
-    while (next < p.tile_pairs || !halves.empty()) {
-        PairsBand r;
-        if (!halves.empty()) {
-            r = halves.back();
-            halves.pop_back();
-        } else {
-            r = p.launch_at(next);
-            next += r.count;
-        }
+    ClustersWalk<ClustersPlan> w(p);
+    PairsBand r;
+    uint64_t accepted = 0, launches = 0;
+    while (w.next(r)) {
         ++launches;
         CHECK(launches <= 4 * p.tile_pairs + 4);  // it ends
-        if (r.count * per_pair > p.ambiguous_cap) {
-            PairsBand lo, hi;
-            CHECK(clusters_split(r, lo, hi));  // a launch that overflowed is never one tile pair
-            halves.push_back(hi);
-            halves.push_back(lo);
-            continue;
-        }
+        const ClustersStep step = w.report(r, r.count * per_pair);
+        CHECK(step != ClustersStep::Impossible);  // a launch that overflowed is never one tile pair
+        CHECK((step == ClustersStep::Split) == (r.count * per_pair > p.ambiguous_cap));
+        if (step == ClustersStep::Split) continue;
         CHECK(r.first == accepted);  // in order, nothing twice, nothing left out
         accepted += r.count;
     }

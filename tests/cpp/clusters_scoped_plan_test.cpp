@@ -4,7 +4,7 @@
 //   * the launches cover triangle and rectangle exactly once, in order — every tile pair named, exhaustively, for T, TA, TB
 //     in 1 .. 40 — and at 78,125 x 78,125 tiles with the launches' ends sampled; launch 0 is the first tile row;
 //   * the two laboratory knobs and their clamps;
-//   * halves tile their parent and splitting ends at one tile pair; the host's walk (index.hip clusters_walk) under the
+//   * halves tile their parent and splitting ends at one tile pair; the host's walk (clusters_plan.hpp ClustersWalk) under the
 //     worst load accepts every tile pair once, in order;
 //   * the three empty joins: a side without a row, one list of fewer than two rows (the same single row behind two handles is
 //     the caller's to notice: the plan says one tile pair).
@@ -93,29 +93,20 @@ static void split_ends(uint64_t first, uint64_t count) {
     CHECK(singles == count);
 }
 
-// index.hip's walk against a device that reports `per_pair` ambiguous pairs for every tile pair of a launch.
+// The calls' walk (ClustersWalk, as index_joins.hip's clusters_walk drives it) against a device that reports `per_pair`
+// ambiguous pairs for every tile pair of a launch.
 static void walk(const ClustersScopedPlan& p, uint64_t per_pair) {
     CHECK(per_pair <= kClustersTilePairAmbiguous && p.ambiguous_cap >= kClustersTilePairAmbiguous);
-    std::vector<PairsBand> halves;
-    uint64_t next = 0, accepted = 0, launches = 0;
-    while (next < p.tile_pairs || !halves.empty()) {
-        PairsBand r;
-        if (!halves.empty()) {
-            r = halves.back();
-            halves.pop_back();
-        } else {
-            r = p.launch_at(next);
-            next += r.count;
-        }
+    ClustersWalk<ClustersScopedPlan> w(p);
+    PairsBand r;
+    uint64_t accepted = 0, launches = 0;
+    while (w.next(r)) {
         ++launches;
         CHECK(launches <= 4 * p.tile_pairs + 4);  // it ends
-        if (r.count * per_pair > p.ambiguous_cap) {
-            PairsBand lo, hi;
-            CHECK(clusters_split(r, lo, hi));  // a launch that overflowed is never one tile pair
-            halves.push_back(hi);
-            halves.push_back(lo);
-            continue;
-        }
+        const ClustersStep step = w.report(r, r.count * per_pair);
+        CHECK(step != ClustersStep::Impossible);  // a launch that overflowed is never one tile pair
+        CHECK((step == ClustersStep::Split) == (r.count * per_pair > p.ambiguous_cap));
+        if (step == ClustersStep::Split) continue;
         CHECK(r.first == accepted);  // in order, nothing twice, nothing left out
         accepted += r.count;
     }
