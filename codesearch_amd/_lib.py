@@ -264,6 +264,8 @@ DIAG_SIGNATURES = {
                                            C.c_uint32, u32p, C.c_uint32, f32p, i32p]),
     "cs_debug_gemm": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, f32p, f32p, f32p, f32p, f32p,
                                   C.c_uint32, C.c_uint32, C.c_uint32, u32p]),
+    "cs_debug_gemm_wide": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p, f32p, f32p, f32p, f32p,
+                                       C.c_uint32, C.c_uint32, C.c_uint32, i32p, u32p, u32p]),
     "cs_debug_rows": (C.c_int32, [C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_int32,
                                   i32p, f32p, f32p, f32p, i32p, C.c_uint32, C.c_uint32, f32p, i32p, f32p, C.c_uint32, f32p, f32p, f32p,
                                   C.c_int32, f32p, f32p, f32p, f32p, u32p]),

@@ -1,11 +1,58 @@
 // diagnostics.hip — cs_debug_*: operator-level entry points for the parity tests of single kernels and for the A/B scripts
 // under benchmarks/.  NOT part of libcsgpu.so: built into libcsgpu_diag.so only (-DCS_DIAGNOSTICS, include/codesearch_gpu_diag.h).
 #include "embedder_state.hpp"
+#include "gemm_wide.hpp"  // gemm_wide_route (cs_debug_gemm_wide)
 #include "scan.hpp"  // launch_synth_fill (cs_debug_gemm_time)
 #include "../../include/codesearch_gpu_diag.h"
 
 using namespace cs;
 using namespace cs::emb;
+
+namespace {
+
+// The LayerNorm epilogue of the wide kernel as the diagnostics run it (cs_debug_gemm epilogues 3 / 4, cs_debug_gemm_wide
+// 6 / 7; N = 384): gamma = bias + 1, beta = -bias, eps 1e-12; sC [M][N/32][64] receives the split output.
+//   split_resid = false: in place over the f32 residual dR, f32 and split outputs, which must describe the same values
+//   split_resid = true:  the encoder's form: the residual handed over in split form in sC and overwritten, no f32 output
+int32_t diag_wide_ln(bool split_resid, const _Float16* sA, const _Float16* sW, const float* dB, float* dR, _Float16* sC,
+                     const float* bias, uint32_t M, uint32_t N, uint32_t K, uint32_t* dF) {
+    const size_t c_n = (size_t)M * N;
+    std::vector<float> gam(N), bet(N);
+    for (uint32_t n = 0; n < N; ++n) { gam[n] = bias[n] + 1.0f; bet[n] = -bias[n]; }
+    float *dG = nullptr, *dBe = nullptr;
+    auto run = [&]() -> int32_t {
+        CS_HIP(hipMalloc(&dG, (size_t)N * 4)); CS_HIP(hipMalloc(&dBe, (size_t)N * 4));
+        CS_HIP(hipMemcpy(dG, gam.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+        CS_HIP(hipMemcpy(dBe, bet.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+        if (split_resid) {
+            CS_TRY(launch_split_rows(dR, sC, M, N, dF, nullptr));
+            return launch_gemm_wide_ln(sA, sW, dB, nullptr, dG, dBe, 1e-12f, nullptr, sC, M, K, dF, nullptr, sC);
+        }
+        return launch_gemm_wide_ln(sA, sW, dB, dR, dG, dBe, 1e-12f, dR, sC, M, K, dF, nullptr);  // in place over resid
+    };
+    const int32_t st = run();
+    const hipError_t sync = hipDeviceSynchronize();
+    (void)hipFree(dG); (void)hipFree(dBe);
+    CS_TRY(st);
+    CS_HIP(sync);
+    if (split_resid) return CS_OK;
+    // the two outputs must describe the same values
+    std::vector<float> f32out(c_n);
+    CS_HIP(hipMemcpy(f32out.data(), dR, c_n * 4, hipMemcpyDeviceToHost));
+    std::vector<_Float16> hs(c_n * 2);
+    CS_HIP(hipMemcpy(hs.data(), sC, c_n * 4, hipMemcpyDeviceToHost));
+    for (size_t m = 0; m < M; ++m)
+        for (size_t n = 0; n < N; ++n) {
+            const _Float16* line = hs.data() + (m * (N / 32) + n / 32) * 64;
+            const float v = (float)line[n % 32] + (float)line[32 + n % 32] * (1.0f / 2048.0f);
+            if (!(fabsf(v - f32out[m * N + n]) <= 1e-6f * fmaxf(1.0f, fabsf(v))))
+                return fail(CS_ERR_HIP, "LayerNorm epilogue: f32 and split outputs disagree at (%zu, %zu): %g vs %g", m, n,
+                            (double)f32out[m * N + n], (double)v);
+        }
+    return CS_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -52,44 +99,9 @@ int32_t cs_debug_gemm(int32_t device, int32_t mode, int32_t epilogue, const floa
                                 uint32_t m_, uint32_t n_, uint32_t k_, uint32_t* f_, hipStream_t st_) {
                 return wide ? launch_gemm_wide(e, a_, w_, b_, r_, c_, cs_, m_, n_, k_, f_, st_, 0) : launch_gemm_split(e, a_, w_, b_, r_, c_, cs_, m_, n_, k_, f_, st_);
             };
-            if (epilogue == 4) {  // LayerNorm epilogue, residual given (and overwritten) in split form, no f32 output
-                std::vector<float> gam(N), bet(N);
-                for (uint32_t n = 0; n < N; ++n) { gam[n] = bias[n] + 1.0f; bet[n] = -bias[n]; }
-                float *dG = nullptr, *dBe = nullptr;
-                CS_HIP(hipMalloc(&dG, (size_t)N * 4)); CS_HIP(hipMalloc(&dBe, (size_t)N * 4));
-                CS_HIP(hipMemcpy(dG, gam.data(), (size_t)N * 4, hipMemcpyHostToDevice));
-                CS_HIP(hipMemcpy(dBe, bet.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+            if (epilogue == 3 || epilogue == 4) {
                 CS_HIP(hipMalloc(&sC, c_n * 4));
-                CS_TRY(launch_split_rows(dR, sC, M, N, dF, nullptr));
-                const int32_t st4 = launch_gemm_wide_ln(sA, sW, dB, nullptr, dG, dBe, 1e-12f, nullptr, sC, M, K, dF, nullptr, sC);
-                CS_HIP(hipDeviceSynchronize());
-                (void)hipFree(dG); (void)hipFree(dBe);
-                CS_TRY(st4);
-            } else if (epilogue == 3) {
-                std::vector<float> gam(N), bet(N);
-                for (uint32_t n = 0; n < N; ++n) { gam[n] = bias[n] + 1.0f; bet[n] = -bias[n]; }
-                float *dG = nullptr, *dBe = nullptr;
-                CS_HIP(hipMalloc(&dG, (size_t)N * 4)); CS_HIP(hipMalloc(&dBe, (size_t)N * 4));
-                CS_HIP(hipMemcpy(dG, gam.data(), (size_t)N * 4, hipMemcpyHostToDevice));
-                CS_HIP(hipMemcpy(dBe, bet.data(), (size_t)N * 4, hipMemcpyHostToDevice));
-                CS_HIP(hipMalloc(&sC, c_n * 4));
-                const int32_t st3 = launch_gemm_wide_ln(sA, sW, dB, dR, dG, dBe, 1e-12f, dR, sC, M, K, dF, nullptr);  // in place over resid
-                CS_HIP(hipDeviceSynchronize());
-                std::vector<float> f32out(c_n);
-                CS_HIP(hipMemcpy(f32out.data(), dR, c_n * 4, hipMemcpyDeviceToHost));
-                (void)hipFree(dG); (void)hipFree(dBe);
-                CS_TRY(st3);
-                // the two outputs must describe the same values: checked here, the split one is what C receives below
-                std::vector<_Float16> hs(c_n * 2);
-                CS_HIP(hipMemcpy(hs.data(), sC, c_n * 4, hipMemcpyDeviceToHost));
-                for (size_t m = 0; m < M; ++m)
-                    for (size_t n = 0; n < N; ++n) {
-                        const _Float16* line = hs.data() + (m * (N / 32) + n / 32) * 64;
-                        const float v = (float)line[n % 32] + (float)line[32 + n % 32] * (1.0f / 2048.0f);
-                        if (!(fabsf(v - f32out[m * N + n]) <= 1e-6f * fmaxf(1.0f, fabsf(v))))
-                            return fail(CS_ERR_HIP, "LayerNorm epilogue: f32 and split outputs disagree at (%zu, %zu): %g vs %g", m, n,
-                                        (double)f32out[m * N + n], (double)v);
-                    }
+                CS_TRY(diag_wide_ln(epilogue == 4, sA, sW, dB, dR, sC, bias, M, N, K, dF));
             } else if (epilogue == 1) {  // the GELU epilogue writes split form: read it back through hi + lo / 2048
                 CS_HIP(hipMalloc(&sC, c_n * 4));
                 CS_TRY(run_gemm(SH_OUT_SPLIT_GELU, sA, sW, dB, nullptr, nullptr, sC, M, N, K, dF, nullptr));
@@ -928,6 +940,83 @@ int32_t cs_debug_gemm_time(int32_t device, int32_t mode, int32_t epilogue, uint3
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     return st;
+}
+
+// Diagnostics: the wide kernel (gemm_wide.hip, gemm_wide32.hip) alone on host buffers, every block shape, MFMA form and
+// epilogue — launch_gemm_wide / launch_gemm_wide_ln as the encoder calls them, the block chosen by gemm_wide_route and
+// reported in *block_out.  Every output is followed by kSpGuardRows guard rows.  Contract in include/codesearch_gpu_diag.h.
+int32_t cs_debug_gemm_wide(int32_t device, int32_t epi, int32_t shape, int32_t mfma, const float* A, const float* W,
+                           const float* bias, const float* resid, float* C, uint32_t M, uint32_t N, uint32_t K,
+                           int32_t* block_out, uint32_t* guard_changed, uint32_t* range_flag) {
+    if (!A || !W || !bias || !C || !block_out || !guard_changed) return fail(CS_ERR_BAD_ARG, "cs_debug_gemm_wide: null buffer");
+    if (epi < 0 || epi > 7) return fail(CS_ERR_BAD_ARG, "cs_debug_gemm_wide: epi = %d (0 f32, 1 GELU -> split, 2 + resid, 3 split, 4 SwiGLU, 5 GEGLU, 6 / 7 LayerNorm)", epi);
+    if ((epi == 2 || epi >= 6) && !resid) return fail(CS_ERR_BAD_ARG, "cs_debug_gemm_wide: epilogue %d needs a residual", epi);
+    if (shape != 0 && shape != 192 && shape != 384 && shape != 256) return fail(CS_ERR_BAD_ARG, "cs_debug_gemm_wide: shape = %d (0, 192, 384, 256)", shape);
+    if (mfma != 0 && mfma != 16 && mfma != 32) return fail(CS_ERR_BAD_ARG, "cs_debug_gemm_wide: mfma = %d (0, 16, 32)", mfma);
+    if (M == 0 || !gemm_wide_supported(N, K)) return fail(CS_ERR_UNSUPPORTED, "cs_debug_gemm_wide needs M > 0, N %% 192 == 0 and K %% 32 == 0 (M=%u N=%u K=%u)", M, N, K);
+    const bool gated = epi == 4 || epi == 5, ln = epi >= 6;
+    if (gated && N % 64) return fail(CS_ERR_UNSUPPORTED, "cs_debug_gemm_wide: the gated epilogues need N %% 64 == 0 (N=%u)", N);
+    if (ln && N != 384) return fail(CS_ERR_UNSUPPORTED, "cs_debug_gemm_wide: the LayerNorm epilogue needs N = 384");
+    CS_TRY(diag_device(device));
+    DeviceGuard g(device);
+    DiagBufs bufs;
+    const int kernel_epi = epi == 0 ? SH_OUT_F32 : epi == 1 ? SH_OUT_SPLIT_GELU : epi == 2 ? SH_OUT_F32_RESID : epi == 3 ? SH_OUT_SPLIT
+                         : epi == 4 ? GW_OUT_SWIGLU : epi == 5 ? GW_OUT_GEGLU : GW_OUT_LN;
+    struct Overrides {  // the launcher's diagnostic overrides, as cs_debug_gemm_time sets them; reset on every exit path
+        Overrides(int s, int m) { cs::g_gemm_wide_shape = s; cs::g_gemm_wide_mfma = m; }
+        ~Overrides() { cs::g_gemm_wide_shape = 0; cs::g_gemm_wide_mfma = 0; }
+    } overrides(shape, mfma);
+    const GwRoute route = gemm_wide_route(kernel_epi, N, 0);
+    if (mfma && (mfma == 32) != route.mfma32) return fail(CS_ERR_UNSUPPORTED, "cs_debug_gemm_wide: epilogue %d is not built on the 32 x 32 x 16 form", epi);
+    *block_out = route.block;
+    const size_t a_n = (size_t)M * K, w_n = (size_t)N * K, c_n = (size_t)M * N;
+    const size_t out_w = gated ? N / 2 : N;  // columns of the output
+    uint32_t* dF = nullptr;  // [0] the kernel's flag, [1] that of the operands' split, [2] scratch of the weight range check
+    float *dA = nullptr, *dW = nullptr, *dB = nullptr, *dR = nullptr, *dC = nullptr;
+    _Float16 *sA = nullptr, *sW = nullptr, *sC = nullptr;
+    CS_TRY(bufs.get(&dF, 16));
+    CS_HIP(hipMemset(dF, 0, 16));
+    CS_TRY(bufs.get(&dA, a_n * 4, A));
+    CS_TRY(bufs.get(&dW, w_n * 4, W));
+    CS_TRY(bufs.get(&dB, (size_t)N * 4, bias));
+    CS_TRY(bufs.get(&sA, a_n * 4));
+    CS_TRY(bufs.get(&sW, w_n * 4));
+    CS_TRY(launch_split_rows(dA, sA, M, K, dF + 1, nullptr));
+    CS_TRY(launch_split_rows(dW, sW, N, K, dF + 1, nullptr));
+    bool fits = false;
+    CS_TRY(sh_weights_fit_wide(sW, (uint64_t)w_n * 2, dF + 2, &fits, nullptr));
+    if (!fits) return fail(CS_ERR_UNSUPPORTED, "cs_debug_gemm_wide: the wide kernel needs |w| <= 31.98");
+    // an output of M rows of `row_bytes` each, followed by the guard rows (cs_debug_small_path)
+    std::vector<std::pair<const char*, size_t>> guards;
+    auto guarded = [&](auto** out, size_t row_bytes) -> int32_t {
+        const size_t body = (size_t)M * row_bytes, tail = (size_t)kSpGuardRows * row_bytes;
+        CS_TRY(bufs.get(out, body + tail));
+        CS_HIP(hipMemset(*out, 0xff, body));  // an element the launch does not write comes back as NaN
+        CS_HIP(hipMemset(reinterpret_cast<char*>(*out) + body, 0xA5, tail));
+        guards.emplace_back(reinterpret_cast<const char*>(*out) + body, tail);
+        return CS_OK;
+    };
+    if (epi == 2) CS_TRY(bufs.get(&dR, c_n * 4, resid));
+    if (ln) {  // read and (epilogue 6) overwritten in place: an output like the others
+        CS_TRY(guarded(&dR, (size_t)N * 4));
+        CS_HIP(hipMemcpy(dR, resid, c_n * 4, hipMemcpyHostToDevice));
+    }
+    if (epi == 0 || epi == 2) CS_TRY(guarded(&dC, (size_t)N * 4));
+    else CS_TRY(guarded(&sC, out_w * 4));
+    if (ln) CS_TRY(diag_wide_ln(epi == 7, sA, sW, dB, dR, sC, bias, M, N, K, dF));
+    else CS_TRY(launch_gemm_wide(kernel_epi, sA, sW, dB, dR, dC, sC, M, N, K, dF, nullptr, 0));
+    CS_HIP(hipDeviceSynchronize());
+    if (sC) CS_TRY(diag_read_split(sC, M, out_w, C));
+    else CS_HIP(hipMemcpy(C, dC, c_n * 4, hipMemcpyDeviceToHost));
+    if (range_flag) CS_HIP(hipMemcpy(range_flag, dF, 4, hipMemcpyDeviceToHost));
+    uint32_t changed = 0;
+    for (const auto& gd : guards) {
+        std::vector<uint32_t> hw(gd.second / 4);
+        CS_HIP(hipMemcpy(hw.data(), gd.first, gd.second, hipMemcpyDeviceToHost));
+        for (uint32_t w : hw) changed += w != kSpGuardWord;
+    }
+    *guard_changed = changed;
+    return CS_OK;
 }
 
 }  // extern "C"

@@ -613,9 +613,7 @@ static int32_t gemm_wide_launch(int epi, const _Float16* A, const _Float16* W, c
     return CS_OK;
 }
 
-// Block shape: 128 x 384 / one block per CU where N allows (and always for the LayerNorm epilogue); 128 x 192 / two
-// blocks per CU for the other multiples of 192 or with CS_GEMM_WIDE_SHAPE=192 (measured level with each other on every
-// layer shape of the encoder: QKV 187 vs 190 us, FFN-up 270 vs 279, FFN-down 223 vs 237).
+// Block shape and MFMA form: gemm_wide_route (gemm_wide.hpp), the one statement of the rule.
 static int32_t gemm_wide_impl(int epi, const _Float16* A, const _Float16* W, const float* bias, const float* resid, float* C,
                               _Float16* Cs, uint32_t M, uint32_t N, uint32_t K, uint32_t* d_flag, hipStream_t s,
                               const float* ln_g, const float* ln_b, float ln_eps, int shape = 0, uint32_t ln_flags = 0) {
@@ -623,26 +621,18 @@ static int32_t gemm_wide_impl(int epi, const _Float16* A, const _Float16* W, con
     if ((uint64_t)M * (K / 32) * 128 >= (1ull << 32) || (uint64_t)N * (K / 32) * 128 >= (1ull << 32))  // (32-bit buffer offsets in the kernel)
         return fail(CS_ERR_UNSUPPORTED, "wide split GEMM: an operand of 4 GiB or more (M=%u N=%u K=%u)", M, N, K);
     if (M == 0) return CS_OK;
-    static const int shape_env = [] { const char* e = cs_lab_env("CS_GEMM_WIDE_SHAPE"); return e ? std::atoi(e) : 0; }();
-    // default: 128 x 384, except the bias -> split-store layer (the QKV projection), which four boxes measured 3-4 % faster
-    // as 128 x 192 tiles, two blocks per CU (169-173 vs 175-181 us at 65,536 x 1,152 x 384; FFN-up level: profiles/
-    // r04_gemm_stagger_by_cu_ab.log code 1000, r04_gemm_role_split_ab.log)
-    const int want = shape ? shape : g_gemm_wide_shape ? g_gemm_wide_shape : shape_env ? shape_env : (epi == SH_OUT_SPLIT ? 192 : 384);
-    const bool big = epi == GW_OUT_LN || g_gemm_wide_ablation || (want == 384 && N % 384 == 0 && N <= (uint32_t)GW_PARAM_FLOATS);
+    const GwRoute route = gemm_wide_route(epi, N, shape);
 #ifdef CS_DIAGNOSTICS
-    // MFMA shape of the main loop: 16 x 16 x 32 (this file) | 32 x 32 x 16 (gemm_wide32.hip, diagnostic library only: parity-green,
-    // 2-8 % slower per layer, profiles/r05_gemm_mfma_shape_ab.log; CS_GEMM_WIDE_MFMA=32)
-    static const int mfma_env = [] { const char* e = cs_lab_env("CS_GEMM_WIDE_MFMA"); return e ? std::atoi(e) : 0; }();
-    const int mfma = g_gemm_wide_mfma ? g_gemm_wide_mfma : mfma_env;
-    if (mfma == 32 && !g_gemm_wide_ablation && epi != GW_OUT_SWIGLU && epi != GW_OUT_GEGLU)
-        return gemm_wide32_launch(big ? 4 : 2, epi, A, W, bias, resid, C, Cs, M, N, K, d_flag, s, ln_g, ln_b, ln_eps, ln_flags);
+    // the main loop on the 32 x 32 x 16 MFMA (gemm_wide32.hip, diagnostic library only; parity shown by tests/test_gpu_gemm_wide.py)
+    if (route.mfma32)
+        return gemm_wide32_launch(route.block == 384 ? 4 : 2, epi, A, W, bias, resid, C, Cs, M, N, K, d_flag, s, ln_g, ln_b, ln_eps, ln_flags);
 #endif
-    if (big) return gemm_wide_launch<4>(epi, A, W, bias, resid, C, Cs, M, N, K, d_flag, s, ln_g, ln_b, ln_eps, ln_flags);
+    if (route.block == 384) return gemm_wide_launch<4>(epi, A, W, bias, resid, C, Cs, M, N, K, d_flag, s, ln_g, ln_b, ln_eps, ln_flags);
 #ifdef CS_DIAGNOSTICS
     // 256 x 192, one block per CU (GwGeom<2, 4>; diagnostic library only): 0.875x / 0.70x the operand bytes per flop of the default
-    // shapes, parity-green, and level with them on every layer shape (profiles/r06_gemm_tall_block_ab.log) — the wide GEMMs are not
-    // bound by what L2 can deliver to LDS
-    if (want == 256) return gemm_wide_launch<2, 4>(epi, A, W, bias, resid, C, Cs, M, N, K, d_flag, s, ln_g, ln_b, ln_eps, ln_flags);
+    // shapes, parity shown by tests/test_gpu_gemm_wide.py, and level with them on every layer shape (profiles/
+    // r06_gemm_tall_block_ab.log) — the wide GEMMs are not bound by what L2 can deliver to LDS
+    if (route.block == 256) return gemm_wide_launch<2, 4>(epi, A, W, bias, resid, C, Cs, M, N, K, d_flag, s, ln_g, ln_b, ln_eps, ln_flags);
 #endif
     return gemm_wide_launch<2>(epi, A, W, bias, resid, C, Cs, M, N, K, d_flag, s, ln_g, ln_b, ln_eps, ln_flags);
 }

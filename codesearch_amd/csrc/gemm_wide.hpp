@@ -2,6 +2,8 @@
 // v_mfma_f32_16x16x32_f16; gemm_wide32.hip: the same block, stage image and epilogues on v_mfma_f32_32x32x16_f16).
 #pragma once
 
+#include <cstdlib>
+
 #include "encoder.hpp"
 #include "split_f16.hpp"
 
@@ -42,6 +44,34 @@ struct GwGeom {
 };
 constexpr uint32_t GW_LN_RESID_SPLIT = 1u, GW_LN_NO_F32 = 2u;  // ln_flags of the LayerNorm epilogue (launch_gemm_wide_ln)
 constexpr int GW_OUT_LN = 16;  // epilogue: + bias + residual, LayerNorm over the 384 columns, store f32 AND split form
+
+// Which kernel a wide launch runs — the one statement of the rule (gemm_wide.hip gemm_wide_impl launches by it,
+// diagnostics.hip cs_debug_gemm_wide reports it).  Block shape: 128 x 384 / one block per CU where N allows (and always for
+// the LayerNorm epilogue); 128 x 192 / two blocks per CU for the other multiples of 192 or with CS_GEMM_WIDE_SHAPE=192
+// (measured level with each other on every layer shape of the encoder: QKV 187 vs 190 us, FFN-up 270 vs 279, FFN-down 223
+// vs 237).  shape: the caller's request (0 = none; 192 | 384, diagnostic library: | 256).
+struct GwRoute {
+    int block;    // 384 = 128 x 384 (GwGeom<4>), 192 = 128 x 192 (GwGeom<2>), 256 = 256 x 192 (GwGeom<2, 4>: diagnostic library only)
+    bool mfma32;  // the main loop on the 32 x 32 x 16 MFMA (gemm_wide32.hip: diagnostic library only)
+};
+inline GwRoute gemm_wide_route(int epi, uint32_t N, int shape) {
+    static const int shape_env = [] { const char* e = cs_lab_env("CS_GEMM_WIDE_SHAPE"); return e ? std::atoi(e) : 0; }();
+    // default: 128 x 384, except the bias -> split-store layer (the QKV projection), which four boxes measured 3-4 % faster
+    // as 128 x 192 tiles, two blocks per CU (169-173 vs 175-181 us at 65,536 x 1,152 x 384; FFN-up level: profiles/
+    // r04_gemm_stagger_by_cu_ab.log code 1000, r04_gemm_role_split_ab.log)
+    const int want = shape ? shape : g_gemm_wide_shape ? g_gemm_wide_shape : shape_env ? shape_env : (epi == SH_OUT_SPLIT ? 192 : 384);
+    const bool big = epi == GW_OUT_LN || g_gemm_wide_ablation || (want == 384 && N % 384 == 0 && N <= (uint32_t)GW_PARAM_FLOATS);
+    GwRoute r{big ? 384 : 192, false};
+#ifdef CS_DIAGNOSTICS
+    // MFMA shape of the main loop: 16 x 16 x 32 (gemm_wide.hip) | 32 x 32 x 16 (gemm_wide32.hip: parity shown by
+    // tests/test_gpu_gemm_wide.py, 2-8 % slower per layer, profiles/r05_gemm_mfma_shape_ab.log; CS_GEMM_WIDE_MFMA=32)
+    static const int mfma_env = [] { const char* e = cs_lab_env("CS_GEMM_WIDE_MFMA"); return e ? std::atoi(e) : 0; }();
+    const int mfma = g_gemm_wide_mfma ? g_gemm_wide_mfma : mfma_env;
+    r.mfma32 = mfma == 32 && !g_gemm_wide_ablation && epi != GW_OUT_SWIGLU && epi != GW_OUT_GEGLU;
+    if (!big && !r.mfma32 && want == 256) r.block = 256;
+#endif
+    return r;
+}
 
 // this wave's LDS-DMA pieces of a stage: element offsets from A / W (32 bits: a [65536, 1536] operand is 2^27.6 elements)
 template <int WCN, int WRN = 2>

@@ -1,7 +1,7 @@
 /*
  * codesearch_gpu_diag.h — operator-level diagnostics of libcsgpu, exported ONLY by codesearch_amd/libcsgpu_diag.so (the
  * product library built once more with -DCS_DIAGNOSTICS: it additionally holds csrc/diagnostics.hip, the ablation
- * instantiations of the wide GEMM kernel and its in-kernel clock stamps).  Used by tests/test_gpu_gemm_split.py,
+ * instantiations of the wide GEMM kernel and its in-kernel clock stamps).  Used by tests/test_gpu_gemm_split.py, tests/test_gpu_gemm_wide.py,
  * tests/test_gpu_quantized.py, tests/test_gpu_attention.py, tests/test_gpu_rows.py, tests/test_gpu_attention_cls.py, tests/test_gpu_small_path.py (operator parity) and benchmarks/ (A/B timing); nothing in INTEGRATION.md binds it and a
  * deployment does not ship it.  The diagnostic library exports every symbol of include/codesearch_gpu.h as well, so a
  * process may use it in place of libcsgpu.so.
@@ -24,6 +24,28 @@ extern "C" {
 CS_API int32_t cs_debug_gemm(int32_t device, int32_t mode, int32_t epilogue, const float* A,
                       const float* W, const float* bias, const float* resid, float* C,
                       uint32_t M, uint32_t N, uint32_t K, uint32_t* range_flag);
+
+/* Diagnostics: the persistent wide kernel (csrc/gemm_wide.hip, csrc/gemm_wide32.hip) alone on host buffers, every block shape,
+ * MFMA form and epilogue, for unit parity against float64 (tests/test_gpu_gemm_wide.py; bounds: tests/gemm_wide_ref.py).
+ * A [M, K], W [N, K], bias [N] f32 (A and W are staged into split form by launch_split_rows), N % 192 == 0, K % 32 == 0,
+ * |w| <= 31.98.
+ *   epi 0  C [M, N] = A W^T + bias, f32 store
+ *       1  erf-GELU, split store            2  + resid [M, N], f32 store            3  split store (SH_OUT_SPLIT)
+ *       4  GW_OUT_SWIGLU, 5 GW_OUT_GEGLU: W's rows and the bias hold value and gate rows interleaved in groups of 16 (16
+ *          value rows, then their 16 gate rows); C [M, N / 2] = value * silu(gate) | value * gelu_erf(gate); N % 64 == 0
+ *       6 / 7  N = 384: + resid, LayerNorm (gamma = bias + 1, beta = -bias, eps 1e-12), exactly as cs_debug_gemm's epilogues
+ *          3 / 4 run it (6: f32 residual, in place, f32 and split outputs, which must agree; 7: the residual in split form
+ *          in the output buffer, no f32 output)
+ *   shape  0 = the launcher's own rule, 192 | 384 | 256 = that block asked for (128 x 192, 128 x 384, 256 x 192)
+ *   mfma   0 = the launcher's own rule, 16 | 32 = the main loop's MFMA form (32: epilogues 0 - 3, 6, 7, not on the 256-row block)
+ * *block_out receives the block the launch ran on (384, 192 or 256: gemm_wide_route, the rule the launcher itself follows;
+ * a request the rule does not grant — 384 at an N it cannot take — shows here).  Split stores are read back as hi + lo / 2048.
+ * Every output buffer is pre-filled with NaN bits (an element the launch does not write comes back as NaN) and followed by
+ * 16 guard rows of a bit pattern: *guard_changed receives how many guard words came back changed.  *range_flag (optional):
+ * the kernel's flag, set when a split-stored value left the f16 range. */
+CS_API int32_t cs_debug_gemm_wide(int32_t device, int32_t epi, int32_t shape, int32_t mfma, const float* A, const float* W,
+                           const float* bias, const float* resid, float* C, uint32_t M, uint32_t N, uint32_t K,
+                           int32_t* block_out, uint32_t* guard_changed, uint32_t* range_flag);
 
 /* Diagnostics: one dynamically quantised dense layer on host buffers (unit parity of csrc/gemm_q8.hip against the ONNX
  * definitions of DynamicQuantizeLinear / MatMulInteger).  A [M,K] f32 activations (a_split & 1: staged through the

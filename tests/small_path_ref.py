@@ -52,7 +52,8 @@ def wave_chunks(K):
 
 
 def _wave_cols(K, w):
-    return np.concatenate([np.arange(32 * c, 32 * c + 32) for c in wave_chunks(K)[w]])
+    # (a K range of fewer than four chunks leaves a wave none: its partial sum is an exact 0)
+    return np.concatenate([np.arange(32 * c, 32 * c + 32) for c in wave_chunks(K)[w]] or [np.arange(0)])
 
 
 _W64 = {}   # id(w) -> (w, its four waves' columns in float64, |w| in float64): the tests reuse a few weight matrices
