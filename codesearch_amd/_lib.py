@@ -176,6 +176,15 @@ SIGNATURES = {
     "cs_shards_search_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p]),
     "cs_shards_search_variants_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p,
                                                      i32p]),
+    "cs_shards_set_groups": (C.c_int32, [vp, u32p, u32p, C.c_uint64]),
+    "cs_shards_groups_info": (C.c_int32, [vp, u64p, u64p]),
+    "cs_shards_search_grouped": (C.c_int32, [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p]),
+    "cs_shards_search_grouped_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p,
+                                                    u32p]),
+    "cs_shards_search_variants_grouped": (C.c_int32, [vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32p, u32p, u32p,
+                                                      i32p]),
+    "cs_shards_search_variants_grouped_scoped": (C.c_int32, [vp, vp, f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32p,
+                                                             u32p, u32p, i32p]),
     "cs_shards_read_rows": (C.c_int32, [vp, C.c_uint64, C.c_uint64, f32p]),
     "cs_index_read_rows": (C.c_int32, [vp, C.c_uint64, C.c_uint64, f32p]),
     "cs_index_debug_counters": (C.c_int32, [vp, u64p, u64p]),

@@ -2002,9 +2002,15 @@ int32_t cs_scope_route_info(const cs_scope* scope, uint64_t* filter_searches, ui
         std::lock_guard<std::mutex> lk(scope->mu);
         extra = (uint64_t)(scope->blocked_words + scope->table_words) * sizeof(uint32_t);
     }
-    if (filter_searches) *filter_searches = scope->filter_searches.load();
-    if (gathered_searches) *gathered_searches = scope->gathered_searches.load();
-    if (overflow_reruns) *overflow_reruns = scope->overflow_reruns.load();
+    uint64_t filter = scope->filter_searches.load(), gathered = scope->gathered_searches.load(), reruns = scope->overflow_reruns.load();
+    for (const cs_scope* part : scope->parts) {  // a sharded scope: what its parts counted (a grouped search counts one per part)
+        filter += part->filter_searches.load();
+        gathered += part->gathered_searches.load();
+        reruns += part->overflow_reruns.load();
+    }
+    if (filter_searches) *filter_searches = filter;
+    if (gathered_searches) *gathered_searches = gathered;
+    if (overflow_reruns) *overflow_reruns = reruns;
     if (extra_bytes) *extra_bytes = extra;
     return CS_OK;
 }
@@ -2192,6 +2198,31 @@ int32_t cs::index_search_masked_device(cs_index* h, const float* d_queries, uint
     Workspace* w = for_stream(h, stream);
     CS_TRY(w->reserve(plan.partial_keys, plan.merge_keys, nq, h->dim, k, false));
     return run_masked(h, w, plan, bound, d_queries, nq, k, allow, allow_bits, d_out_keys, stream);
+}
+
+// search_grouped's two kinds with the queries in HBM and the keys to a device pointer (scan.hpp): the same plan, scan and
+// merge, on the caller's stream.
+int32_t cs::index_search_grouped_device(cs_index* h, cs_scope* scope, const float* d_queries, uint32_t nq, uint32_t k,
+                                        uint32_t per_group, uint64_t* d_out_keys, hipStream_t stream) {
+    CS_TRY(check_search(h, nq, h ? h->dim : 0, k));
+    if (!d_queries || !d_out_keys) return fail(CS_ERR_BAD_ARG, "null buffer");
+    if (per_group == 0) return fail(CS_ERR_BAD_ARG, "per_group must be at least 1");
+    DeviceGuard g(h->device);
+    uint64_t rows = h->ledger.stored();
+    if (scope) CS_TRY(scope_ready(h, scope, &rows));
+    if (rows == 0) {  // empty lists for the merge behind: the gather slot may hold an earlier search's keys
+        CS_HIP(hipMemsetAsync(d_out_keys, 0, (size_t)nq * k * sizeof(uint64_t), stream));
+        return CS_OK;
+    }
+    GroupView gv;
+    CS_TRY(ensure_groups(h, per_group, &gv));
+    const GroupedPlan plan = plan_grouped(rows, h->dim, nq, k, h->num_cus);  // a scope: the grid follows the list's length
+    Workspace* w = for_stream(h, stream);
+    CS_TRY(w->reserve(plan.partial_keys, plan.merge_keys, nq, h->dim, k, false));
+    if (!scope) return run_grouped(h, w, plan, gv, d_queries, nq, k, d_out_keys, stream);
+    scope->gathered_searches.fetch_add(1);
+    return run_grouped_list(h, w, plan, gv, scope->d_list, scope->d_blocks + scope_list_blocks(scope->n_ids), d_queries, nq, k,
+                            d_out_keys, stream);
 }
 
 int32_t cs::index_scope_live_rows(cs_index* h, cs_scope* scope, uint64_t* live_rows) {

@@ -156,8 +156,10 @@ template <class T, T NONE>
 class IdTable {
 public:
     // values[i] becomes the value of ids[i] (NONE un-assigns it).  An id the ledger never issued: nothing is changed
-    // and its position in ids is returned; -1 otherwise.
-    int64_t set(const uint32_t* ids, const T* values, uint64_t n, const IndexLedger& ledger) {
+    // and its position in ids is returned; -1 otherwise.  Ledger: issued(id) and id_base() — an index's IndexLedger, or
+    // the sharded store's count of ids issued (shards.hip).
+    template <class Ledger>
+    int64_t set(const uint32_t* ids, const T* values, uint64_t n, const Ledger& ledger) {
         uint32_t top = 0;  // the highest entry touched
         for (uint64_t i = 0; i < n; ++i) {
             if (!ledger.issued(ids[i])) return (int64_t)i;

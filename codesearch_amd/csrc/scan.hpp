@@ -87,6 +87,14 @@ int32_t launch_scan_masked(const ScanPlan& plan, const float* d_corpus, uint32_t
 // stay valid until the stream has passed the search.  Used by the sharded store.
 int32_t index_search_masked_device(cs_index* h, const float* d_queries, uint32_t nq, uint32_t k, const uint32_t* allow,
                                    uint64_t allow_bits, uint64_t* d_out_keys, hipStream_t stream);
+// index.hip: a grouped search (scan_grouped.hip) of nq queries already in HBM enqueued on `stream` with the same scratch,
+// nothing waited for: the capped scan over every stored row (scope null) or the gathered capped scan over the scope's row
+// list, then launch_merge_grouped; the capped best k per query as packed keys into d_out_keys [nq][k], zeros behind the
+// count.  Where the host form returns the empty answer without a launch (a scope with no live row, an index with no stored
+// row) the slot is zeroed on the stream instead.  A scope counts the call in its gathered_searches; it is refreshed first
+// when that is due (which waits for the device, as cs_index_search_scoped_device does).  Used by the sharded store.
+int32_t index_search_grouped_device(cs_index* h, cs_scope* scope, const float* d_queries, uint32_t nq, uint32_t k,
+                                    uint32_t per_group, uint64_t* d_out_keys, hipStream_t stream);
 
 // ---- scopes (index.hip cs_scope; plan: masked_plan.hpp) ------------------------------------------
 // Row list of a scope: for the strictly ascending chunk ids d_scope_ids[0, n_ids), the stored rows [0, n_rows) that hold
@@ -152,6 +160,15 @@ int32_t launch_scan_grouped_list(const GroupedPlan& plan, const float* d_corpus,
 int32_t launch_merge_variants_grouped(const uint64_t* d_keys, uint32_t nv, uint32_t k, const GroupView& gv, uint64_t* d_tmp_a,
                                       uint64_t* d_tmp_b, uint64_t* d_out_keys, float* d_out_cos, uint32_t* d_out_ids,
                                       uint32_t* d_out_count, uint32_t* d_out_high_confidence, hipStream_t stream);
+
+// ---- grouped search over a sharded store (scan_shards_grouped.hip, plan: shards_grouped_plan.hpp) ---------
+struct ShardsGroupedPlan;
+// The root's capped shard merge: d_gathered = [nshards][nq][k] capped lists of (cosine, local row) keys -> the capped best
+// k per query as global keys in d_out_keys [nq][k] (may be pinned host memory), under gv = the root's table by global id.
+// d_first: plan.first_keys keys, d_tmp_a / d_tmp_b: plan.merge_keys keys each (each may be null when that is 0).
+int32_t launch_merge_shards_grouped(const ShardsGroupedPlan& plan, const uint64_t* d_gathered, uint32_t nshards, uint32_t nq,
+                                    uint32_t k, uint32_t stripe, const GroupView& gv, uint64_t* d_first, uint64_t* d_tmp_a,
+                                    uint64_t* d_tmp_b, uint64_t* d_out_keys, hipStream_t stream);
 
 // ---- similar-chunk search (scan_similar.hip, sources: similar_sources.hpp) -------------------------------
 // What a similar-chunk search may not return, per query, and its bound: query q never gets the row whose id is

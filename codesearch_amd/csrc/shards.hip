@@ -24,6 +24,10 @@
 //      pinned host memory.
 // top-k of a union = top-k of the per-shard top-ks and a shard's local order is its global order, so the
 // result equals the single-index search of the whole corpus bit for bit.
+// The grouped search (cs_shards_search_grouped & co.: at most per_group rows of a group) is the same exchange with a cap
+// at both ends: every shard runs its grouped device search under its own slice of the group table (local ids), the root
+// merges under a table by global id and caps again (scan_shards_grouped.hip; levels, scratch and why every level must
+// cap: shards_grouped_plan.hpp).  Boosted, similar, pairs and clusters searches have no sharded form yet.
 // The multi-process variant (one rank per GPU, RCCL all-gather) is codesearch_amd/sharded.py.
 #include <algorithm>
 #include <cstdlib>
@@ -31,10 +35,12 @@
 #include <mutex>
 #include <vector>
 
+#include "index_ledger.hpp"
 #include "masked_plan.hpp"
 #include "scan.hpp"
 #include "scope.hpp"
 #include "scope_ops_plan.hpp"
+#include "shards_grouped_plan.hpp"
 
 using namespace cs;
 
@@ -78,6 +84,15 @@ struct cs_shards {
     std::mutex mu;
     std::vector<SearchCtx*> pool;
     std::vector<SearchCtx*> all;  // every context ever created (cs_shards_search_status visits their shard streams)
+    // Groups of the grouped search by GLOBAL id, for the root's capped shard merge (scan_shards_grouped.hip); every shard
+    // keeps its own slice by local id for its capped scan (cs_index_set_groups).  groups[id] for the ids assigned so far
+    // (shorter than `next` when ids were appended since: those are CS_NO_GROUP), empty = none assigned.  The copy in HBM
+    // of the root device is brought up to date under groups_mu by the first grouped search that finds it behind
+    // (ensure_root_groups), as an index does; searches read it only.
+    GroupTable groups;  // index_ledger.hpp: the table an index keeps, here over global ids
+    uint32_t* d_groups = nullptr;
+    uint64_t groups_cap = 0;                        // elements allocated on the root device
+    std::mutex groups_mu;
 };
 
 namespace {
@@ -148,7 +163,8 @@ int32_t new_ctx(cs_shards* h, SearchCtx** out) {
     return CS_OK;
 }
 
-int32_t reserve_ctx(cs_shards* h, SearchCtx* c, uint32_t nq, uint32_t k, bool host_io) {
+// scratch_keys: root scratch a grouped search asks for behind the shard slots and the spare block (ShardsGroupedPlan)
+int32_t reserve_ctx(cs_shards* h, SearchCtx* c, uint32_t nq, uint32_t k, bool host_io, size_t scratch_keys = 0) {
     const size_t qn = (size_t)nq * h->dim, kn = (size_t)nq * k;
     if (host_io && qn > c->h_q_cap) {
         if (c->h_queries) (void)hipHostFree(c->h_queries);
@@ -164,11 +180,13 @@ int32_t reserve_ctx(cs_shards* h, SearchCtx* c, uint32_t nq, uint32_t k, bool ho
     }
     {
         DeviceGuard g(h->root);
-        if (kn * (h->n + 1) > c->gathered_cap) {  // [N][nq][k] shard slots + one merged [nq][k] block (variant searches)
+        // [N][nq][k] shard slots + one merged [nq][k] block (variant searches) + a grouped search's merge scratch
+        const size_t want = kn * (h->n + 1) + scratch_keys;
+        if (want > c->gathered_cap) {
             if (c->d_gathered) { CS_HIP(hipStreamSynchronize(c->root_stream)); (void)hipFree(c->d_gathered); }
             c->d_gathered = nullptr; c->gathered_cap = 0;
-            CS_HIP(hipMalloc(&c->d_gathered, kn * (h->n + 1) * sizeof(uint64_t)));
-            c->gathered_cap = kn * (h->n + 1);
+            CS_HIP(hipMalloc(&c->d_gathered, want * sizeof(uint64_t)));
+            c->gathered_cap = want;
         }
         if (!c->h_meta) CS_HIP(hipHostMalloc(&c->h_meta, 2 * sizeof(uint32_t), hipHostMallocPortable | hipHostMallocMapped));
     }
@@ -197,8 +215,11 @@ int32_t reserve_ctx(cs_shards* h, SearchCtx* c, uint32_t nq, uint32_t k, bool ho
 // device-pointer search; a shard living on that device reads them in place).
 // masks != null: the masked search of that shard (index.hip index_search_masked_device) instead; scope != null: its
 // scoped device search through the scope's part for that shard (cs_index_search_scoped_device).
+// per_group != 0: the shard's grouped device search (index.hip index_search_grouped_device) over the whole shard or, with
+// a scope, over its part — the shard's capped best k under its own slice of the group table.
 int32_t enqueue_shard(cs_shards* h, SearchCtx* c, uint32_t s, uint32_t q0, uint32_t qn, uint32_t nq, uint32_t k,
-                      const float* src, int src_device, const ShardMasks* masks = nullptr, cs_scope* scope = nullptr) {
+                      const float* src, int src_device, const ShardMasks* masks = nullptr, cs_scope* scope = nullptr,
+                      uint32_t per_group = 0) {
     DeviceGuard g(h->devices[s]);
     ShardCtx& x = c->sh[s];
     const size_t qbytes = (size_t)nq * h->dim * sizeof(float);
@@ -215,7 +236,10 @@ int32_t enqueue_shard(cs_shards* h, SearchCtx* c, uint32_t s, uint32_t q0, uint3
     // its slot itself
     const bool local = !h->direct && (h->force_copy || h->devices[s] != h->root);
     uint64_t* dst = local ? x.d_keys + (size_t)q0 * k : slot;
-    if (masks)
+    if (per_group)
+        CS_TRY(index_search_grouped_device(h->idx[s], scope ? scope->parts[s] : nullptr, q + (size_t)q0 * h->dim, qn, k, per_group,
+                                           dst, x.stream));
+    else if (masks)
         CS_TRY(index_search_masked_device(h->idx[s], q + (size_t)q0 * h->dim, qn, k, masks->words[s].data(), masks->bits[s],
                                           dst, x.stream));
     else if (scope)
@@ -287,29 +311,81 @@ int32_t check_shards_search(const cs_shards* h, uint32_t nq, uint32_t dim, uint3
     return CS_OK;
 }
 
+// The group table by global id as the root's merge kernels read it: ensure_groups (index.hip) for the store's table on the
+// root device.  A table that is behind is brought up to date first, under groups_mu, with synchronous copies (and after
+// the root device has finished what was enqueued, when the table has to move): a concurrent grouped search either waits
+// here or finds it current.  No group assigned: a null table, every id CS_NO_GROUP.
+int32_t ensure_root_groups(cs_shards* h, uint32_t per_group, GroupView* gv) {
+    std::lock_guard<std::mutex> lk(h->groups_mu);
+    *gv = GroupView{nullptr, 0, 0, per_group};
+    if (h->groups.assigned() == 0) return CS_OK;
+    DeviceGuard g(h->root);
+    const uint64_t n = h->groups.size();
+    if (n > h->groups_cap) {
+        CS_HIP(hipDeviceSynchronize());  // a search that was only enqueued may still read the old table
+        const uint64_t cap = std::max<uint64_t>(n, std::min<uint64_t>(2 * h->groups_cap, 0xffffffffull));
+        if (h->d_groups) (void)hipFree(h->d_groups);
+        h->d_groups = nullptr;
+        h->groups_cap = 0;
+        h->groups.uploaded(0);  // the new table holds nothing yet
+        CS_HIP(hipMalloc(&h->d_groups, (size_t)cap * sizeof(uint32_t)));
+        h->groups_cap = cap;
+    }
+    uint64_t lo = 0, hi = 0;
+    if (h->groups.pending(&lo, &hi))
+        CS_HIP(hipMemcpy(h->d_groups + lo, h->groups.data() + lo, (size_t)(hi - lo) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    h->groups.uploaded(n);
+    gv->groups = h->d_groups;
+    gv->len = (uint32_t)n;
+    return CS_OK;
+}
+
 // variants != null: after the shard merge the nq lists are merged as query variants (scan.hip merge_variants_kernel) and
 // out_cos / out_ids hold ONE list of k; variants[0] = count, variants[1] = high-confidence flag.
 // masks != null / scope != null: every shard runs the masked / scoped search (never a batched path: nothing to rerun).
+// per_group != 0: the grouped search.  Every shard runs its grouped device search (over its part of `scope`, if one is
+// given) and the root merges under the cap (scan_shards_grouped.hip; levels and scratch: shards_grouped_plan.hpp); with
+// variants the per-variant capped global lists go to the spare block and the capped variants merge
+// (launch_merge_variants_grouped) writes the one list — the single index's sequence.  A grouped search never takes the
+// int8 filter: nothing to rerun.
 int32_t shards_search_impl(cs_shards* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k, float* out_cos,
                            uint32_t* out_ids, uint32_t* out_counts, uint32_t* variants, const ShardMasks* masks = nullptr,
-                           cs_scope* scope = nullptr) {
+                           cs_scope* scope = nullptr, uint32_t per_group = 0) {
     CS_TRY(check_shards_search(h, nq, dim, k));
     if (!queries || !out_cos || !out_ids || !out_counts) return fail(CS_ERR_BAD_ARG, "null buffer");
     SearchCtx* c = take_ctx(h);
     if (!c) CS_TRY(new_ctx(h, &c));
     const int32_t st = [&]() -> int32_t {
-        CS_TRY(reserve_ctx(h, c, nq, k, true));
+        const ShardsGroupedPlan gplan = per_group ? plan_shards_grouped(h->n, nq, k, variants != nullptr) : ShardsGroupedPlan();
+        CS_TRY(reserve_ctx(h, c, nq, k, true, gplan.scratch_keys));
+        GroupView gv;
+        if (per_group) CS_TRY(ensure_root_groups(h, per_group, &gv));
         CS_TRY(order_behind_previous(h, c));
         memcpy(c->h_queries, queries, (size_t)nq * h->dim * sizeof(float));
         for (uint32_t s = 0; s < h->n; ++s) {
-            CS_TRY(enqueue_shard(h, c, s, 0, nq, nq, k, c->h_queries, -1, masks, scope));
+            CS_TRY(enqueue_shard(h, c, s, 0, nq, nq, k, c->h_queries, -1, masks, scope, per_group));
             DeviceGuard g(h->devices[s]);
             CS_HIP(hipEventRecord(c->sh[s].done, c->sh[s].stream));
         }
         auto merge = [&]() -> int32_t {
             DeviceGuard g(h->root);
             for (uint32_t s = 0; s < h->n; ++s) CS_HIP(hipStreamWaitEvent(c->root_stream, c->sh[s].done, 0));
-            if (variants) {
+            if (per_group) {
+                // behind the shard slots: the spare [nq][k] block, then the plan's scratch in the order it counts it
+                uint64_t* d_merged = c->d_gathered + (size_t)h->n * nq * k;
+                uint64_t* at = d_merged + (size_t)nq * k;
+                auto take = [&](size_t keys) { uint64_t* p = keys ? at : nullptr; at += keys; return p; };
+                uint64_t* d_first = take(gplan.first_keys);
+                uint64_t* d_tmp_a = take(gplan.merge_keys);
+                uint64_t* d_tmp_b = take(gplan.merge_keys);
+                uint64_t* d_var_a = take(gplan.variants_keys);
+                uint64_t* d_var_b = take(gplan.variants_keys);
+                CS_TRY(launch_merge_shards_grouped(gplan, c->d_gathered, h->n, nq, k, (uint32_t)h->stripe, gv, d_first, d_tmp_a,
+                                                   d_tmp_b, variants ? d_merged : c->h_keys, c->root_stream));
+                if (variants)
+                    CS_TRY(launch_merge_variants_grouped(d_merged, nq, k, gv, d_var_a, d_var_b, c->h_keys, nullptr, nullptr,
+                                                         c->h_meta, c->h_meta + 1, c->root_stream));
+            } else if (variants) {
                 // shard merge into the spare block behind the shard slots, then the variant merge into pinned memory
                 uint64_t* d_merged = c->d_gathered + (size_t)h->n * nq * k;
                 CS_TRY(merge_topk_device_impl(h->root, c->d_gathered, h->n, nq, k, d_merged, nullptr, nullptr, nullptr,
@@ -326,7 +402,7 @@ int32_t shards_search_impl(cs_shards* h, const float* queries, uint32_t nq, uint
         CS_TRY(merge());
         c->merged_pending = false;  // every stream of the context is idle now
         bool again = false;
-        if (!masks && !scope) CS_TRY(rerun_overflowed(h, c, nq, k, &again));
+        if (!masks && !scope && !per_group) CS_TRY(rerun_overflowed(h, c, nq, k, &again));
         if (again) CS_TRY(merge());
         if (variants) {
             unpack_keys(c->h_keys, 1, k, out_cos, out_ids, nullptr);
@@ -434,6 +510,10 @@ int32_t cs_shards_create(uint32_t dim, uint32_t nshards, const int32_t* devices,
 void cs_shards_destroy(cs_shards* h) {
     if (!h) return;
     for (SearchCtx* c : h->all) free_ctx(h, c);
+    if (h->d_groups) {
+        DeviceGuard g(h->root);
+        (void)hipFree(h->d_groups);
+    }
     for (cs_index* ix : h->idx) cs_index_destroy(ix);
     delete h;
 }
@@ -585,6 +665,58 @@ int32_t cs_shards_clear(cs_shards* h) {
     h->next = 0;
     h->built = false;
     h->poisoned = false;
+    {  // the groups go with the ids (the root's device table keeps its room)
+        std::lock_guard<std::mutex> lk(h->groups_mu);
+        h->groups.clear();
+    }
+    return CS_OK;
+}
+
+// Groups by global id.  Every id is checked before anything is written (GroupTable::set: an id at or above `next` changes
+// nothing); then the root's table takes them, then every shard its slice by local id.  A shard has issued the local id of
+// every global id below `next`, so its cs_index_set_groups cannot refuse one; a shard that fails for another reason (its
+// table's allocation) leaves the root and the earlier shards assigned: all-or-nothing covers the validation only.
+int32_t cs_shards_set_groups(cs_shards* h, const uint32_t* ids, const uint32_t* groups, uint64_t n) {
+    if (!h) return fail(CS_ERR_BAD_ARG, "null shards handle");
+    if (n == 0) return CS_OK;
+    if (!ids || !groups) return fail(CS_ERR_BAD_ARG, "ids or groups is null");
+    if (h->poisoned)
+        return fail(CS_ERR_BAD_ARG, "sharded store is inconsistent after a failed append; clear() or reopen it");
+    struct Issued {  // the ledger GroupTable::set asks: a sharded store has issued ids [0, next)
+        uint64_t next;
+        bool issued(uint32_t id) const { return id < next; }
+        uint32_t id_base() const { return 0; }
+    };
+    {
+        std::lock_guard<std::mutex> lk(h->groups_mu);
+        const int64_t bad = h->groups.set(ids, groups, n, Issued{h->next});
+        if (bad >= 0)
+            return fail(CS_ERR_BAD_ARG, "ids[%llu] = %u was never issued (the index has issued ids %u to %llu)",
+                        (unsigned long long)bad, ids[bad], 0u, (unsigned long long)h->next);
+    }
+    std::vector<std::vector<uint32_t>> local(h->n), value(h->n);
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint32_t s = shards_shard_of(ids[i], (uint32_t)h->stripe, h->n);
+        local[s].push_back(shards_local_of(ids[i], (uint32_t)h->stripe, h->n));
+        value[s].push_back(groups[i]);
+    }
+    for (uint32_t s = 0; s < h->n; ++s)
+        if (!local[s].empty()) CS_TRY(cs_index_set_groups(h->idx[s], local[s].data(), value[s].data(), local[s].size()));
+    return CS_OK;
+}
+
+// *table_bytes: the root's table by global id and every shard's by local id.
+int32_t cs_shards_groups_info(cs_shards* h, uint64_t* assigned_ids, uint64_t* table_bytes) {
+    if (!h) return fail(CS_ERR_BAD_ARG, "null shards handle");
+    uint64_t bytes = 0;
+    for (cs_index* ix : h->idx) {
+        uint64_t b = 0;
+        CS_TRY(cs_index_groups_info(ix, nullptr, &b));
+        bytes += b;
+    }
+    std::lock_guard<std::mutex> lk(h->groups_mu);
+    if (assigned_ids) *assigned_ids = h->groups.assigned();
+    if (table_bytes) *table_bytes = bytes + h->groups_cap * sizeof(uint32_t);
     return CS_OK;
 }
 
@@ -738,12 +870,8 @@ int32_t cs_shards_search_variants_masked(cs_shards* h, const float* queries, uin
 
 namespace {
 
-// Argument checks of a scoped shard search, then every shard's refresh that is due.  *empty: no shard holds a live row
-// of the scope (no launch).
-int32_t prepare_scope(cs_shards* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
-                      const void* out_a, const void* out_b, const void* out_c, bool* empty) {
-    CS_TRY(check_shards_search(h, nq, dim, k));
-    if (!queries || !out_a || !out_b || !out_c) return fail(CS_ERR_BAD_ARG, "null buffer");
+// The scope's own checks, then every shard's refresh that is due.  *empty: no shard holds a live row of the scope.
+int32_t scope_parts_ready(cs_shards* h, cs_scope* scope, bool* empty) {
     if (!scope) return fail(CS_ERR_BAD_ARG, "null scope handle");
     if (scope->shards != h || scope->parts.size() != h->n) return fail(CS_ERR_BAD_ARG, "the scope was made for another store");
     *empty = true;
@@ -752,6 +880,60 @@ int32_t prepare_scope(cs_shards* h, cs_scope* scope, const float* queries, uint3
         CS_TRY(index_scope_live_rows(h->idx[s], scope->parts[s], &live));
         if (live) *empty = false;
     }
+    return CS_OK;
+}
+
+// Argument checks of a scoped shard search, then every shard's refresh that is due.  *empty: no shard holds a live row
+// of the scope (no launch).
+int32_t prepare_scope(cs_shards* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                      const void* out_a, const void* out_b, const void* out_c, bool* empty) {
+    CS_TRY(check_shards_search(h, nq, dim, k));
+    if (!queries || !out_a || !out_b || !out_c) return fail(CS_ERR_BAD_ARG, "null buffer");
+    return scope_parts_ready(h, scope, empty);
+}
+
+// The argument checks of a grouped shard search in the order of the cs_index_* grouped calls (index.hip search_grouped):
+// the search's own, the variants limit, the buffers, per_group, then — for a scoped form — the scope's, and every shard's
+// refresh that is due.  *empty: a scoped form whose scope has no live row on any shard (no launch).
+int32_t prepare_grouped(cs_shards* h, bool scope_given, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,
+                        uint32_t k, uint32_t per_group, bool variants, const void* out_a, const void* out_b, const void* out_c,
+                        bool* empty) {
+    CS_TRY(check_shards_search(h, nq, dim, k));
+    if (variants && nq > CS_MAX_VARIANTS)
+        return fail(CS_ERR_BAD_ARG, "at most %u query variants per call, got %u", CS_MAX_VARIANTS, nq);
+    if (!queries || !out_a || !out_b || !out_c) return fail(CS_ERR_BAD_ARG, "null buffer");
+    if (per_group == 0) return fail(CS_ERR_BAD_ARG, "per_group must be at least 1");
+    *empty = false;
+    return scope_given ? scope_parts_ready(h, scope, empty) : CS_OK;
+}
+
+int32_t shards_search_grouped(cs_shards* h, bool scope_given, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,
+                              uint32_t k, uint32_t per_group, float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
+    bool empty = false;
+    CS_TRY(prepare_grouped(h, scope_given, scope, queries, nq, dim, k, per_group, false, out_cos, out_ids, out_counts, &empty));
+    if (empty) {
+        fill_empty_lists(nq, k, out_cos, out_ids);
+        memset(out_counts, 0, (size_t)nq * sizeof(uint32_t));
+        return CS_OK;
+    }
+    return shards_search_impl(h, queries, nq, dim, k, out_cos, out_ids, out_counts, nullptr, nullptr, scope, per_group);
+}
+
+int32_t shards_search_variants_grouped(cs_shards* h, bool scope_given, cs_scope* scope, const float* queries, uint32_t nq,
+                                       uint32_t dim, uint32_t k, uint32_t per_group, float* out_cos, uint32_t* out_ids,
+                                       uint32_t* out_count, int32_t* out_high_confidence) {
+    bool empty = false;
+    CS_TRY(prepare_grouped(h, scope_given, scope, queries, nq, dim, k, per_group, true, out_cos, out_ids, out_count, &empty));
+    if (empty) {
+        fill_empty_lists(1, k, out_cos, out_ids);
+        *out_count = 0;
+        if (out_high_confidence) *out_high_confidence = 0;
+        return CS_OK;
+    }
+    uint32_t meta[2] = {0, 0};
+    CS_TRY(shards_search_impl(h, queries, nq, dim, k, out_cos, out_ids, out_count, meta, nullptr, scope, per_group));
+    *out_count = meta[0];
+    if (out_high_confidence) *out_high_confidence = (int32_t)meta[1];
     return CS_OK;
 }
 
@@ -834,6 +1016,32 @@ int32_t cs_shards_search_variants_scoped(cs_shards* h, cs_scope* scope, const fl
     *out_count = meta[0];
     if (out_high_confidence) *out_high_confidence = (int32_t)meta[1];
     return CS_OK;
+}
+
+// ---- grouped search (shards_grouped_plan.hpp) -----------------------------------------------------------
+
+int32_t cs_shards_search_grouped(cs_shards* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k, uint32_t per_group,
+                                 float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
+    return shards_search_grouped(h, false, nullptr, queries, nq, dim, k, per_group, out_cos, out_ids, out_counts);
+}
+
+int32_t cs_shards_search_grouped_scoped(cs_shards* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,
+                                        uint32_t k, uint32_t per_group, float* out_cos, uint32_t* out_ids, uint32_t* out_counts) {
+    return shards_search_grouped(h, true, scope, queries, nq, dim, k, per_group, out_cos, out_ids, out_counts);
+}
+
+int32_t cs_shards_search_variants_grouped(cs_shards* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                                          uint32_t per_group, float* out_cos, uint32_t* out_ids, uint32_t* out_count,
+                                          int32_t* out_high_confidence) {
+    return shards_search_variants_grouped(h, false, nullptr, queries, nq, dim, k, per_group, out_cos, out_ids, out_count,
+                                          out_high_confidence);
+}
+
+int32_t cs_shards_search_variants_grouped_scoped(cs_shards* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,
+                                                 uint32_t k, uint32_t per_group, float* out_cos, uint32_t* out_ids,
+                                                 uint32_t* out_count, int32_t* out_high_confidence) {
+    return shards_search_variants_grouped(h, true, scope, queries, nq, dim, k, per_group, out_cos, out_ids, out_count,
+                                          out_high_confidence);
 }
 
 }  // extern "C"

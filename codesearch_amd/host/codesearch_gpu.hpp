@@ -96,10 +96,11 @@ class VectorStore {
     }
     // The same store row-sharded over several GPUs of the node inside this process (cs_shards_*):
     // ids stay contiguous, rows are dealt in stripes of rows_per_stripe ids, a search scans every shard and merges
-    // on devices[0].
+    // on devices[0].  grouped = true: the store keeps groups (set_groups, search_per_file, search_variants_per_file go to
+    // cs_shards_set_groups and cs_shards_search_grouped & co.: 8 B per id); without it a sharded store refuses them.
     VectorStore(const std::string& /*db_path*/, size_t dimensions, const std::vector<int32_t>& devices,
-                uint64_t rows_per_stripe = 65536, uint64_t capacity = 0)
-        : dimensions_(dimensions) {
+                uint64_t rows_per_stripe = 65536, uint64_t capacity = 0, bool grouped = false)
+        : dimensions_(dimensions), grouped_(grouped) {
         check(cs_shards_create((uint32_t)dimensions, (uint32_t)devices.size(), devices.data(), rows_per_stripe, capacity, &sh_));
     }
     ~VectorStore() { if (sh_) cs_shards_destroy(sh_); else cs_index_destroy(h_); }
@@ -200,17 +201,21 @@ class VectorStore {
     // `per_file` of one group, decided on the device (cs_index_search_grouped).  A chunk's group is its file once
     // set_groups has said so; chunks without a group are never capped.  One index only: no sharded form yet.
     void set_groups(const std::vector<uint32_t>& ids, const std::vector<uint32_t>& groups) {
-        if (sh_) throw Error(CS_ERR_UNSUPPORTED, "a sharded store has no grouped search");
+        needs_groups();
         if (ids.size() != groups.size()) throw Error(CS_ERR_BAD_ARG, "ids and groups of unequal length");
-        check(cs_index_set_groups(h_, ids.data(), groups.data(), ids.size()));
+        check(sh_ ? cs_shards_set_groups(sh_, ids.data(), groups.data(), ids.size())
+                  : cs_index_set_groups(h_, ids.data(), groups.data(), ids.size()));
     }
     std::vector<SearchResult> search_per_file(const std::vector<float>& query_embedding, size_t limit,
                                               uint32_t per_file) const {
-        if (sh_) throw Error(CS_ERR_UNSUPPORTED, "a sharded store has no grouped search");
+        needs_groups();
         std::vector<float> cos(limit);
         std::vector<uint32_t> ids(limit), counts(1);
-        check(cs_index_search_grouped(h_, query_embedding.data(), 1, (uint32_t)query_embedding.size(), (uint32_t)limit,
-                                      per_file, cos.data(), ids.data(), counts.data()));
+        const uint32_t dim = (uint32_t)query_embedding.size();
+        check(sh_ ? cs_shards_search_grouped(sh_, query_embedding.data(), 1, dim, (uint32_t)limit, per_file, cos.data(), ids.data(),
+                                             counts.data())
+                  : cs_index_search_grouped(h_, query_embedding.data(), 1, dim, (uint32_t)limit, per_file, cos.data(), ids.data(),
+                                            counts.data()));
         return results(cos, ids, counts[0]);
     }
     // The kind and language boosts done exactly (src/search/mod.rs:238-252, :789-806 multiply the scores of hits already
@@ -455,11 +460,14 @@ class VectorStore {
     // scope's rows and to the merged order; the flag is the predicate on the capped list.  One index only.
     std::vector<SearchResult> search_per_file(const std::vector<float>& query_embedding, size_t limit, uint32_t per_file,
                                               const Scope& scope) const {
-        if (sh_) throw Error(CS_ERR_UNSUPPORTED, "a sharded store has no grouped search");
+        needs_groups();
         std::vector<float> cos(limit);
         std::vector<uint32_t> ids(limit), counts(1);
-        check(cs_index_search_grouped_scoped(h_, scope.handle(), query_embedding.data(), 1, (uint32_t)query_embedding.size(),
-                                             (uint32_t)limit, per_file, cos.data(), ids.data(), counts.data()));
+        const uint32_t dim = (uint32_t)query_embedding.size();
+        check(sh_ ? cs_shards_search_grouped_scoped(sh_, scope.handle(), query_embedding.data(), 1, dim, (uint32_t)limit, per_file,
+                                                    cos.data(), ids.data(), counts.data())
+                  : cs_index_search_grouped_scoped(h_, scope.handle(), query_embedding.data(), 1, dim, (uint32_t)limit, per_file,
+                                                   cos.data(), ids.data(), counts.data()));
         return results(cos, ids, counts[0]);
     }
     // The boosted search (set_classes, above) over the whole store or, with `scope`, over its chunks.
@@ -573,7 +581,7 @@ class VectorStore {
     std::vector<SearchResult> search_variants_per_file(const std::vector<std::vector<float>>& variants, size_t limit,
                                                        uint32_t per_file, const Scope* scope = nullptr,
                                                        bool* high_confidence = nullptr) const {
-        if (sh_) throw Error(CS_ERR_UNSUPPORTED, "a sharded store has no grouped search");
+        needs_groups();
         const size_t nq = variants.size();
         if (nq == 0) return {};
         const size_t qdim = variants[0].size();
@@ -586,10 +594,16 @@ class VectorStore {
         std::vector<uint32_t> ids(limit);
         uint32_t count = 0;
         int32_t flag = 0;
-        check(scope ? cs_index_search_variants_grouped_scoped(h_, scope->handle(), q.data(), (uint32_t)nq, (uint32_t)qdim,
-                                                              (uint32_t)limit, per_file, cos.data(), ids.data(), &count, &flag)
-                    : cs_index_search_variants_grouped(h_, q.data(), (uint32_t)nq, (uint32_t)qdim, (uint32_t)limit, per_file,
-                                                       cos.data(), ids.data(), &count, &flag));
+        if (sh_)
+            check(scope ? cs_shards_search_variants_grouped_scoped(sh_, scope->handle(), q.data(), (uint32_t)nq, (uint32_t)qdim,
+                                                                   (uint32_t)limit, per_file, cos.data(), ids.data(), &count, &flag)
+                        : cs_shards_search_variants_grouped(sh_, q.data(), (uint32_t)nq, (uint32_t)qdim, (uint32_t)limit, per_file,
+                                                            cos.data(), ids.data(), &count, &flag));
+        else
+            check(scope ? cs_index_search_variants_grouped_scoped(h_, scope->handle(), q.data(), (uint32_t)nq, (uint32_t)qdim,
+                                                                  (uint32_t)limit, per_file, cos.data(), ids.data(), &count, &flag)
+                        : cs_index_search_variants_grouped(h_, q.data(), (uint32_t)nq, (uint32_t)qdim, (uint32_t)limit, per_file,
+                                                           cos.data(), ids.data(), &count, &flag));
         if (high_confidence) *high_confidence = flag != 0;
         return results(cos, ids, count);
     }
@@ -653,6 +667,10 @@ class VectorStore {
     cs_index* h_ = nullptr;
     cs_shards* sh_ = nullptr;
     size_t dimensions_;
+    bool grouped_ = true;  // a sharded store: whether it was opened with grouped = true
+    void needs_groups() const {
+        if (sh_ && !grouped_) throw Error(CS_ERR_UNSUPPORTED, "a sharded store has no grouped search unless it is opened with grouped = true");
+    }
     uint32_t id_base_ = 0;
     std::map<uint32_t, ChunkMetadata> meta_;
 };

@@ -345,11 +345,16 @@ class VectorStore:
     FORMAT = 1
 
     def __init__(self, db_path, dimensions: int, device: int = 0, capacity: int = 0, id_base: int = 0,
-                 devices: Optional[Sequence[int]] = None, rows_per_stripe: int = 65536):
+                 devices: Optional[Sequence[int]] = None, rows_per_stripe: int = 65536, grouped: bool = False):
         """devices=[d0, d1, ...]: the store is row-sharded over those GPUs inside this one process
         (cs_shards_*: ids stay contiguous, rows dealt in stripes of `rows_per_stripe`; a search broadcasts
-        the queries, scans every shard and merges on d0).  Otherwise one cs_index on `device`."""
+        the queries, scans every shard and merges on d0).  Otherwise one cs_index on `device`.
+        grouped=True (a sharded store only; one index always is): the store keeps groups — set_groups, groups_info, a
+        chunk's file as its group, and per_file= on the searches, alone and with scope= (cs_shards_set_groups,
+        cs_shards_search_grouped & co.: 8 B per id, a table on the first device and one on every shard).  A sharded store
+        opened without it refuses those calls, as it always has."""
         self._lib = _lib.load()
+        self._grouped = bool(grouped) or devices is None
         self.db_path = None if db_path is None else str(db_path)
         self.dimensions = int(dimensions)
         self.id_base = int(id_base)
@@ -432,8 +437,9 @@ class VectorStore:
                     continue
                 self._meta[cid] = ChunkMetadata(**d)
             self._persisted_meta_ids = set(self._meta)
-            if not self.sharded:  # the groups are not stored: they follow from the sidecar's paths
+            if self._grouped:  # the groups are not stored: they follow from the sidecar's paths
                 self._assign_file_groups([i for i in sorted(self._meta) if i >= self.id_base])  # (< next_id: above)
+            if not self.sharded:
                 self._assign_kind_classes([i for i in sorted(self._meta) if i >= self.id_base])  # (nor are the classes)
         for cid in self._removed:  # deletes committed after the last build (delete_chunks) win over older lines
             if self._meta.pop(cid, None) is not None:
@@ -595,8 +601,9 @@ class VectorStore:
                                           ids.ctypes.data_as(u32p)))
         for i, ch in zip(ids.tolist(), chunks):
             self._meta[i] = ChunkMetadata.from_embedded_chunk(ch)
-        if not self.sharded:
+        if self._grouped:
             self._assign_file_groups(ids.tolist())
+        if not self.sharded:
             self._assign_kind_classes(ids.tolist())
         return ids.tolist()
 
@@ -704,20 +711,25 @@ class VectorStore:
         order of first sight (insert_chunks_with_ids), so a caller who groups other rows by hand and does not mean to
         join them to a file numbers them from the top down (below NO_GROUP)."""
         self._writable()
-        if self.sharded:
-            raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no grouped search (per_file): no cs_shards_ form yet")
+        self._needs_groups()
         ids = np.ascontiguousarray(ids, np.uint32).ravel()
         groups = np.ascontiguousarray(groups, np.uint32).ravel()
         if ids.size != groups.size:
             raise ValueError("ids and groups must have one entry per id")
-        _lib.check(self._lib.cs_index_set_groups(self._h, ids.ctypes.data_as(u32p), groups.ctypes.data_as(u32p), ids.size))
+        _lib.check(self._fn("set_groups")(self._h, ids.ctypes.data_as(u32p), groups.ctypes.data_as(u32p), ids.size))
+
+    def _needs_groups(self) -> None:
+        """The grouped calls of a sharded store are its opt-in: VectorStore(..., devices=[...], grouped=True)."""
+        if not self._grouped:
+            raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no grouped search (per_file) unless it is opened with "
+                          "grouped=True (cs_shards_set_groups, cs_shards_search_grouped & co.)")
 
     def groups_info(self):
-        """-> (ids that carry a group, bytes of HBM the group table holds) (cs_index_groups_info)."""
-        if self.sharded:
-            raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no grouped search (per_file): no cs_shards_ form yet")
+        """-> (ids that carry a group, bytes of HBM the group tables hold) (cs_index_groups_info; a sharded store opened with
+        grouped=True: cs_shards_groups_info, the root's table by global id and every shard's by local id)."""
+        self._needs_groups()
         a, b = C.c_uint64(), C.c_uint64()
-        _lib.check(self._lib.cs_index_groups_info(self._h, C.byref(a), C.byref(b)))
+        _lib.check(self._fn("groups_info")(self._h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
     def _assign_file_groups(self, ids) -> None:
@@ -727,7 +739,7 @@ class VectorStore:
         groups = [self._file_groups.setdefault(self._meta[i].path, len(self._file_groups)) for i in ids]
         ids = np.ascontiguousarray(ids, np.uint32)
         groups = np.ascontiguousarray(groups, np.uint32)
-        _lib.check(self._lib.cs_index_set_groups(self._h, ids.ctypes.data_as(u32p), groups.ctypes.data_as(u32p), ids.size))
+        _lib.check(self._fn("set_groups")(self._h, ids.ctypes.data_as(u32p), groups.ctypes.data_as(u32p), ids.size))
 
     def set_classes(self, ids, classes) -> None:
         """cs_index_set_classes: classes[i] (16 bits) becomes the class of chunk id ids[i] (NO_CLASS un-assigns it); takes
@@ -831,14 +843,13 @@ class VectorStore:
                 _lib.check(self._lib.cs_index_search_boosted(self._h, q.ctypes.data_as(f32p), nq, dim, limit, *tail))
             return score, cos, ids, counts
         if per_file is not None:
-            if self.sharded:
-                raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no grouped search (per_file): no cs_shards_ form yet")
+            self._needs_groups()
             if scope is not None:
-                _lib.check(self._lib.cs_index_search_grouped_scoped(self._h, self._scope_handle(scope), q.ctypes.data_as(f32p),
+                _lib.check(self._fn("search_grouped_scoped")(self._h, self._scope_handle(scope), q.ctypes.data_as(f32p),
                                                                     nq, dim, limit, int(per_file), cos.ctypes.data_as(f32p),
                                                                     ids.ctypes.data_as(u32p), counts.ctypes.data_as(u32p)))
             else:
-                _lib.check(self._lib.cs_index_search_grouped(self._h, q.ctypes.data_as(f32p), nq, dim, limit, int(per_file),
+                _lib.check(self._fn("search_grouped")(self._h, q.ctypes.data_as(f32p), nq, dim, limit, int(per_file),
                                                              cos.ctypes.data_as(f32p), ids.ctypes.data_as(u32p),
                                                              counts.ctypes.data_as(u32p)))
         elif scope is not None:
@@ -935,15 +946,14 @@ class VectorStore:
             _lib.check(getattr(self._lib, name)(*head, *cap, *tail))
             return score, cos, ids, int(count.value), bool(flag.value)
         if per_file is not None:
-            if self.sharded:
-                raise CsError(_lib.CS_ERR_UNSUPPORTED, "a sharded store has no grouped search (per_file): no cs_shards_ form yet")
+            self._needs_groups()
             out = (cos.ctypes.data_as(f32p), ids.ctypes.data_as(u32p), C.byref(count), C.byref(flag))
             if scope is not None:
-                _lib.check(self._lib.cs_index_search_variants_grouped_scoped(self._h, self._scope_handle(scope),
+                _lib.check(self._fn("search_variants_grouped_scoped")(self._h, self._scope_handle(scope),
                                                                              q.ctypes.data_as(f32p), nq, dim, limit,
                                                                              int(per_file), *out))
             else:
-                _lib.check(self._lib.cs_index_search_variants_grouped(self._h, q.ctypes.data_as(f32p), nq, dim, limit,
+                _lib.check(self._fn("search_variants_grouped")(self._h, q.ctypes.data_as(f32p), nq, dim, limit,
                                                                       int(per_file), *out))
         elif scope is not None:
             _lib.check(self._fn("search_variants_scoped")(self._h, self._scope_handle(scope), q.ctypes.data_as(f32p), nq, dim,

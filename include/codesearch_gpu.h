@@ -248,7 +248,9 @@ CS_API int32_t cs_scope_set_route(cs_scope* scope, int32_t route);
 /* Host-buffer searches answered through the filter / by the gathered scan, exact reruns after an overflow, and the
  * bytes of HBM the scope holds beyond its 8 per id: the 1,024-stride table (4 B per 1,024 ids, kept by a scope of more
  * than 3,072 ids over an index with an int8 copy and one of the three dims) and, while its list as last made outgrows
- * 3,072 rows, the bitmap; 0 for every other scope.  Each output optional.  Over a sharded store all are 0. */
+ * 3,072 rows, the bitmap; 0 for every other scope.  Each output optional.  Over a sharded store the counters are summed
+ * over the scope's parts — a grouped search counts one gathered search per shard part that holds a live row, the other
+ * sharded searches count nothing — and the bytes are 0. */
 CS_API int32_t cs_scope_route_info(const cs_scope* scope, uint64_t* filter_searches, uint64_t* gathered_searches,
                                    uint64_t* overflow_reruns, uint64_t* extra_bytes);
 /* Scope algebra — union, intersection and difference of two scopes, on the device.  Real filters are compositions:
@@ -333,7 +335,8 @@ CS_API int32_t cs_index_search_grouped(cs_index* h, const float* queries, uint32
  * per_group == 0 (CS_ERR_BAD_ARG), then the scope's (a null scope, a scope made for another store: CS_ERR_BAD_ARG).  A
  * scope with no live row gives the empty answer and launches nothing.  The scoped forms always take the gathered scan
  * (counted in cs_scope_route_info's gathered_searches), whatever cs_scope_set_route says: the int8 filter's threshold is
- * the uncapped k-th.  Concurrent calls are safe.  No cs_shards_, masked (bitmap) or device-pointer form yet. */
+ * the uncapped k-th.  Concurrent calls are safe.  Over a sharded store: cs_shards_search_grouped & co. below.  No masked
+ * (bitmap) or device-pointer form yet. */
 CS_API int32_t cs_index_search_grouped_scoped(cs_index* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,
                                               uint32_t k, uint32_t per_group, float* out_cos, uint32_t* out_ids,
                                               uint32_t* out_counts);
@@ -771,6 +774,35 @@ CS_API int32_t cs_shards_search_scoped(cs_shards* h, cs_scope* scope, const floa
 CS_API int32_t cs_shards_search_variants_scoped(cs_shards* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,
                                          uint32_t k, float* out_cos, uint32_t* out_ids, uint32_t* out_count,
                                          int32_t* out_high_confidence);
+/* Grouped search over the sharded store (cs_index_set_groups, cs_index_search_grouped & co.).  Each search returns, bit for
+ * bit (cosines, ids, counts, count, flag), what the cs_index_* call of the same name returns on one index holding the same
+ * rows, ids and groups; so it equals cs_shards_search / _scoped / _variants / _variants_scoped when per_group >= k or no
+ * group is assigned.  `ids` are global ids.  The store keeps two tables: every shard its slice by local id (its capped scan
+ * reads it) and, for the root's capped shard merge, one by global id on the host and — from the first grouped search after
+ * an assignment — in HBM of the first device: 8 B per id issued in all.  Every shard leaves its capped best k, and the
+ * root caps again while it merges (a group spread over the shards fills per_group slots of every shard's list); with
+ * variants the per-variant capped lists are then merged by the de-duplicating capped merge, as on one index.
+ * Rules of cs_shards_set_groups: those of cs_index_set_groups with its texts — an id at or above cs_shards_next_id fails
+ * with CS_ERR_BAD_ARG and nothing is assigned on any shard; groups belong to ids: they survive cs_shards_remove +
+ * cs_shards_build, apply to the next search without a build, ids appended later are CS_NO_GROUP until assigned, and
+ * cs_shards_clear drops them.  Not to be called while the store is searched (like add / remove / build).
+ * cs_shards_groups_info: *table_bytes = the root's table + every shard's.
+ * Errors of the searches, their texts and order: the checks of cs_shards_search (for the variants forms then the variants
+ * limit), then per_group == 0, then the scope's (null, or made for another store).  Searches are re-entrant, as
+ * cs_shards_search is.  Boosted, similar, pairs and clusters searches have no cs_shards_ form yet. */
+CS_API int32_t cs_shards_set_groups(cs_shards* h, const uint32_t* ids, const uint32_t* groups, uint64_t n);
+CS_API int32_t cs_shards_groups_info(cs_shards* h, uint64_t* assigned_ids, uint64_t* table_bytes);
+CS_API int32_t cs_shards_search_grouped(cs_shards* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                                        uint32_t per_group, float* out_cos, uint32_t* out_ids, uint32_t* out_counts);
+CS_API int32_t cs_shards_search_grouped_scoped(cs_shards* h, cs_scope* scope, const float* queries, uint32_t nq, uint32_t dim,
+                                               uint32_t k, uint32_t per_group, float* out_cos, uint32_t* out_ids,
+                                               uint32_t* out_counts);
+CS_API int32_t cs_shards_search_variants_grouped(cs_shards* h, const float* queries, uint32_t nq, uint32_t dim, uint32_t k,
+                                                 uint32_t per_group, float* out_cos, uint32_t* out_ids, uint32_t* out_count,
+                                                 int32_t* out_high_confidence);
+CS_API int32_t cs_shards_search_variants_grouped_scoped(cs_shards* h, cs_scope* scope, const float* queries, uint32_t nq,
+                                                        uint32_t dim, uint32_t k, uint32_t per_group, float* out_cos,
+                                                        uint32_t* out_ids, uint32_t* out_count, int32_t* out_high_confidence);
 CS_API int32_t cs_shards_read_rows(cs_shards* h, uint64_t first_id, uint64_t n, float* out_rows);
 
 /* Copy the rows of ids [id_base + first_row, id_base + first_row + n) back to host memory (test and
