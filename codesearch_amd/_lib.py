@@ -271,6 +271,10 @@ DIAG_SIGNATURES = {
                                      C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), f32p, i32p]),
     "cs_debug_gemm_q8_units": (C.c_int32, [C.c_int32, C.c_int32, f32p, f32p, f32p, f32p, f32p, f32p, C.c_uint32, C.c_uint32,
                                            C.c_uint32, u32p, C.c_uint32, f32p, i32p]),
+    "cs_debug_gemm_q8_ln": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, f32p, f32p, f32p, f32p, f32p, f32p, C.c_float, f32p,
+                                        C.c_uint32, C.c_uint32, f32p, f32p, C.c_uint32, u32p, u32p, C.POINTER(C.c_uint8), f32p]),
+    "cs_debug_q8_unit_ranges": (C.c_int32, [C.c_int32, u32p, u32p, C.c_uint32, C.c_uint32, C.c_uint32, f32p, C.c_uint32,
+                                            C.c_int32, u32p, u32p]),
     "cs_debug_gemm": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, f32p, f32p, f32p, f32p, f32p,
                                   C.c_uint32, C.c_uint32, C.c_uint32, u32p]),
     "cs_debug_gemm_wide": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p, f32p, f32p, f32p, f32p,

@@ -1019,4 +1019,138 @@ int32_t cs_debug_gemm_wide(int32_t device, int32_t epi, int32_t shape, int32_t m
     return CS_OK;
 }
 
+// Diagnostics: the LayerNorm-fused quantised product alone on host buffers, from either production source, at any M —
+// launch_gemm_q8_ln as the forward calls it (embedder_forward.hip: out-proj from the split context, FFN-down from the s8 rows
+// FFN-up left).  X is followed by CS_DEBUG_Q8_LN_GUARD_ROWS guard rows (a whole row group of the kernel: a store that forgot
+// `row < M` lands there).  Contract in include/codesearch_gpu_diag.h.
+int32_t cs_debug_gemm_q8_ln(int32_t device, int32_t source, int32_t flags, const float* A, const float* W, const float* wscale,
+                            const float* bias, const float* gamma, const float* beta, float eps, const float* resid, uint32_t M,
+                            uint32_t K, float* out, float* pairs, uint32_t pairs_cap, uint32_t* out_pairs, uint32_t* slot,
+                            uint8_t* xq, float* xparams) {
+    if (!A || !W || !wscale || !bias || !gamma || !beta || !resid || !out || !out_pairs || !slot) return fail(CS_ERR_BAD_ARG, "cs_debug_gemm_q8_ln: null buffer");
+    if ((source != 0 && source != 1) || (flags & ~3)) return fail(CS_ERR_BAD_ARG, "cs_debug_gemm_q8_ln: source = %d (0 split, 1 prequant), flags = %d (1 stage-major weight, 2 range slot)", source, flags);
+    if (M == 0 || (K != 384 && K != 1536) || (source == 0 && K != 384))
+        return fail(CS_ERR_UNSUPPORTED, "cs_debug_gemm_q8_ln needs M > 0 and K = 384 (either source) or 1536 (prequant) (M=%u K=%u)", M, K);
+    const bool stage_major = flags & 1, slot_mode = flags & 2;
+    const uint32_t N = QN_N, pairs_room = (M + 127) / 128 * 8;  // eight pairs per 128-row group (the four-wave form, four per 64 rows, never leaves more)
+    if (!slot_mode && (!pairs || pairs_cap < pairs_room)) return fail(CS_ERR_BAD_ARG, "cs_debug_gemm_q8_ln: pairs needs room for %u", pairs_room);
+    CS_TRY(diag_device(device));
+    DeviceGuard g(device);
+    DiagBufs bufs;
+    const size_t a_n = (size_t)M * K, w_n = (size_t)N * K, x_n = (size_t)M * N, guard_n = (size_t)CS_DEBUG_Q8_LN_GUARD_ROWS * N;
+    float *dA = nullptr, *dW = nullptr, *dS = nullptr, *dB = nullptr, *dG = nullptr, *dBe = nullptr, *dX = nullptr, *dPairs = nullptr;
+    _Float16* sA = nullptr;
+    int8_t *dXq = nullptr, *dWq = nullptr, *dWst = nullptr;
+    Q8RowMeta* dRm = nullptr;
+    Q8ColMeta* dCm = nullptr;
+    uint32_t *dF = nullptr, *dRanges = nullptr;  // dRanges: slot 0 the fused kernel's input range, 1 the separate pass's, 2 the output's
+    CS_TRY(bufs.get(&dF, 16));
+    CS_HIP(hipMemset(dF, 0, 16));
+    CS_TRY(bufs.get(&dRanges, 3 * Q8_RANGE_WORDS * 4));
+    CS_HIP(hipMemset(dRanges, 0, 3 * Q8_RANGE_WORDS * 4));
+    CS_TRY(bufs.get(&dA, a_n * 4, A));
+    CS_TRY(bufs.get(&dW, w_n * 4, W));
+    CS_TRY(bufs.get(&dS, (size_t)N * 4, wscale));
+    CS_TRY(bufs.get(&dB, (size_t)N * 4, bias));
+    CS_TRY(bufs.get(&dG, (size_t)N * 4, gamma));
+    CS_TRY(bufs.get(&dBe, (size_t)N * 4, beta));
+    CS_TRY(bufs.get(&dWq, w_n));
+    CS_TRY(bufs.get(&dCm, (size_t)N * sizeof(Q8ColMeta)));
+    CS_TRY(bufs.get(&dXq, a_n));
+    CS_TRY(bufs.get(&dRm, (size_t)M * sizeof(Q8RowMeta)));
+    CS_TRY(bufs.get(&dX, (x_n + guard_n) * 4));
+    CS_HIP(hipMemcpy(dX, resid, x_n * 4, hipMemcpyHostToDevice));
+    {
+        const std::vector<uint32_t> pattern(guard_n, CS_DEBUG_Q8_LN_GUARD_WORD);
+        CS_HIP(hipMemcpy(dX + x_n, pattern.data(), guard_n * 4, hipMemcpyHostToDevice));
+    }
+    CS_TRY(bufs.get(&dPairs, (size_t)pairs_room * 8));
+    CS_HIP(hipMemset(dPairs, 0xff, (size_t)pairs_room * 8));  // a pair the launch does not write comes back as NaN
+    CS_TRY(launch_q8_pack_weight(dW, dS, dB, N, K, dWq, dCm, dF + 1, nullptr));
+    CS_HIP(hipDeviceSynchronize());
+    uint32_t bad = 0;
+    CS_HIP(hipMemcpy(&bad, dF + 1, 4, hipMemcpyDeviceToHost));
+    if (bad) return fail(CS_ERR_BAD_ARG, "cs_debug_gemm_q8_ln: W is not a quantised matrix for these column scales (flag %u)", bad);
+    const int8_t* w_used = dWq;
+    if (stage_major) {
+        CS_TRY(bufs.get(&dWst, w_n));
+        CS_TRY(launch_q8_stage_major(dWq, N, K, dWst, nullptr));
+        w_used = dWst;
+    }
+    uint32_t *in_range = dRanges, *sep_range = dRanges + Q8_RANGE_WORDS, *out_slot = dRanges + 2 * Q8_RANGE_WORDS;
+    uint32_t n_pairs = 0;
+    if (source == 0) {
+        CS_TRY(bufs.get(&sA, a_n * 4));
+        CS_TRY(launch_split_rows(dA, sA, M, K, dF, nullptr));
+        CS_TRY(launch_q8_range(Q8_SRC_SPLIT, sA, M, K, in_range, nullptr));
+        CS_TRY(launch_q8_quantize(Q8_SRC_SPLIT, sA, M, K, sep_range, nullptr, dXq, dRm, nullptr));  // (for xq / xparams only)
+        CS_TRY(launch_gemm_q8_ln(Q8_SRC_SPLIT, sA, nullptr, in_range, w_used, dCm, dX, dG, dBe, eps, M, K, dPairs, &n_pairs, nullptr,
+                                 slot_mode ? out_slot : nullptr, stage_major));
+    } else {
+        CS_TRY(launch_q8_quantize(Q8_SRC_F32, dA, M, K, sep_range, nullptr, dXq, dRm, nullptr));
+        CS_TRY(launch_gemm_q8_ln(Q8_SRC_PREQUANT, dXq, dRm, nullptr, w_used, dCm, dX, dG, dBe, eps, M, K, dPairs, &n_pairs, nullptr,
+                                 slot_mode ? out_slot : nullptr, stage_major));
+    }
+    if (!slot_mode) {
+        if (n_pairs == 0 || n_pairs > pairs_room) return fail(CS_ERR_HIP, "cs_debug_gemm_q8_ln: the launcher reported %u pairs (room for %u)", n_pairs, pairs_room);
+        CS_TRY(launch_q8_range(Q8_SRC_F32, dX, M, N, out_slot, nullptr, dPairs, n_pairs));
+    }
+    CS_HIP(hipDeviceSynchronize());
+    *out_pairs = n_pairs;
+    CS_HIP(hipMemcpy(out, dX, (x_n + guard_n) * 4, hipMemcpyDeviceToHost));
+    CS_HIP(hipMemcpy(slot, out_slot, 8, hipMemcpyDeviceToHost));
+    if (!slot_mode) CS_HIP(hipMemcpy(pairs, dPairs, (size_t)pairs_room * 8, hipMemcpyDeviceToHost));
+    if (xq) {
+        std::vector<int8_t> hq(a_n);
+        CS_HIP(hipMemcpy(hq.data(), dXq, a_n, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < a_n; ++i) xq[i] = (uint8_t)((int)hq[i] + 128);
+    }
+    if (xparams) {
+        Q8RowMeta rm0;
+        CS_HIP(hipMemcpy(&rm0, dRm, sizeof(rm0), hipMemcpyDeviceToHost));
+        xparams[0] = rm0.xs;
+        xparams[1] = (float)(rm0.za + 128);
+    }
+    return CS_OK;
+}
+
+// Diagnostics: launch_q8_row_slots and launch_q8_range_units alone.  Contract in include/codesearch_gpu_diag.h.
+int32_t cs_debug_q8_unit_ranges(int32_t device, const uint32_t* seq_unit, const uint32_t* unit_len, uint32_t B, uint32_t units,
+                                uint32_t L, const float* pairs, uint32_t pairs_per_seq, int32_t pairs_are_rows, uint32_t* row_slot,
+                                uint32_t* slots) {
+    if (!seq_unit || !unit_len || (!pairs) != (!slots) || (!row_slot && !slots)) return fail(CS_ERR_BAD_ARG, "cs_debug_q8_unit_ranges: null buffer");
+    if (B == 0 || units == 0 || L == 0 || (pairs && pairs_per_seq == 0)) return fail(CS_ERR_BAD_ARG, "cs_debug_q8_unit_ranges needs B, units, L, pairs_per_seq > 0");
+    if (pairs && pairs_are_rows && pairs_per_seq != L) return fail(CS_ERR_BAD_ARG, "cs_debug_q8_unit_ranges: row pairs come L = %u per sequence (pairs_per_seq = %u)", L, pairs_per_seq);
+    for (uint32_t b = 0; b < B; ++b)
+        if (seq_unit[b] >= units || (b && seq_unit[b] < seq_unit[b - 1]))
+            return fail(CS_ERR_BAD_ARG, "seq_unit[%u]: units must be consecutive runs of sequences, in order", b);
+    CS_TRY(diag_device(device));
+    DeviceGuard g(device);
+    DiagBufs bufs;
+    uint32_t *dSu = nullptr, *dUl = nullptr, *dRs = nullptr, *dRange = nullptr;
+    float* dP = nullptr;
+    CS_TRY(bufs.get(&dSu, (size_t)B * 4, seq_unit));
+    CS_TRY(bufs.get(&dUl, (size_t)units * 4, unit_len));
+    if (row_slot) {
+        const size_t T = (size_t)B * L;
+        CS_TRY(bufs.get(&dRs, T * 4));
+        CS_HIP(hipMemset(dRs, 0xA5, T * 4));
+        CS_TRY(launch_q8_row_slots(dSu, dUl, (uint32_t)T, L, dRs, nullptr));
+        CS_HIP(hipDeviceSynchronize());
+        CS_HIP(hipMemcpy(row_slot, dRs, T * 4, hipMemcpyDeviceToHost));
+    }
+    if (slots) {
+        const size_t rbytes = (size_t)units * Q8_RANGE_WORDS * 4;
+        CS_TRY(bufs.get(&dP, (size_t)B * pairs_per_seq * 8, pairs));
+        CS_TRY(bufs.get(&dRange, rbytes));
+        CS_HIP(hipMemset(dRange, 0xA5, rbytes));  // (the kernel writes words 0, 1: it must not depend on what they held)
+        CS_TRY(launch_q8_range_units(dP, pairs_per_seq, pairs_are_rows != 0, dSu, dUl, B, units, dRange, nullptr));
+        CS_HIP(hipDeviceSynchronize());
+        std::vector<uint32_t> hr((size_t)units * Q8_RANGE_WORDS);
+        CS_HIP(hipMemcpy(hr.data(), dRange, rbytes, hipMemcpyDeviceToHost));
+        for (uint32_t u = 0; u < units; ++u) { slots[2 * u] = hr[(size_t)u * Q8_RANGE_WORDS]; slots[2 * u + 1] = hr[(size_t)u * Q8_RANGE_WORDS + 1]; }
+    }
+    return CS_OK;
+}
+
 }  // extern "C"

@@ -1900,10 +1900,17 @@ int32_t launch_gemm_q8_ln(int src_kind, const void* d_src, const Q8RowMeta* d_rm
         CS_HIP(allow(gemm_q8_ln_kernel<QR_PREQUANT, 24, 8, 5>, 5));
         return CS_OK;
     }));
+    // CS_Q8_LN_MAX_BLOCKS=n (diagnostic library only, read per launch): at most n blocks, so that a block walks several row
+    // groups — the ring restarting in the slots the previous group's last stages left, the (lo, hi) words of LDS used again —
+    // at a few hundred rows instead of above 128 x CUs (tests/test_gpu_q8_ln.py)
+    const char* be = cs_lab_env("CS_Q8_LN_MAX_BLOCKS");
+    const uint32_t max_blocks = be ? (uint32_t)std::strtoul(be, nullptr, 10) : 0u;
     auto go = [&](auto kernel, uint32_t nw, int nst) -> int32_t {
         const size_t ldsb = (size_t)qn_lds(nst, nst == 3);
         const uint32_t groups = (M + 16 * nw - 1) / (16 * nw), slots = (uint32_t)cu_count() * (nw == 4 ? 2u : 1u);
-        hipLaunchKernelGGL(kernel, dim3(groups < slots ? groups : slots), dim3(64 * nw), ldsb, s, d_src, d_rmeta, d_in_range, d_wq, d_cmeta, X, ln_g, ln_b,
+        uint32_t blocks = groups < slots ? groups : slots;
+        if (max_blocks && max_blocks < blocks) blocks = max_blocks;
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64 * nw), ldsb, s, d_src, d_rmeta, d_in_range, d_wq, d_cmeta, X, ln_g, ln_b,
                            eps, M, d_range_pairs, d_out_slot, w_stage_major ? 1u : 0u);
         CS_HIP(hipGetLastError());
         if (out_pairs) *out_pairs = d_out_slot ? 0 : groups * nw;

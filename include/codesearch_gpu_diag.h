@@ -2,7 +2,7 @@
  * codesearch_gpu_diag.h — operator-level diagnostics of libcsgpu, exported ONLY by codesearch_amd/libcsgpu_diag.so (the
  * product library built once more with -DCS_DIAGNOSTICS: it additionally holds csrc/diagnostics.hip, the ablation
  * instantiations of the wide GEMM kernel and its in-kernel clock stamps).  Used by tests/test_gpu_gemm_split.py, tests/test_gpu_gemm_wide.py,
- * tests/test_gpu_quantized.py, tests/test_gpu_attention.py, tests/test_gpu_rows.py, tests/test_gpu_attention_cls.py, tests/test_gpu_small_path.py (operator parity) and benchmarks/ (A/B timing); nothing in INTEGRATION.md binds it and a
+ * tests/test_gpu_quantized.py, tests/test_gpu_q8_ln.py, tests/test_gpu_attention.py, tests/test_gpu_rows.py, tests/test_gpu_attention_cls.py, tests/test_gpu_small_path.py (operator parity) and benchmarks/ (A/B timing); nothing in INTEGRATION.md binds it and a
  * deployment does not ship it.  The diagnostic library exports every symbol of include/codesearch_gpu.h as well, so a
  * process may use it in place of libcsgpu.so.
  */
@@ -72,6 +72,40 @@ CS_API int32_t cs_debug_gemm_q8(int32_t device, int32_t epilogue, int32_t a_spli
 CS_API int32_t cs_debug_gemm_q8_units(int32_t device, int32_t epilogue, const float* A, const float* W, const float* wscale,
                                const float* bias, const float* resid, float* C, uint32_t M, uint32_t N, uint32_t K,
                                const uint32_t* row_slot, uint32_t units, float* row_params, int32_t* rowsums);
+
+/* Diagnostics: the LayerNorm-fused quantised product (gemm_q8_ln_kernel, csrc/gemm_q8.hip: out-proj and FFN-down of the
+ * 384-wide quantised models from 4,096 token rows) alone on host buffers, at ANY M, for unit parity against float64
+ * (tests/test_gpu_q8_ln.py; reference and bound: tests/q8_ln_ref.py).  A [M, K] f32 activations, W [384, K] f32 = integer
+ * multiples of wscale[n] (packed by launch_q8_pack_weight; anything else: CS_ERR_BAD_ARG, "not a quantised matrix"), bias,
+ * gamma, beta [384], resid [M, 384] the residual.
+ *   source 0  "split" (out-proj, K = 384): launch_split_rows, launch_q8_range(Q8_SRC_SPLIT) by a pass over the tensor,
+ *             launch_gemm_q8_ln(Q8_SRC_SPLIT): the kernel quantises its rows on the way in
+ *          1  "prequant" (FFN-down, K = 384 | 1536): launch_q8_quantize(Q8_SRC_F32), launch_gemm_q8_ln(Q8_SRC_PREQUANT)
+ *   flags & 1 the weight goes through launch_q8_stage_major (w_stage_major = true), else row-major
+ *         & 2 the output range is widened into a zeroed slot by the kernel itself (d_out_slot), else left as pairs
+ * out [M + CS_DEBUG_Q8_LN_GUARD_ROWS, 384]: the M normalised rows, then the guard rows behind them as they came back — the
+ * device tensor holds the residual in its first M rows and CS_DEBUG_Q8_LN_GUARD_WORD in every word of the guard rows.
+ * Pairs mode: pairs [ceil(M / 128) * 8][2] (pairs_cap >= that many) receives the pair buffer, pre-filled with NaN bits,
+ * *out_pairs what the launcher reported; slot [2] the words 0, 1 of a zeroed slot after
+ * launch_q8_range(Q8_SRC_F32, X, ..., pairs, *out_pairs), the reduction the forward runs next.  Slot mode: slot [2] the two
+ * words the kernel widened, *out_pairs the launcher's count (0).
+ * xq [M, K] (optional) and xparams [2] (optional): the uint8 activations and (x_scale, x_zero_point) of the SEPARATE
+ * quantising pass over the same source (source 0: launch_q8_quantize(Q8_SRC_SPLIT) on the split tensor, run for this only). */
+#define CS_DEBUG_Q8_LN_GUARD_ROWS 128u
+#define CS_DEBUG_Q8_LN_GUARD_WORD 0xA5A5A5A5u
+CS_API int32_t cs_debug_gemm_q8_ln(int32_t device, int32_t source, int32_t flags, const float* A, const float* W, const float* wscale,
+                            const float* bias, const float* gamma, const float* beta, float eps, const float* resid, uint32_t M,
+                            uint32_t K, float* out, float* pairs, uint32_t pairs_cap, uint32_t* out_pairs, uint32_t* slot,
+                            uint8_t* xq, float* xparams);
+
+/* Diagnostics: the unit bookkeeping of queued quantised batches (csrc/gemm_q8.hip) alone: seq_unit [B] the unit of each
+ * sequence (a unit's sequences consecutive), unit_len [units] each unit's own padded length, L the batch's padded length.
+ * row_slot [B * L] (optional) receives launch_q8_row_slots' output.  pairs [B * pairs_per_seq][2] (optional, with slots)
+ * go through launch_q8_range_units (pairs_are_rows != 0: a pair per token row, pairs_per_seq == L) into slots
+ * pre-filled with a non-zero pattern — the kernel writes words 0, 1 rather than widening them; slots [units][2] receives them. */
+CS_API int32_t cs_debug_q8_unit_ranges(int32_t device, const uint32_t* seq_unit, const uint32_t* unit_len, uint32_t B, uint32_t units,
+                                uint32_t L, const float* pairs, uint32_t pairs_per_seq, int32_t pairs_are_rows, uint32_t* row_slot,
+                                uint32_t* slots);
 
 /* Diagnostics: the one-launch forward of short queries (csrc/small_forward.hip; embed_one / embed_queries_batch,
  * src/embed/mod.rs:164-226) — mini-batches of a 384-d BERT model with at most 192 token rows in split-f16 mode as ONE kernel,

@@ -17,39 +17,9 @@ from codesearch_amd import _lib
 from codesearch_amd._lib import f32p
 from codesearch_amd.bert_params import (POOL_CLS, POOL_MEAN, BertConfig, quant_columns, quantize_linear_weights,
                                         synth_params, synth_token_batch)
+from tests.q8_ln_ref import dynamic_quantize, quantize_matrix, split_round_trip
 
 pytestmark = pytest.mark.gpu
-
-
-def quantize_matrix(W, per_channel, unsigned):
-    """onnxruntime's weight quantisation of one [N, K] matrix -> (dequantised W, integers q - zp, scale [N])."""
-    W = np.asarray(W, np.float32)
-    axis = 1 if per_channel else None
-    lo = np.minimum(W.min(axis=axis, keepdims=True), np.float32(0))
-    hi = np.maximum(W.max(axis=axis, keepdims=True), np.float32(0))
-    if unsigned:
-        scale = ((hi - lo) / np.float32(255)).astype(np.float32)
-        zp = np.clip(np.rint(-lo / scale), 0, 255)
-        q = np.clip(np.rint(W / scale) + zp, 0, 255)
-    else:
-        scale = (np.maximum(np.abs(lo), np.abs(hi)) / np.float32(127)).astype(np.float32)
-        zp = np.zeros_like(scale)
-        q = np.clip(np.rint(W / scale), -127, 127)
-    d = (q - zp).astype(np.int64)
-    sc = np.broadcast_to(scale.reshape(-1), (W.shape[0],)).astype(np.float32) if per_channel \
-        else np.full(W.shape[0], scale.reshape(-1)[0], np.float32)
-    return (d.astype(np.float32) * sc[:, None]).astype(np.float32), d, sc
-
-
-def dynamic_quantize(x):
-    """ONNX DynamicQuantizeLinear (opset 11), float32 arithmetic -> (uint8 tensor, scale, zero point)."""
-    x = np.asarray(x, np.float32)
-    lo = np.minimum(np.float32(0), x.min())
-    hi = np.maximum(np.float32(0), x.max())
-    scale = np.float32(1) if hi == lo else np.float32((hi - lo) / np.float32(255))
-    zp = np.float32(np.rint(np.clip(np.float32(0) - np.float32(lo / scale), 0, 255)))
-    q = np.clip(np.rint((x / scale).astype(np.float32)) + zp, 0, 255).astype(np.uint8)
-    return q, scale, int(zp)
 
 
 def run_q8(lib, epi, A, W, sc, bias, resid=None, a_split=0):
@@ -64,14 +34,6 @@ def run_q8(lib, epi, A, W, sc, bias, resid=None, a_split=0):
                                     C_.ctypes.data_as(f32p), M, N, K, xq.ctypes.data_as(C.POINTER(C.c_uint8)),
                                     xp.ctypes.data_as(f32p), acc.ctypes.data_as(C.POINTER(C.c_int32))))
     return C_, xq, xp, acc
-
-
-def split_round_trip(A):
-    """What an f32 value becomes on its way through the split-f16 hand-over: hi + lo / 2048."""
-    A = np.asarray(A, np.float32)
-    hi = A.astype(np.float16)
-    lo = ((A - hi.astype(np.float32)) * np.float32(2048)).astype(np.float16)
-    return (hi.astype(np.float32) + lo.astype(np.float32) * np.float32(1 / 2048)).astype(np.float32)
 
 
 # (from 4,096 rows on a K = 384 layer runs on the row-block kernel, gemm_q8_rows_kernel: the last three shapes)
@@ -772,7 +734,8 @@ def test_layernorm_fused_products_repeat_their_bits(gpu_lib, oracle, B, L):
     by clean runs").  Token-row counts with one 128-row group per block (4,096), a ragged last group (4,224), several
     groups per block (32,768; 65,536 = two per block on 256 CUs): the same call eight times must leave the same bytes
     (a stage read before it landed shows as a run that differs), and the first run meets the quantised oracle at the
-    model level's bar."""
+    model level's bar.  That the bits are the RIGHT ones — the kernel alone against float64 inside a derived bound, every
+    source, ragged groups, several groups per block — is tests/test_gpu_q8_ln.py."""
     from codesearch_amd import FastEmbedder, ModelType
 
     cfg = small_cfg(POOL_MEAN)
