@@ -293,6 +293,10 @@ DIAG_SIGNATURES = {
                                         C.c_uint32, f32p, f32p, f32p, f32p, f32p, f32p, u32p, u32p]),
     "cs_debug_attention": (C.c_int32, [C.c_int32, f32p, i32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, f32p, C.c_uint32,
                                        u32p, u32p, C.c_uint32, f32p, f32p, f32p, f32p, f32p, C.c_uint32, u32p, u32p]),
+    "cs_debug_filter": (C.c_int32, [C.c_int32, C.c_uint32, f32p, C.c_uint64, f32p, C.c_uint32, f32p, u32p, f32p, C.c_int32,
+                                    C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, f32p, f32p,
+                                    C.POINTER(C.c_uint16), C.POINTER(C.c_int8), f32p, C.POINTER(C.c_uint16), C.POINTER(C.c_int8),
+                                    C.POINTER(C.c_int8), C.POINTER(C.c_int8), f32p, f32p, u32p, u32p, u32p]),
 }
 
 _LIB = None

@@ -1153,4 +1153,175 @@ int32_t cs_debug_q8_unit_ranges(int32_t device, const uint32_t* seq_unit, const 
     return CS_OK;
 }
 
+// Diagnostics: one filter phase alone on host buffers — the copies built, the queries prepared and the phase launched by the
+// launchers the index and launch_scan_split call.  Contract in include/codesearch_gpu_diag.h.
+int32_t cs_debug_filter(int32_t device, uint32_t dim, const float* corpus, uint64_t n_rows, const float* queries, uint32_t nq,
+                        const float* tau, const uint32_t* dead, const float* mu_in, int32_t kernel, uint32_t nqt, uint64_t row_lo,
+                        uint64_t row_hi, uint32_t cap, uint32_t grid, uint64_t tail_lo, uint64_t tail_hi, float* norms_out,
+                        float* mu_out, uint16_t* f16_out, int8_t* q8_out, float* tmeta_out, uint16_t* qunit_out, int8_t* q8q_out,
+                        int8_t* q8q_hi_out, int8_t* q8q_lo_out, float* qmeta_out, float* qmag_out, uint32_t* cnt_out,
+                        uint32_t* cand_out, uint32_t* guard_changed) {
+    using K = FilterKernel;
+    if (!corpus || !queries || !tau || !cnt_out || !cand_out || !guard_changed) return fail(CS_ERR_BAD_ARG, "cs_debug_filter: null buffer");
+    if (!split_scan_supported(dim)) return fail(CS_ERR_UNSUPPORTED, "cs_debug_filter: dim 384 / 768 / 1024, got %u", dim);
+    if (n_rows == 0 || n_rows > (1u << 20) || nq == 0 || nq > 4096 || cap == 0 || cap > (1u << 16))
+        return fail(CS_ERR_BAD_ARG, "cs_debug_filter needs 1 <= n_rows <= 2^20, 1 <= nq <= 4,096, 1 <= cap <= 65,536");
+    if (kernel < (int32_t)K::None || kernel > (int32_t)K::F16Tile128) return fail(CS_ERR_BAD_ARG, "cs_debug_filter: kernel = %d", kernel);
+    const K kern = (K)kernel;
+    const bool i8 = kern == K::Q8Tile256 || kern == K::Q8Rq || kern == K::Q8Rq1 || kern == K::Q8Rw || kern == K::Q8Rw2;
+    const bool tiles256 = kern == K::Q8Tile256 || kern == K::F16Tile256;
+    const uint64_t q8_rows = n_rows / 128 * 128;  // complete tiles only
+    if (kern != K::None && (row_hi <= row_lo || row_hi > (i8 ? q8_rows : n_rows)))
+        return fail(CS_ERR_BAD_ARG, "cs_debug_filter: rows [%llu, %llu) of %llu stored (int8: %llu in complete tiles)",
+                    (unsigned long long)row_lo, (unsigned long long)row_hi, (unsigned long long)n_rows, (unsigned long long)q8_rows);
+    if (tail_hi < tail_lo || tail_hi > n_rows || tail_hi - tail_lo >= 128)
+        return fail(CS_ERR_BAD_ARG, "cs_debug_filter: the tail is fewer than 128 stored rows");
+    CS_TRY(diag_device(device));
+    DeviceGuard g(device);
+    DiagBufs bufs;
+    // both copies in whole tiles, an even number of them (index.hip: the 256-row kernels read whole pairs) and one pair
+    // more, for a row_lo on an odd tile
+    const size_t tiles = ((size_t)n_rows + 255) / 256 * 2 + 2, kq8 = (size_t)dim * 128, pad_q = CS_DEBUG_FILTER_CNT_PAD;
+    const size_t q_n = (size_t)nq * dim, cnt_words = (nq + pad_q) * kCntStride, cand_slots = ((size_t)nq + 1) * cap;
+    float *dC = nullptr, *dN = nullptr, *dMu = nullptr, *dQ = nullptr, *dTau = nullptr, *dQmag = nullptr;
+    _Float16 *dSplit = nullptr, *dQs = nullptr;
+    int8_t *dQ8 = nullptr, *dQ8q = nullptr, *dQhi = nullptr;
+    float4 *dTm = nullptr, *dQm = nullptr;
+    uint32_t *dDead = nullptr, *dCnt = nullptr, *dOv = nullptr;
+    uint64_t *dCand = nullptr, *dCarry = nullptr;
+    CS_TRY(bufs.get(&dC, (size_t)n_rows * dim * 4, corpus));
+    CS_TRY(bufs.get(&dN, tiles * 128 * 4));
+    CS_HIP(hipMemset(dN, 0, tiles * 128 * 4));
+    CS_TRY(bufs.get(&dMu, (size_t)dim * 4));
+    CS_TRY(bufs.get(&dQ, q_n * 4, queries));
+    CS_TRY(bufs.get(&dTau, (size_t)nq * 4));
+    CS_TRY(bufs.get(&dQmag, (size_t)nq * 4));
+    CS_TRY(bufs.get(&dSplit, tiles * kq8 * 2));
+    CS_HIP(hipMemset(dSplit, 0, tiles * kq8 * 2));
+    CS_TRY(bufs.get(&dQ8, tiles * kq8));
+    CS_HIP(hipMemset(dQ8, 0, tiles * kq8));
+    CS_TRY(bufs.get(&dTm, tiles * sizeof(float4)));
+    CS_HIP(hipMemset(dTm, 0, tiles * sizeof(float4)));
+    CS_TRY(bufs.get(&dQs, q_n * 2));
+    CS_TRY(bufs.get(&dQ8q, q_n));
+    CS_TRY(bufs.get(&dQhi, 2 * q_n));
+    CS_TRY(bufs.get(&dQm, (size_t)4 * nq * sizeof(float4)));
+    CS_HIP(hipMemset(dQm, 0, (size_t)4 * nq * sizeof(float4)));
+    if (dead) CS_TRY(bufs.get(&dDead, (tiles * 128 / 32) * 4));
+    if (dead) {
+        CS_HIP(hipMemset(dDead, 0xff, (tiles * 128 / 32) * 4));  // rows that are not stored are blocked
+        CS_HIP(hipMemcpy(dDead, dead, (size_t)((n_rows + 31) / 32) * 4, hipMemcpyHostToDevice));
+    }
+    CS_TRY(bufs.get(&dCnt, cnt_words * 4));
+    CS_TRY(bufs.get(&dOv, 16));
+    CS_HIP(hipMemset(dOv, 0, 16));
+    CS_TRY(bufs.get(&dCand, cand_slots * 8));
+    CS_TRY(bufs.get(&dCarry, 8));
+
+    // 1, 2: the norms and the copies, as cs_index_build makes them
+    CS_TRY(launch_row_norms(dC, 0, n_rows, dim, dN, nullptr));
+    CS_TRY(launch_corpus_split(dC, dN, dSplit, 0, n_rows, dim, nullptr));
+    if (mu_in) CS_HIP(hipMemcpy(dMu, mu_in, (size_t)dim * 4, hipMemcpyHostToDevice));
+    else CS_TRY(launch_unit_mean(dC, dN, n_rows, dim, dMu, nullptr));
+    if (q8_rows) CS_TRY(launch_corpus_q8(dC, dN, dQ8, dTm, 0, q8_rows / 128, dim, dMu, nullptr));
+    // 3: the queries, both planes
+    BatchedState st;
+    st.d_cand = dCand; st.d_cnt = dCnt; st.d_tau = dTau; st.d_carry = dCarry; st.d_overflow = dOv;
+    SplitQueryWs qw;
+    qw.d_qsplit = dQs; qw.d_qmag = dQmag; qw.d_q8q = dQ8q; qw.d_qmeta = dQm; qw.d_q8q_hi = dQhi; qw.d_q8q_lo = dQhi + q_n;
+    CS_TRY(launch_prep_queries(dim, st, qw, dQ, nq, 0, 0, dMu, true, true, nullptr));
+    CS_HIP(hipDeviceSynchronize());
+    // 4: the caller's tau; zeroed counters (word 0 of a line) between pattern words; pattern in every candidate slot
+    CS_HIP(hipMemcpy(dTau, tau, (size_t)nq * 4, hipMemcpyHostToDevice));
+    {
+        std::vector<uint32_t> hc(cnt_words, CS_DEBUG_FILTER_GUARD_WORD);
+        for (size_t q = 0; q < nq + pad_q; ++q) hc[q * kCntStride] = 0;
+        CS_HIP(hipMemcpy(dCnt, hc.data(), cnt_words * 4, hipMemcpyHostToDevice));
+        const std::vector<uint32_t> pattern(cand_slots * 2, CS_DEBUG_FILTER_GUARD_WORD);
+        CS_HIP(hipMemcpy(dCand, pattern.data(), cand_slots * 8, hipMemcpyHostToDevice));
+    }
+    // 5: one phase, filled by hand; grid 0 = plan_filter's rule for the kernel
+    FilterPhase ph;
+    ph.kernel = kern;
+    ph.nqt = nqt;
+    ph.lo = row_lo;
+    ph.hi = ph.filter_hi = row_hi;
+    ph.tail_lo = tail_lo;
+    ph.tail_hi = tail_hi;
+    if (kern != K::None) {
+        const int cus = cu_count(), cus8 = cus >= 8 ? cus / 8 * 8 : 256;
+        const uint64_t rows = row_hi - row_lo;
+        if (tiles256) {
+            ph.slots = filter_grid_slots((uint32_t)((rows + 255) / 256), (nq + 255) / 256);
+            if (grid % 8) return fail(CS_ERR_BAD_ARG, "cs_debug_filter: a persistent tile kernel's grid is a multiple of 8 (%u)", grid);
+            ph.grid = grid ? grid : std::min<uint32_t>(ph.slots, kern == K::Q8Tile256 ? (uint32_t)cus8 : ((uint32_t)cus + 7) / 8 * 8);
+        } else if (kern == K::F16Tile128) {
+            ph.grid = filter_grid_slots((uint32_t)((rows + 127) / 128), (nq + 127) / 128);  // a block per tile
+            if (grid && grid < ph.grid) return fail(CS_ERR_BAD_ARG, "cs_debug_filter: the 128 x 128 kernel needs a block per tile slot (%u < %u)", grid, ph.grid);
+            if (grid) ph.grid = grid;
+        } else {
+            if (nqt == 0 || nqt > 8) return fail(CS_ERR_BAD_ARG, "cs_debug_filter: nqt = %u", nqt);
+            ph.qtiles = (nq + 32 * nqt - 1) / (32 * nqt);
+            const uint64_t groups = (kern == K::Q8Rq || kern == K::Q8Rq1) ? (rows / 128 + 1) / 2 : (rows + 127) / 128;
+            ph.grid = grid ? grid : filter_resident_grid(groups, ph.qtiles, cus8);
+        }
+        if (ph.grid > 65536) return fail(CS_ERR_BAD_ARG, "cs_debug_filter: grid = %u", ph.grid);
+    }
+    Q8View q8;
+    q8.d_q8 = dQ8; q8.d_tmeta = dTm; q8.d_mu = dMu; q8.rows = q8_rows;
+    bool sub_ok = false;
+    CS_TRY(sh_denorm_selftest(&sub_ok, nullptr));
+    FilterOperands op;
+    op.st = &st; op.qw = &qw; op.d_split = dSplit; op.q8 = &q8; op.d_dead = dDead;
+    op.nq = nq; op.cap = cap; op.margin = filter_margin(dim, sub_ok); op.nt_stream = filter_knobs().nt; op.stream = nullptr;
+    CS_TRY(launch_filter_phase(dim, ph, op));
+    CS_HIP(hipGetLastError());
+    CS_HIP(hipDeviceSynchronize());
+
+    if (norms_out) CS_HIP(hipMemcpy(norms_out, dN, (size_t)n_rows * 4, hipMemcpyDeviceToHost));
+    if (mu_out) CS_HIP(hipMemcpy(mu_out, dMu, (size_t)dim * 4, hipMemcpyDeviceToHost));
+    if (f16_out) {  // [tile][dim / 64][128 rows][64] -> [n_rows][dim]
+        std::vector<uint16_t> h(tiles * kq8);
+        CS_HIP(hipMemcpy(h.data(), dSplit, tiles * kq8 * 2, hipMemcpyDeviceToHost));
+        const size_t kc = dim / 64;
+        for (size_t r = 0; r < n_rows; ++r)
+            for (size_t c = 0; c < kc; ++c)
+                memcpy(f16_out + r * dim + c * 64, h.data() + (((r >> 7) * kc + c) * 128 + (r & 127)) * 64, 128);
+    }
+    if (q8_out) {   // [tile][dim / 128][128 rows][128] -> [q8_rows][dim]
+        std::vector<int8_t> h(tiles * kq8);
+        CS_HIP(hipMemcpy(h.data(), dQ8, tiles * kq8, hipMemcpyDeviceToHost));
+        const size_t kc = dim / 128;
+        for (size_t r = 0; r < q8_rows; ++r)
+            for (size_t c = 0; c < kc; ++c)
+                memcpy(q8_out + r * dim + c * 128, h.data() + (((r >> 7) * kc + c) * 128 + (r & 127)) * 128, 128);
+    }
+    if (tmeta_out && q8_rows) CS_HIP(hipMemcpy(tmeta_out, dTm, (size_t)(q8_rows / 128) * sizeof(float4), hipMemcpyDeviceToHost));
+    if (qunit_out) CS_HIP(hipMemcpy(qunit_out, dQs, q_n * 2, hipMemcpyDeviceToHost));
+    if (q8q_out) CS_HIP(hipMemcpy(q8q_out, dQ8q, q_n, hipMemcpyDeviceToHost));
+    if (q8q_hi_out) CS_HIP(hipMemcpy(q8q_hi_out, dQhi, q_n, hipMemcpyDeviceToHost));
+    if (q8q_lo_out) CS_HIP(hipMemcpy(q8q_lo_out, dQhi + q_n, q_n, hipMemcpyDeviceToHost));
+    if (qmeta_out) CS_HIP(hipMemcpy(qmeta_out, dQm, (size_t)4 * nq * sizeof(float4), hipMemcpyDeviceToHost));
+    if (qmag_out) CS_HIP(hipMemcpy(qmag_out, dQmag, (size_t)nq * 4, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> hc(cnt_words), hcand(cand_slots * 2);
+    CS_HIP(hipMemcpy(hc.data(), dCnt, cnt_words * 4, hipMemcpyDeviceToHost));
+    CS_HIP(hipMemcpy(hcand.data(), dCand, cand_slots * 8, hipMemcpyDeviceToHost));
+    uint32_t changed = 0;
+    for (size_t i = 0; i < cnt_words; ++i) {
+        if (i % kCntStride == 0) cnt_out[i / kCntStride] = hc[i];
+        else changed += hc[i] != CS_DEBUG_FILTER_GUARD_WORD;
+    }
+    for (size_t q = 0; q <= nq; ++q) {  // (query nq: the spare query's slots)
+        const size_t used = q < nq ? std::min<size_t>(hc[q * kCntStride], cap) : 0;
+        for (size_t i = 0; i < cap; ++i) {
+            const size_t s = q * cap + i;
+            if (q < nq) cand_out[s] = hcand[2 * s];
+            changed += hcand[2 * s + 1] != CS_DEBUG_FILTER_GUARD_WORD;  // a filter writes the low word of a slot only
+            if (i >= used) changed += hcand[2 * s] != CS_DEBUG_FILTER_GUARD_WORD;
+        }
+    }
+    *guard_changed = changed;
+    return CS_OK;
+}
+
 }  // extern "C"

@@ -437,6 +437,30 @@ int32_t launch_scan_split(const BatchedState& st, const SplitQueryWs& qw, const 
                           uint32_t* d_out_counts, hipStream_t stream, float margin, const Q8View* q8 = nullptr,
                           const FilterPlan* prepared = nullptr, const uint32_t* d_phase0_list = nullptr,
                           const SimilarRefine* similar = nullptr);
+// What one phase's filter launch reads and writes beside the phase itself: the search state (tau, the counters and the
+// candidate slots), the query workspace prep_queries_kernel filled, the two corpus copies and the tombstones.
+struct FilterOperands {
+    const BatchedState* st = nullptr;
+    const SplitQueryWs* qw = nullptr;
+    const _Float16* d_split = nullptr;  // the f16 kernels' operand
+    const Q8View* q8 = nullptr;         // the int8 kernels' operand
+    const uint32_t* d_dead = nullptr;   // may be null
+    uint32_t nq = 0, cap = 0;           // cap: candidate slots per query
+    float margin = 0.0f;                // filter_margin (the f16 kernels)
+    uint32_t nt_stream = 1;             // FilterKnobs::nt
+    hipStream_t stream = nullptr;
+};
+// The first kernel of a filter search (prep_queries_kernel): magnitudes, the f16 unit queries, with use_q8 the int8 plane and
+// its constants against d_mu (with two_planes the hi / lo planes too), and the search state reset — tau = -inf, every
+// counter = first_rows, the carried keys zeroed.
+int32_t launch_prep_queries(uint32_t dim, const BatchedState& st, const SplitQueryWs& qw, const float* d_queries, uint32_t nq,
+                            uint32_t k, uint32_t first_rows, const float* d_mu, bool use_q8, bool two_planes, hipStream_t stream);
+// One phase as planned (filter_plan.hpp): the filter kernel ph.kernel / ph.nqt over rows [ph.lo, ph.filter_hi) (f16: ph.hi)
+// on ph.grid blocks, then tail_candidates_kernel over [ph.tail_lo, ph.tail_hi).  launch_scan_split calls it per phase;
+// cs_debug_filter (diagnostics.hip) calls it alone.  CS_ERR_BAD_ARG: a (kernel, nqt) that was never instantiated for this
+// dim, rows that are not whole tiles where the kernel needs them, a resident-query grid off the XCD octets or below one
+// octet per query tile, a missing operand.
+int32_t launch_filter_phase(uint32_t dim, const FilterPhase& ph, const FilterOperands& op);
 const FilterKnobs& filter_knobs();  // the plan's laboratory knobs as the launcher reads them (the product: the defaults)
 // prepared (a scoped search, scoped_filter_plan.hpp): launch that plan instead of plan_filter's — its phase 0 re-scores
 // the first prepared->phase0_rows entries of d_phase0_list, and d_dead is the scope's blocked-rows bitmap.

@@ -169,8 +169,9 @@ __device__ __forceinline__ float q8_threshold(float tqs, float hA, float nb, flo
     const float tB = fminf(tm.y, tm.w * Dq);
     const float tC = fminf(dimq, tm.z * Dq);
     // the f32 evaluation of the line itself: a relative term (with two-plane queries |T| reaches 1e9: an ulp is 64)
+    // (capped, so that tau = +inf keeps T = +inf — nothing passes — instead of inf - inf = NaN, which passes every row)
     const float lead = tqs * tm.x;
-    return floorf(lead - (tA + tB + tC + kQ8Guard + fabsf(lead) * 4.0e-7f));
+    return floorf(lead - (tA + tB + tC + kQ8Guard + fminf(fabsf(lead) * 4.0e-7f, 3.0e38f)));
 }
 
 // Everything a batched search needs before its first phase, in one launch (three kernels of ~2 us
@@ -1545,6 +1546,114 @@ static void for_each_filter(F&& f) {
 
 static_assert(UF2_BM == 256 && UF2_BN == 256 && SH_BM == 128 && SH_BN == 128, "filter_plan.hpp's tile sizes");
 
+// The dynamic-LDS limits of every instantiation of filter_insts<J>(), once per device: before the first launch of any of them.
+template <int J>
+static int32_t filter_attributes() {
+    static PerDeviceOnce attr_set;  // function attributes are per device
+    return attr_set.run([&]() -> int32_t {
+        hipError_t e = hipSuccess;
+        for_each_filter<J>([&](auto i) {
+            const auto f = filter_fn<J, i>();
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute(reinterpret_cast<const void*>(f.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds);
+        });
+        CS_HIP(e);
+        return CS_OK;
+    });
+}
+
+template <int J>
+static int32_t prep_queries_impl(const BatchedState& st, const SplitQueryWs& qw, const float* d_queries, uint32_t nq, uint32_t k,
+                                 uint32_t first_rows, const float* d_mu, bool use_q8, bool two_planes, hipStream_t stream) {
+    hipLaunchKernelGGL(prep_queries_kernel<J>, dim3((nq + 7) / 8), dim3(256), 0, stream,
+                       qw.q_pinned ? qw.q_pinned : d_queries, qw.q_pinned ? const_cast<float*>(d_queries) : nullptr, nq,
+                       qw.d_qmag, qw.d_qsplit, st.d_tau, st.d_cnt, st.d_carry, k, st.d_overflow, first_rows,
+                       use_q8 ? qw.d_q8q : nullptr, qw.d_qmeta, use_q8 ? d_mu : nullptr, st.h_mirror,
+                       two_planes ? qw.d_q8q_hi : nullptr, qw.d_q8q_lo);
+    CS_HIP(hipGetLastError());
+    return CS_OK;
+}
+
+int32_t launch_prep_queries(uint32_t dim, const BatchedState& st, const SplitQueryWs& qw, const float* d_queries, uint32_t nq,
+                            uint32_t k, uint32_t first_rows, const float* d_mu, bool use_q8, bool two_planes, hipStream_t stream) {
+    const auto impl = dim == 384 ? prep_queries_impl<3> : dim == 768 ? prep_queries_impl<6> : dim == 1024 ? prep_queries_impl<8> : nullptr;
+    if (!impl) return fail(CS_ERR_UNSUPPORTED, "split scan supports dim 384/768/1024, got %u", dim);
+    return impl(st, qw, d_queries, nq, k, first_rows, d_mu, use_q8, two_planes, stream);
+}
+
+// One phase's filter launch and the int8 tail behind it, as planned.
+template <int J>
+static int32_t filter_phase_impl(const FilterPhase& ph, const FilterOperands& op) {
+    constexpr uint32_t dim = 128 * J;
+    CS_TRY(filter_attributes<J>());
+    const BatchedState& st = *op.st;
+    const SplitQueryWs& qw = *op.qw;
+    const Q8View* q8 = op.q8;
+    const _Float16* d_split = op.d_split;
+    const uint32_t* d_dead = op.d_dead;
+    const uint32_t nq = op.nq, cap = op.cap, nt = op.nt_stream;
+    const float margin = op.margin;
+    hipStream_t stream = op.stream;
+    uint32_t* cand = reinterpret_cast<uint32_t*>(st.d_cand);
+    using K = FilterKernel;
+    if (ph.kernel != K::None) {
+        // what the kernels take for granted (plan_filter and scoped_filter_plan.hpp keep to it)
+        const bool i8 = ph.kernel == K::Q8Tile256 || ph.kernel == K::Q8Rq || ph.kernel == K::Q8Rq1 || ph.kernel == K::Q8Rw || ph.kernel == K::Q8Rw2;
+        const bool resident = ph.kernel != K::Q8Tile256 && ph.kernel != K::F16Tile256 && ph.kernel != K::F16Tile128;
+        bool found = false;
+        for_each_filter<J>([&](auto i) {
+            constexpr FilterInst f = filter_insts<J>()[i];
+            found = found || (ph.kernel == f.kernel && ph.nqt == f.nqt);
+        });
+        if (!found) return fail(CS_ERR_BAD_ARG, "filter phase: no kernel %d with %u query groups at dim %u", (int)ph.kernel, ph.nqt, dim);
+        if (ph.lo % 128 || (i8 && ph.filter_hi % 128))
+            return fail(CS_ERR_BAD_ARG, "filter phase: rows [%llu, %llu) are not whole 128-row tiles", (unsigned long long)ph.lo,
+                        (unsigned long long)(i8 ? ph.filter_hi : ph.hi));
+        if (resident && (ph.qtiles == 0 || ph.grid % 8 || ph.grid < 8 * ph.qtiles))
+            return fail(CS_ERR_BAD_ARG, "filter phase: a resident-query grid is a multiple of 8, at least 8 per query tile (grid %u, %u query tiles)",
+                        ph.grid, ph.qtiles);
+        if (ph.grid == 0 || nq == 0 || (i8 ? !(q8 && q8->d_q8 && q8->d_tmeta && qw.d_q8q && qw.d_qmeta) : !(d_split && qw.d_qsplit)) ||
+            (ph.kernel == K::Q8Rw2 && !(qw.d_q8q_hi && qw.d_q8q_lo)))
+            return fail(CS_ERR_BAD_ARG, "filter phase: no grid, no queries or no operands for kernel %d", (int)ph.kernel);
+    }
+    for_each_filter<J>([&](auto i) {
+        constexpr FilterInst f = filter_insts<J>()[i];
+        if (ph.kernel != f.kernel || ph.nqt != f.nqt) return;
+        const auto k = filter_fn<J, i>();
+        if constexpr (f.kernel == K::F16Tile128)
+            hipLaunchKernelGGL(k.fn, dim3(ph.grid), dim3(256), k.lds, stream, d_split, ph.lo, ph.hi, dim / 64, qw.d_qsplit, nq,
+                               st.d_tau, d_dead, cand, st.d_cnt, cap, margin);
+        else if constexpr (f.kernel == K::F16Tile256)
+            hipLaunchKernelGGL(k.fn, dim3(ph.grid), dim3(512), k.lds, stream, d_split, ph.lo, ph.hi, dim / 64, qw.d_qsplit, nq,
+                               st.d_tau, d_dead, cand, st.d_cnt, cap, ph.slots, margin, (const float4*)nullptr,
+                               (const float4*)nullptr);
+        else if constexpr (f.kernel == K::Q8Tile256)
+            hipLaunchKernelGGL(k.fn, dim3(ph.grid), dim3(512), k.lds, stream, reinterpret_cast<const _Float16*>(q8->d_q8), ph.lo,
+                               ph.filter_hi, dim / 128, reinterpret_cast<const _Float16*>(qw.d_q8q), nq, st.d_tau, d_dead,
+                               cand, st.d_cnt, cap, ph.slots, q8_slack(dim), q8->d_tmeta, qw.d_qmeta);
+        else if constexpr (f.kernel == K::F16Rw)
+            hipLaunchKernelGGL(k.fn, dim3(ph.grid), dim3(256), k.lds, stream, d_split, ph.lo, ph.hi, qw.d_qsplit, nq, st.d_tau,
+                               d_dead, cand, st.d_cnt, cap, ph.qtiles, nt, margin);
+        else if constexpr (f.kernel == K::Q8Rw || f.kernel == K::Q8Rw2)
+            hipLaunchKernelGGL(k.fn, dim3(ph.grid), dim3(256), k.lds, stream, q8->d_q8, q8->d_tmeta, ph.lo, ph.filter_hi,
+                               f.kernel == K::Q8Rw2 ? qw.d_q8q_hi : qw.d_q8q, qw.d_qmeta, nq, st.d_tau, d_dead, cand,
+                               st.d_cnt, cap, ph.qtiles, nt, q8_slack(dim), f.kernel == K::Q8Rw2 ? qw.d_q8q_lo : nullptr);
+        else
+            hipLaunchKernelGGL(k.fn, dim3(ph.grid), dim3(512), k.lds, stream, q8->d_q8, q8->d_tmeta, ph.lo, ph.filter_hi,
+                               qw.d_q8q, qw.d_qmeta, nq, st.d_tau, d_dead, cand, st.d_cnt, cap, ph.qtiles, q8_slack(dim));
+    });
+    if (ph.tail_hi > ph.tail_lo)  // fewer than 128 rows behind the int8 copy's last complete tile
+        hipLaunchKernelGGL(tail_candidates_kernel, dim3(nq), dim3(128), 0, stream, ph.tail_lo, ph.tail_hi, d_dead, cand,
+                           st.d_cnt, cap);
+    return CS_OK;
+}
+
+int32_t launch_filter_phase(uint32_t dim, const FilterPhase& ph, const FilterOperands& op) {
+    const auto impl = dim == 384 ? filter_phase_impl<3> : dim == 768 ? filter_phase_impl<6> : dim == 1024 ? filter_phase_impl<8> : nullptr;
+    if (!impl) return fail(CS_ERR_UNSUPPORTED, "split scan supports dim 384/768/1024, got %u", dim);
+    return impl(ph, op);
+}
+
 // Launches what plan_filter plans: prep, then per phase the filter kernel, the int8 tail, the exact re-score and the select.
 template <int J>
 static int32_t scan_split_impl(const BatchedState& st, const SplitQueryWs& qw, const float* d_corpus,
@@ -1555,17 +1664,7 @@ static int32_t scan_split_impl(const BatchedState& st, const SplitQueryWs& qw, c
                                const SimilarRefine* similar) {
     constexpr uint32_t dim = 128 * J;
     const uint32_t cap = batched_cap(k);
-    static PerDeviceOnce attr_set;  // function attributes are per device
-    CS_TRY(attr_set.run([&]() -> int32_t {
-        hipError_t e = hipSuccess;
-        for_each_filter<J>([&](auto i) {
-            const auto f = filter_fn<J, i>();
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(f.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds);
-        });
-        CS_HIP(e);
-        return CS_OK;
-    }));
+    CS_TRY(filter_attributes<J>());
     const FilterKnobs& kn = filter_knobs();
     const bool q8_ready = q8 && q8->d_q8 && qw.d_q8q && qw.d_qmeta;
     // a prepared plan (a scoped search: scoped_filter_plan.hpp) is launched as it stands: its phase 0 are the first
@@ -1574,46 +1673,13 @@ static int32_t scan_split_impl(const BatchedState& st, const SplitQueryWs& qw, c
         return fail(CS_ERR_BAD_ARG, "a prepared filter plan needs the int8 copy, its query planes, a bitmap and a phase-0 list");
     const FilterPlan plan = prepared ? *prepared
                                      : plan_filter(dim, n_rows, nq, k, q8_ready ? q8->rows : 0, qw.d_q8q_hi && qw.d_q8q_lo, cu_count(), kn);
-    hipLaunchKernelGGL(prep_queries_kernel<J>, dim3((nq + 7) / 8), dim3(256), 0, stream,
-                       qw.q_pinned ? qw.q_pinned : d_queries, qw.q_pinned ? const_cast<float*>(d_queries) : nullptr, nq,
-                       qw.d_qmag, qw.d_qsplit, st.d_tau, st.d_cnt, st.d_carry, k, st.d_overflow, plan.phase0_rows,
-                       plan.use_q8 ? qw.d_q8q : nullptr, qw.d_qmeta, plan.use_q8 ? q8->d_mu : nullptr, st.h_mirror,
-                       plan.two_planes ? qw.d_q8q_hi : nullptr, qw.d_q8q_lo);
-    CS_HIP(hipGetLastError());
-    uint32_t* cand = reinterpret_cast<uint32_t*>(st.d_cand);
-    const uint32_t nt = kn.nt;
+    CS_TRY(prep_queries_impl<J>(st, qw, d_queries, nq, k, plan.phase0_rows, q8 ? q8->d_mu : nullptr, plan.use_q8, plan.two_planes, stream));
+    FilterOperands op;
+    op.st = &st; op.qw = &qw; op.d_split = d_split; op.q8 = q8; op.d_dead = d_dead;
+    op.nq = nq; op.cap = cap; op.margin = margin; op.nt_stream = kn.nt; op.stream = stream;
     for (uint32_t p = 0; p < plan.nphases; ++p) {
         const FilterPhase& ph = plan.phase[p];
-        for_each_filter<J>([&](auto i) {
-            constexpr FilterInst f = filter_insts<J>()[i];
-            if (ph.kernel != f.kernel || ph.nqt != f.nqt) return;
-            const auto k = filter_fn<J, i>();
-            using K = FilterKernel;
-            if constexpr (f.kernel == K::F16Tile128)
-                hipLaunchKernelGGL(k.fn, dim3(ph.grid), dim3(256), k.lds, stream, d_split, ph.lo, ph.hi, dim / 64, qw.d_qsplit, nq,
-                                   st.d_tau, d_dead, cand, st.d_cnt, cap, margin);
-            else if constexpr (f.kernel == K::F16Tile256)
-                hipLaunchKernelGGL(k.fn, dim3(ph.grid), dim3(512), k.lds, stream, d_split, ph.lo, ph.hi, dim / 64, qw.d_qsplit, nq,
-                                   st.d_tau, d_dead, cand, st.d_cnt, cap, ph.slots, margin, (const float4*)nullptr,
-                                   (const float4*)nullptr);
-            else if constexpr (f.kernel == K::Q8Tile256)
-                hipLaunchKernelGGL(k.fn, dim3(ph.grid), dim3(512), k.lds, stream, reinterpret_cast<const _Float16*>(q8->d_q8), ph.lo,
-                                   ph.filter_hi, dim / 128, reinterpret_cast<const _Float16*>(qw.d_q8q), nq, st.d_tau, d_dead,
-                                   cand, st.d_cnt, cap, ph.slots, q8_slack(dim), q8->d_tmeta, qw.d_qmeta);
-            else if constexpr (f.kernel == K::F16Rw)
-                hipLaunchKernelGGL(k.fn, dim3(ph.grid), dim3(256), k.lds, stream, d_split, ph.lo, ph.hi, qw.d_qsplit, nq, st.d_tau,
-                                   d_dead, cand, st.d_cnt, cap, ph.qtiles, nt, margin);
-            else if constexpr (f.kernel == K::Q8Rw || f.kernel == K::Q8Rw2)
-                hipLaunchKernelGGL(k.fn, dim3(ph.grid), dim3(256), k.lds, stream, q8->d_q8, q8->d_tmeta, ph.lo, ph.filter_hi,
-                                   f.kernel == K::Q8Rw2 ? qw.d_q8q_hi : qw.d_q8q, qw.d_qmeta, nq, st.d_tau, d_dead, cand,
-                                   st.d_cnt, cap, ph.qtiles, nt, q8_slack(dim), f.kernel == K::Q8Rw2 ? qw.d_q8q_lo : nullptr);
-            else
-                hipLaunchKernelGGL(k.fn, dim3(ph.grid), dim3(512), k.lds, stream, q8->d_q8, q8->d_tmeta, ph.lo, ph.filter_hi,
-                                   qw.d_q8q, qw.d_qmeta, nq, st.d_tau, d_dead, cand, st.d_cnt, cap, ph.qtiles, q8_slack(dim));
-        });
-        if (ph.tail_hi > ph.tail_lo)  // fewer than 128 rows behind the int8 copy's last complete tile
-            hipLaunchKernelGGL(tail_candidates_kernel, dim3(nq), dim3(128), 0, stream, ph.tail_lo, ph.tail_hi, d_dead, cand,
-                               st.d_cnt, cap);
+        CS_TRY(filter_phase_impl<J>(ph, op));
         const bool first = ph.lo == 0, last = p + 1 == plan.nphases;  // (plan_filter: the phase that reaches n_rows)
         if (ph.hi > ph.lo && !first) CS_HIP(hipGetLastError());
         if (similar) {  // a similar-chunk search: its own refine and fold (scan_similar_filter.hip), same grids

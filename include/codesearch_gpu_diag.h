@@ -2,7 +2,7 @@
  * codesearch_gpu_diag.h — operator-level diagnostics of libcsgpu, exported ONLY by codesearch_amd/libcsgpu_diag.so (the
  * product library built once more with -DCS_DIAGNOSTICS: it additionally holds csrc/diagnostics.hip, the ablation
  * instantiations of the wide GEMM kernel and its in-kernel clock stamps).  Used by tests/test_gpu_gemm_split.py, tests/test_gpu_gemm_wide.py,
- * tests/test_gpu_quantized.py, tests/test_gpu_q8_ln.py, tests/test_gpu_attention.py, tests/test_gpu_rows.py, tests/test_gpu_attention_cls.py, tests/test_gpu_small_path.py (operator parity) and benchmarks/ (A/B timing); nothing in INTEGRATION.md binds it and a
+ * tests/test_gpu_quantized.py, tests/test_gpu_q8_ln.py, tests/test_gpu_attention.py, tests/test_gpu_rows.py, tests/test_gpu_attention_cls.py, tests/test_gpu_small_path.py, tests/test_gpu_filter_kernels.py (operator parity) and benchmarks/ (A/B timing); nothing in INTEGRATION.md binds it and a
  * deployment does not ship it.  The diagnostic library exports every symbol of include/codesearch_gpu.h as well, so a
  * process may use it in place of libcsgpu.so.
  */
@@ -212,6 +212,40 @@ CS_API int32_t cs_debug_small_path(int32_t device, int32_t op, int32_t epi, int3
                             const float* type_table, const int32_t* types, uint32_t ntypes, uint32_t vocab, const float* W,
                             const float* bias, float* xout, float* cs_out, float* x_after, float* parts_out, uint32_t* flags,
                             uint32_t* guard_changed);
+
+/* Diagnostics: ONE phase of the batched filter search (csrc/scan_filter.hip) alone on host buffers, for parity of the candidate
+ * set with float64 cosines (tests/test_gpu_filter_kernels.py; references and decision rules: tests/filter_ref.py).  dim = 384 |
+ * 768 | 1024; corpus [n_rows, dim], queries [nq, dim], tau [nq] f32; dead (optional) the tombstone bitmap, one bit per stored
+ * row; mu_in [dim] (optional) the vector the int8 copy is centred on, else launch_unit_mean over the n_rows rows.
+ * Runs launch_row_norms, launch_corpus_split (the f16 copy), launch_unit_mean and launch_corpus_q8 (the int8 copy: the
+ * n_rows / 128 complete tiles), launch_prep_queries with the int8 plane and the hi / lo planes, then — tau overwritten with the
+ * caller's, the counters zeroed — one launch_filter_phase filled by hand:
+ *   kernel    a cs::FilterKernel value (filter_plan.hpp: 0 None, 1 Q8Tile256, 2 Q8Rq, 3 Q8Rq1, 4 Q8Rw, 5 Q8Rw2, 6 F16Rw,
+ *             7 F16Tile256, 8 F16Tile128), nqt its 32-query groups per query tile (0 for the tile kernels)
+ *   rows      [row_lo, row_hi), row_lo % 128 == 0; int8 kernels: whole complete tiles; f16: row_hi <= n_rows
+ *   cap       candidate slots per query
+ *   grid      0 = plan_filter's rule for that kernel, else the blocks to launch
+ *   tail      [tail_lo, tail_hi), fewer than 128 rows: tail_candidates_kernel (equal: none)
+ * A combination the launcher refuses is its CS_ERR_BAD_ARG: a (kernel, nqt) filter_insts<dim / 128>() does not hold, row_lo
+ * off a tile, an int8 row_hi off a tile, a resident-query grid that is no multiple of 8 or below 8 per query tile.
+ * Outputs (each optional but cnt_out, cand_out, guard_changed): norms_out [n_rows], mu_out [dim]; f16_out [n_rows, dim] the
+ * f16 copy's bit patterns un-tiled; q8_out [n_rows / 128 * 128, dim] the int8 copy un-tiled, tmeta_out [n_rows / 128][4];
+ * qunit_out [nq, dim] the f16 unit queries' bit patterns; q8q_out, q8q_hi_out, q8q_lo_out [nq, dim] the query planes;
+ * qmeta_out [4 nq][4] (SplitQueryWs::d_qmeta), qmag_out [nq]; cnt_out [nq + CS_DEBUG_FILTER_CNT_PAD] the candidate counters
+ * of the queries and of the padded queries behind them; cand_out [nq, cap] the low word of every candidate slot: query q's
+ * candidates are its first min(cnt, cap) entries, the rest CS_DEBUG_FILTER_GUARD_WORD.
+ * Guards: every candidate slot (both words) and every unused word of a counter line is pre-filled with
+ * CS_DEBUG_FILTER_GUARD_WORD, and one spare query's slots lie behind the last query's; *guard_changed = the words that came
+ * back changed among: the spare slots, a query's slots at or past min(cnt, cap), the high word of any slot, the unused
+ * counter words. */
+#define CS_DEBUG_FILTER_CNT_PAD 256u
+#define CS_DEBUG_FILTER_GUARD_WORD 0xA5A5A5A5u
+CS_API int32_t cs_debug_filter(int32_t device, uint32_t dim, const float* corpus, uint64_t n_rows, const float* queries, uint32_t nq,
+                        const float* tau, const uint32_t* dead, const float* mu_in, int32_t kernel, uint32_t nqt, uint64_t row_lo,
+                        uint64_t row_hi, uint32_t cap, uint32_t grid, uint64_t tail_lo, uint64_t tail_hi, float* norms_out,
+                        float* mu_out, uint16_t* f16_out, int8_t* q8_out, float* tmeta_out, uint16_t* qunit_out, int8_t* q8q_out,
+                        int8_t* q8q_hi_out, int8_t* q8q_lo_out, float* qmeta_out, float* qmag_out, uint32_t* cnt_out,
+                        uint32_t* cand_out, uint32_t* guard_changed);
 
 /* Diagnostics: device milliseconds per launch of one dense layer on synthetic operands resident in HBM.
  * mode 0 exact-f32 MFMA, 1 split-f16 (128 x 128 / skinny kernels), 2 split-f16 wide kernel (N % 384 == 0);

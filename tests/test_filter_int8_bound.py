@@ -1,51 +1,14 @@
 """The error bound of the int8 filter copy (codesearch_amd/csrc/scan_filter.hip, "int8 filter copy" and q8_threshold),
 restated in numpy and checked numerically on the CPU: for every (row, query) pair the cosine must lie within the band
 the kernels subtract from tau — otherwise a row that beats tau could be dropped before the exact refine sees it.  The
-quantiser below follows corpus_q8_kernel / prep_queries_kernel step by step in float32; the cosine is float64."""
+quantiser (tests/filter_ref.py) follows corpus_q8_kernel / prep_queries_kernel step by step in float32 — the kernels' bytes and
+constants are checked against it on the GPU, tests/test_gpu_filter_kernels.py; the cosine is float64."""
 import numpy as np
 import pytest
 
+from tests.filter_ref import _quantise_query, _quantise_query_two_planes, _quantise_tile
+
 F = np.float32
-
-
-def _quantise_tile(rows, mu):
-    """rows: [128, dim] f32 -> (a int8-valued f32, inv_t, hB, E, N) as corpus_q8_kernel."""
-    nrm = np.sqrt((rows.astype(F) ** 2).sum(axis=1, dtype=F)).astype(F)
-    u = np.where(nrm[:, None] == 0, F(0), rows / np.where(nrm == 0, F(1), nrm)[:, None]).astype(F) - mu
-    mx = np.abs(u).max()
-    inv = F(127.0) / mx if mx > 0 else F(1.0)
-    t = (u * inv).astype(F)
-    a = np.clip(np.rint(t), -127, 127).astype(F)
-    hB = F(0.5001) * np.abs(a).sum(axis=1).max()
-    E = F(np.sqrt(((t - a) ** 2).sum(axis=1, dtype=F).max())) * F(1.001) + F(1e-3)
-    N = F(np.sqrt((a * a).sum(axis=1, dtype=F).max())) * F(1.0001)
-    return a, inv, hB, E, N
-
-
-def _quantise_query(q, mu):
-    m = F(np.sqrt((q.astype(F) ** 2).sum(dtype=F)))
-    v = (q / m).astype(F) if m > 0 else np.zeros_like(q, F)
-    mx = np.abs(v).max()
-    inv = F(127.0) / mx if (mx > 0 and np.isfinite(mx)) else F(1.0)
-    t = (v * inv).astype(F)
-    b = np.clip(np.rint(t), -127, 127).astype(F)
-    return (b, inv, F(0.5001) * np.abs(b).sum(), F(np.sqrt((b * b).sum(dtype=F))) * F(1.0001),
-            F(np.sqrt(((t - b) ** 2).sum(dtype=F))) * F(1.001) + F(1e-3), F((v * mu).sum(dtype=F)))
-
-
-def _quantise_query_two_planes(q, mu):
-    """prep_queries_kernel's second quantisation: B = rint(v * 128 inv) = 128 hi + lo; the MFMAs compute a . hi and a . lo."""
-    m = F(np.sqrt((q.astype(F) ** 2).sum(dtype=F)))
-    v = (q / m).astype(F) if m > 0 else np.zeros_like(q, F)
-    mx = np.abs(v).max()
-    inv = (F(127.0) / mx if (mx > 0 and np.isfinite(mx)) else F(1.0)) * F(128.0)
-    t = (v * inv).astype(F)
-    B = np.clip(np.rint(t), -16256, 16256).astype(F)
-    hi = np.rint(B * F(0.0078125)).astype(F)
-    lo = (B - F(128.0) * hi).astype(F)
-    assert np.abs(hi).max() <= 127 and np.abs(lo).max() <= 64
-    return (hi, lo, inv, F(0.5001) * np.abs(B).sum(dtype=F) * F(1.0001), F(np.sqrt((B * B).sum(dtype=F))) * F(1.0001),
-            F(np.sqrt(((t - B) ** 2).sum(dtype=F))) * F(1.001) + F(1e-3), F((v * mu).sum(dtype=F)))
 
 
 def _check(rows, queries, dim):
